@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- tokens/sec of the llm.f90 decode hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" = one token through the whole forward pass (`transformer`, /root/reference/llama2.f90:480-640)
 via the C-ABI entry llmk_forward, weights already resident in HBM; logits (V floats) are handed back
@@ -13,14 +13,21 @@ N>1: the path does not shard for a 1.1B model ("replicas only"): N in
 replicas, one process per GPU (launched by torch.distributed.run), barrier on both sides of the
 timed region, max over ranks, value = total tokens of all replicas / that time ("weak").
 
-Prints ONE JSON line on rank 0, with `roofline` for the dominant kernel -- the persistent whole-token kernel
-(token_kernel.h: its launch IS the hot path) wherever it is instantiated, the fused w1|w3 GEMV on the multi-kernel path
-(--multi-kernel, other shapes) -- and `cpu_baseline` (the real reference binary from oracle/_ref when present, else the
-C port).
+Prints ONE JSON line on rank 0.  A plain run sets up, runs W warm-up positions and EXACTLY K timed positions once,
+and prints the line (`value`, `ms_per_step` = milliseconds of one timed position).
 
-Short runs (--steps < 64, e.g. the driver's --steps 20 --warmup 5: a 14 ms timed region) repeat the whole
-warm-up + K-step loop REPEATS times on a reset context and report the MEDIAN repetition (every repetition's rate is in
-`value_all`): one scheduling hiccup on the host is 3-5 % of a 14 ms region.
+--dump-outputs DIR: after the timed positions, what the timed path handed its caller -- logits.npy (the last timed
+position's logits, float32 [V]; not with --greedy-on-device, whose logits never leave the device) and ids.npy (the
+greedy ids of the K timed positions, float64; --prefill: logits.npy of the prompt's last position only) -- for
+output-for-output comparison of two builds on the same seeded inputs.
+
+--full adds everything that takes runs of its own: `roofline` for the dominant kernel -- the persistent whole-token
+kernel (token_kernel.h: its launch IS the hot path) wherever it is instantiated, the fused w1|w3 GEMV on the multi-kernel
+path (--multi-kernel, other shapes) -- `cpu_baseline` (the real reference binary from oracle/_ref when present, else the
+C port; --no-cpu-baseline drops it) and `fortran_host` (the Fortran CLI on the same weights).  Short runs under --full
+(--steps < 64, e.g. --steps 20 --warmup 5: a 14 ms timed region) repeat the whole warm-up + K-step loop REPEATS times on a
+reset context and report the MEDIAN repetition (every repetition's rate is in `value_all`): one scheduling hiccup on the
+host is 3-5 % of a 14 ms region.
 """
 from __future__ import annotations
 
@@ -283,6 +290,9 @@ def prefill_line(a):
     for _ in range(reps):
         lg = m.prefill(prompt, 1)
     dt = (time.perf_counter() - t0) / reps
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "logits.npy"), np.asarray(lg, np.float32))
     m.reset()
     t0 = time.perf_counter()
     nseq = min(n, 64)
@@ -361,9 +371,15 @@ def main():
                     help="--tp: one-shot all-reduce over peer memory (csrc/tp_p2p.h, default) or ncclAllReduce (library baseline)")
     ap.add_argument("--greedy-on-device", action="store_true", help="auxiliary line: time llmk_decode_greedy (argmax on the device, launches enqueued back to back) instead of the host consumer")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="repetitions of the whole warm-up + K-step run (median reported); default 5 when --steps < 64, else 1")
+                    help="repetitions of the whole warm-up + K-step run (median reported); default 1, under --full 5 when --steps < 64")
     ap.add_argument("--prefill", type=int, default=0, metavar="N",
-                    help="auxiliary line (not the headline metric): time llmk_prefill on an N-token prompt (SURVEY.md 8f rank 1)")
+                    help="auxiliary line (not the headline metric): time llmk_prefill on an N-token prompt (SURVEY.md 8f rank 1); "
+                         "it always carries its token-by-token comparison and its w1|w3 kernel timing, --full does not change it")
+    ap.add_argument("--full", action="store_true",
+                    help="decode line: also the figures that take runs of their own: roofline of the dominant kernel, cpu_baseline, "
+                         "fortran_host, and the median of 5 repetitions when --steps < 64 (no effect on a --prefill line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (logits.npy, ids.npy)")
     a = ap.parse_args()
     if a.prefill:
         return prefill_line(a)
@@ -443,7 +459,7 @@ def main():
         return rep.max_over_ranks(time.perf_counter() - t_start), ids
 
     # a 20-step timed region is 14 ms: repeat the whole run on a reset context and report the median repetition
-    repeats = a.repeats if a.repeats > 0 else (5 if K < 64 else 1)
+    repeats = a.repeats if a.repeats > 0 else (5 if a.full and K < 64 else 1)
     runs = []
     for r in range(repeats):
         if r:
@@ -455,6 +471,12 @@ def main():
         raise SystemExit("greedy transcripts differ between repetitions")
     if not step and not np.all(np.isfinite(lg)):     # (--greedy-on-device never brings logits to the host)
         raise SystemExit("non-finite logits")
+    if a.dump_outputs and rank == 0:
+        # what the caller of the timed path received: the last position's logits (host consumer) and the K greedy ids
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        if not step:
+            np.save(os.path.join(a.dump_outputs, "logits.npy"), lg.astype(np.float32))
+        np.save(os.path.join(a.dump_outputs, "ids.npy"), np.asarray(gpu_ids[W:], np.float64))
 
     tok_s = (1 if a.tp else world) * K / elapsed   # --tp: ONE model over all ranks; else N replicas
     mean_pos = W + (K + 1) / 2.0
@@ -482,35 +504,36 @@ def main():
         # its launch IS the hot path, so achieved = whole-token algorithmic bytes / its HIP-event duration.
         # Multi-kernel path (other shapes / types, --multi-kernel): the fused w1|w3 GEMV (92.3 MB of the
         # 176.2 MB a layer streams).
-        try:
-            ms, b = m.time_kernel(6, 100)
-            out["roofline"] = {"bound": "hbm", "kernel": f"token_kernel<{a.shape}, {a.type}> (persistent whole-token pass: "
-                                                         f"{shape.n_layers} layers + classifier)",
-                               "achieved": b / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                               "frac": b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": pmc_traffic("token_kernel", a.shape, a.type + ("_q6k" if a.cls_q6k else "")),
-                               "bytes_per_launch": b, "us_per_launch": ms * 1000,
-                               "note": f"bytes_per_launch = algorithmic bytes of one token at KV length {W + K}"}
-        except llmk.LlmkError:
-            kern = 3
-            m.reset()
-            ms, b = m.time_kernel(kern, 10 * shape.n_layers)
-            per_k = {}
-            for k in KERNEL_NAMES:
-                kms, kb = m.time_kernel(k, 5 * shape.n_layers)
-                per_k[KERNEL_NAMES[k]] = {"us": round(kms * 1000, 3), "GBps": round(kb / kms / 1e6, 1)}
-            ach = b / (ms * 1e-3) / 1e9
-            kname = "gemv_q4_kernel<SWIGLU,NORM>" if wtype == 2 else f"gemv_kernel<{a.type},SWIGLU,NORM>"
-            out["roofline"] = {"bound": "hbm", "kernel": kname + " (rmsnorm+w1|w3 GEMV+SwiGLU)",
-                               "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                               "traffic": pmc_traffic("gemv_q4_kernel<3, true" if wtype == 2 else f"gemv_kernel<{wtype}, 3, true", a.shape, a.type),
-                               "bytes_per_launch": b,
-                               "us_per_launch": ms * 1000, "kernels": per_k}
+        if a.full:
+            try:
+                ms, b = m.time_kernel(6, 100)
+                out["roofline"] = {"bound": "hbm", "kernel": f"token_kernel<{a.shape}, {a.type}> (persistent whole-token pass: "
+                                                             f"{shape.n_layers} layers + classifier)",
+                                   "achieved": b / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": pmc_traffic("token_kernel", a.shape, a.type + ("_q6k" if a.cls_q6k else "")),
+                                   "bytes_per_launch": b, "us_per_launch": ms * 1000,
+                                   "note": f"bytes_per_launch = algorithmic bytes of one token at KV length {W + K}"}
+            except llmk.LlmkError:
+                kern = 3
+                m.reset()
+                ms, b = m.time_kernel(kern, 10 * shape.n_layers)
+                per_k = {}
+                for k in KERNEL_NAMES:
+                    kms, kb = m.time_kernel(k, 5 * shape.n_layers)
+                    per_k[KERNEL_NAMES[k]] = {"us": round(kms * 1000, 3), "GBps": round(kb / kms / 1e6, 1)}
+                ach = b / (ms * 1e-3) / 1e9
+                kname = "gemv_q4_kernel<SWIGLU,NORM>" if wtype == 2 else f"gemv_kernel<{a.type},SWIGLU,NORM>"
+                out["roofline"] = {"bound": "hbm", "kernel": kname + " (rmsnorm+w1|w3 GEMV+SwiGLU)",
+                                   "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                                   "traffic": pmc_traffic("gemv_q4_kernel<3, true" if wtype == 2 else f"gemv_kernel<{wtype}, 3, true", a.shape, a.type),
+                                   "bytes_per_launch": b,
+                                   "us_per_launch": ms * 1000, "kernels": per_k}
         tok_gbs = bpt * (tok_s / (1 if a.tp else world)) / 1e9 / (world if a.tp else 1)   # per-GPU HBM rate
         out["token_roofline"] = {"bytes_per_token": bpt, "achieved": tok_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                  "frac": tok_gbs / HBM_PEAK_GBS, "roofline_tok_s": HBM_PEAK_GBS * 1e9 / bpt}
         out["setup_s"] = {"weights_gen": round(t_gen, 1), "upload": round(t_up, 1)}
-        want_cb = world == 1 and not a.no_cpu_baseline and fw is not None
-        want_fh = (world == 1 and not a.no_fortran_host and (a.fortran_host or not a.no_cpu_baseline) and fw is not None
+        want_cb = a.full and world == 1 and not a.no_cpu_baseline and fw is not None
+        want_fh = (a.full and world == 1 and not a.no_fortran_host and (a.fortran_host or not a.no_cpu_baseline) and fw is not None
                    and not a.multi_kernel and not a.no_graph and not a.greedy_on_device)
         td = tempfile.TemporaryDirectory(dir=os.environ.get("LLMK_TMP", "/tmp")) if (want_cb or want_fh) else None
         try:            # (the 4.4 GB file must not outlive an exception in the CPU / Fortran legs: advisor, round 5)

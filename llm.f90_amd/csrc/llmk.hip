@@ -435,7 +435,9 @@ hipError_t launch_token_kernel(llmk_ctx* c, bool direct = false, const TkGreedy&
     return tk_table[c->tk_shape - 1].launch(c, direct, g);
 }
 // the last position of a pipelined greedy run has no next launch to fold its candidates: this does (1 wave)
-// (no id while the sticky error word is set, and none from candidates without a finite maximum: see tk_token)
+// (no id while the sticky error word is set, and none from candidates without a finite maximum: see tk_token).  Like tk_token it
+// adds 0x2000 only to a clear word: behind a range event (0x4000) the drained launches leave candidates that need not be finite,
+// and 0x2000 on top would make the host retire the kernel instead of redoing the one position (tk_range_only)
 __global__ __launch_bounds__(64) void cand_resolve_kernel(const float2* __restrict__ cand, int* id_out, int* next, unsigned* err, int V) {
     float bv = -INFINITY;
     int bi = 0x7fffffff;
@@ -447,8 +449,9 @@ __global__ __launch_bounds__(64) void cand_resolve_kernel(const float2* __restri
     tk_wave_argmax(bv, bi);
     if (threadIdx.x == 0) {
         const bool none = (unsigned)bi >= (unsigned)V;
-        if (none) atomicOr(err, 0x2000u);
-        if (!none && *err == 0) {
+        const unsigned e = *err;
+        if (none && e == 0) atomicOr(err, 0x2000u);
+        if (!none && e == 0) {
             next[0] = bi + 1;
             __hip_atomic_store(id_out, bi + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }

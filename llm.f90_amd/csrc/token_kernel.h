@@ -1292,9 +1292,11 @@ __device__ __forceinline__ int tk_token(const TokenArgs& a, int c, int lane) {
             // The id of the PREVIOUS position is published only while the error word is clear: once a launch has timed out its
             // candidates are garbage, and so is everything folded from them.  The host then sees no id from that position on,
             // retires the token kernel and redoes exactly those positions on the multi-kernel path (llmk_decode_greedy).
+            // With the word already raised (a range event or a timeout behind these candidates) no finite maximum is expected: 0x2000
+            // is added only to a clear word, so a range event of the previous position stays a range event (the kernel stays in use).
             if (c == 0 && lane == 0) {
-                if (none) atomicOr(a.err, 0x2000u);
                 const unsigned e = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (none && e == 0) atomicOr(a.err, 0x2000u);
                 if ((a.gflags & TKG_ID) && e == 0 && !none)
                     __hip_atomic_store(reinterpret_cast<int*>(a.herr + 4) + a.tok_imm, bi + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }

@@ -14,7 +14,7 @@ for v in "$@"; do
 done
 for i in $(seq 1 $N); do
   for v in "$@"; do
-    line=$(LLMK_LIB=$(lib $v) timeout 600 python bench.py --no-cpu-baseline $ARGS 2>/dev/null | tail -1)
+    line=$(LLMK_LIB=$(lib $v) timeout 600 python bench.py --full --no-cpu-baseline $ARGS 2>/dev/null | tail -1)
     echo "{\"variant\": \"$v\", \"round\": $i, \"line\": ${line:-null}}" >> $OUT/ab.jsonl
   done
 done

@@ -11,7 +11,9 @@
 #   nine N                   the control behind tests/test_tp70_gpu.py::_run_ranks: N runs of the jitter test with this pytest
 #                            process holding a GPU context, rank 0 in-process (8 GPU processes) and spawned (9)   -> nine.log
 #   dirty                    does a process see another (or its own earlier) process's freed VRAM?   -> dirty.log
-#   bench NAME [bench args]  python bench.py [args]                              -> NAME.json
+#   bench NAME [bench args]  python bench.py [args] (--full for roofline, cpu_baseline, fortran_host)   -> NAME.json
+#   benchl NAME [bench args] the same, the line appended to NAME.jsonl   (both: time limit LLMK_BENCH_LIMIT, default 600 s;
+#                            LLMK_JOB_TAG=. writes at the top of the job output instead of under a tag)
 #   ab NAME N <env>... : [bench args]   N interleaved pairs of bench.py with / without the env setting   -> NAME.jsonl
 #   prof TAG                 the evidence run: per single-GPU configuration of BASELINE.json a bench line, the pipelined-greedy
 #                            line, rocprofv3 --kernel-trace --stats and a FETCH_SIZE pass (separate runs); the 70B rank's
@@ -51,21 +53,21 @@ PY
 stats_of() {  # name, bench args...: rocprofv3 --kernel-trace --stats of that bench command (eager: the profiler dies on hipGraphLaunch)
   local name=$1; shift
   rm -rf /tmp/st_$name
-  (cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st_$name -- python $ROOT/bench.py "$@" > $OUT/${name}_bench_under_rocprof.json 2> /tmp/st_$name.err) || tail -3 /tmp/st_$name.err
+  (cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st_$name -- python $ROOT/bench.py --full "$@" > $OUT/${name}_bench_under_rocprof.json 2> /tmp/st_$name.err) || tail -3 /tmp/st_$name.err
   reduce_stats /tmp/st_$name $OUT/${name}_kernel_stats.csv
 }
 fetch_of() {  # name, kernel-name filter, bench args...: FETCH_SIZE per launch (its own pass: never --pmc with --stats)
   local name=$1 filt=$2; shift 2
   rm -rf /tmp/pm_$name
-  (cd /tmp && timeout 500 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pm_$name -- python $ROOT/bench.py "$@" > /dev/null 2> /tmp/pm_$name.err) || tail -3 /tmp/pm_$name.err
+  (cd /tmp && timeout 500 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/pm_$name -- python $ROOT/bench.py --full "$@" > /dev/null 2> /tmp/pm_$name.err) || tail -3 /tmp/pm_$name.err
   local cc; cc=$(find /tmp/pm_$name -name "*counter_collection.csv" | head -1)
   [ -n "$cc" ] && python $ROOT/profiles/summarize_pmc.py "$cc" FETCH_SIZE $filt | head -8 | tee $OUT/${name}_pmc_fetch_size.csv
 }
 run_cfg() {  # name, cpu-baseline flag, bench args...: bench line, pipelined-greedy line, rocprofv3 stats, FETCH_SIZE pass
   local name=$1 cb=$2; shift 2
   echo "=== $name: $*"
-  timeout 400 python bench.py "$@" $cb > $OUT/${name}_bench.json 2> $OUT/${name}_bench.err; cut -c1-600 $OUT/${name}_bench.json
-  timeout 300 python bench.py "$@" --no-cpu-baseline --greedy-on-device > $OUT/${name}_bench_greedy_pipeline.json 2>> $OUT/${name}_bench.err
+  timeout 400 python bench.py --full "$@" $cb > $OUT/${name}_bench.json 2> $OUT/${name}_bench.err; cut -c1-600 $OUT/${name}_bench.json
+  timeout 300 python bench.py --full "$@" --no-cpu-baseline --greedy-on-device > $OUT/${name}_bench_greedy_pipeline.json 2>> $OUT/${name}_bench.err
   cut -c1-300 $OUT/${name}_bench_greedy_pipeline.json
   stats_of $name "$@" --no-cpu-baseline --no-graph
   fetch_of $name "" "$@" --no-cpu-baseline --steps 20 --warmup 4 --repeats 1
@@ -73,7 +75,7 @@ run_cfg() {  # name, cpu-baseline flag, bench args...: bench line, pipelined-gre
 job_prof() {
   local cfg name
   run_cfg tinyllama_f32 ""
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/tinyllama_f32_bench_driver_workload.json 2>/dev/null; cut -c1-400 $OUT/tinyllama_f32_bench_driver_workload.json
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/tinyllama_f32_bench_driver_workload.json 2>/dev/null; cut -c1-400 $OUT/tinyllama_f32_bench_driver_workload.json
   run_cfg tinyllama_f16 --no-cpu-baseline --type f16
   run_cfg llama2-7b_q4_0 --no-cpu-baseline --shape llama2-7b --type q4_0
   # round 6: a stock llama.cpp Q4_0 file's layout (q6_K classifier rows on the device), and Llama-2-7B f16 on the persistent kernel
@@ -104,7 +106,7 @@ job_pmc() {
   for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVES" \
              "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU GRBM_GUI_ACTIVE SQ_WAIT_INST_LDS"; do
     d=/tmp/pmc_$(echo $set | md5sum | cut -c1-6); rm -rf $d
-    (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -- python $ROOT/bench.py $args > /dev/null 2>$d.err) || tail -2 $d.err
+    (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -- python $ROOT/bench.py --full $args > /dev/null 2>$d.err) || tail -2 $d.err
     python - "$d" "$filt" <<'PY' | tee -a $OUT/pmc_$kind.txt
 import csv, glob, collections, statistics, sys
 d = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -147,8 +149,8 @@ job_ab() {  # NAME N ENV... : bench args     (":" -- the job list itself is spli
   : > $OUT/$name.jsonl
   local i line
   for i in $(seq 1 $n); do
-    line=$(timeout 400 python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1); echo "{\"variant\": \"base\", \"line\": $line}" >> $OUT/$name.jsonl
-    line=$(env "${envs[@]}" timeout 400 python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1); echo "{\"variant\": \"${envs[*]}\", \"line\": $line}" >> $OUT/$name.jsonl
+    line=$(timeout 400 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1); echo "{\"variant\": \"base\", \"line\": $line}" >> $OUT/$name.jsonl
+    line=$(env "${envs[@]}" timeout 400 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1); echo "{\"variant\": \"${envs[*]}\", \"line\": $line}" >> $OUT/$name.jsonl
   done
   python - $OUT/$name.jsonl <<'PY'
 import json, sys
@@ -170,7 +172,8 @@ while [ $# -gt 0 ]; do
     repeat) job_repeat "${args[@]}" ;;
     dirty)  job_dirty ;;
     nine)   job_nine "${args[@]}" ;;
-    bench)  name=${args[0]}; timeout 600 python bench.py "${args[@]:1}" > $OUT/$name.json 2> $OUT/$name.err; cut -c1-1200 $OUT/$name.json ;;
+    bench)  name=${args[0]}; timeout ${LLMK_BENCH_LIMIT:-600} python bench.py "${args[@]:1}" > $OUT/$name.json 2> $OUT/$name.err; cut -c1-1200 $OUT/$name.json ;;
+    benchl) name=${args[0]}; timeout ${LLMK_BENCH_LIMIT:-600} python bench.py "${args[@]:1}" 2>> $OUT/$name.err | tail -1 | tee -a $OUT/$name.jsonl | cut -c1-600 ;;
     ab)     job_ab "${args[@]}" ;;
     prof)   OUT=$ROOT/gpurun_out/prof_${args[0]:-r04}; mkdir -p $OUT; job_prof ;;
     profcfg) OUT=$ROOT/gpurun_out/prof_${args[0]}; mkdir -p $OUT; run_cfg "${args[1]}" --no-cpu-baseline "${args[@]:2}"; timeout 300 python tests/host_tools/tk_curve.py $(case "${args[1]}" in *f16*) echo --type f16;; *7b*) echo --shape llama2-7b;; esac) 1 256 512 1024 2048 2>&1 | tail -1 | tee $OUT/kv_length_curve_${args[1]}.txt ;;

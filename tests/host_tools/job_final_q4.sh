@@ -6,7 +6,7 @@ export LLMK_JOB_TAG=r06f
 bash tests/host_tools/gpu_job.sh profcfg r06f llama2-7b_q4_0 --shape llama2-7b --type q4_0
 bash tests/host_tools/gpu_job.sh profcfg r06f llama2-7b_q4_0_q6k --shape llama2-7b --type q4_0 --cls-q6k
 bash tests/host_tools/gpu_job.sh profcfg r06f mistral-7b_q4_0_q6k --shape mistral-7b --type q4_0 --cls-q6k
-timeout 300 python bench.py --no-cpu-baseline --type q4_0 > gpurun_out/prof_r06f/tinyllama_q4_0_bench.json 2>/dev/null; cut -c1-300 gpurun_out/prof_r06f/tinyllama_q4_0_bench.json
+LLMK_JOB_TAG=prof_r06f LLMK_BENCH_LIMIT=300 bash tests/host_tools/gpu_job.sh bench tinyllama_q4_0_bench --full --no-cpu-baseline --type q4_0
 bash tests/host_tools/decomp.sh r06f_decomp7 "--shape llama2-7b --type q4_0" base nohbm debug debug:nosync d_nohbm:nosync
-timeout 300 python bench.py --no-cpu-baseline > gpurun_out/prof_r06f/tinyllama_f32_bench.json 2>/dev/null; cut -c1-200 gpurun_out/prof_r06f/tinyllama_f32_bench.json
-timeout 300 python bench.py --no-cpu-baseline --type f16 > gpurun_out/prof_r06f/tinyllama_f16_bench.json 2>/dev/null; cut -c1-200 gpurun_out/prof_r06f/tinyllama_f16_bench.json
+LLMK_JOB_TAG=prof_r06f LLMK_BENCH_LIMIT=300 bash tests/host_tools/gpu_job.sh bench tinyllama_f32_bench --full --no-cpu-baseline
+LLMK_JOB_TAG=prof_r06f LLMK_BENCH_LIMIT=300 bash tests/host_tools/gpu_job.sh bench tinyllama_f16_bench --full --no-cpu-baseline --type f16

@@ -1,6 +1,6 @@
-"""bench.py's one-line contract, run the way the driver runs it (`--steps 20 --warmup 5`, N = 1): ONE JSON line on stdout with the
-fields the driver reads, the `roofline` and `cpu_baseline` objects of the tier framing, and a greedy transcript that matches the
-reference's (`ids_match`).  The numbers themselves are not asserted beyond sanity: this guards the plumbing, not the performance."""
+"""bench.py's one-line contract at the driver's size (`--steps 20 --warmup 5`, N = 1): with `--full`, ONE JSON line on stdout with
+the fields the driver reads, the `roofline` and `cpu_baseline` objects of the tier framing, and a greedy transcript that matches the
+reference's (`ids_match`); without it, the same headline fields alone.  The numbers themselves are not asserted beyond sanity: this guards the plumbing, not the performance."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_driver_invocation_prints_one_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                        capture_output=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:].decode(errors="replace")
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -47,3 +47,29 @@ def test_driver_invocation_prints_one_contract_line():
     # 248-step line (bench.py's default, same positions) it is the verdict's 3 %: tests/test_host_gpu.py.
     assert fh["tok_s"] > 0.94 * d["value"], (fh, d["value"])
     assert fh["tok_s_device_argmax"] >= 0.97 * fh["tok_s"], fh
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_its_steps_and_dumps_what_the_timed_path_returned(tmp_path):
+    """A plain line (no --full): ONE run of W warm-up + exactly K timed positions, none of the --full figures; --dump-outputs
+    writes the last timed position's logits and the K greedy ids, the same from run to run (seeded inputs)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3",
+                            "--dump-outputs", str(out)], capture_output=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:].decode(errors="replace")
+        lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 12 and d["warmup"] == 3 and d["timing"] == "one run" and len(d["value_all"]) == 1
+        for k in ("roofline", "cpu_baseline", "fortran_host"):
+            assert k not in d, k
+        logits, ids = np.load(out / "logits.npy"), np.load(out / "ids.npy")
+        assert logits.dtype == np.float32 and logits.shape == (32000,) and np.all(np.isfinite(logits))
+        assert ids.dtype == np.float64 and ids.shape == (12,) and np.all(ids == np.round(ids)) and ids.min() >= 1 and ids.max() <= 32000
+        dumps.append((logits, ids))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])

@@ -242,7 +242,7 @@ def test_fortran_cli_rate_is_the_ctypes_rate_at_full_tinyllama_size():
     CLI's rate must be within 3 % of the ctypes rate, and its transcript identical."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--fortran-host"], capture_output=True, cwd=ROOT, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--fortran-host"], capture_output=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:].decode(errors="replace")
     d = json.loads(r.stdout.decode().strip().splitlines()[-1])
     fh = d["fortran_host"]
