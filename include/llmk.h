@@ -209,6 +209,25 @@ int llmk_forward_greedy(llmk_ctx *ctx, int token, int pos, int *next_token);
 typedef void (*llmk_token_fn)(int index, int token, void *user);
 int llmk_decode_greedy(llmk_ctx *ctx, int token, int pos0, int n, int *ids_out, llmk_token_fn on_token, void *user);
 
+/* The sampling twins of llmk_forward_greedy / llmk_decode_greedy: the consumer at temperature T > 0
+ * (`token ~ softmax(logits / T)`, llama2.f90:390) runs on the device, by the Gumbel-max rule
+ *
+ *     token = 1 + argmax_i ( logits[i] * invT + g(seed, pos, i) )      first maximum wins, i 0-based
+ *     g     = -log(-log(u)),  u = float((w >> 8) | 1) * 2^-24          (odd / 2^24: exact in f32, never 0 or 1)
+ *     w     = Philox4x32-10(counter = (i >> 2, pos, 0, 0), key = (seed & 0xffffffff, seed >> 32))[i & 3]
+ *     invT  = f32(1 / T), rounded once on the host; pos 1-based (the position whose logits are sampled)
+ *
+ * (each product and sum rounded to f32; llm.f90_amd/csrc/sample.h holds the arithmetic).  In exact arithmetic this
+ * draws from exactly the reference's distribution; it is NOT draw-for-draw the reference's random_number stream.  The
+ * noise is stateless, keyed by (seed, pos, row): the pipelined launches of llmk_decode_sample, a chain of
+ * llmk_forward_sample calls, the multi-kernel path and a redone position all pick the same token from the same logits,
+ * so a transcript is a function of (model, prompt, T, seed).  Positions, callbacks, streaming and errors are those of
+ * the greedy functions (LLMK_E_NONFINITE when no score is above -inf).  temperature must be finite and > 0 with 1/T a
+ * normal f32, otherwise LLMK_E_ARG (temperature 0 is the greedy functions' job). */
+int llmk_forward_sample(llmk_ctx *ctx, int token, int pos, float temperature, uint64_t seed, int *next_token);
+int llmk_decode_sample(llmk_ctx *ctx, int token, int pos0, int n, float temperature, uint64_t seed,
+                       int *ids_out, llmk_token_fn on_token, void *user);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318. */
 int llmk_reset(llmk_ctx *ctx);
 

@@ -12,6 +12,8 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include "sample.h"
+
 namespace llmk {
 
 constexpr int WAVE = 64;
@@ -758,6 +760,38 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
         for (int w = 1; w < 16; ++w)
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
         out[0] = (unsigned)idx < (unsigned)n ? idx + 1 : 0;   // no finite maximum (all NaN / -inf): 0 is no token -- the next call rejects it (LLMK_E_ARG)
+    }
+}
+
+// token ~ softmax(logits / T) by the Gumbel-max rule of sample.h: argmax of llmk_sample_score over the logits, first maximum wins,
+// writes the 1-based id.  pos comes from the token pass's own device word (tokpos[1]), invT and the seed from `sp` (both set by
+// host copies inside the graph, as the token and position are).  The same rules as argmax_kernel: no score above -inf, no token.
+__global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ logits, int n, const int* __restrict__ tokpos,
+                                                      const llmk_sample_params* __restrict__ sp, int* __restrict__ out) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const int pos = tokpos[1];
+    const float invT = sp->invT;
+    const uint64_t seed = (uint64_t)sp->seed_lo | ((uint64_t)sp->seed_hi << 32);
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const float v = llmk_sample_score(logits[i], invT, seed, pos, i);
+        if (v > best) { best = v; idx = i; }  // ascending i per thread: keeps the first maximum
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { bv[wid] = best; bi[wid] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+        out[0] = (unsigned)idx < (unsigned)n ? idx + 1 : 0;   // 0 = no token: LLMK_E_NONFINITE on the host
     }
 }
 

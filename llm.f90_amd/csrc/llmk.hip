@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -107,7 +108,11 @@ struct llmk_ctx {
     bool tk_direct = true;
     int* h_next = nullptr;      // pinned
     hipStream_t stream = nullptr;
-    hipGraphExec_t graph_logits = nullptr, graph_greedy = nullptr;
+    hipGraphExec_t graph_logits = nullptr, graph_greedy = nullptr, graph_sample = nullptr;
+    llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current llmk_forward_sample / llmk_decode_sample call
+    // what the device's copy of them (d_sample_params) holds once the stream has drained: zeros from llmk_create on; pad = 1 while
+    // unknown.  A pipelined decode writes them only when they differ, so a greedy one on a ctx that never sampled enqueues nothing new
+    llmk_sample_params samp_dev = {};
     hipEvent_t ev[8] = {};
     float times[5] = {0, 0, 0, 0, 0};
     int n_cu = 256;
@@ -504,9 +509,21 @@ int tk_setup_all(llmk_ctx* c) {
 
 __global__ void bump_serial_kernel(int* tokpos) { tokpos[2] += 1; }
 
-hipError_t enqueue_tail(llmk_ctx* c, bool greedy) {
-    if (greedy) {
-        hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_next);
+// What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
+// (llmk_forward_sample); the last two leave the 1-based id in h_next[0] and the sticky error word in h_next[1]
+enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE };
+// the sampling parameters in device memory: behind the error word and the pipelined decode's two candidate buffers
+// (token_kernel.h tk_sample_params reads the same words)
+llmk_sample_params* d_sample_params(llmk_ctx* c) { return reinterpret_cast<llmk_sample_params*>(c->d_logits + c->V + 4 + 4 * TK_NCU); }
+hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
+    if (tail != TAIL_LOGITS) {
+        if (tail == TAIL_SAMPLE) {
+            // invT and the seed travel like token and position: a copy out of pinned memory, read when the graph replays it
+            HIPRET(hipMemcpyAsync(d_sample_params(c), c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_tokpos, d_sample_params(c), c->d_next);
+        } else {
+            hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_next);
+        }
         HIPRET(hipGetLastError());
         HIPRET(hipMemcpyAsync(c->h_next, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPRET(hipMemcpyAsync(c->h_next + 1, c->d_logits + c->V, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -570,7 +587,7 @@ hipError_t launch_tp_allgather(llmk_ctx* c, unsigned jseed = 0) {   // every ran
     return hipGetLastError();
 }
 
-hipError_t enqueue_token(llmk_ctx* c, bool greedy, bool timed) {
+hipError_t enqueue_token(llmk_ctx* c, TailMode tail, bool timed) {
     HIPRET(hipMemcpyAsync(c->d_tokpos, c->h_tokpos, 4 * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (c->p2p) {   // tensor-parallel over peer memory: the whole token is stream work (replayable from a hipGraph)
         HIPRET(launch_embed(c));
@@ -585,11 +602,11 @@ hipError_t enqueue_token(llmk_ctx* c, bool greedy, bool timed) {
         }
         HIPRET(launch_cls(c));
         HIPRET(launch_tp_allgather(c));
-        return enqueue_tail(c, greedy);
+        return enqueue_tail(c, tail);
     }
     if (c->use_tk) {
         HIPRET(launch_token_kernel(c));
-        return enqueue_tail(c, greedy);
+        return enqueue_tail(c, tail);
     }
     HIPRET(launch_embed(c));
     for (int l = 0; l < c->L; ++l) {
@@ -620,13 +637,13 @@ hipError_t enqueue_token(llmk_ctx* c, bool greedy, bool timed) {
         float ms;
         HIPRET(hipEventElapsedTime(&ms, c->ev[4], c->ev[5])); c->times[4] += ms;  // 5 = final norm + classifier
     }
-    return enqueue_tail(c, greedy);
+    return enqueue_tail(c, tail);
 }
 
-int build_graph(llmk_ctx* c, bool greedy, hipGraphExec_t* out) {
+int build_graph(llmk_ctx* c, TailMode tail, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    hipError_t e = enqueue_token(c, greedy, false);
+    hipError_t e = enqueue_token(c, tail, false);
     hipError_t e2 = hipStreamEndCapture(c->stream, &g);
     if (e != hipSuccess) { if (g) hipGraphDestroy(g); return LLMK_E_HIP + (int)e; }
     HIPCHK(e2);
@@ -665,6 +682,7 @@ int tk_retire(llmk_ctx* c, unsigned code, int pos) {
     c->tk_retired = true;
     if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
+    if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     for (int i = 0; i < LLMK_N_TENSORS; ++i)       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
         if (c->q16[i]) { hipFree(c->q16[i]); c->q16[i] = nullptr; }
     c->q16_dirty = true;
@@ -691,7 +709,7 @@ const char* tp_describe_err(const llmk_ctx* c, unsigned code, char* buf, size_t 
                   call, serial, call / 2u, (call & 1u) ? "w2" : "wo");
     return buf;
 }
-int run_token(llmk_ctx* c, int token, int pos, bool greedy) {
+int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
     int rc = check_ready(c);
     if (rc) return rc;
     if (token < 1 || token > c->V || pos < 1 || pos > c->S) return LLMK_E_ARG;
@@ -706,30 +724,30 @@ int run_token(llmk_ctx* c, int token, int pos, bool greedy) {
         if ((c->tp_size > 1 || c->comm) && !c->p2p) {   // tensor-parallel over RCCL: eager launches with the collectives in between
             rc = enqueue_token_tp(c);
             if (rc) return rc;
-            HIPCHK(enqueue_tail(c, greedy));
+            HIPCHK(enqueue_tail(c, tail));
         } else if (timed || (c->cfg.flags & LLMK_FLAG_NO_GRAPH)) {
-            HIPCHK(enqueue_token(c, greedy, timed));
-        } else if (c->use_tk && !greedy && c->tk_direct) {
+            HIPCHK(enqueue_token(c, tail, timed));
+        } else if (c->use_tk && tail == TAIL_LOGITS && c->tk_direct) {
             reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
             HIPCHK(launch_token_kernel(c, true));
         } else {
-            hipGraphExec_t* g = greedy ? &c->graph_greedy : &c->graph_logits;
+            hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : &c->graph_logits;
             if (!*g) {
-                rc = build_graph(c, greedy, g);
+                rc = build_graph(c, tail, g);
                 if (rc) return rc;
             }
             HIPCHK(hipGraphLaunch(*g, c->stream));
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         if (c->p2p) {   // a peer never delivered its granules: the sticky word says so (cleared by llmk_reset)
-            const unsigned perr = greedy ? (unsigned)c->h_next[1] : reinterpret_cast<unsigned*>(c->h_logits)[c->V];
+            const unsigned perr = tail != TAIL_LOGITS ? (unsigned)c->h_next[1] : reinterpret_cast<unsigned*>(c->h_logits)[c->V];
             char what[160];
             if (perr) fprintf(stderr, "llmk: rank %d of %d: a peer's granules never arrived (%s; position %d, serial %d)\n",
                               c->tp_rank, c->tp_size, tp_describe_err(c, perr, what, sizeof(what)), pos, c->h_tokpos[2]);
             return perr ? LLMK_E_TIMEOUT : LLMK_OK;
         }
         if (!c->use_tk) return LLMK_OK;
-        const unsigned err = greedy ? (unsigned)c->h_next[1] : reinterpret_cast<unsigned*>(c->h_logits)[c->V];
+        const unsigned err = tail != TAIL_LOGITS ? (unsigned)c->h_next[1] : reinterpret_cast<unsigned*>(c->h_logits)[c->V];
         if (err == 0) { c->tk_range_run = 0; return LLMK_OK; }
         if (tk_range_only(err) && c->tk_range_run + 1 < TK_RANGE_LIMIT) {
             // THIS position on the multi-kernel path (f32 activations throughout; eager launches: the ctx's graphs hold the token
@@ -741,7 +759,7 @@ int run_token(llmk_ctx* c, int token, int pos, bool greedy) {
             rc = tk_clear_err(c);
             if (rc) return rc;
             c->use_tk = false;
-            const hipError_t e = enqueue_token(c, greedy, false);
+            const hipError_t e = enqueue_token(c, tail, false);
             c->use_tk = true;
             HIPCHK(e);
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -751,6 +769,13 @@ int run_token(llmk_ctx* c, int token, int pos, bool greedy) {
         if (rc) return rc;
     }
     return LLMK_E_TIMEOUT;
+}
+int run_token(llmk_ctx* c, int token, int pos, TailMode tail) {
+    if (tail != TAIL_SAMPLE) return run_token_pass(c, token, pos, tail);
+    c->samp_dev.pad = 1;                     // (the sampling tail copies h_samp to the device: known again once the pass is through)
+    const int rc = run_token_pass(c, token, pos, tail);
+    if (rc == LLMK_OK) c->samp_dev = *c->h_samp;
+    return rc;
 }
 
 // ---- batched prefill (prefill.h) ------------------------------------------------------------------------
@@ -1040,7 +1065,7 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
 
 extern "C" {
 
-int llmk_version(void) { return 100; }
+int llmk_version(void) { return 200; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -1055,7 +1080,7 @@ const char* llmk_strerror(int code) {
         case LLMK_E_TIMEOUT: return "llmk: device-side exchange timed out (persistent kernel not fully resident?)";
         case LLMK_E_COMM: return "llmk: tensor-parallel communicator missing or RCCL error";
         case LLMK_E_VERIFY: return "llmk: uploaded weights did not arrive intact on the device (three attempts)";
-        case LLMK_E_NONFINITE: return "llmk: no finite logit at this position (the greedy pick has no answer)";
+        case LLMK_E_NONFINITE: return "llmk: no finite logit at this position (the greedy or sampled pick has no answer)";
     }
     if (code >= LLMK_E_HIP) return hipGetErrorString((hipError_t)(code - LLMK_E_HIP));
     return "llmk: unknown error";
@@ -1155,8 +1180,9 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(dev_alloc(&c->d_xb, (size_t)E * sizeof(float)));
     CK(dev_alloc(&c->d_hb, (size_t)H * sizeof(float)));
     CK(dev_alloc(&c->d_part, (size_t)E * sizeof(float)));
-    // [V] = sticky device error word; behind it (at V + 4) the two candidate buffers of the pipelined greedy decode
-    CK(dev_alloc(&c->d_logits, ((size_t)V + 4 + 4 * TK_NCU) * sizeof(float)));
+    // [V] = sticky device error word; behind it (at V + 4) the two candidate buffers of the pipelined greedy decode, and behind
+    // those (at V + 4 + 4 * TK_NCU) the sampling parameters (d_sample_params)
+    CK(dev_alloc(&c->d_logits, ((size_t)V + 8 + 4 * TK_NCU) * sizeof(float)));
     CK(dev_alloc(&c->d_rope, (size_t)(hs / 2) * sizeof(float)));
     CK(dev_alloc(&c->d_tokpos, 4 * sizeof(int)));
     CK(dev_alloc(&c->d_next, 2 * sizeof(int)));
@@ -1166,6 +1192,7 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(hipHostGetDevicePointer((void**)&c->h_logits_dev, c->h_logits, 0));
     c->tk_direct = !(getenv("LLMK_TK_DIRECT") && getenv("LLMK_TK_DIRECT")[0] == '0');
     CK(hipHostMalloc(&c->h_next, 2 * sizeof(int), hipHostMallocDefault));
+    CK(hipHostMalloc(&c->h_samp, sizeof(llmk_sample_params), hipHostMallocDefault));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int i = 0; i < 8; ++i) CK(hipEventCreate(&c->ev[i]));
     // The whole-token persistent kernel serves the shapes it is instantiated for, on a full 256-CU part
@@ -1183,7 +1210,7 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
         else CK(pe);
     }
     if (rc == LLMK_OK) {
-        CK(hipMemset(c->d_logits, 0, ((size_t)V + 4 + 4 * TK_NCU) * sizeof(float)));
+        CK(hipMemset(c->d_logits, 0, ((size_t)V + 8 + 4 * TK_NCU) * sizeof(float)));
         c->h_tokpos[0] = 0; c->h_tokpos[1] = 0; c->h_tokpos[2] = 0; c->h_tokpos[3] = 0;
         CK(hipMemset(c->d_kc, 0, kvn * sizeof(float)));  // s%key_cache(:,:,:) = 0   llama2.f90:317
         CK(hipMemset(c->d_vc, 0, kvn * sizeof(float)));
@@ -1501,6 +1528,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
         c->use_tk = false;
         if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
         if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
+        if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     }
     // the persistent kernel again, if one is instantiated for this shape with a classifier of this type (round 6: q6_K rows beside
     // q4_0 matrices -- a stock llama.cpp q4_0 file keeps the fast path); otherwise the multi-kernel path
@@ -1522,6 +1550,7 @@ int llmk_set_rms_eps(llmk_ctx* c, float eps) {
     c->eps = eps;
     if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }   // kernel arguments are baked in
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
+    if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     return LLMK_OK;
 }
 
@@ -1534,7 +1563,7 @@ int llmk_set_rope_freqs(llmk_ctx* c, const float* freqs, int n) {
 
 int llmk_forward(llmk_ctx* c, int token, int pos, float* logits_out) {
     if (!c || !logits_out) return LLMK_E_ARG;
-    int rc = run_token(c, token, pos, false);
+    int rc = run_token(c, token, pos, TAIL_LOGITS);
     if (rc) return rc;
     memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
     return LLMK_OK;
@@ -1554,7 +1583,7 @@ int llmk_prefill(llmk_ctx* c, const int* tokens, int n, int pos0, float* logits_
     const bool batched = c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0 && !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
     if (!batched) {
         for (int i = 0; i < n; ++i) {
-            rc = run_token(c, tokens[i], pos0 + i, false);
+            rc = run_token(c, tokens[i], pos0 + i, TAIL_LOGITS);
             if (rc) return rc;
         }
         memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
@@ -1619,9 +1648,9 @@ int llmk_prefill(llmk_ctx* c, const int* tokens, int n, int pos0, float* logits_
     return LLMK_OK;
 }
 
-int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
-    if (!c || !next_token) return LLMK_E_ARG;
-    int rc = run_token(c, token, pos, true);
+// the id a TAIL_GREEDY / TAIL_SAMPLE pass left in h_next
+int token_out(llmk_ctx* c, int token, int pos, TailMode tail, int* next_token) {
+    int rc = run_token(c, token, pos, tail);
     if (rc) return rc;
     // the device argmax answers 0 ("no token") when no logit is finite (a damaged upload, an overflow): an error, not an id --
     // a host that indexes its vocabulary with it reads out of bounds (advisor, round 4)
@@ -1629,10 +1658,32 @@ int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
     *next_token = *c->h_next;
     return LLMK_OK;
 }
+int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
+    if (!c || !next_token) return LLMK_E_ARG;
+    return token_out(c, token, pos, TAIL_GREEDY, next_token);
+}
 
-// The temperature-0 generation loop of llama2.f90:379-396 for n positions with no host round trip between them.
-int llmk_decode_greedy(llmk_ctx* c, int token, int pos0, int n, int* ids_out, llmk_token_fn on_token, void* user) {
-    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
+// invT = f32(1 / T), rounded once; the pinned words every sampling pass copies to the device (d_sample_params)
+int set_sample_params(llmk_ctx* c, float temperature, uint64_t seed) {
+    if (!(temperature > 0.f) || !isfinite(temperature)) return LLMK_E_ARG;      // (NaN fails the first test)
+    const float invT = 1.0f / temperature;
+    if (!isfinite(invT) || !(invT >= FLT_MIN)) return LLMK_E_ARG;              // 1/T beyond the normal f32 range
+    c->h_samp->invT = invT;
+    c->h_samp->seed_lo = (uint32_t)seed;
+    c->h_samp->seed_hi = (uint32_t)(seed >> 32);
+    c->h_samp->pad = 0;
+    return LLMK_OK;
+}
+int llmk_forward_sample(llmk_ctx* c, int token, int pos, float temperature, uint64_t seed, int* next_token) {
+    if (!c || !next_token) return LLMK_E_ARG;
+    const int rc = set_sample_params(c, temperature, seed);
+    if (rc) return rc;
+    return token_out(c, token, pos, TAIL_SAMPLE, next_token);
+}
+
+// The generation loop of llama2.f90:379-396 for n positions with no host round trip between them: at temperature 0
+// (TAIL_GREEDY, the argmax) or by the sampling rule of sample.h (TAIL_SAMPLE, parameters already in c->h_samp).
+int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_out, llmk_token_fn on_token, void* user) {
     int rc = check_ready(c);
     if (rc) return rc;
     const bool timed = (c->cfg.flags & (LLMK_FLAG_TIMINGS | LLMK_FLAG_NO_GRAPH)) != 0;
@@ -1646,6 +1697,15 @@ int llmk_decode_greedy(llmk_ctx* c, int token, int pos0, int n, int* ids_out, ll
         float2* d_cand = reinterpret_cast<float2*>(c->d_logits + c->V + 4);
         memset(h_ids, 0, (size_t)n * sizeof(int));
         reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
+        // the GR launches score their classifier rows with these parameters (token_kernel.h tk_sample_params); invT = 0 is greedy
+        const llmk_sample_params want = tail == TAIL_SAMPLE ? *c->h_samp : llmk_sample_params{};
+        if (memcmp(&want, &c->samp_dev, sizeof(want)) != 0) {
+            if (tail == TAIL_SAMPLE)
+                HIPCHK(hipMemcpyAsync(d_sample_params(c), c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
+            else
+                HIPCHK(hipMemsetAsync(d_sample_params(c), 0, sizeof(llmk_sample_params), c->stream));
+            c->samp_dev = want;
+        }
         for (int i = 0; i < n; ++i) {
             c->h_tokpos[0] = token - 1;
             c->h_tokpos[1] = pos0 + i;
@@ -1691,13 +1751,24 @@ int llmk_decode_greedy(llmk_ctx* c, int token, int pos0, int n, int* ids_out, ll
         c->tk_short_grid = false;
     }
     for (int i = done; i < n; ++i) {
-        rc = run_token(c, token, pos0 + i, true);
+        rc = run_token(c, token, pos0 + i, tail);
         if (rc) return rc;
         if (*c->h_next < 1 || *c->h_next > c->V) return LLMK_E_NONFINITE;      // (before the callback sees it)
         token = ids_out[i] = *c->h_next;
         if (on_token) on_token(i, token, user);
     }
     return LLMK_OK;
+}
+int llmk_decode_greedy(llmk_ctx* c, int token, int pos0, int n, int* ids_out, llmk_token_fn on_token, void* user) {
+    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
+    return decode_run(c, token, pos0, n, TAIL_GREEDY, ids_out, on_token, user);
+}
+int llmk_decode_sample(llmk_ctx* c, int token, int pos0, int n, float temperature, uint64_t seed, int* ids_out,
+                       llmk_token_fn on_token, void* user) {
+    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
+    const int rc = set_sample_params(c, temperature, seed);
+    if (rc) return rc;
+    return decode_run(c, token, pos0, n, TAIL_SAMPLE, ids_out, on_token, user);
 }
 
 int llmk_reset(llmk_ctx* c) {
@@ -2058,6 +2129,7 @@ int llmk_tp_p2p_disable(llmk_ctx* c) {
     c->p2p = false;
     if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
+    if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     return LLMK_OK;
 }
 
@@ -2196,6 +2268,7 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->d_tp_bad) hipFree(c->d_tp_bad);
     if (c->graph_logits) hipGraphExecDestroy(c->graph_logits);
     if (c->graph_greedy) hipGraphExecDestroy(c->graph_greedy);
+    if (c->graph_sample) hipGraphExecDestroy(c->graph_sample);
     for (int i = 0; i < LLMK_N_TENSORS; ++i) {
         if (c->t[i].data && !c->t[i].alias) hipFree(c->t[i].data);
     }
@@ -2215,6 +2288,7 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->h_tokpos) hipHostFree(c->h_tokpos);
     if (c->h_logits) hipHostFree(c->h_logits);
     if (c->h_next) hipHostFree(c->h_next);
+    if (c->h_samp) hipHostFree(c->h_samp);
     for (int i = 0; i < 8; ++i)
         if (c->ev[i]) hipEventDestroy(c->ev[i]);
     if (c->stream) hipStreamDestroy(c->stream);

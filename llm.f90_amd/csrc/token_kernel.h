@@ -227,6 +227,10 @@ constexpr int TKG_NOSYNC = 32;     // debug build only: do not wait for exchange
 __device__ __forceinline__ float2* tk_cand(const TokenArgs& a, int buf) {
     return reinterpret_cast<float2*>(a.err + 4) + buf * TK_NCU;
 }
+// behind the two candidate buffers: the sampling parameters of the pipelined decode (invT == 0: greedy, llmk_decode_greedy)
+__device__ __forceinline__ const llmk_sample_params* tk_sample_params(const TokenArgs& a) {
+    return reinterpret_cast<const llmk_sample_params*>(a.err + 4 + 4 * TK_NCU);
+}
 // first-maximum-wins fold of {value, index-as-float-bits} pairs over a wave; every lane ends with the winner
 __device__ __forceinline__ void tk_wave_argmax(float& v, int& i) {
 #pragma unroll
@@ -1751,9 +1755,22 @@ __device__ __forceinline__ void tk_service(const TokenArgs& a, char* lds, int c,
     if constexpr (GR) {
         float bv = -INFINITY;
         int bi = 0x7fffffff;
-        for (int j = lane; j < cn; j += WAVE) {       // the same quotient as the stored logit; ascending j per lane
-            const float v = logit(j);
-            if (v > bv) { bv = v; bi = c0 + j; }
+        // sampling (llmk_decode_sample): the candidate is the first maximum of the Gumbel-max SCORE of sample.h over the CU's rows
+        // instead of the logit -- the fold of the next launch and cand_resolve_kernel stay as they are.  invT == 0 is greedy.
+        // The parameters are read here, after the layer loop (a flag kept live across it costs registers: see TokenArgs).
+        const llmk_sample_params* sp = tk_sample_params(a);
+        const float invT = sp->invT;
+        if (invT != 0.f) {
+            const uint64_t seed = (uint64_t)sp->seed_lo | ((uint64_t)sp->seed_hi << 32);
+            for (int j = lane; j < cn; j += WAVE) {
+                const float v = llmk_sample_score(logit(j), invT, seed, pos, c0 + j);
+                if (v > bv) { bv = v; bi = c0 + j; }
+            }
+        } else {
+            for (int j = lane; j < cn; j += WAVE) {       // the same quotient as the stored logit; ascending j per lane
+                const float v = logit(j);
+                if (v > bv) { bv = v; bi = c0 + j; }
+            }
         }
         tk_wave_argmax(bv, bi);
         if (lane == 0) tk_cand(a, pos & 1)[c] = make_float2(bv, __int_as_float(bi));

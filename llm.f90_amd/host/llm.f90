@@ -6,7 +6,7 @@
 ! llama2.f90:102-108).  There is no CPU forward pass in this program.
 !
 !   ./llm -m model.gguf [-p prompt] [-n tokens] [-t temperature] [-s tokenizer.bin] [-v]
-!         [--ak] [-d device] [--device-argmax] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
+!         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode]
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
@@ -26,6 +26,7 @@ module arg_parse
      integer :: n
      integer :: device            ! extension: HIP device ordinal
      logical :: device_argmax     ! extension: greedy pick on the GPU (SURVEY.md 8f rank 1)
+     logical :: device_sample     ! extension: temperature sampling on the GPU (-t > 0; the Gumbel-max rule of include/llmk.h)
      logical :: prefill           ! extension: the prompt goes through the model as ONE batched pass (llmk_prefill)
      logical :: stream_load       ! extension: matrices go from the file to the device tensor by tensor (always with --ngpu)
      logical :: timings           ! extension: fill the five "Timings" lines from hipEvent section timers (slow path)
@@ -56,6 +57,7 @@ contains
     a%n = 256
     a%device = 0
     a%device_argmax = .false.
+    a%device_sample = .false.
     a%prefill = .false.
     a%stream_load = .false.
     a%timings = .false.
@@ -85,6 +87,7 @@ contains
        case ("--vx");                a%verbose = .true.; a%verbose_ext = .true.; i = i + 1
        case ("--ak");                a%ak = .true.;            i = i + 1
        case ("--device-argmax");     a%device_argmax = .true.; i = i + 1
+       case ("--device-sample");     a%device_sample = .true.; i = i + 1
        case ("--prefill");           a%prefill = .true.;       i = i + 1
        case ("--stream-load");       a%stream_load = .true.;   i = i + 1
        case ("--timings");           a%timings = .true.;       i = i + 1
@@ -177,6 +180,9 @@ program llm
   integer, allocatable :: hash_tab(:)               ! open-addressing index over vocab (lookup)
   integer :: hash_mask
   real(kind=wp) :: rope_base
+  logical :: dsample                                ! --device-sample in its case: -t > 0 on one GPU
+  integer(c_int64_t) :: dseed                       ! its seed: --seed N, or the clock's
+  integer(c_int) :: dnext
 
   call parse_args(opts)
   lead = opts%tp_rank == 0
@@ -280,11 +286,39 @@ program llm
 
   prompt_tokens = bpe_encode(opts%prompt)
 
+  ! --device-sample: EVERY id after the prompt is drawn on the device (llmk_forward_sample / llmk_decode_sample), the first one
+  ! and the one after a --prefill prompt included, so the transcript is a function of (model, prompt, T, seed) alone
+  dsample = opts%device_sample .and. opts%temperature > 0 .and. opts%ngpu == 1
+  if (dsample) then
+     if (opts%seed >= 0) then
+        dseed = int(opts%seed, c_int64_t)
+     else
+        call system_clock(dseed)
+     end if
+     if (opts%verbose .and. lead) print *, "device sampler seed:", dseed
+  end if
+
   ! ---- generation loop (llama2.f90:376-402) -------------------------------------------------------
   t_start = 0
   token = 2                                          ! BOS: 1-based index of <s>
   pos0 = 1
-  if (opts%prefill .and. size(prompt_tokens) > 0 .and. size(prompt_tokens) < seq_len) then
+  if (dsample .and. opts%prefill .and. size(prompt_tokens) > 0 .and. size(prompt_tokens) < seq_len) then
+     ! positions 1 .. k (BOS, then the first k-1 prompt tokens) in one call; the last prompt token goes through the loop below,
+     ! whose llmk_forward_sample draws the first id on the device
+     k = size(prompt_tokens)
+     allocate(batch(k))
+     batch(1) = 2
+     batch(2:) = int(prompt_tokens(1:k - 1), c_int)
+     t_start = clock_ticks()
+     call llmk_check(llmk_prefill(ctx, batch, int(k, c_int), 1_c_int, logits), "llmk_prefill")
+     if (lead) then
+        do pos = 1, k
+           write (*, fmt="(A)", advance="no") vocab(prompt_tokens(pos))(1:vocab_len(prompt_tokens(pos)))
+        end do
+     end if
+     token = prompt_tokens(k)
+     pos0 = k + 1
+  else if (opts%prefill .and. size(prompt_tokens) > 0 .and. size(prompt_tokens) < seq_len) then
      ! positions 1 .. k+1 of the loop below (BOS, then the k prompt tokens) in one call: same cache, same logits
      ! at position k+1, same text on stdout
      k = size(prompt_tokens)
@@ -314,8 +348,19 @@ program llm
   ! tokens by what follows, so that token is produced, and the clock started, before the pipelined launches are enqueued
   ! (started at the first streamed id instead, several tokens had already completed: the printed rate was slightly high).
   loop_end = seq_len
-  if (opts%device_argmax .and. opts%temperature == 0 .and. opts%ngpu == 1) loop_end = min(seq_len, max(size(prompt_tokens), pos0))
+  ! --device-sample likewise, with llmk_forward_sample / llmk_decode_sample
+  if ((opts%device_argmax .and. opts%temperature == 0 .and. opts%ngpu == 1) .or. dsample) &
+       loop_end = min(seq_len, max(size(prompt_tokens), pos0))
   do pos = pos0, loop_end
+     if (dsample .and. pos > size(prompt_tokens)) then
+        call llmk_check(llmk_forward_sample(ctx, int(token, c_int), int(pos, c_int), real(opts%temperature, c_float), dseed, &
+             dnext), "llmk_forward_sample")
+        next_tok = dnext
+        token = next_tok
+        if (lead) write (*, fmt="(A)", advance="no") vocab(token)(1:vocab_len(token))
+        if (t_start == 0) t_start = clock_ticks()
+        cycle
+     end if
      call llmk_check(llmk_forward(ctx, int(token, c_int), int(pos, c_int), logits), "llmk_forward")
      if (pos <= size(prompt_tokens)) then
         next_tok = prompt_tokens(pos)
@@ -334,8 +379,13 @@ program llm
      ts_vocab = vocab
      ts_len = vocab_len
      ts_print = lead
-     call llmk_check(llmk_decode_greedy(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
-          stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_greedy")
+     if (dsample) then
+        call llmk_check(llmk_decode_sample(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
+             real(opts%temperature, c_float), dseed, stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample")
+     else
+        call llmk_check(llmk_decode_greedy(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
+             stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_greedy")
+     end if
      token = stream_ids(size(stream_ids))
      if (t_start == 0) t_start = ts_first
   end if

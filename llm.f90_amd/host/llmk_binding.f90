@@ -120,6 +120,27 @@ module llmk_binding
        type(c_funptr), value :: on_token
        type(c_ptr), value :: user
      end function
+     ! the sampling twins of the two above (temperature > 0, the Gumbel-max rule of include/llmk.h): the same draw from the
+     ! same logits on every path, keyed by (seed, pos, row)
+     integer(c_int) function llmk_forward_sample(ctx, token, pos, temperature, seed, next_token) bind(C, name="llmk_forward_sample")
+       import :: c_int, c_ptr, c_float, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos
+       real(c_float), value :: temperature
+       integer(c_int64_t), value :: seed
+       integer(c_int), intent(out) :: next_token
+     end function
+     integer(c_int) function llmk_decode_sample(ctx, token, pos0, n, temperature, seed, ids_out, on_token, user) &
+          bind(C, name="llmk_decode_sample")
+       import :: c_int, c_ptr, c_funptr, c_float, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos0, n
+       real(c_float), value :: temperature
+       integer(c_int64_t), value :: seed
+       integer(c_int), intent(out) :: ids_out(*)
+       type(c_funptr), value :: on_token
+       type(c_ptr), value :: user
+     end function
      integer(c_int) function llmk_path(ctx) bind(C, name="llmk_path")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

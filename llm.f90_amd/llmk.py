@@ -24,7 +24,8 @@ FLAG_NO_GRAPH, FLAG_TIMINGS, FLAG_MULTI_KERNEL = 1, 2, 4
 SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_comm", "llmk_tp_p2p_handle", "llmk_tp_p2p_connect",
            "llmk_tp_p2p_connect_local", "llmk_tp_p2p_selftest", "llmk_tp_p2p_stress", "llmk_tp_p2p_disable", "llmk_tp_begin", "llmk_tp_segment",
            "llmk_tp_read_partial", "llmk_tp_write_partial", "llmk_tp_read_logits", "llmk_upload", "llmk_upload_rows",
-           "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy", "llmk_reset", "llmk_timings",
+           "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
+           "llmk_forward_sample", "llmk_decode_sample", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -86,6 +87,9 @@ def lib():
         L.llmk_prefill.argtypes = [vp, C.POINTER(ci), ci, ci, cf]
         L.llmk_forward_greedy.argtypes = [vp, ci, ci, C.POINTER(ci)]
         L.llmk_decode_greedy.argtypes = [vp, ci, ci, ci, C.POINTER(ci), vp, vp]
+        if hasattr(L, "llmk_forward_sample"):     # (absent from an older build selected with LLMK_LIB for an A/B)
+            L.llmk_forward_sample.argtypes = [vp, ci, ci, C.c_float, C.c_uint64, C.POINTER(ci)]
+            L.llmk_decode_sample.argtypes = [vp, ci, ci, ci, C.c_float, C.c_uint64, C.POINTER(ci), vp, vp]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -209,6 +213,20 @@ class Llmk:
         cb = TOKEN_FN(on_token) if on_token else None
         _ck(lib().llmk_decode_greedy(self._h, token, pos0, n, ids.ctypes.data_as(C.POINTER(C.c_int)),
                                      C.cast(cb, C.c_void_p) if cb else None, None))
+        return ids
+
+    def forward_sample(self, token: int, pos: int, temperature: float, seed: int) -> int:
+        """One position; the next token drawn on the device at temperature T > 0 (llmk_forward_sample, the rule of sample.h)."""
+        nxt = C.c_int(0)
+        _ck(lib().llmk_forward_sample(self._h, token, pos, temperature, seed & 0xFFFFFFFFFFFFFFFF, C.byref(nxt)))
+        return nxt.value
+
+    def decode_sample(self, token: int, pos0: int, n: int, temperature: float, seed: int, on_token=None) -> np.ndarray:
+        """n positions from pos0 at temperature T > 0 with the draw on the device (llmk_decode_sample); returns the n ids."""
+        ids = np.zeros(n, np.int32)
+        cb = TOKEN_FN(on_token) if on_token else None
+        _ck(lib().llmk_decode_sample(self._h, token, pos0, n, temperature, seed & 0xFFFFFFFFFFFFFFFF,
+                                     ids.ctypes.data_as(C.POINTER(C.c_int)), C.cast(cb, C.c_void_p) if cb else None, None))
         return ids
 
     def generate(self, n: int, prompt=(), want_logits: bool = True, greedy_on_device: bool = False):
