@@ -70,7 +70,7 @@ extern "C" {
 #define LLMK_E_TIMEOUT 8   /* an in-kernel exchange timed out (GPU shared with other work?)        */
 #define LLMK_E_COMM 9      /* tensor-parallel ctx used before llmk_tp_init_comm, or an RCCL error       */
 #define LLMK_E_VERIFY 10   /* an uploaded block's word sum on the device differed from the host's, three times over      */
-#define LLMK_E_NONFINITE 11 /* llmk_forward_greedy / llmk_decode_greedy: no logit of the position is finite, there is no greedy token  */
+#define LLMK_E_NONFINITE 11 /* llmk_forward_greedy / llmk_decode_greedy / llmk_score: no logit of the position is finite, there is no greedy token  */
 #define LLMK_E_HIP 1000    /* 1000 + hipError_t                                                     */
 
 /* Run-time replacement of the reference's compile-time dims (llama2.f90:102-108) and of
@@ -192,6 +192,23 @@ int llmk_forward(llmk_ctx *ctx, int token, int pos, float *logits_out);
  * f32 instruction from the start. */
 int llmk_prefill(llmk_ctx* ctx, const int* tokens, int n, int pos0, float* logits_out);
 
+/* Scoring: llmk_prefill's pass with the classifier and a log-softmax for EVERY position, on the device (DESIGN.md
+ * section 3h).  tokens, n, pos0: exactly as for llmk_prefill (same checks, same KV-cache rows written, decode may continue
+ * behind it).  With z = the vocab_size logits of position pos0+i:
+ *   logprob_out[i] = z[targets[i]-1] - lse(z),  lse(z) = m + log(sum_j exp(z[j] - m)),  m = max_j z[j],  for targets[i] in
+ *                    [1, vocab_size]; targets[i] == 0 means "no target here" and gives 0.0f; any other value is LLMK_E_ARG
+ *                    before anything runs.  targets may be NULL only if logprob_out is NULL;
+ *   argmax_out[i]  = the 1-based first maximum of z (the rule of llmk_forward_greedy, llama2.f90:388);
+ *   logits_out[i*vocab_size .. (i+1)*vocab_size) = z.
+ * Each of the three outputs may be NULL (what is not asked for is not copied); all three NULL is LLMK_E_ARG.  A position none of
+ * whose logits is finite: LLMK_E_NONFINITE (on any error the contents of the outputs are unspecified).  All arithmetic is f32 in a fixed reduction order (llm.f90_amd/csrc/score.h): two
+ * calls with the same input on the same context return bit-identical outputs, whichever outputs are asked for.  Contexts that
+ * take llmk_prefill's batched path run the classifier as a GEMM over each batch of 128 positions (a q6_K classifier: the decode
+ * classifier per position); the others -- and a vocab_size that is not a multiple of 4 (said once on stderr) -- go token by token inside.  The logits are within the parity bar of llmk_forward's, not
+ * bit-identical to them. */
+int llmk_score(llmk_ctx *ctx, const int *tokens, int n, int pos0, const int *targets, float *logprob_out, int *argmax_out,
+               float *logits_out);
+
 /* Same pass, but the temperature-0 consumer (`token = maxloc(logits,DIM=1)`, llama2.f90:388) runs
  * on the device: returns the 1-based argmax (first maximum wins) and skips the logits copy.
  * SURVEY.md section 8(f) rank 1. */
@@ -241,10 +258,12 @@ int llmk_timings(llmk_ctx *ctx, float ms[5]);
  * 5 classifier (successive launches walk the layers), 6 the persistent whole-token kernel
  * (LLMK_E_ARG when the ctx runs the multi-kernel path), 7..10 the w1|w3, wqkv, wo, w2 GEMMs of llmk_prefill at 128 positions
  * (bytes = that matrix of one layer; flop = 2 * 128 * rows * K), 11 the five per-layer kernels of the multi-kernel path (a
- * tensor-parallel rank's too, without its exchanges) for all layers as one hipGraph: milliseconds and bytes per LAYER.
+ * tensor-parallel rank's too, without its exchanges) for all layers as one hipGraph: milliseconds and bytes per LAYER,
+ * 12 the classifier GEMM of llmk_score at 128 positions (all its row chunks, without the scoring epilogue; bytes = wcls;
+ * LLMK_E_ARG for a q6_K classifier, which has no GEMM).
  * STATE: a measurement hook, not part of the generation path.  Kernels 0..6 and 11 run real kernels of the pass at the ctx's
  * current position (position 1 if none was run yet): they overwrite x, that position's K/V rows and the exchange state, kernel 11
- * for every layer; kernels 7..10 overwrite the prefill workspaces.  Call llmk_reset before generating on the ctx again. */
+ * for every layer; kernels 7..10 and 12 overwrite the prefill workspaces.  Call llmk_reset before generating on the ctx again. */
 int llmk_time_kernel(llmk_ctx *ctx, int kernel, int iters, float *avg_ms, double *bytes_per_launch);
 
 /* Debug/verification: copy internal device vectors to the host. which: 0 = x (residual stream, E),

@@ -161,6 +161,18 @@ struct llmk_ctx {
     bool q16_dirty = true;
     bool pf_hm = false;                    // GEMMs on v_mfma_f32_16x16x32_f16, activations (and f32 / q4_0 weights) as two f16 pieces (prefill.h)
     unsigned* pf_flag = nullptr;           // device word: an activation did not fit f16 (the call is redone on the f32 instruction)
+    size_t pf_pcap = 0;                    // floats in each lane's partial-tile workspace P
+    // llmk_score (prefill.h pf_score_kernel), allocated by the first scoring call: per lane the positions' partial results and target
+    // logits (and, for a q6_K classifier, a batch of logits rows); the call's targets and results; the logits of a call that asks for them
+    float4* sc_part[2] = {nullptr, nullptr};
+    float* sc_tgt[2] = {nullptr, nullptr};
+    float* sc_z[2] = {nullptr, nullptr};
+    int* sc_targets = nullptr;             // [S] 0-based, < 0: none
+    float* sc_out = nullptr;               // [2S]: a call's n log-probs, then its n argmax ids
+    float* h_sc = nullptr;                 // pinned image of sc_out
+    float* sc_logits = nullptr;            // [sc_logits_cap][V]
+    size_t sc_logits_cap = 0;
+    bool sc_ready = false;
 };
 typedef llmk_ctx::PfLane PfLane;
 
@@ -792,7 +804,9 @@ int run_token(llmk_ctx* c, int token, int pos, TailMode tail) {
 #define LLMK_PF_HQ_STEP2 1.92
 #endif
 struct PfPlan { int nr, nk, total, U, grid; };
-PfPlan pf_plan(const llmk_ctx* c, int rows, int K, int T = PF_TMAX) {
+// wt: the matrix's own type where it differs from the context's (the classifier: llmk_set_tensor_type), -1 = the context's
+PfPlan pf_plan(const llmk_ctx* c, int rows, int K, int T = PF_TMAX, int wt = -1) {
+    if (wt < 0) wt = c->cfg.weight_type;
     // ONE workgroup per CU (pinned by the LDS request), one or two 16-row groups per wave.  Step times measured at 128
     // positions (tests/host_tools/pf_trace.py, profiles/README.md round 2): 2.45 us with one row group, 4.25 us with two;
     // ~4 us until the first weights arrive; every partial tile is written once and read once by the epilogue.  Also
@@ -804,8 +818,8 @@ PfPlan pf_plan(const llmk_ctx* c, int rows, int K, int T = PF_TMAX) {
     static const double step_f32[2] = {2.45, 4.25}, step_h[2] = {LLMK_PF_H_STEP1, LLMK_PF_H_STEP2}, step_hq[2] = {LLMK_PF_HQ_STEP1, LLMK_PF_HQ_STEP2};
     // (f32 weights: three instructions per chunk, as q4_0; q4_0 at whole batches: the two-group strip runs on eight waves, pf_gemm_launch)
     static const double step_q8[2] = {LLMK_PF_HQ_STEP1, LLMK_PF_HQ_STEP2 * 0.925};
-    const double* step_us = !c->pf_hm ? step_f32 : c->cfg.weight_type == LLMK_TYPE_F16 ? step_h
-                            : (c->cfg.weight_type == LLMK_TYPE_Q4_0 && (T + 15) / 16 == 8) ? step_q8 : step_hq;
+    const double* step_us = !c->pf_hm ? step_f32 : wt == LLMK_TYPE_F16 ? step_h
+                            : (wt == LLMK_TYPE_Q4_0 && (T + 15) / 16 == 8) ? step_q8 : step_hq;
     PfPlan best{};
     double best_t = 1e30;
     for (int nr = 1; nr <= 2; ++nr) {
@@ -859,6 +873,7 @@ int pf_setup_inner(llmk_ctx* c) {
     const int Ks[4] = {c->E, c->E, c->E, c->H};
     for (int i = 0; i < 4; ++i)
         for (int t : {(int)PF_TMAX, 96}) pcap = std::max(pcap, (size_t)pf_max_slots(pf_plan(c, rows[i], Ks[i], t)) * T * rows[i]);   // (the plan may depend on the batch length)
+    c->pf_pcap = pcap;
     HIPCHK(pf_prepare(c));
     for (int i = 0; i < 2; ++i) {
         PfLane& w = c->pf[i];
@@ -932,12 +947,15 @@ hipError_t pf_gemm_prepare() {
     HIPRET((pf_gemm_prepare_one<7, WT>()));
     return pf_gemm_prepare_one<8, WT>();
 }
-hipError_t pf_prepare(const llmk_ctx* c) {
-    switch (c->cfg.weight_type) {
-        case LLMK_TYPE_Q4_0: HIPRET(pf_gemm_prepare<WT_Q4_0>()); HIPRET(pf_gemm_h_prepare<WT_Q4_0>()); break;
-        case LLMK_TYPE_F16: HIPRET(pf_gemm_prepare<WT_F16>()); HIPRET(pf_gemm_h_prepare<WT_F16>()); break;
-        default: HIPRET(pf_gemm_prepare<WT_F32>()); HIPRET(pf_gemm_h_prepare<WT_F32>()); break;
+hipError_t pf_prepare_type(int wt) {
+    switch (wt) {
+        case LLMK_TYPE_Q4_0: HIPRET(pf_gemm_prepare<WT_Q4_0>()); return pf_gemm_h_prepare<WT_Q4_0>();
+        case LLMK_TYPE_F16: HIPRET(pf_gemm_prepare<WT_F16>()); return pf_gemm_h_prepare<WT_F16>();
+        default: HIPRET(pf_gemm_prepare<WT_F32>()); return pf_gemm_h_prepare<WT_F32>();
     }
+}
+hipError_t pf_prepare(const llmk_ctx* c) {
+    HIPRET(pf_prepare_type(c->cfg.weight_type));
     const int smem = (int)pf_attn_smem(c->hs);
     switch (c->hs) {
         case 16: return hipFuncSetAttribute((const void*)pf_attn_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -948,7 +966,7 @@ hipError_t pf_prepare(const llmk_ctx* c) {
     return hipErrorInvalidValue;
 }
 template <int NG, int NR>
-hipError_t pf_gemm_launch(llmk_ctx* c, const PfLane& w, const PfGemmArgs& a, const PfPlan& p) {
+hipError_t pf_gemm_launch(llmk_ctx* c, const PfLane& w, const PfGemmArgs& a, const PfPlan& p, int wt) {
     constexpr size_t smem = pf_gemm_smem<NG, NR>();
     const dim3 grid(p.grid), block(PF_WAVES * WAVE);
     if (c->pf_hm) {
@@ -957,23 +975,24 @@ hipError_t pf_gemm_launch(llmk_ctx* c, const PfLane& w, const PfGemmArgs& a, con
             // q4_0, whole batches: the same 128-row strips on EIGHT waves of one row group each -- two waves per SIMD, one wave's nibble
             // arithmetic under the other's matrix instructions (round 5, profiles/r05_prefill_eight_waves.txt: w1|w3 GEMM 33.0 -> 30.9 us on
             // TinyLlama q4_0, 96.2 -> 88.8 at 7B; f16 and f32 weights, which have no such arithmetic, lose 4-6 % to the doubled LDS reads)
-            if (c->cfg.weight_type == LLMK_TYPE_Q4_0) {
+            if (wt == LLMK_TYPE_Q4_0) {
                 hipLaunchKernelGGL((pf_gemm_h_kernel<8, 1, WT_Q4_0, 8>), grid, dim3(8 * WAVE), smem_h, w.stream, a, c->pf_flag, w.lowcnt);
                 return hipGetLastError();
             }
         }
-        if (c->cfg.weight_type == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q4_0>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
-        else if (c->cfg.weight_type == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F16>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
+        if (wt == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q4_0>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
+        else if (wt == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F16>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
         else hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F32>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
         return hipGetLastError();
     }
-    if (c->cfg.weight_type == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_Q4_0, NR>), grid, block, smem, w.stream, a);
-    else if (c->cfg.weight_type == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_F16, NR>), grid, block, smem, w.stream, a);
+    if (wt == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_Q4_0, NR>), grid, block, smem, w.stream, a);
+    else if (wt == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_F16, NR>), grid, block, smem, w.stream, a);
     else hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_F32, NR>), grid, block, smem, w.stream, a);
     return hipGetLastError();
 }
-hipError_t pf_gemm(llmk_ctx* c, const PfLane& w, const void* W, int row_stride, const float* X, int rows, int K, int T, PfEpiArgs* e) {
-    const PfPlan p = pf_plan(c, rows, K, T);
+hipError_t pf_gemm(llmk_ctx* c, const PfLane& w, const void* W, int row_stride, const float* X, int rows, int K, int T, PfEpiArgs* e, int wt = -1) {
+    if (wt < 0) wt = c->cfg.weight_type;
+    const PfPlan p = pf_plan(c, rows, K, T, wt);
     PfGemmArgs a;
     a.W = W; a.X = X; a.P = w.P; a.rows = rows; a.K = K; a.T = T; a.RS = row_stride;
     a.nk = p.nk; a.U = p.U; a.total = p.total;
@@ -983,16 +1002,128 @@ hipError_t pf_gemm(llmk_ctx* c, const PfLane& w, const void* W, int row_stride, 
     e->U = p.U; e->nk = p.nk; e->sh = p.nr == 2 ? 7 : 6;
     e->lowcnt = c->pf_hm ? w.lowcnt : nullptr; e->flag = c->pf_flag; e->gemm_blocks = p.grid;
 #define PF_CASE(NG_)                                                                         \
-    case NG_: return p.nr == 2 ? pf_gemm_launch<NG_, 2>(c, w, a, p) : pf_gemm_launch<NG_, 1>(c, w, a, p)
+    case NG_: return p.nr == 2 ? pf_gemm_launch<NG_, 2>(c, w, a, p, wt) : pf_gemm_launch<NG_, 1>(c, w, a, p, wt)
     switch ((T + 15) / 16) {
         PF_CASE(1); PF_CASE(2); PF_CASE(3); PF_CASE(4); PF_CASE(5); PF_CASE(6); PF_CASE(7);
-        default: return p.nr == 2 ? pf_gemm_launch<8, 2>(c, w, a, p) : pf_gemm_launch<8, 1>(c, w, a, p);
+        default: return p.nr == 2 ? pf_gemm_launch<8, 2>(c, w, a, p, wt) : pf_gemm_launch<8, 1>(c, w, a, p, wt);
     }
 #undef PF_CASE
 }
+// ---- llmk_score: classifier + log-softmax for every position of a batch (prefill.h pf_score_kernel) ----
+// What a scoring call asks of its batches: the call's targets are in sc_targets, its results go to sc_out (log-probs, then ids)
+struct ScPlan { int R, nchunks, nparts; };
+struct ScoreJob {
+    bool want_lp, want_logits;
+    int n;                   // positions of the call
+    ScPlan sp;               // the classifier's row chunks: sc_plan, once per call (it depends on the context and its matrix instruction only)
+};
+// The classifier GEMM runs in chunks of R rows (a multiple of 128, or all V rows) whose partial tiles fit the workspace the layers'
+// GEMMs already have: V is 2.8x the largest row count that one is sized for (2H; Llama-3: 9x), and a context that scores allocates
+// no partial-tile workspace beyond what a prefill needs.  R = 0: no chunk fits (or V is not whole 4-row vectors): the call
+// goes token by token.
+ScPlan sc_plan(const llmk_ctx* c) {
+    const int V = c->V, wt = c->t[LLMK_WCLS].type;
+    ScPlan sp{0, 0, (V + PF_SC_ROWS - 1) / PF_SC_ROWS};
+    if (wt == LLMK_TYPE_Q6_K) return sp;         // (no GEMM: the decode classifier per position, one chunk of partials)
+    if (V % 4) return sp;
+    auto need = [&](int rows) {
+        size_t m = 0;
+        for (int t : {(int)PF_TMAX, 96}) m = std::max(m, (size_t)pf_max_slots(pf_plan(c, rows, c->E, t, wt)) * PF_TMAX * rows);
+        return m;
+    };
+    for (int nch = 1; nch <= V / 128 + 1; ++nch) {
+        int R = ((V + nch - 1) / nch + 127) / 128 * 128;
+        if (R >= V) R = V;
+        const int n = (V + R - 1) / R, lastr = V - (n - 1) * R;
+        if (need(R) <= c->pf_pcap && need(lastr) <= c->pf_pcap) {
+            sp.R = R; sp.nchunks = n;
+            sp.nparts = (n - 1) * ((R + PF_SC_ROWS - 1) / PF_SC_ROWS) + (lastr + PF_SC_ROWS - 1) / PF_SC_ROWS;
+            return sp;
+        }
+        if (R == V && V <= 128) break;
+    }
+    return sp;
+}
+void sc_teardown(llmk_ctx* c) {
+    for (int i = 0; i < 2; ++i) {
+        if (c->sc_part[i]) { hipFree(c->sc_part[i]); c->sc_part[i] = nullptr; }
+        if (c->sc_tgt[i]) { hipFree(c->sc_tgt[i]); c->sc_tgt[i] = nullptr; }
+        if (c->sc_z[i]) { hipFree(c->sc_z[i]); c->sc_z[i] = nullptr; }
+    }
+    if (c->sc_targets) { hipFree(c->sc_targets); c->sc_targets = nullptr; }
+    if (c->sc_out) { hipFree(c->sc_out); c->sc_out = nullptr; }
+    if (c->h_sc) { hipHostFree(c->h_sc); c->h_sc = nullptr; }
+    if (c->sc_logits) { hipFree(c->sc_logits); c->sc_logits = nullptr; }
+    c->sc_logits_cap = 0;
+    c->sc_ready = false;
+}
+int sc_setup_inner(llmk_ctx* c) {
+    // partial slots per position: at most one more than V / PF_SC_ROWS per chunk, and a chunk has at least 128 rows
+    const size_t slots = (size_t)(c->V + PF_SC_ROWS - 1) / PF_SC_ROWS + (size_t)c->V / 128 + 2;
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(dev_alloc(&c->sc_part[i], (size_t)PF_TMAX * slots * sizeof(float4)));
+        HIPCHK(dev_alloc(&c->sc_tgt[i], (size_t)PF_TMAX * sizeof(float)));
+    }
+    HIPCHK(dev_alloc(&c->sc_targets, (size_t)c->S * sizeof(int)));
+    HIPCHK(dev_alloc(&c->sc_out, (size_t)2 * c->S * sizeof(float)));
+    HIPCHK(hipHostMalloc(&c->h_sc, (size_t)2 * c->S * sizeof(float), hipHostMallocDefault));
+    if (c->t[LLMK_WCLS].type == LLMK_TYPE_Q6_K)
+        for (int i = 0; i < 2; ++i) HIPCHK(dev_alloc(&c->sc_z[i], (size_t)PF_TMAX * c->V * sizeof(float)));
+    return LLMK_OK;
+}
+int sc_setup(llmk_ctx* c) {
+    if (c->sc_ready) return LLMK_OK;
+    const int rc = sc_setup_inner(c);
+    if (rc) { sc_teardown(c); return rc; }
+    c->sc_ready = true;
+    return LLMK_OK;
+}
+// the merge of a batch's partials: log-probs and ids of positions i0 .. i0+T-1 of the call
+hipError_t sc_merge(llmk_ctx* c, int lane, hipStream_t st, const ScoreJob& sj, int nparts, int T, int i0) {
+    hipLaunchKernelGGL(pf_score_merge_kernel, dim3(T), dim3(64), 0, st, c->sc_part[lane], nparts, sj.want_lp ? c->sc_targets + i0 : nullptr,
+                       c->sc_tgt[lane], c->sc_out + i0, reinterpret_cast<int*>(c->sc_out + sj.n) + i0);
+    return hipGetLastError();
+}
+// after the last layer of a batch (w.Xs = x * final gains, w.xn: pf_epi_resid_norm_kernel): positions i0 .. i0+T-1 of the call
+hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const ScoreJob& sj, int T, int i0) {
+    const DevTensor& ct = c->t[LLMK_WCLS];
+    const int V = c->V, E = c->E;
+    const ScPlan& sp = sj.sp;
+    PfScoreArgs s;
+    memset(&s, 0, sizeof(s));
+    s.zp = (size_t)V; s.V = V; s.nparts = sp.nparts; s.part = c->sc_part[lane];
+    s.targets = sj.want_lp ? c->sc_targets + i0 : nullptr; s.tgt = c->sc_tgt[lane];
+    if (ct.type == LLMK_TYPE_Q6_K) {
+        // no batched q6_K GEMM: the decode classifier (final rmsnorm inside, q6k.h) on each of the batch's rows
+        float* Z = sj.want_logits ? c->sc_logits + (size_t)i0 * V : c->sc_z[lane];
+        const size_t smem = 16 + (size_t)E * sizeof(float);
+        const int blocks = (V + GEMV_WAVES * Q6K_RPW - 1) / (GEMV_WAVES * Q6K_RPW);
+        for (int t = 0; t < T; ++t) {
+            const GemvArgs a = base_args(c, LLMK_WCLS, 0, w.X + (size_t)t * E, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, Z + (size_t)t * V);
+            hipLaunchKernelGGL((gemv_q6k_kernel<true>), dim3(blocks), dim3(GEMV_THREADS), smem, w.stream, a);
+        }
+        HIPRET(hipGetLastError());
+        s.Z = Z;
+        hipLaunchKernelGGL((pf_score_kernel<false>), dim3(sp.nparts, T), dim3(256), 0, w.stream, e, s);
+        HIPRET(hipGetLastError());
+        return sc_merge(c, lane, w.stream, sj, sp.nparts, T, i0);
+    }
+    for (int k = 0; k < sp.nchunks; ++k) {
+        const int r0 = k * sp.R, rows = std::min(sp.R, V - r0);
+        HIPRET(pf_gemm(c, w, (const char*)ct.data + (size_t)r0 * ct.row_bytes, (int)ct.row_bytes, w.Xs, rows, E, T, &e, ct.type));
+        e.rows = rows; e.out = nullptr;
+        s.r0 = r0; s.part0 = k * ((sp.R + PF_SC_ROWS - 1) / PF_SC_ROWS);
+        s.zout = sj.want_logits ? c->sc_logits + (size_t)i0 * V + r0 : nullptr;
+        hipLaunchKernelGGL((pf_score_kernel<true>), dim3((rows + PF_SC_ROWS - 1) / PF_SC_ROWS, T), dim3(256), 0, w.stream, e, s);
+        HIPRET(hipGetLastError());
+    }
+    return sc_merge(c, lane, w.stream, sj, sp.nparts, T, i0);
+}
+
 // one batch of T <= PF_TMAX prompt positions pos0 .. pos0+T-1 (1-based) through all layers; X[T-1] ends up in d_x
 // `prev`: the lane of the batch before this one (null for the first batch of a call); `last`: this batch ends the prompt
-hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, int T, int pos0, bool last) {
+// `sj` (llmk_score): the final rmsnorm, the classifier and the log-softmax of all T positions follow; i0 = the batch's first position in the call
+hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, int T, int pos0, bool last, const ScoreJob* sj = nullptr, int i0 = 0) {
     const int E = c->E, H = c->H, KV = c->KV, QKV = E + 2 * KV, Tp = (T + 15) / 16 * 16;
     const float* emb = (const float*)c->t[LLMK_TOKEN_EMBEDDING_TABLE].data;
     hipLaunchKernelGGL(pf_embed_kernel, dim3((E + 255) / 256, T), dim3(256), 0, w.stream, emb, tok, w.X, E);
@@ -1053,10 +1184,12 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
         HIPRET(gemm(LLMK_W2, E, w.HB, H));
         e.rows = E; e.out = w.X;
         hipLaunchKernelGGL(pf_epi_resid_norm_kernel, dim3(T), dim3(1024), 0, w.stream, e,
-                           l + 1 < c->L ? (const float*)c->t[LLMK_RMS_ATT_WEIGHT].data + (size_t)(l + 1) * E : nullptr, w.Xs,
+                           l + 1 < c->L ? (const float*)c->t[LLMK_RMS_ATT_WEIGHT].data + (size_t)(l + 1) * E
+                           : sj ? (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data : nullptr, w.Xs,      // (scoring: the FINAL rmsnorm of every row)
                            w.xn, c->eps);
         HIPRET(hipGetLastError());
     }
+    if (sj) HIPRET(sc_batch(c, w, &w == &c->pf[1] ? 1 : 0, e, *sj, T, i0));
     if (last) HIPRET(hipMemcpyAsync(c->d_x, w.X + (size_t)(T - 1) * E, (size_t)E * sizeof(float), hipMemcpyDeviceToDevice, w.stream));
     return hipEventRecord(w.done, w.stream);
 }
@@ -1065,7 +1198,7 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
 
 extern "C" {
 
-int llmk_version(void) { return 200; }
+int llmk_version(void) { return 300; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -1569,6 +1702,27 @@ int llmk_forward(llmk_ctx* c, int token, int pos, float* logits_out) {
     return LLMK_OK;
 }
 
+// The f16-range flag of a batched call (prefill.h pf_gemm_h_kernel, pf_low_check) came back raised.
+// bit 0: an activation of this prompt does not fit an f16 (|x| >= 65504, or not finite): this context's GEMMs go back to
+// the f32 matrix instruction for good.  Bit 1 alone: a position whose whole row is below 2^-7 (the lo piece of the split
+// is an f16 subnormal there): THIS call is redone on the f32 instruction, the next one tries the f16 one again (advisor,
+// round 4: a BOS or early-layer row with genuinely small values must not cost the context the fast path).
+// Either way the caller redoes the call (the K/V rows it wrote are rewritten) and the first event says so once.
+static int pf_redo_setup(llmk_ctx* c, unsigned flag, const char* who, bool* told, bool* for_good_out) {
+    const bool for_good = (flag & 1u) != 0;
+    if (!*told) {
+        *told = true;
+        fprintf(stderr, "llmk: %s met %s; %s\n", who, for_good ? "an activation beyond the f16 range" : "a position whose activations are all below 2^-7",
+                for_good ? "this context's prompt GEMMs run on the f32 matrix instruction from now on" : "this call is redone on the f32 matrix instruction");
+    }
+    HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    pf_teardown(c);
+    c->pf_hm = false;
+    *for_good_out = for_good;
+    return pf_setup(c);
+}
+
 // The prompt loop of llama2.f90:376-402 as ONE call: tokens[0..n) (1-based ids) sit at positions pos0 .. pos0+n-1,
 // the KV cache rows of those positions are written, and logits_out receives the logits of the LAST position --
 // exactly what n llmk_forward calls leave behind.  f32 single-GPU contexts run the batched MFMA path (prefill.h);
@@ -1622,29 +1776,125 @@ int llmk_prefill(llmk_ctx* c, const int* tokens, int n, int pos0, float* logits_
     if (c->pf_hm) HIPCHK(hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->pf_hm && *h_flag) {
-        // bit 0: an activation of this prompt does not fit an f16 (|x| >= 65504, or not finite): this context's GEMMs go back to
-        // the f32 matrix instruction for good.  Bit 1 alone: a position whose whole row is below 2^-7 (the lo piece of the split
-        // is an f16 subnormal there): THIS call is redone on the f32 instruction, the next one tries the f16 one again (advisor,
-        // round 4: a BOS or early-layer row with genuinely small values must not cost the context the fast path).
-        // Either way the call is redone (the K/V rows it wrote are rewritten) and the first event says so once.
-        const bool for_good = (*h_flag & 1u) != 0;
-        static bool told = false;
-        if (!told) {
-            told = true;
-            fprintf(stderr, "llmk: llmk_prefill met %s; %s\n", for_good ? "an activation beyond the f16 range" : "a position whose activations are all below 2^-7",
-                    for_good ? "this context's prompt GEMMs run on the f32 matrix instruction from now on" : "this call is redone on the f32 matrix instruction");
-        }
-        HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        pf_teardown(c);
-        c->pf_hm = false;
-        rc = pf_setup(c);
+        bool for_good;
+        static bool told = false;           // (each entry point reports its own first event)
+        rc = pf_redo_setup(c, *h_flag, "llmk_prefill", &told, &for_good);
         if (rc) return rc;
         rc = llmk_prefill(c, tokens, n, pos0, logits_out);
         if (!for_good) pf_teardown(c);          // (pf_ready = false: the next call sets the f16 instruction up again)
         return rc;
     }
     memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
+    return LLMK_OK;
+}
+
+// llmk_prefill's pass with the classifier and a log-softmax for EVERY position: per position the
+// log-probability of a given target, the first maximum's id and, when asked for, the logits.  Same argument checks, same KV rows,
+// decode may continue behind it.
+int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targets, float* logprob_out, int* argmax_out, float* logits_out) {
+    if (!c || !tokens || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
+    if ((!logprob_out && !argmax_out && !logits_out) || (logprob_out && !targets)) return LLMK_E_ARG;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i)
+        if (tokens[i] < 1 || tokens[i] > c->V || (targets && (targets[i] < 0 || targets[i] > c->V))) return LLMK_E_ARG;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    rc = sc_setup(c);
+    if (rc) return rc;
+    const int V = c->V, pf_step = PF_KSTEP;
+    ScoreJob sj{logprob_out != nullptr, logits_out != nullptr, n, ScPlan{0, 0, 0}};
+    bool batched = c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0 && !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
+    if (batched) {
+        rc = pf_setup(c, true);
+        if (rc) return rc;
+        const int ct = c->t[LLMK_WCLS].type;
+        if (ct != LLMK_TYPE_Q6_K) {
+            if (ct != c->cfg.weight_type) HIPCHK(pf_prepare_type(ct));      // the classifier's own GEMM kernels: dynamic-LDS limits
+        }
+        sj.sp = sc_plan(c);
+        if (ct != LLMK_TYPE_Q6_K && sj.sp.R == 0) {
+            batched = false;
+            static bool told_slow = false;          // (a call some 30x slower than its neighbours must not be silent)
+            if (!told_slow) {
+                told_slow = true;
+                fprintf(stderr, "llmk: llmk_score runs token by token on this context: %s\n",
+                        V % 4 ? "vocab_size is not a multiple of 4 (the classifier GEMM's partial tiles are read as 4-row vectors)"
+                              : "no 128-row chunk of the classifier fits the prefill's partial-tile workspace");
+            }
+        }
+    }
+    if (batched && sj.want_logits && c->sc_logits_cap < (size_t)n) {
+        if (c->sc_logits) { hipFree(c->sc_logits); c->sc_logits = nullptr; c->sc_logits_cap = 0; }
+        HIPCHK(dev_alloc(&c->sc_logits, (size_t)n * V * sizeof(float)));
+        c->sc_logits_cap = (size_t)n;
+    }
+    std::vector<int> tg0;
+    if (sj.want_lp) {
+        tg0.assign(targets, targets + n);
+        for (int& t : tg0) --t;                                  // 0-based; -1 = no target here
+        HIPCHK(hipMemcpyAsync(c->sc_targets, tg0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    }
+    unsigned* h_flag = reinterpret_cast<unsigned*>(c->h_logits + V + 1);
+    *h_flag = 0;
+    std::vector<int> tok0;
+    if (!batched) {
+        // tensor-parallel ranks, shapes off the 64-column step, LLMK_PREFILL=0: token by token; the pass leaves the position's logits in
+        // the pinned vector (as for llmk_forward), one workgroup row of pf_score_kernel reads them from there
+        const int np = (V + PF_SC_ROWS - 1) / PF_SC_ROWS;
+        PfEpiArgs e;
+        memset(&e, 0, sizeof(e));
+        for (int i = 0; i < n; ++i) {
+            rc = run_token(c, tokens[i], pos0 + i, TAIL_LOGITS);
+            if (rc) return rc;
+            if (logits_out) memcpy(logits_out + (size_t)i * V, c->h_logits, (size_t)V * sizeof(float));
+            PfScoreArgs s;
+            memset(&s, 0, sizeof(s));
+            s.Z = c->h_logits_dev; s.zp = (size_t)V; s.V = V; s.nparts = np; s.part = c->sc_part[0];
+            s.targets = sj.want_lp ? c->sc_targets + i : nullptr; s.tgt = c->sc_tgt[0];
+            hipLaunchKernelGGL((pf_score_kernel<false>), dim3(np, 1), dim3(256), 0, c->stream, e, s);
+            HIPCHK(hipGetLastError());
+            HIPCHK(sc_merge(c, 0, c->stream, sj, np, 1, i));
+            HIPCHK(hipStreamSynchronize(c->stream));             // (the next pass overwrites the pinned vector)
+        }
+    } else {
+        tok0.assign(tokens, tokens + n);
+        for (int& t : tok0) --t;
+        HIPCHK(hipMemcpyAsync(c->pf_tok, tok0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        if (c->d_gran && c->tk_ngran)        // (as llmk_prefill: the q4_0 persistent kernel's scale records of these positions)
+            HIPCHK(hipMemsetAsync(c->d_gran + c->tk_ngran - 4 * TK_QSC_LMAX, 0, 4 * TK_QSC_LMAX * sizeof(unsigned long long), c->stream));
+        HIPCHK(hipEventRecord(c->pf_start, c->stream));
+        HIPCHK(hipStreamWaitEvent(c->pf[1].stream, c->pf_start, 0));
+        int k = 0;
+        for (int i = 0; i < n; i += PF_TMAX, ++k) {
+            const bool last = i + PF_TMAX >= n;
+            const hipError_t pe = pf_batch(c, c->pf[k & 1], k > 0 ? &c->pf[(k - 1) & 1] : nullptr, c->pf_tok + i, std::min(PF_TMAX, n - i), pos0 + i, last, &sj, i);
+            if (pe != hipSuccess) {
+                hipStreamSynchronize(c->pf[1].stream);
+                hipStreamSynchronize(c->stream);
+                return LLMK_E_HIP + (int)pe;
+            }
+        }
+        if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->pf[1].done, 0));
+        if (c->pf_hm) HIPCHK(hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    }
+    // the results: one copy, n floats and n ints
+    HIPCHK(hipMemcpyAsync(c->h_sc, c->sc_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (batched && c->pf_hm && *h_flag) {
+        bool for_good;
+        static bool told = false;
+        rc = pf_redo_setup(c, *h_flag, "llmk_score", &told, &for_good);
+        if (rc) return rc;
+        rc = llmk_score(c, tokens, n, pos0, targets, logprob_out, argmax_out, logits_out);
+        if (!for_good) pf_teardown(c);
+        return rc;
+    }
+    const int* ids = reinterpret_cast<const int*>(c->h_sc + n);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 1 || ids[i] > V) return LLMK_E_NONFINITE;      // no logit of the position is finite (pf_score_merge_kernel answers id 0)
+    if (logprob_out) memcpy(logprob_out, c->h_sc, (size_t)n * sizeof(float));
+    if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
+    if (batched && logits_out) HIPCHK(hipMemcpy(logits_out, c->sc_logits, (size_t)n * V * sizeof(float), hipMemcpyDeviceToHost));
     return LLMK_OK;
 }
 
@@ -1796,7 +2046,7 @@ int llmk_timings(llmk_ctx* c, float ms[5]) {
 int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* bytes_per_launch) {
     int rc = check_ready(c);
     if (rc) return rc;
-    if (kernel < 0 || kernel > 11 || iters <= 0 || !avg_ms) return LLMK_E_ARG;
+    if (kernel < 0 || kernel > 12 || iters <= 0 || !avg_ms) return LLMK_E_ARG;
     if (kernel == 6 && !c->use_tk) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     if (kernel == 11) {
@@ -1838,11 +2088,19 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
         }
         return LLMK_OK;
     }
+    ScPlan sp{0, 0, 0};
     if (kernel >= 7) {   // the prefill GEMMs at PF_TMAX positions: 7 w1|w3, 8 wqkv, 9 wo, 10 w2 (whatever the workspaces hold: timing only)
         const int pf_step = PF_KSTEP;
         if (c->tp_size != 1 || c->E % pf_step || c->H % pf_step) return LLMK_E_ARG;
         rc = pf_setup(c, true);
         if (rc) return rc;
+        if (kernel == 12) {   // llmk_score's classifier GEMM: all its row chunks, without the scoring epilogue (a q6_K classifier has no GEMM)
+            const int ct = c->t[LLMK_WCLS].type;
+            if (ct == LLMK_TYPE_Q6_K) return LLMK_E_ARG;
+            if (ct != c->cfg.weight_type) HIPCHK(pf_prepare_type(ct));
+            sp = sc_plan(c);
+            if (sp.R == 0) return LLMK_E_ARG;
+        }
         // activations of ordinary size (every float 0x3c3c3c3c = 0.0115): an all-zero workspace would make every workgroup of the f16-instruction
         // GEMM cast its low-end votes (prefill.h pf_low_check: 32k atomics per launch, +16 us) -- a path real activations do not take
         HIPCHK(hipMemsetAsync(c->pf[0].Xs, 0x3c, (size_t)PF_TMAX * c->E * sizeof(float), c->stream));
@@ -1861,6 +2119,16 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
         if (kernel == 6) {  // whole-token kernel: fresh exchange epochs for every launch
             hipLaunchKernelGGL(bump_serial_kernel, dim3(1), dim3(1), 0, c->stream, c->d_tokpos);
             return launch_token_kernel(c);
+        }
+        if (kernel == 12) {
+            PfEpiArgs e;
+            const DevTensor& ct = c->t[LLMK_WCLS];
+            for (int k = 0; k < sp.nchunks; ++k) {
+                const int r0 = k * sp.R;
+                HIPRET(pf_gemm(c, c->pf[0], (const char*)ct.data + (size_t)r0 * ct.row_bytes, (int)ct.row_bytes, c->pf[0].Xs, std::min(sp.R, c->V - r0), c->E,
+                               PF_TMAX, &e, ct.type));
+            }
+            return hipSuccess;
         }
         if (kernel >= 7) {
             PfEpiArgs e;
@@ -1891,7 +2159,7 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
     if (kernel == 6) c->h_tokpos[2] += iters + 3;   // the device-side serial was bumped once per launch: keep the host's in step
                                                      // (exchange epochs must stay unique per serial)
     if (bytes_per_launch) {
-        const int tids[11] = {LLMK_WQKV, -1, LLMK_WO, LLMK_W13, LLMK_W2, LLMK_WCLS, -1, LLMK_W13, LLMK_WQKV, LLMK_WO, LLMK_W2};
+        const int tids[13] = {LLMK_WQKV, -1, LLMK_WO, LLMK_W13, LLMK_W2, LLMK_WCLS, -1, LLMK_W13, LLMK_WQKV, LLMK_WO, LLMK_W2, -1, LLMK_WCLS};
         double b = 0;
         if (kernel == 6) {
             double w = 0;
@@ -2273,6 +2541,7 @@ int llmk_destroy(llmk_ctx* c) {
         if (c->t[i].data && !c->t[i].alias) hipFree(c->t[i].data);
     }
     pf_teardown(c);
+    sc_teardown(c);
     void* dev[] = {c->d_kc, c->d_vc, c->d_x, c->d_q, c->d_xb, c->d_hb, c->d_logits, c->d_rope, c->d_tokpos, c->d_next,
                    c->d_gran, c->d_zeros, c->d_trace, c->d_part};
     for (void* p : dev)

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "score.h"
 
 namespace llmk {
 
@@ -951,6 +952,141 @@ __global__ void pf_epi_swiglu_kernel(PfEpiArgs a) {
         return gate * (1.0f / (1.0f + expf(-gate))) * up;
     };
     *reinterpret_cast<float4*>(a.out + (size_t)t * a.H + g) = make_float4(unit(gs.x, us.x), unit(gs.y, us.y), unit(gs.z, us.z), unit(gs.w, us.w));
+}
+
+// ---- scoring: classifier + log-softmax for every position of a batch (llmk_score) ---------------------
+// The classifier runs as a GEMM over the batch's normed rows (pf_gemm, in row chunks that fit the partial-tile workspace); this
+// epilogue adds a chunk's partial tiles in slot order, divides by xn[t] and reduces the logits of position t on the spot: a
+// workgroup takes PF_SC_ROWS consecutive classifier rows of one position and leaves ONE partial result -- the running
+// log-sum-exp state (m, s) and the first maximum with its index (score.h) -- in part[t][slot]; the thread that meets the
+// target's row writes its logit to tgt[t].  pf_score_merge_kernel folds a position's partials in slot order.  No float atomics:
+// the same logits give the same bits.  The logits rows are written only when the caller asked for them.
+// FROM_P = false: the logits already lie in memory (Z: the q6_K classifier's per-position GEMV, or d_logits on a context off
+// the batched path); same arithmetic from there on.
+constexpr int PF_SC_ROWS = 1024;          // logits per workgroup: 256 threads x 4 consecutive rows
+struct PfScoreArgs {
+    const float* Z;        // FROM_P = false: logits, position t at Z + t * zp
+    float* zout;           // FROM_P = true: where the chunk's logits go (position t, chunk row r at zout + t * zp + r), or null
+    size_t zp;
+    int r0;                // classifier row of the chunk's row 0
+    int V;                 // FROM_P = false: rows in Z
+    int part0, nparts;     // the chunk's first partial slot; slots per position
+    float4* part;          // [T][nparts] {m, s, maximum, pf_sc_pack(its index, a finite logit was seen)}
+    const int* targets;    // [T] 0-based target rows, < 0: none; null: no log-probs wanted
+    float* tgt;            // [T] the target's logit
+};
+// the fourth word of a partial: the first maximum's index (0x3fffffff = none yet; V < 2^30) and, in bit 30, whether any FINITE logit was
+// seen -- a position none of whose logits is finite has no score (LLMK_E_NONFINITE), even if one of them is +inf
+__device__ __forceinline__ float pf_sc_pack(int i, int fin) { return __int_as_float((i < 0 ? 0x3fffffff : i) | (fin << 30)); }
+__device__ __forceinline__ void pf_sc_unpack(float w, int* i, int* fin) {
+    const int b = __float_as_int(w);
+    *fin = (b >> 30) & 1;
+    *i = (b & 0x3fffffff) == 0x3fffffff ? -1 : (b & 0x3fffffff);
+}
+template <bool FROM_P>
+__global__ __launch_bounds__(256) void pf_score_kernel(PfEpiArgs a, PfScoreArgs s) {
+    __shared__ float4 red[4];
+    const int t = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (FROM_P) pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    const int nrows = FROM_P ? a.rows : s.V;
+    const int r = blockIdx.x * PF_SC_ROWS + 4 * tid;          // (chunk rows are a multiple of 4: a ragged strip ends on a whole vector)
+    llmk_lse st = llmk_lse_empty();
+    llmk_amax am = llmk_amax_empty();
+    int fin = 0;
+    if (r < nrows) {
+        float z[4];
+        int nz = 4;
+        if (FROM_P) {
+            const float4 d = pf_sum4(a, t, r);
+            const float xn = a.xn[t];
+            z[0] = d.x / xn; z[1] = d.y / xn; z[2] = d.z / xn; z[3] = d.w / xn;
+            if (s.zout) *reinterpret_cast<float4*>(s.zout + (size_t)t * s.zp + r) = make_float4(z[0], z[1], z[2], z[3]);
+        } else {
+            const float* zr = s.Z + (size_t)t * s.zp + r;
+            nz = min(4, nrows - r);
+            if (nz == 4 && (s.zp & 3) == 0) {
+                const float4 d = *reinterpret_cast<const float4*>(zr);
+                z[0] = d.x; z[1] = d.y; z[2] = d.z; z[3] = d.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) z[e] = e < nz ? zr[e] : -INFINITY;
+            }
+        }
+        const int g = s.r0 + r, tg = s.targets ? s.targets[t] : -1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e < nz) {
+                st = llmk_lse_step(st, z[e]);
+                am = llmk_amax_step(am, z[e], g + e);
+                fin |= isfinite(z[e]) ? 1 : 0;
+                if (g + e == tg) s.tgt[t] = z[e];
+            }
+        }
+    }
+    // the wave's 64 states, then the workgroup's four: both merges are symmetric in their arguments (a float sum, a tie broken by
+    // index), so every lane of a butterfly step computes the same bits
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        llmk_lse so;
+        llmk_amax ao;
+        so.m = __shfl_xor(st.m, o, 64); so.s = __shfl_xor(st.s, o, 64);
+        ao.v = __shfl_xor(am.v, o, 64); ao.i = __shfl_xor(am.i, o, 64);
+        st = llmk_lse_merge(st, so);
+        am = llmk_amax_merge(am, ao);
+        fin |= __shfl_xor(fin, o, 64);
+    }
+    if (lane == 0) red[wid] = make_float4(st.m, st.s, am.v, pf_sc_pack(am.i, fin));
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            llmk_lse so;
+            llmk_amax ao;
+            int fo;
+            so.m = red[w].x; so.s = red[w].y; ao.v = red[w].z;
+            pf_sc_unpack(red[w].w, &ao.i, &fo);
+            st = llmk_lse_merge(st, so);
+            am = llmk_amax_merge(am, ao);
+            fin |= fo;
+        }
+        s.part[(size_t)t * s.nparts + s.part0 + blockIdx.x] = make_float4(st.m, st.s, am.v, pf_sc_pack(am.i, fin));
+    }
+}
+// one wave per position: lane l folds partials l, l + 64, ... in ascending order, the 64 lanes fold as above.
+// logprob = z[target] - (m + log s), 0 where there is no target; argmax 1-based, 0 = no finite logit (the caller's
+// LLMK_E_NONFINITE)
+__global__ __launch_bounds__(64) void pf_score_merge_kernel(const float4* __restrict__ part, int nparts, const int* __restrict__ targets,
+                                                            const float* __restrict__ tgt, float* __restrict__ logprob,
+                                                            int* __restrict__ argmax) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    llmk_lse st = llmk_lse_empty();
+    llmk_amax am = llmk_amax_empty();
+    int fin = 0;
+    for (int j = lane; j < nparts; j += 64) {
+        const float4 p = part[(size_t)t * nparts + j];
+        llmk_lse so;
+        llmk_amax ao;
+        int fo;
+        so.m = p.x; so.s = p.y; ao.v = p.z;
+        pf_sc_unpack(p.w, &ao.i, &fo);
+        st = llmk_lse_merge(st, so);
+        am = llmk_amax_merge(am, ao);
+        fin |= fo;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        llmk_lse so;
+        llmk_amax ao;
+        so.m = __shfl_xor(st.m, o, 64); so.s = __shfl_xor(st.s, o, 64);
+        ao.v = __shfl_xor(am.v, o, 64); ao.i = __shfl_xor(am.i, o, 64);
+        st = llmk_lse_merge(st, so);
+        am = llmk_amax_merge(am, ao);
+        fin |= __shfl_xor(fin, o, 64);
+    }
+    if (lane == 0) {
+        argmax[t] = fin && am.i >= 0 ? am.i + 1 : 0;
+        if (targets) logprob[t] = targets[t] >= 0 ? tgt[t] - llmk_lse_value(st) : 0.0f;
+    }
 }
 
 }  // namespace llmk

@@ -7,7 +7,7 @@
 !
 !   ./llm -m model.gguf [-p prompt] [-n tokens] [-t temperature] [-s tokenizer.bin] [-v]
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score]
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
 ! (one process per GPU, devices d..d+N-1), every rank loads the file and keeps its shard, the ranks meet through a
@@ -38,6 +38,7 @@ module arg_parse
      logical :: gguf_eps, gguf_rope_base   ! extension: honour the file's rms epsilon / RoPE base (the reference hard-codes
                                            ! 1e-5 and 10000, llama2.f90:454,545)
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
+     logical :: score             ! extension: score the prompt instead of continuing it (llmk_score): log-prob per token, perplexity
   end type args
 
 contains
@@ -69,6 +70,7 @@ contains
     a%gguf_eps = .false.
     a%gguf_rope_base = .false.
     a%encode_only = .false.
+    a%score = .false.
 
     nargs = command_argument_count()
     i = 1
@@ -99,6 +101,7 @@ contains
        case ("--gguf-eps");          a%gguf_eps = .true.;      i = i + 1
        case ("--gguf-rope-base");    a%gguf_rope_base = .true.; i = i + 1
        case ("--encode");            a%encode_only = .true.;   i = i + 1
+       case ("--score");             a%score = .true.;         i = i + 1
        case default
           print *, "Unrecognized option:", trim(opt)
           stop
@@ -183,6 +186,9 @@ program llm
   logical :: dsample                                ! --device-sample in its case: -t > 0 on one GPU
   integer(c_int64_t) :: dseed                       ! its seed: --seed N, or the clock's
   integer(c_int) :: dnext
+  integer(c_int), allocatable, target :: sc_targets(:)   ! --score: the prompt's tokens, each the target of the position before it
+  real(c_float), allocatable, target :: sc_logprob(:)
+  real(kind=wp) :: sc_sum
 
   call parse_args(opts)
   lead = opts%tp_rank == 0
@@ -285,6 +291,40 @@ program llm
   end if
 
   prompt_tokens = bpe_encode(opts%prompt)
+
+  ! --score: the prompt is scored, not continued -- positions 1 .. k hold BOS and the first k-1 prompt tokens, the target of
+  ! position i is prompt token i; classifier and log-softmax of all k positions run on the device in the one call (llmk_score)
+  if (opts%score) then
+     k = size(prompt_tokens)
+     if (k < 1) then
+        print *, "--score needs a prompt of at least one token (-p)"
+        stop 1
+     end if
+     if (k > conf%seq_len .or. opts%ngpu > 1) then
+        print *, "--score: the prompt must fit the context (", conf%seq_len, "positions ) on one GPU"
+        stop 1
+     end if
+     allocate(batch(k), sc_targets(k), sc_logprob(k))
+     batch(1) = 2
+     batch(2:) = int(prompt_tokens(1:k - 1), c_int)
+     sc_targets = int(prompt_tokens, c_int)
+     t_start = clock_ticks()
+     call llmk_check(llmk_score(ctx, batch, int(k, c_int), 1_c_int, c_loc(sc_targets), c_loc(sc_logprob), c_null_ptr, c_null_ptr), &
+          "llmk_score")
+     t_end = clock_ticks()
+     dt_ms = elapsed_ms(t_start, t_end)
+     sc_sum = 0
+     do pos = 1, k
+        print '(I0,1X,I0,1X,ES15.8)', pos, prompt_tokens(pos), sc_logprob(pos)
+        sc_sum = sc_sum + sc_logprob(pos)
+     end do
+     print '(A,1X,I0)', "tokens", k
+     print '(A,1X,ES15.8)', "sum logprob", sc_sum
+     print '(A,1X,ES15.8)', "perplexity", exp(-sc_sum / k)
+     print *, 1000 * k / dt_ms, "positions/second"
+     rc = llmk_destroy(ctx)
+     stop
+  end if
 
   ! --device-sample: EVERY id after the prompt is drawn on the device (llmk_forward_sample / llmk_decode_sample), the first one
   ! and the one after a --prefill prompt included, so the transcript is a function of (model, prompt, T, seed) alone

@@ -104,6 +104,14 @@ module llmk_binding
        integer(c_int), value :: n, pos0
        real(c_float), intent(out) :: logits(*)
      end function
+     ! targets and the three outputs travel as C addresses (c_loc of a `target` array): each output may be c_null_ptr = not asked for
+     integer(c_int) function llmk_score(ctx, tokens, n, pos0, targets, logprob_out, argmax_out, logits_out) bind(C, name="llmk_score")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(in) :: tokens(*)
+       integer(c_int), value :: n, pos0
+       type(c_ptr), value :: targets, logprob_out, argmax_out, logits_out
+     end function
      integer(c_int) function llmk_forward_greedy(ctx, token, pos, next_token) bind(C, name="llmk_forward_greedy")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -25,7 +25,7 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_tp_p2p_connect_local", "llmk_tp_p2p_selftest", "llmk_tp_p2p_stress", "llmk_tp_p2p_disable", "llmk_tp_begin", "llmk_tp_segment",
            "llmk_tp_read_partial", "llmk_tp_write_partial", "llmk_tp_read_logits", "llmk_upload", "llmk_upload_rows",
            "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
-           "llmk_forward_sample", "llmk_decode_sample", "llmk_reset", "llmk_timings",
+           "llmk_forward_sample", "llmk_decode_sample", "llmk_score", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -90,6 +90,8 @@ def lib():
         if hasattr(L, "llmk_forward_sample"):     # (absent from an older build selected with LLMK_LIB for an A/B)
             L.llmk_forward_sample.argtypes = [vp, ci, ci, C.c_float, C.c_uint64, C.POINTER(ci)]
             L.llmk_decode_sample.argtypes = [vp, ci, ci, ci, C.c_float, C.c_uint64, C.POINTER(ci), vp, vp]
+        if hasattr(L, "llmk_score"):
+            L.llmk_score.argtypes = [vp, C.POINTER(ci), ci, ci, C.POINTER(ci), cf, C.POINTER(ci), cf]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -201,6 +203,29 @@ class Llmk:
         _ck(lib().llmk_prefill(self._h, t.ctypes.data_as(C.POINTER(C.c_int)), len(t), pos0,
                                self._logits.ctypes.data_as(C.POINTER(C.c_float))))
         return self._logits.copy()
+
+    def score(self, tokens, pos0: int = 1, targets=None, want_argmax: bool = False, want_logits: bool = False, want_logprob: bool = True):
+        """tokens (1-based ids) at positions pos0.. in one call, scored on the device (llmk_score): the log-probability of
+        targets[i] at every position (targets=None: the next token, and 0 = no target = log-prob 0.0 at the last position),
+        the 1-based argmax and the logits [n][V] when asked for.  Returns the arrays asked for, in that order (one array: itself)."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        n = len(t)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        tg = lp = am = lg = None
+        if want_logprob:
+            tg = np.ascontiguousarray(np.append(t[1:], 0) if targets is None else targets, np.int32)
+            if len(tg) != n:
+                raise ValueError("one target per token")
+            lp = np.empty(n, np.float32)
+        if want_argmax:
+            am = np.empty(n, np.int32)
+        if want_logits:
+            lg = np.empty((n, self.V), np.float32)
+        _ck(lib().llmk_score(self._h, t.ctypes.data_as(ip), n, pos0, tg.ctypes.data_as(ip) if tg is not None else None,
+                             lp.ctypes.data_as(fp) if lp is not None else None, am.ctypes.data_as(ip) if am is not None else None,
+                             lg.ctypes.data_as(fp) if lg is not None else None))
+        out = [a for a in (lp, am, lg) if a is not None]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def forward_greedy(self, token: int, pos: int) -> int:
         nxt = C.c_int(0)
