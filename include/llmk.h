@@ -245,6 +245,42 @@ int llmk_forward_sample(llmk_ctx *ctx, int token, int pos, float temperature, ui
 int llmk_decode_sample(llmk_ctx *ctx, int token, int pos0, int n, float temperature, uint64_t seed,
                        int *ids_out, llmk_token_fn on_token, void *user);
 
+/* The same two with the truncations stock llama.cpp files are sampled with: top-k, top-p (nucleus) and min-p in front of the
+ * Gumbel-max draw (llm.f90_amd/csrc/sample_filter.h holds the rule).  With z the logits of the position
+ * (-0.0 counts as +0.0), s[i] = z[i] * invT, m = max s, e[i] = expf(s[i] - m), Q[i] = (uint64) floorf(e[i] * 2^32):
+ *   top_k  >= 1 (0 = off; so is top_k >= the number of non-NaN rows): tau_k = the k-th largest logit counting duplicates; rows that
+ *          tie with it are ALL kept, so more than k rows may be (the rule knows no index order);
+ *   top_p  in (0, 1) (exactly 1 = off): with S = sum of Q[j] over z[j] >= tau_k and G(t) = sum of Q[j] over z[j] > t, row i is kept
+ *          iff (double)G(z[i]) < (double)top_p * (double)S -- the nucleus of the distribution after top-k, renormalised over it;
+ *          integer sums: exact, whatever the order of the additions.  The row of the maximum is always kept;
+ *   min_p  in [0, 1] (0 = off): row i is kept iff e[i] >= min_p;
+ *   token = 1 + argmax over the kept rows of the score above (the same stateless noise, first maximum wins): a draw from the
+ *          distribution renormalised over the kept rows.
+ * All three are monotone in z: the kept set is { i : z[i] >= tau }, tau the largest of the three thresholds.  NaN and -inf rows are
+ * never kept; a maximum of +inf keeps the rows equal to it; no row above -inf is LLMK_E_NONFINITE.  top_k < 0, top_p outside (0, 1],
+ * min_p outside [0, 1] or a NaN: LLMK_E_ARG before anything runs; temperature as above.  With all filters off the two functions ARE
+ * llmk_forward_sample / llmk_decode_sample (same code path, same ids).  With a filter on, one more one-workgroup kernel runs per
+ * position (behind each launch of the pipelined decode, which stays pipelined: the token still never leaves the device); every path
+ * runs that one kernel, so pipelined and per-position ids are bit-identical. */
+typedef struct llmk_sampler {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    float min_p;
+    uint64_t seed;
+} llmk_sampler;
+int llmk_forward_sample_ex(llmk_ctx *ctx, int token, int pos, const llmk_sampler *sampler, int *next_token);
+int llmk_decode_sample_ex(llmk_ctx *ctx, int token, int pos0, int n, const llmk_sampler *sampler, int *ids_out,
+                          llmk_token_fn on_token, void *user);
+/* Verification hook, like llmk_peek: the rule applied by the same kernel to caller-supplied logits (vocab_size floats, host
+ * memory) as if they were those of position `pos` -- no token pass, the KV cache is untouched.  token_out = the 1-based pick;
+ * kept_out (optional) = the number of rows kept; tau_out (optional) = the threshold (-inf with all filters off).
+ * The ctx's logits buffer is overwritten with `logits`: what llmk_forward left there is gone, so a following llmk_peek of the
+ * logits (or any other read of them) sees the caller's vector, not the last position's.  The ctx must hold all its tensors
+ * (LLMK_E_STATE otherwise) and be a whole-model one: a tensor-parallel rank gives LLMK_E_ARG. */
+int llmk_sample_logits(llmk_ctx *ctx, const float *logits, int pos, const llmk_sampler *sampler, int *token_out, int *kept_out,
+                       float *tau_out);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318. */
 int llmk_reset(llmk_ctx *ctx);
 

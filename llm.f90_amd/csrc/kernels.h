@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "sample.h"
+#include "sample_filter.h"
 
 namespace llmk {
 
@@ -793,6 +794,232 @@ __global__ __launch_bounds__(1024) void sample_kernel(const float* __restrict__ 
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
         out[0] = (unsigned)idx < (unsigned)n ? idx + 1 : 0;   // 0 = no token: LLMK_E_NONFINITE on the host
     }
+}
+
+// token ~ the top-k / top-p / min-p truncation of softmax(logits / T): the rule of sample_filter.h by ONE workgroup of 1,024 threads.
+// The logits stay where the classifier left them (L2; V floats need not fit in LDS): pass 1 finds the maximum, every level of the
+// radix descent is one more pass that bins the rows under the descent's prefix, the last pass is sample_kernel's argmax over
+// z >= tau.  A bin is a u32 count and a u64 sum of Q, filled with integer LDS atomics only, so no result depends on the order of the
+// additions.  Logits share their sign and high exponent bits, so at level 0 a wave's 64 rows land in a handful of bins; each bin is
+// therefore kept as SF_COPIES copies in consecutive words (= distinct banks), lane l adding to copy l % SF_COPIES, and the copies
+// are summed once per level.  Level 0 is shared by the two descents (kept in l0c / l0s); top-p starts only when top-k has settled S.
+// pos: tokpos[1], or pos_imm when tokpos is null (a launch of the pipelined decode).  Outputs: next[0] = the 1-based id (0 = no
+// token); cand, when not null: the ncand candidates of that position as the persistent kernel's fold expects them -- the winner in
+// entry 0, {-inf, 0x7fffffff} in the others (in all of them without a token); out2 = {rows kept, tau bits}.
+constexpr int SF_THREADS = 1024, SF_COPIES = 16;
+__device__ __forceinline__ unsigned long long sf_shfl_down_u64(unsigned long long v, int o) {
+    const unsigned lo = __shfl_down((unsigned)v, o, 64), hi = __shfl_down((unsigned)(v >> 32), o, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* __restrict__ logits, int n, const int* __restrict__ tokpos,
+                                                                   int pos_imm, const llmk_filter_params* __restrict__ fp,
+                                                                   int* __restrict__ next, float2* __restrict__ cand, int ncand,
+                                                                   unsigned* __restrict__ out2) {
+    __shared__ unsigned long long hs[256 * SF_COPIES];      // the level's sums of Q, SF_COPIES copies per bin
+    __shared__ unsigned hc[256 * SF_COPIES];                // ... and counts
+    __shared__ llmk_filter_bins bins, bins0;                // the copies summed; level 0 kept for the second descent
+    __shared__ float wv[16];
+    __shared__ int wi[16];
+    __shared__ unsigned wk[16], wc[16];
+    __shared__ llmk_filter_walk walk;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int pos = tokpos ? tokpos[1] : pos_imm;
+    const float invT = fp->invT, top_p = fp->top_p, min_p = fp->min_p;
+    const int top_k = fp->top_k;
+    const uint64_t seed = (uint64_t)fp->seed_lo | ((uint64_t)fp->seed_hi << 32);
+
+    // ---- pass 1: the largest logit and the number of non-NaN rows
+    float zmax = -INFINITY;
+    unsigned valid = 0;
+    for (int i = tid; i < n; i += SF_THREADS) {
+        const float z = logits[i];
+        if (z == z) { ++valid; zmax = fmaxf(zmax, z); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        zmax = fmaxf(zmax, __shfl_xor(zmax, o, 64));
+        valid += __shfl_xor(valid, o, 64);
+    }
+    if (lane == 0) { wv[wid] = zmax; wc[wid] = valid; }
+    __syncthreads();
+    zmax = wv[0];
+    valid = wc[0];
+    for (int w = 1; w < 16; ++w) { zmax = fmaxf(zmax, wv[w]); valid += wc[w]; }
+    __syncthreads();
+    const bool none = valid == 0 || zmax == -INFINITY;
+    const float m = llmk_filter_m(zmax, invT);
+    unsigned tau = LLMK_FILTER_KEY_NINF;
+
+    // one level of a descent: bins <- the rows under `prefix` (all rows at level 0); with_minp: also the smallest key with e >= min_p
+    auto fill = [&](int level, unsigned prefix, bool with_hist, bool with_minp) -> unsigned {
+        const int shift = 24 - 8 * level;
+        if (with_hist) {
+            for (int j = tid; j < 256 * SF_COPIES; j += SF_THREADS) { hc[j] = 0u; hs[j] = 0ull; }
+            __syncthreads();
+        }
+        unsigned kmin = 0xffffffffu;
+        for (int i = tid; i < n; i += SF_THREADS) {
+            const float z = logits[i];
+            if (z != z) continue;
+            const unsigned key = llmk_filter_key(z);
+            if (level > 0 && (key >> (shift + 8)) != prefix) continue;
+            const float e = llmk_filter_e(z, invT, m);
+            if (with_minp && e >= min_p) kmin = key < kmin ? key : kmin;
+            if (with_hist) {
+                const int slot = (int)((key >> shift) & 255u) * SF_COPIES + (lane & (SF_COPIES - 1));
+                atomicAdd(&hc[slot], 1u);
+                atomicAdd(&hs[slot], (unsigned long long)llmk_filter_q(e));
+            }
+        }
+        if (with_minp) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { const unsigned ok = __shfl_xor(kmin, o, 64); kmin = ok < kmin ? ok : kmin; }
+            if (lane == 0) wk[wid] = kmin;
+        }
+        __syncthreads();
+        if (with_hist && tid < 256) {      // (the copies read rotated by the bin: 64 lanes, 64 banks)
+            unsigned c = 0;
+            unsigned long long s = 0;
+#pragma unroll
+            for (int k = 0; k < SF_COPIES; ++k) {
+                const int slot = tid * SF_COPIES + ((k + tid) & (SF_COPIES - 1));
+                c += hc[slot];
+                s += hs[slot];
+            }
+            bins.cnt[tid] = c;
+            bins.sum[tid] = s;
+            if (level == 0) { bins0.cnt[tid] = c; bins0.sum[tid] = s; }
+        }
+        if (with_minp) { kmin = wk[0]; for (int w = 1; w < 16; ++w) kmin = wk[w] < kmin ? wk[w] : kmin; }
+        __syncthreads();
+        return kmin;
+    };
+    // wave 0 walks the bins from the top, four per lane: what lies above each lane's bins is a suffix sum over the lanes
+    auto walk_bins = [&](const llmk_filter_bins& b, unsigned cnt_above, unsigned long long sum_above, bool by_count, unsigned k, double target) {
+        if (wid == 0) {
+            unsigned c[4], ct = 0;
+            unsigned long long s[4], st = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { c[j] = b.cnt[4 * lane + j]; s[j] = b.sum[4 * lane + j]; ct += c[j]; st += s[j]; }
+            unsigned ca = ct;
+            unsigned long long sa = st;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned oc = __shfl_down(ca, o, 64);
+                const unsigned long long os = sf_shfl_down_u64(sa, o);
+                if (lane + o < 64) { ca += oc; sa += os; }
+            }
+            ca = ca - ct + cnt_above;      // above this lane's four bins
+            sa = sa - st + sum_above;
+            int digit = 256;
+            unsigned dca = 0;
+            unsigned long long dsa = 0;
+#pragma unroll
+            for (int j = 3; j >= 0; --j) {      // from the lane's top bin down: the LOWEST qualifying bin stays
+                const bool q = c[j] != 0 && (by_count ? (ca < k && ca + c[j] >= k) : ((double)sa < target));
+                if (q) { digit = 4 * lane + j; dca = ca; dsa = sa; }
+                ca += c[j];
+                sa += s[j];
+            }
+            int low = digit;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { const int od = __shfl_xor(low, o, 64); low = od < low ? od : low; }
+            if (digit == low && digit < 256) { walk.digit = digit; walk.cnt_above = dca; walk.sum_above = dsa; }
+        }
+        __syncthreads();
+    };
+
+    if (!none) {
+        if (!isfinite(m)) {
+            tau = llmk_filter_key(zmax);      // a maximum of +inf, or a scaled one beyond f32: the rows equal to the maximum
+        } else {
+            const bool k_on = top_k > 0 && (unsigned)top_k < valid, p_on = top_p < 1.f, m_on = min_p > 0.f;
+            unsigned long long S = 0, ties = 0;
+            if (k_on || p_on || m_on) {
+                const unsigned tm = fill(0, 0u, k_on || p_on, m_on);
+                if (m_on && tm != 0xffffffffu && tm > tau) tau = tm;
+            }
+            if (k_on) {
+                unsigned prefix = 0, ca = 0;
+                unsigned long long sa = 0;
+                for (int level = 0; level < 4; ++level) {
+                    if (level > 0) fill(level, prefix, true, false);
+                    walk_bins(bins, ca, sa, true, (unsigned)top_k, 0.0);
+                    prefix = (prefix << 8) | (unsigned)walk.digit;
+                    ca = walk.cnt_above;
+                    sa = walk.sum_above;
+                    ties = bins.sum[walk.digit];
+                    __syncthreads();      // (walk and bins are rewritten by the next level)
+                }
+                S = sa + ties;
+                if (prefix > tau) tau = prefix;
+            } else if (p_on) {
+                if (tid < 64) {
+                    unsigned long long st = bins0.sum[4 * lane] + bins0.sum[4 * lane + 1] + bins0.sum[4 * lane + 2] + bins0.sum[4 * lane + 3];
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) st += sf_shfl_down_u64(st, o);
+                    if (lane == 0) walk.sum_above = st;
+                }
+                __syncthreads();
+                S = walk.sum_above;
+                __syncthreads();
+            }
+            if (p_on) {
+                const double target = llmk_filter_target(top_p, S);
+                if (!(k_on && (double)(S - ties) < target)) {      // (else the whole top-k set is inside the nucleus: tau_p <= tau_k)
+                    unsigned prefix = 0;
+                    unsigned long long sa = 0;
+                    for (int level = 0; level < 4; ++level) {
+                        if (level > 0) fill(level, prefix, true, false);
+                        walk_bins(level == 0 ? bins0 : bins, 0u, sa, false, 0u, target);
+                        prefix = (prefix << 8) | (unsigned)walk.digit;
+                        sa = walk.sum_above;
+                        __syncthreads();
+                    }
+                    if (prefix > tau) tau = prefix;
+                }
+            }
+        }
+    }
+
+    // ---- last pass: the Gumbel-max argmax of sample_kernel over z >= tau
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    unsigned kept = 0;
+    if (!none) {
+        for (int i = tid; i < n; i += SF_THREADS) {
+            const float z = logits[i];
+            if (z != z || z == -INFINITY || llmk_filter_key(z) < tau) continue;
+            ++kept;
+            const float v = llmk_sample_score(z, invT, seed, pos, i);
+            if (v > best) { best = v; idx = i; }  // ascending i per thread: keeps the first maximum
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+        kept += __shfl_xor(kept, o, 64);
+    }
+    if (lane == 0) { wv[wid] = best; wi[wid] = idx; wc[wid] = kept; }
+    __syncthreads();
+    best = wv[0];
+    idx = wi[0];
+    kept = wc[0];
+    for (int w = 1; w < 16; ++w) {
+        if (wv[w] > best || (wv[w] == best && wi[w] < idx)) { best = wv[w]; idx = wi[w]; }
+        kept += wc[w];
+    }
+    const bool have = (unsigned)idx < (unsigned)n;
+    if (tid == 0) {
+        next[0] = have ? idx + 1 : 0;      // 0 = no token: LLMK_E_NONFINITE on the host
+        out2[0] = kept;
+        out2[1] = none ? 0x7f800000u : llmk_filter_bits(llmk_filter_unkey(tau));
+    }
+    if (cand)
+        for (int j = tid; j < ncand; j += SF_THREADS)
+            cand[j] = (j == 0 && have) ? make_float2(best, __int_as_float(idx)) : make_float2(-INFINITY, __int_as_float(0x7fffffff));
 }
 
 // q4_0 re-pack on upload: ggml blocks {f16 d; u8 qs[16]} (18 B, 2-byte aligned), bpr per row -> device rows of

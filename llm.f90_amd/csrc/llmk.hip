@@ -108,11 +108,16 @@ struct llmk_ctx {
     bool tk_direct = true;
     int* h_next = nullptr;      // pinned
     hipStream_t stream = nullptr;
-    hipGraphExec_t graph_logits = nullptr, graph_greedy = nullptr, graph_sample = nullptr;
+    hipGraphExec_t graph_logits = nullptr, graph_greedy = nullptr, graph_sample = nullptr, graph_filter = nullptr;
     llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current llmk_forward_sample / llmk_decode_sample call
     // what the device's copy of them (d_sample_params) holds once the stream has drained: zeros from llmk_create on; pad = 1 while
     // unknown.  A pipelined decode writes them only when they differ, so a greedy one on a ctx that never sampled enqueues nothing new
     llmk_sample_params samp_dev = {};
+    // the same pair for the truncated sampler (llmk_*_sample_ex with a filter on): its parameters sit behind the sampling words
+    // (d_filter_params); filt_known = filt_dev is what the device holds
+    llmk_filter_params* h_filt = nullptr;
+    llmk_filter_params filt_dev = {};
+    bool filt_known = false;
     hipEvent_t ev[8] = {};
     float times[5] = {0, 0, 0, 0, 0};
     int n_cu = 256;
@@ -522,14 +527,22 @@ int tk_setup_all(llmk_ctx* c) {
 __global__ void bump_serial_kernel(int* tokpos) { tokpos[2] += 1; }
 
 // What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
-// (llmk_forward_sample); the last two leave the 1-based id in h_next[0] and the sticky error word in h_next[1]
-enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE };
+// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h); the last three leave the 1-based id in h_next[0] and
+// the sticky error word in h_next[1]
+enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE, TAIL_FILTER };
 // the sampling parameters in device memory: behind the error word and the pipelined decode's two candidate buffers
 // (token_kernel.h tk_sample_params reads the same words)
 llmk_sample_params* d_sample_params(llmk_ctx* c) { return reinterpret_cast<llmk_sample_params*>(c->d_logits + c->V + 4 + 4 * TK_NCU); }
+llmk_filter_params* d_filter_params(llmk_ctx* c) { return reinterpret_cast<llmk_filter_params*>(c->d_logits + c->V + 8 + 4 * TK_NCU); }
+unsigned* d_filter_out(llmk_ctx* c) { return reinterpret_cast<unsigned*>(c->d_logits + c->V + 16 + 4 * TK_NCU); }
 hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
     if (tail != TAIL_LOGITS) {
-        if (tail == TAIL_SAMPLE) {
+        if (tail == TAIL_FILTER) {
+            // the same kernel as behind a launch of the pipelined decode (decode_run), with the position from the pass's device word
+            HIPRET(hipMemcpyAsync(d_filter_params(c), c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, d_filter_params(c),
+                               c->d_next, (float2*)nullptr, 0, d_filter_out(c));
+        } else if (tail == TAIL_SAMPLE) {
             // invT and the seed travel like token and position: a copy out of pinned memory, read when the graph replays it
             HIPRET(hipMemcpyAsync(d_sample_params(c), c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_tokpos, d_sample_params(c), c->d_next);
@@ -695,6 +708,7 @@ int tk_retire(llmk_ctx* c, unsigned code, int pos) {
     if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
     if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
+    if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
     for (int i = 0; i < LLMK_N_TENSORS; ++i)       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
         if (c->q16[i]) { hipFree(c->q16[i]); c->q16[i] = nullptr; }
     c->q16_dirty = true;
@@ -743,7 +757,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
             reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
             HIPCHK(launch_token_kernel(c, true));
         } else {
-            hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : &c->graph_logits;
+            hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : tail == TAIL_FILTER ? &c->graph_filter : &c->graph_logits;
             if (!*g) {
                 rc = build_graph(c, tail, g);
                 if (rc) return rc;
@@ -783,6 +797,12 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
     return LLMK_E_TIMEOUT;
 }
 int run_token(llmk_ctx* c, int token, int pos, TailMode tail) {
+    if (tail == TAIL_FILTER) {               // (its tail copies h_filt to the device in the same way)
+        c->filt_known = false;
+        const int rc = run_token_pass(c, token, pos, tail);
+        if (rc == LLMK_OK) { c->filt_dev = *c->h_filt; c->filt_known = true; }
+        return rc;
+    }
     if (tail != TAIL_SAMPLE) return run_token_pass(c, token, pos, tail);
     c->samp_dev.pad = 1;                     // (the sampling tail copies h_samp to the device: known again once the pass is through)
     const int rc = run_token_pass(c, token, pos, tail);
@@ -1198,7 +1218,7 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
 
 extern "C" {
 
-int llmk_version(void) { return 300; }
+int llmk_version(void) { return 400; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -1314,8 +1334,9 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(dev_alloc(&c->d_hb, (size_t)H * sizeof(float)));
     CK(dev_alloc(&c->d_part, (size_t)E * sizeof(float)));
     // [V] = sticky device error word; behind it (at V + 4) the two candidate buffers of the pipelined greedy decode, and behind
-    // those (at V + 4 + 4 * TK_NCU) the sampling parameters (d_sample_params)
-    CK(dev_alloc(&c->d_logits, ((size_t)V + 8 + 4 * TK_NCU) * sizeof(float)));
+    // those (at V + 4 + 4 * TK_NCU) the sampling parameters (d_sample_params), the truncated sampler's (d_filter_params, 8 words)
+    // and the two words its kernel leaves for verification (d_filter_out)
+    CK(dev_alloc(&c->d_logits, ((size_t)V + 24 + 4 * TK_NCU) * sizeof(float)));
     CK(dev_alloc(&c->d_rope, (size_t)(hs / 2) * sizeof(float)));
     CK(dev_alloc(&c->d_tokpos, 4 * sizeof(int)));
     CK(dev_alloc(&c->d_next, 2 * sizeof(int)));
@@ -1324,8 +1345,9 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(hipHostMalloc(&c->h_logits, ((size_t)V + 4 + S) * sizeof(float), hipHostMallocMapped));
     CK(hipHostGetDevicePointer((void**)&c->h_logits_dev, c->h_logits, 0));
     c->tk_direct = !(getenv("LLMK_TK_DIRECT") && getenv("LLMK_TK_DIRECT")[0] == '0');
-    CK(hipHostMalloc(&c->h_next, 2 * sizeof(int), hipHostMallocDefault));
+    CK(hipHostMalloc(&c->h_next, 4 * sizeof(int), hipHostMallocDefault));      // id, error word; rows kept, tau bits (llmk_sample_logits)
     CK(hipHostMalloc(&c->h_samp, sizeof(llmk_sample_params), hipHostMallocDefault));
+    CK(hipHostMalloc(&c->h_filt, sizeof(llmk_filter_params), hipHostMallocDefault));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int i = 0; i < 8; ++i) CK(hipEventCreate(&c->ev[i]));
     // The whole-token persistent kernel serves the shapes it is instantiated for, on a full 256-CU part
@@ -1343,7 +1365,7 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
         else CK(pe);
     }
     if (rc == LLMK_OK) {
-        CK(hipMemset(c->d_logits, 0, ((size_t)V + 8 + 4 * TK_NCU) * sizeof(float)));
+        CK(hipMemset(c->d_logits, 0, ((size_t)V + 24 + 4 * TK_NCU) * sizeof(float)));
         c->h_tokpos[0] = 0; c->h_tokpos[1] = 0; c->h_tokpos[2] = 0; c->h_tokpos[3] = 0;
         CK(hipMemset(c->d_kc, 0, kvn * sizeof(float)));  // s%key_cache(:,:,:) = 0   llama2.f90:317
         CK(hipMemset(c->d_vc, 0, kvn * sizeof(float)));
@@ -1662,6 +1684,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
         if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
         if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
         if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
+        if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
     }
     // the persistent kernel again, if one is instantiated for this shape with a classifier of this type (round 6: q6_K rows beside
     // q4_0 matrices -- a stock llama.cpp q4_0 file keeps the fast path); otherwise the multi-kernel path
@@ -1684,6 +1707,7 @@ int llmk_set_rms_eps(llmk_ctx* c, float eps) {
     if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }   // kernel arguments are baked in
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
     if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
+    if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
     return LLMK_OK;
 }
 
@@ -1948,7 +1972,14 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         memset(h_ids, 0, (size_t)n * sizeof(int));
         reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
         // the GR launches score their classifier rows with these parameters (token_kernel.h tk_sample_params); invT = 0 is greedy
+        // (TAIL_FILTER: greedy words -- the cheap tail -- and sample_filter_kernel behind every launch, which replaces the launch's
+        // candidates by its own single winner: the next launch's fold and cand_resolve_kernel pick that up like any other candidate)
         const llmk_sample_params want = tail == TAIL_SAMPLE ? *c->h_samp : llmk_sample_params{};
+        if (tail == TAIL_FILTER && !(c->filt_known && memcmp(c->h_filt, &c->filt_dev, sizeof(llmk_filter_params)) == 0)) {
+            HIPCHK(hipMemcpyAsync(d_filter_params(c), c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+            c->filt_dev = *c->h_filt;
+            c->filt_known = true;
+        }
         if (memcmp(&want, &c->samp_dev, sizeof(want)) != 0) {
             if (tail == TAIL_SAMPLE)
                 HIPCHK(hipMemcpyAsync(d_sample_params(c), c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
@@ -1966,6 +1997,11 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             // debug library only: this launch one workgroup short, so its peers really time out INSIDE the pipeline
             c->tk_short_grid = TK_DEBUG && getenv("LLMK_TK_INJECT_TIMEOUT") && atoi(getenv("LLMK_TK_INJECT_TIMEOUT")) == pos0 + i;
             HIPCHK(launch_token_kernel(c, false, g));
+            if (tail == TAIL_FILTER) {
+                hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos0 + i,
+                                   d_filter_params(c), c->d_next, d_cand + (size_t)((pos0 + i) & 1) * TK_NCU, TK_NCU, d_filter_out(c));
+                HIPCHK(hipGetLastError());
+            }
         }
         hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, d_cand + (size_t)((pos0 + n - 1) & 1) * TK_NCU,
                            h_ids_dev + (n - 1), c->d_next, reinterpret_cast<unsigned*>(c->d_logits + c->V), c->V);
@@ -2019,6 +2055,66 @@ int llmk_decode_sample(llmk_ctx* c, int token, int pos0, int n, float temperatur
     const int rc = set_sample_params(c, temperature, seed);
     if (rc) return rc;
     return decode_run(c, token, pos0, n, TAIL_SAMPLE, ids_out, on_token, user);
+}
+
+// The truncated sampler: checks, then the pinned words of sample_filter.h.  *filtered = a filter is on (none: the _ex functions ARE
+// llmk_forward_sample / llmk_decode_sample)
+int set_filter_params(llmk_ctx* c, const llmk_sampler* sp, bool* filtered) {
+    if (!sp) return LLMK_E_ARG;
+    if (sp->top_k < 0 || !(sp->top_p > 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f)) return LLMK_E_ARG;      // (NaN fails)
+    const int rc = set_sample_params(c, sp->temperature, sp->seed);
+    if (rc) return rc;
+    llmk_filter_params f = {};
+    f.invT = c->h_samp->invT;
+    f.seed_lo = c->h_samp->seed_lo;
+    f.seed_hi = c->h_samp->seed_hi;
+    f.top_k = sp->top_k;
+    f.top_p = sp->top_p;
+    f.min_p = sp->min_p;
+    *c->h_filt = f;
+    *filtered = sp->top_k != 0 || sp->top_p != 1.f || sp->min_p != 0.f;
+    return LLMK_OK;
+}
+int llmk_forward_sample_ex(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, int* next_token) {
+    if (!c || !next_token) return LLMK_E_ARG;
+    bool filtered = false;
+    const int rc = set_filter_params(c, sp, &filtered);
+    if (rc) return rc;
+    return token_out(c, token, pos, filtered ? TAIL_FILTER : TAIL_SAMPLE, next_token);
+}
+int llmk_decode_sample_ex(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, int* ids_out, llmk_token_fn on_token, void* user) {
+    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
+    bool filtered = false;
+    const int rc = set_filter_params(c, sp, &filtered);
+    if (rc) return rc;
+    return decode_run(c, token, pos0, n, filtered ? TAIL_FILTER : TAIL_SAMPLE, ids_out, on_token, user);
+}
+// Verification hook: the rule on the caller's logits, by the kernel every path runs (no token pass; the ctx's own logits buffer
+// is overwritten, nothing else -- the sticky error word behind it included).  Whole-model contexts only: a TP rank's classifier
+// owns a slice of the vocabulary, and its logits buffer belongs to the collective.
+int llmk_sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, int* token_out_, int* kept_out, float* tau_out) {
+    if (!c || !logits || !token_out_ || pos < 1 || c->tp_size != 1) return LLMK_E_ARG;
+    bool filtered = false;
+    int rc = set_filter_params(c, sp, &filtered);
+    if (rc) return rc;
+    if ((rc = check_ready(c)) != LLMK_OK) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    c->filt_known = false;
+    HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_filter_params(c), c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, d_filter_params(c),
+                       c->d_next, (float2*)nullptr, 0, d_filter_out(c));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_next, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_next + 2, d_filter_out(c), 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->filt_dev = *c->h_filt;
+    c->filt_known = true;
+    if (kept_out) *kept_out = c->h_next[2];
+    if (tau_out) memcpy(tau_out, c->h_next + 3, sizeof(float));
+    if (*c->h_next < 1 || *c->h_next > c->V) return LLMK_E_NONFINITE;
+    *token_out_ = *c->h_next;
+    return LLMK_OK;
 }
 
 int llmk_reset(llmk_ctx* c) {
@@ -2398,6 +2494,7 @@ int llmk_tp_p2p_disable(llmk_ctx* c) {
     if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
     if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
+    if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
     return LLMK_OK;
 }
 
@@ -2537,6 +2634,7 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->graph_logits) hipGraphExecDestroy(c->graph_logits);
     if (c->graph_greedy) hipGraphExecDestroy(c->graph_greedy);
     if (c->graph_sample) hipGraphExecDestroy(c->graph_sample);
+    if (c->graph_filter) hipGraphExecDestroy(c->graph_filter);
     for (int i = 0; i < LLMK_N_TENSORS; ++i) {
         if (c->t[i].data && !c->t[i].alias) hipFree(c->t[i].data);
     }
@@ -2558,6 +2656,7 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->h_logits) hipHostFree(c->h_logits);
     if (c->h_next) hipHostFree(c->h_next);
     if (c->h_samp) hipHostFree(c->h_samp);
+    if (c->h_filt) hipHostFree(c->h_filt);
     for (int i = 0; i < 8; ++i)
         if (c->ev[i]) hipEventDestroy(c->ev[i]);
     if (c->stream) hipStreamDestroy(c->stream);

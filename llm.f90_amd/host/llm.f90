@@ -7,6 +7,7 @@
 !
 !   ./llm -m model.gguf [-p prompt] [-n tokens] [-t temperature] [-s tokenizer.bin] [-v]
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
+!         [--top-k N] [--top-p P] [--min-p M]
 !         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score]
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
@@ -27,6 +28,8 @@ module arg_parse
      integer :: device            ! extension: HIP device ordinal
      logical :: device_argmax     ! extension: greedy pick on the GPU (SURVEY.md 8f rank 1)
      logical :: device_sample     ! extension: temperature sampling on the GPU (-t > 0; the Gumbel-max rule of include/llmk.h)
+     integer :: top_k             ! extension: truncated sampling on the GPU (llmk_decode_sample_ex); any of the three with -t > 0
+     real :: top_p, min_p         !   selects the device sampler.  0, 1, 0 = off
      logical :: prefill           ! extension: the prompt goes through the model as ONE batched pass (llmk_prefill)
      logical :: stream_load       ! extension: matrices go from the file to the device tensor by tensor (always with --ngpu)
      logical :: timings           ! extension: fill the five "Timings" lines from hipEvent section timers (slow path)
@@ -59,6 +62,9 @@ contains
     a%device = 0
     a%device_argmax = .false.
     a%device_sample = .false.
+    a%top_k = 0
+    a%top_p = 1
+    a%min_p = 0
     a%prefill = .false.
     a%stream_load = .false.
     a%timings = .false.
@@ -90,6 +96,9 @@ contains
        case ("--ak");                a%ak = .true.;            i = i + 1
        case ("--device-argmax");     a%device_argmax = .true.; i = i + 1
        case ("--device-sample");     a%device_sample = .true.; i = i + 1
+       case ("--top-k");             read (val, *) a%top_k;       i = i + 2
+       case ("--top-p");             read (val, *) a%top_p;       i = i + 2
+       case ("--min-p");             read (val, *) a%min_p;       i = i + 2
        case ("--prefill");           a%prefill = .true.;       i = i + 1
        case ("--stream-load");       a%stream_load = .true.;   i = i + 1
        case ("--timings");           a%timings = .true.;       i = i + 1
@@ -185,6 +194,8 @@ program llm
   real(kind=wp) :: rope_base
   logical :: dsample                                ! --device-sample in its case: -t > 0 on one GPU
   integer(c_int64_t) :: dseed                       ! its seed: --seed N, or the clock's
+  logical :: filtered                               ! --top-k / --top-p / --min-p given
+  type(llmk_sampler) :: sampler
   integer(c_int) :: dnext
   integer(c_int), allocatable, target :: sc_targets(:)   ! --score: the prompt's tokens, each the target of the position before it
   real(c_float), allocatable, target :: sc_logprob(:)
@@ -328,7 +339,14 @@ program llm
 
   ! --device-sample: EVERY id after the prompt is drawn on the device (llmk_forward_sample / llmk_decode_sample), the first one
   ! and the one after a --prefill prompt included, so the transcript is a function of (model, prompt, T, seed) alone
-  dsample = opts%device_sample .and. opts%temperature > 0 .and. opts%ngpu == 1
+  ! --top-k / --top-p / --min-p: the truncations live in the device sampler only, so with -t > 0 they select it
+  filtered = opts%top_k /= 0 .or. opts%top_p /= 1 .or. opts%min_p /= 0
+  if (filtered .and. opts%temperature == 0 .and. lead) &
+       write (0, '(A)') "llm: --top-k / --top-p / --min-p are ignored at temperature 0 (the greedy pick needs no truncation)"
+  if (filtered .and. opts%temperature > 0 .and. opts%ngpu /= 1 .and. lead) &
+       write (0, '(A)') "llm: --top-k / --top-p / --min-p are ignored with --ngpu > 1 (the device sampler runs on one GPU, " // &
+       "the host sampler does not truncate)"
+  dsample = (opts%device_sample .or. filtered) .and. opts%temperature > 0 .and. opts%ngpu == 1
   if (dsample) then
      if (opts%seed >= 0) then
         dseed = int(opts%seed, c_int64_t)
@@ -336,6 +354,13 @@ program llm
         call system_clock(dseed)
      end if
      if (opts%verbose .and. lead) print *, "device sampler seed:", dseed
+     sampler%temperature = real(opts%temperature, c_float)
+     sampler%top_k = int(opts%top_k, c_int32_t)
+     sampler%top_p = real(opts%top_p, c_float)
+     sampler%min_p = real(opts%min_p, c_float)
+     sampler%seed = dseed
+     if (opts%verbose_ext .and. lead) print '(A,F8.4,A,I0,A,F8.5,A,F8.5)', " device sampler: temperature", opts%temperature, &
+          " top_k ", opts%top_k, " top_p", opts%top_p, " min_p", opts%min_p
   end if
 
   ! ---- generation loop (llama2.f90:376-402) -------------------------------------------------------
@@ -388,13 +413,12 @@ program llm
   ! tokens by what follows, so that token is produced, and the clock started, before the pipelined launches are enqueued
   ! (started at the first streamed id instead, several tokens had already completed: the printed rate was slightly high).
   loop_end = seq_len
-  ! --device-sample likewise, with llmk_forward_sample / llmk_decode_sample
+  ! --device-sample likewise, with llmk_forward_sample_ex / llmk_decode_sample_ex (all filters off: llmk_forward_sample / llmk_decode_sample)
   if ((opts%device_argmax .and. opts%temperature == 0 .and. opts%ngpu == 1) .or. dsample) &
        loop_end = min(seq_len, max(size(prompt_tokens), pos0))
   do pos = pos0, loop_end
      if (dsample .and. pos > size(prompt_tokens)) then
-        call llmk_check(llmk_forward_sample(ctx, int(token, c_int), int(pos, c_int), real(opts%temperature, c_float), dseed, &
-             dnext), "llmk_forward_sample")
+        call llmk_check(llmk_forward_sample_ex(ctx, int(token, c_int), int(pos, c_int), sampler, dnext), "llmk_forward_sample_ex")
         next_tok = dnext
         token = next_tok
         if (lead) write (*, fmt="(A)", advance="no") vocab(token)(1:vocab_len(token))
@@ -420,8 +444,8 @@ program llm
      ts_len = vocab_len
      ts_print = lead
      if (dsample) then
-        call llmk_check(llmk_decode_sample(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
-             real(opts%temperature, c_float), dseed, stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample")
+        call llmk_check(llmk_decode_sample_ex(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
+             sampler, stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample_ex")
      else
         call llmk_check(llmk_decode_greedy(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
              stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_greedy")

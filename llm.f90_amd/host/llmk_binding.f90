@@ -16,6 +16,14 @@ module llmk_binding
      integer(c_int32_t) :: weight_type, device, flags
   end type llmk_config
 
+  ! the sampler of llmk_forward_sample_ex / llmk_decode_sample_ex: top_k = 0, top_p = 1, min_p = 0 are "off"
+  type, bind(C) :: llmk_sampler
+     real(c_float) :: temperature
+     integer(c_int32_t) :: top_k
+     real(c_float) :: top_p, min_p
+     integer(c_int64_t) :: seed
+  end type llmk_sampler
+
   interface
      integer(c_int) function llmk_create(cfg, ctx) bind(C, name="llmk_create")
        import :: c_int, c_ptr, llmk_config
@@ -148,6 +156,34 @@ module llmk_binding
        integer(c_int), intent(out) :: ids_out(*)
        type(c_funptr), value :: on_token
        type(c_ptr), value :: user
+     end function
+     ! ... and with top-k / top-p / min-p truncation in front of the draw (include/llmk.h; all filters off: the two above)
+     integer(c_int) function llmk_forward_sample_ex(ctx, token, pos, sampler, next_token) bind(C, name="llmk_forward_sample_ex")
+       import :: c_int, c_ptr, llmk_sampler
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos
+       type(llmk_sampler), intent(in) :: sampler
+       integer(c_int), intent(out) :: next_token
+     end function
+     integer(c_int) function llmk_decode_sample_ex(ctx, token, pos0, n, sampler, ids_out, on_token, user) &
+          bind(C, name="llmk_decode_sample_ex")
+       import :: c_int, c_ptr, c_funptr, llmk_sampler
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos0, n
+       type(llmk_sampler), intent(in) :: sampler
+       integer(c_int), intent(out) :: ids_out(*)
+       type(c_funptr), value :: on_token
+       type(c_ptr), value :: user
+     end function
+     ! verification hook: the rule on caller-supplied logits (vocab_size floats), no token pass
+     integer(c_int) function llmk_sample_logits(ctx, logits, pos, sampler, token_out, kept_out, tau_out) bind(C, name="llmk_sample_logits")
+       import :: c_int, c_ptr, c_float, llmk_sampler
+       type(c_ptr), value :: ctx
+       real(c_float), intent(in) :: logits(*)
+       integer(c_int), value :: pos
+       type(llmk_sampler), intent(in) :: sampler
+       integer(c_int), intent(out) :: token_out, kept_out
+       real(c_float), intent(out) :: tau_out
      end function
      integer(c_int) function llmk_path(ctx) bind(C, name="llmk_path")
        import :: c_int, c_ptr

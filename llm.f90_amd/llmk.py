@@ -25,7 +25,7 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_tp_p2p_connect_local", "llmk_tp_p2p_selftest", "llmk_tp_p2p_stress", "llmk_tp_p2p_disable", "llmk_tp_begin", "llmk_tp_segment",
            "llmk_tp_read_partial", "llmk_tp_write_partial", "llmk_tp_read_logits", "llmk_upload", "llmk_upload_rows",
            "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
-           "llmk_forward_sample", "llmk_decode_sample", "llmk_score", "llmk_reset", "llmk_timings",
+           "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_score", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -44,6 +44,15 @@ class LlmkError(RuntimeError):
 class Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("emb_dim", "hidden_dim", "n_layers", "n_heads", "n_kv_heads", "vocab_size",
                                          "seq_len", "weight_type", "device", "flags")]
+
+
+class Sampler(C.Structure):
+    """llmk_sampler: temperature T > 0; top_k = 0, top_p = 1, min_p = 0 are "off" (include/llmk.h)"""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("seed", C.c_uint64)]
+
+
+def sampler(temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> Sampler:
+    return Sampler(temperature, top_k, top_p, min_p, seed & 0xFFFFFFFFFFFFFFFF)
 
 
 def build_lib(force: bool = False) -> str:
@@ -90,6 +99,10 @@ def lib():
         if hasattr(L, "llmk_forward_sample"):     # (absent from an older build selected with LLMK_LIB for an A/B)
             L.llmk_forward_sample.argtypes = [vp, ci, ci, C.c_float, C.c_uint64, C.POINTER(ci)]
             L.llmk_decode_sample.argtypes = [vp, ci, ci, ci, C.c_float, C.c_uint64, C.POINTER(ci), vp, vp]
+        if hasattr(L, "llmk_sample_logits"):
+            L.llmk_forward_sample_ex.argtypes = [vp, ci, ci, C.POINTER(Sampler), C.POINTER(ci)]
+            L.llmk_decode_sample_ex.argtypes = [vp, ci, ci, ci, C.POINTER(Sampler), C.POINTER(ci), vp, vp]
+            L.llmk_sample_logits.argtypes = [vp, cf, ci, C.POINTER(Sampler), C.POINTER(ci), C.POINTER(ci), cf]
         if hasattr(L, "llmk_score"):
             L.llmk_score.argtypes = [vp, C.POINTER(ci), ci, ci, C.POINTER(ci), cf, C.POINTER(ci), cf]
         L.llmk_reset.argtypes = [vp]
@@ -253,6 +266,36 @@ class Llmk:
         _ck(lib().llmk_decode_sample(self._h, token, pos0, n, temperature, seed & 0xFFFFFFFFFFFFFFFF,
                                      ids.ctypes.data_as(C.POINTER(C.c_int)), C.cast(cb, C.c_void_p) if cb else None, None))
         return ids
+
+    def forward_sample_ex(self, token: int, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
+                          min_p: float = 0.0) -> int:
+        """forward_sample with top-k / top-p / min-p truncation in front of the draw (llmk_forward_sample_ex, sample_filter.h)."""
+        nxt = C.c_int(0)
+        sp = sampler(temperature, seed, top_k, top_p, min_p)
+        _ck(lib().llmk_forward_sample_ex(self._h, token, pos, C.byref(sp), C.byref(nxt)))
+        return nxt.value
+
+    def decode_sample_ex(self, token: int, pos0: int, n: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
+                         min_p: float = 0.0, on_token=None) -> np.ndarray:
+        """decode_sample with top-k / top-p / min-p truncation (llmk_decode_sample_ex); returns the n ids."""
+        ids = np.zeros(n, np.int32)
+        cb = TOKEN_FN(on_token) if on_token else None
+        sp = sampler(temperature, seed, top_k, top_p, min_p)
+        _ck(lib().llmk_decode_sample_ex(self._h, token, pos0, n, C.byref(sp), ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                        C.cast(cb, C.c_void_p) if cb else None, None))
+        return ids
+
+    def sample_logits(self, logits, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
+        """The device sampler's rule on caller-supplied logits (V floats), no token pass (llmk_sample_logits):
+        (1-based token, rows kept, tau)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.shape != (self.V,):
+            raise ValueError("one logit per vocabulary row")
+        tok, kept, tau = C.c_int(0), C.c_int(0), C.c_float(0)
+        sp = sampler(temperature, seed, top_k, top_p, min_p)
+        _ck(lib().llmk_sample_logits(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, C.byref(sp), C.byref(tok), C.byref(kept),
+                                     C.byref(tau)))
+        return tok.value, kept.value, tau.value
 
     def generate(self, n: int, prompt=(), want_logits: bool = True, greedy_on_device: bool = False):
         """The reference generation loop at temperature 0 (llama2.f90:376-402)."""
