@@ -103,18 +103,22 @@ struct llmk_ctx {
     float *d_x = nullptr, *d_q = nullptr, *d_xb = nullptr, *d_hb = nullptr, *d_logits = nullptr, *d_rope = nullptr;
     int *d_tokpos = nullptr, *d_next = nullptr;
     int* h_tokpos = nullptr;  // pinned {token0, pos1}
-    float* h_logits = nullptr;  // pinned [V] (+ error word)
+    float* h_logits = nullptr;  // pinned [V], then host_words()
     float* h_logits_dev = nullptr;   // the same buffer as the device sees it (token kernel direct mode)
     bool tk_direct = true;
-    int* h_next = nullptr;      // pinned
+    TkNext* h_next = nullptr;   // pinned
+    // the scratch words behind the logits vectors (scratch_layout.h): the device's, the host's, the host's as the device sees them
+    TkDevWords* dev_words() const { return tk_words_behind<TkDevWords>(d_logits, V); }
+    TkHostWords* host_words() const { return tk_words_behind<TkHostWords>(h_logits, V); }
+    TkHostWords* host_words_dev() const { return tk_words_behind<TkHostWords>(h_logits_dev, V); }
     hipStream_t stream = nullptr;
     hipGraphExec_t graph_logits = nullptr, graph_greedy = nullptr, graph_sample = nullptr, graph_filter = nullptr;
     llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current llmk_forward_sample / llmk_decode_sample call
-    // what the device's copy of them (d_sample_params) holds once the stream has drained: zeros from llmk_create on; pad = 1 while
+    // what the device's copy of them (TkDevWords::samp) holds once the stream has drained: zeros from llmk_create on; pad = 1 while
     // unknown.  A pipelined decode writes them only when they differ, so a greedy one on a ctx that never sampled enqueues nothing new
     llmk_sample_params samp_dev = {};
     // the same pair for the truncated sampler (llmk_*_sample_ex with a filter on): its parameters sit behind the sampling words
-    // (d_filter_params); filt_known = filt_dev is what the device holds
+    // (TkDevWords::filt); filt_known = filt_dev is what the device holds
     llmk_filter_params* h_filt = nullptr;
     llmk_filter_params filt_dev = {};
     bool filt_known = false;
@@ -135,10 +139,10 @@ struct llmk_ctx {
     float4* d_zeros = nullptr;
     unsigned long long* d_trace = nullptr;  // debug stamps (LLMK_TK_TRACE=1)
     size_t tk_lds = 0;
-    size_t tk_ngran = 0;   // granules in d_gran (the last 4 * TK_QSC_LMAX: the q4_0 kernels' per-layer scale records)
+    size_t tk_ngran = 0;   // granules in d_gran (the last TK_QSC_GRANULES: the q4_0 kernels' per-layer scale records, tk_qsc_records)
     // pipelined greedy decode (llmk_decode_greedy): per-CU classifier maxima of the last two launches, and the ids as they
     // are resolved (host-mapped; 0 = not there yet)
-    // (the candidates sit behind the device error word, the ids behind the host error word: token_kernel.h tk_cand)
+    // (the candidates sit behind the device error word, the ids behind the host error word: scratch_layout.h)
     // batched prefill (prefill.h), allocated by the first llmk_prefill.  Two LANES = workspace set + stream: consecutive
     // 128-position batches of a prompt alternate between them, so one batch's small kernels (epilogues, attention) and
     // launch gaps run under the other's GEMMs.  The only cross-batch dependency is the KV cache: batch k+1's attention in
@@ -151,6 +155,7 @@ struct llmk_ctx {
         hipEvent_t done = nullptr;         // this lane's batch has left the last layer
     } pf[2];
     int* pf_tok = nullptr;
+    std::vector<int> pf_tok0;              // what pf_tok is uploaded from: alive until the call has synchronised
     hipEvent_t pf_start = nullptr;         // tokens are on the device (and everything before the prefill call is done)
     bool pf_ready = false;                 // pf_setup ran to its end
     // uploads are staged through the shim's OWN pinned memory (upload_block): two buffers, an event each
@@ -289,26 +294,28 @@ hipError_t launch_gemv_t(int wt, hipStream_t st, const GemvArgs& a, int n_cu) {
     }
 }
 
+// f(std::integral_constant<int, hs>()) for the head sizes llmk_create_tp admits: the head size as a compile-time constant
+template <class F>
+hipError_t with_head_size(int hs, F f) {
+    switch (hs) {
+        case 16: return f(std::integral_constant<int, 16>());
+        case 32: return f(std::integral_constant<int, 32>());
+        case 64: return f(std::integral_constant<int, 64>());
+        case 128: return f(std::integral_constant<int, 128>());
+    }
+    return hipErrorInvalidValue;
+}
 hipError_t launch_attn(llmk_ctx* c, int l) {
     const float* kc = c->d_kc + (size_t)l * c->S * c->KVl;
     const float* vc = c->d_vc + (size_t)l * c->S * c->KVl;
     const size_t smem = (516 + (size_t)c->S) * sizeof(float);
-#define ATT(HS_)                                                                                                 \
-    do {                                                                                                         \
-        hipError_t pe;                                                                                           \
-        if (prepare_only(attn_kernel<HS_>, smem, &pe)) return pe;                                                \
-        hipLaunchKernelGGL((attn_kernel<HS_>), dim3(c->nhl), dim3(256), smem, c->stream, c->d_q, kc, vc, c->d_xb, \
-                           c->d_tokpos, c->KVl, c->kv_mul);                                                      \
-    } while (0)
-    switch (c->hs) {
-        case 16: ATT(16); break;
-        case 32: ATT(32); break;
-        case 64: ATT(64); break;
-        case 128: ATT(128); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef ATT
-    return hipGetLastError();
+    return with_head_size(c->hs, [&](auto hs) {
+        constexpr int HS = decltype(hs)::value;
+        hipError_t pe;
+        if (prepare_only(attn_kernel<HS>, smem, &pe)) return pe;
+        hipLaunchKernelGGL((attn_kernel<HS>), dim3(c->nhl), dim3(256), smem, c->stream, c->d_q, kc, vc, c->d_xb, c->d_tokpos, c->KVl, c->kv_mul);
+        return hipGetLastError();
+    });
 }
 
 GemvArgs base_args(llmk_ctx* c, int tid, int l, const float* x, const float* norm_w, float* y) {
@@ -413,8 +420,8 @@ hipError_t launch_token_kernel_t(llmk_ctx* c, bool direct, const TkGreedy& g) {
     a.serial_imm = c->h_tokpos[2];
     a.g_qkv = c->d_gran;         // qkv | xb | xa | hb | x (token_kernel.h tk_g_xb ...)
     a.logits = direct ? c->h_logits_dev : c->d_logits;
-    a.err = reinterpret_cast<unsigned*>(c->d_logits + c->V);
-    a.herr = (direct || g.gflags) ? reinterpret_cast<unsigned*>(c->h_logits_dev + c->V) : nullptr;
+    a.err = &c->dev_words()->err;
+    a.herr = (direct || g.gflags) ? &c->host_words_dev()->err : nullptr;
     a.zeros = c->d_zeros;
 #ifdef LLMK_TK_DEBUG
     a.trace = c->d_trace;
@@ -503,7 +510,9 @@ int tk_setup(llmk_ctx* c, int id) {
     // qkv | xb | xa | hb | x | per head: the (PMAX - 1) other parts of a long context's attention (HS values + maximum + sum each)
     // (+ 4 granule slots per layer behind them (two buffers by position parity): the q4_0 kernels' per-layer records of the previous position's largest xb / hb elements,
     // token_kernel.h tk_qsc; cleared by llmk_reset)
-    const size_t ngran = (size_t)TK::QKV + 3 * (size_t)TK::E + TK::H + (size_t)TK::NH * (TkAttPlan<TK>::PMAX - 1) * (TK::HS + 2) + 4 * (size_t)TK_QSC_LMAX;
+    static_assert(tk_qsc_front<TK>() == (size_t)TK::QKV + 3 * (size_t)TK::E + TK::H + (size_t)TK::NH * (TkAttPlan<TK>::PMAX - 1) * (TK::HS + 2),
+                  "tk_qsc_front: the attention parts are TkAttPlan's");
+    const size_t ngran = tk_qsc_front<TK>() + TK_QSC_GRANULES;
     c->tk_ngran = ngran;
     if (!c->d_gran) HIPCHK(dev_alloc(&c->d_gran, ngran * sizeof(unsigned long long)));      // (kept over a re-type of the classifier: same shape)
     if (!c->d_zeros) HIPCHK(dev_alloc(&c->d_zeros, (size_t)TK_NCU * TK_WAVES * 1024));
@@ -527,33 +536,39 @@ int tk_setup_all(llmk_ctx* c) {
 __global__ void bump_serial_kernel(int* tokpos) { tokpos[2] += 1; }
 
 // What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
-// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h); the last three leave the 1-based id in h_next[0] and
-// the sticky error word in h_next[1]
+// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h); the last three leave the 1-based id in h_next->id and
+// the sticky error word in h_next->err
 enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE, TAIL_FILTER };
-// the sampling parameters in device memory: behind the error word and the pipelined decode's two candidate buffers
-// (token_kernel.h tk_sample_params reads the same words)
-llmk_sample_params* d_sample_params(llmk_ctx* c) { return reinterpret_cast<llmk_sample_params*>(c->d_logits + c->V + 4 + 4 * TK_NCU); }
-llmk_filter_params* d_filter_params(llmk_ctx* c) { return reinterpret_cast<llmk_filter_params*>(c->d_logits + c->V + 8 + 4 * TK_NCU); }
-unsigned* d_filter_out(llmk_ctx* c) { return reinterpret_cast<unsigned*>(c->d_logits + c->V + 16 + 4 * TK_NCU); }
+// the q4_0 persistent kernels' per-layer scale records (token_kernel.h tk_qsc): the last *n granules of d_gran; null on a context
+// that has none
+unsigned long long* tk_qsc_records(const llmk_ctx* c, size_t* n) {
+    *n = TK_QSC_GRANULES;
+    return c->d_gran && c->tk_ngran ? c->d_gran + (c->tk_ngran - TK_QSC_GRANULES) : nullptr;
+}
+hipError_t tk_qsc_clear(llmk_ctx* c, hipStream_t st) {
+    size_t n;
+    unsigned long long* rec = tk_qsc_records(c, &n);
+    return rec ? hipMemsetAsync(rec, 0, n * sizeof(unsigned long long), st) : hipSuccess;
+}
 hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
     if (tail != TAIL_LOGITS) {
         if (tail == TAIL_FILTER) {
             // the same kernel as behind a launch of the pipelined decode (decode_run), with the position from the pass's device word
-            HIPRET(hipMemcpyAsync(d_filter_params(c), c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, d_filter_params(c),
-                               c->d_next, (float2*)nullptr, 0, d_filter_out(c));
+            HIPRET(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, &c->dev_words()->filt,
+                               c->d_next, (float2*)nullptr, 0, c->dev_words()->filter_out);
         } else if (tail == TAIL_SAMPLE) {
             // invT and the seed travel like token and position: a copy out of pinned memory, read when the graph replays it
-            HIPRET(hipMemcpyAsync(d_sample_params(c), c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_tokpos, d_sample_params(c), c->d_next);
+            HIPRET(hipMemcpyAsync(&c->dev_words()->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_tokpos, &c->dev_words()->samp, c->d_next);
         } else {
             hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_next);
         }
         HIPRET(hipGetLastError());
-        HIPRET(hipMemcpyAsync(c->h_next, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPRET(hipMemcpyAsync(c->h_next + 1, c->d_logits + c->V, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    } else {
-        HIPRET(hipMemcpyAsync(c->h_logits, c->d_logits, ((size_t)c->V + 1) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPRET(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPRET(hipMemcpyAsync(&c->h_next->err, &c->dev_words()->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    } else {      // the logits and, behind them, the error word: TkDevWords::err lands in TkHostWords::err
+        HIPRET(hipMemcpyAsync(c->h_logits, c->d_logits, (size_t)c->V * sizeof(float) + sizeof(TkDevWords::err), hipMemcpyDeviceToHost, c->stream));
     }
     return hipSuccess;
 }
@@ -595,7 +610,7 @@ int enqueue_token_tp(llmk_ctx* c) {
 // jseed != 0: the jittered instantiation (llmk_tp_p2p_stress only)
 hipError_t launch_tp_allreduce_add(llmk_ctx* c, int call, unsigned jseed = 0) {   // x += sum over ranks of d_part   (:603-605, :618-620)
     const dim3 grid((c->E + 255) / 256), block(256);
-    unsigned* err = reinterpret_cast<unsigned*>(c->d_logits + c->V);
+    unsigned* err = &c->dev_words()->err;
     if (jseed) hipLaunchKernelGGL(tp_allreduce_add_kernel<true>, grid, block, 0, c->stream, c->peers, c->d_part, c->d_x, c->d_tokpos, call,
                                   2 * c->L, c->tp_rank, c->tp_size, c->E, err, jseed);
     else hipLaunchKernelGGL(tp_allreduce_add_kernel<false>, grid, block, 0, c->stream, c->peers, c->d_part, c->d_x, c->d_tokpos, call,
@@ -604,7 +619,7 @@ hipError_t launch_tp_allreduce_add(llmk_ctx* c, int call, unsigned jseed = 0) { 
 }
 hipError_t launch_tp_allgather(llmk_ctx* c, unsigned jseed = 0) {   // every rank's classifier rows into every rank's logits   (:634-636)
     const dim3 grid((c->V + 255) / 256), block(256);
-    unsigned* err = reinterpret_cast<unsigned*>(c->d_logits + c->V);
+    unsigned* err = &c->dev_words()->err;
     if (jseed) hipLaunchKernelGGL(tp_allgather_kernel<true>, grid, block, 0, c->stream, c->peers, c->d_logits, c->d_tokpos, 2 * c->L,
                                   c->tp_rank, c->tp_size, c->E, c->V, err, jseed);
     else hipLaunchKernelGGL(tp_allgather_kernel<false>, grid, block, 0, c->stream, c->peers, c->d_logits, c->d_tokpos, 2 * c->L,
@@ -692,10 +707,10 @@ int check_ready(llmk_ctx* c) {
 // which rewrites that position's KV rows and recomputes x from the embedding: nothing of the failed launch survives.
 constexpr int TK_RANGE_LIMIT = 4;
 int tk_clear_err(llmk_ctx* c) {
-    HIPCHK(hipMemsetAsync(c->d_logits + c->V, 0, sizeof(float), c->stream));
+    HIPCHK(hipMemsetAsync(&c->dev_words()->err, 0, sizeof(unsigned), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
-    c->h_next[1] = 0;
+    c->host_words()->err = 0;
+    c->h_next->err = 0;
     return LLMK_OK;
 }
 // 0x4000 and nothing else: this position's activations did not fit the q4_0 kernels' f16 image; the kernel itself is sound
@@ -754,7 +769,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
         } else if (timed || (c->cfg.flags & LLMK_FLAG_NO_GRAPH)) {
             HIPCHK(enqueue_token(c, tail, timed));
         } else if (c->use_tk && tail == TAIL_LOGITS && c->tk_direct) {
-            reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
+            c->host_words()->err = 0;
             HIPCHK(launch_token_kernel(c, true));
         } else {
             hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : tail == TAIL_FILTER ? &c->graph_filter : &c->graph_logits;
@@ -766,14 +781,14 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         if (c->p2p) {   // a peer never delivered its granules: the sticky word says so (cleared by llmk_reset)
-            const unsigned perr = tail != TAIL_LOGITS ? (unsigned)c->h_next[1] : reinterpret_cast<unsigned*>(c->h_logits)[c->V];
+            const unsigned perr = tail != TAIL_LOGITS ? c->h_next->err : c->host_words()->err;
             char what[160];
             if (perr) fprintf(stderr, "llmk: rank %d of %d: a peer's granules never arrived (%s; position %d, serial %d)\n",
                               c->tp_rank, c->tp_size, tp_describe_err(c, perr, what, sizeof(what)), pos, c->h_tokpos[2]);
             return perr ? LLMK_E_TIMEOUT : LLMK_OK;
         }
         if (!c->use_tk) return LLMK_OK;
-        const unsigned err = tail != TAIL_LOGITS ? (unsigned)c->h_next[1] : reinterpret_cast<unsigned*>(c->h_logits)[c->V];
+        const unsigned err = tail != TAIL_LOGITS ? c->h_next->err : c->host_words()->err;
         if (err == 0) { c->tk_range_run = 0; return LLMK_OK; }
         if (tk_range_only(err) && c->tk_range_run + 1 < TK_RANGE_LIMIT) {
             // THIS position on the multi-kernel path (f32 activations throughout; eager launches: the ctx's graphs hold the token
@@ -976,14 +991,10 @@ hipError_t pf_prepare_type(int wt) {
 }
 hipError_t pf_prepare(const llmk_ctx* c) {
     HIPRET(pf_prepare_type(c->cfg.weight_type));
-    const int smem = (int)pf_attn_smem(c->hs);
-    switch (c->hs) {
-        case 16: return hipFuncSetAttribute((const void*)pf_attn_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        case 32: return hipFuncSetAttribute((const void*)pf_attn_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        case 64: return hipFuncSetAttribute((const void*)pf_attn_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        case 128: return hipFuncSetAttribute((const void*)pf_attn_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    }
-    return hipErrorInvalidValue;
+    return with_head_size(c->hs, [](auto hs) {
+        constexpr int HS = decltype(hs)::value;
+        return hipFuncSetAttribute((const void*)pf_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pf_attn_smem(HS));
+    });
 }
 template <int NG, int NR>
 hipError_t pf_gemm_launch(llmk_ctx* c, const PfLane& w, const PfGemmArgs& a, const PfPlan& p, int wt) {
@@ -1174,21 +1185,12 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
         if (!last) HIPRET(hipEventRecord(w.kv[l], w.stream));             // the next batch's attention reads these rows
         if (prev) HIPRET(hipStreamWaitEvent(w.stream, prev->kv[l], 0));   // ... as this one reads the previous batch's
         // causal attention: position pos0+t sees cache rows 0 .. pos0+t-1                 :572-598
-#define ATT(HS_)                                                                                                         \
-    do {                                                                                                                 \
-        const size_t smem = pf_attn_smem(HS_);                                                                           \
-        hipLaunchKernelGGL((pf_attn_kernel<HS_>), dim3(c->nh, (T + 15) / 16), dim3(PF_ATT_WAVES * WAVE), smem, w.stream, \
-                           w.Q, kc, vc, w.XB, KV, c->kv_mul, pos0, T, E);                                        \
-    } while (0)
-        switch (c->hs) {
-            case 16: ATT(16); break;
-            case 32: ATT(32); break;
-            case 64: ATT(64); break;
-            case 128: ATT(128); break;
-            default: return hipErrorInvalidValue;
-        }
-#undef ATT
-        HIPRET(hipGetLastError());
+        HIPRET(with_head_size(c->hs, [&](auto hs) {
+            constexpr int HS = decltype(hs)::value;
+            hipLaunchKernelGGL((pf_attn_kernel<HS>), dim3(c->nh, (T + 15) / 16), dim3(PF_ATT_WAVES * WAVE), pf_attn_smem(HS), w.stream,
+                               w.Q, kc, vc, w.XB, KV, c->kv_mul, pos0, T, E);
+            return hipGetLastError();
+        }));
         // x += wo . xb                                                                    :603-605
         HIPRET(gemm(LLMK_WO, E, w.XB, E));
         e.rows = E; e.out = w.X;
@@ -1212,6 +1214,71 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
     if (sj) HIPRET(sc_batch(c, w, &w == &c->pf[1] ? 1 : 0, e, *sj, T, i0));
     if (last) HIPRET(hipMemcpyAsync(c->d_x, w.X + (size_t)(T - 1) * E, (size_t)E * sizeof(float), hipMemcpyDeviceToDevice, w.stream));
     return hipEventRecord(w.done, w.stream);
+}
+
+// May this context take the batched pass (llmk_prefill, llmk_score)?  Single GPU, shapes on the GEMMs' 64-column step, not switched off
+bool pf_eligible(const llmk_ctx* c) {
+    const int pf_step = PF_KSTEP;
+    return c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0 &&
+           !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
+}
+// The batched pass of llmk_prefill and (sj: with the classifier and log-softmax of every position) llmk_score, ENQUEUED: tokens[0..n)
+// (1-based ids) at positions pos0 .. pos0+n-1 in batches of PF_TMAX that alternate between the two lanes, then the f16-range flag on
+// its way to TkHostWords::pf_flag.  The caller adds its own tail to the ctx stream and synchronises that stream once: everything
+// lane 1 was given is ordered in front of it.
+int pf_run(llmk_ctx* c, const int* tokens, int n, int pos0, const ScoreJob* sj) {
+    c->pf_tok0.assign(tokens, tokens + n);
+    for (int& t : c->pf_tok0) --t;
+    HIPCHK(hipMemcpyAsync(c->pf_tok, c->pf_tok0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // these positions are being rewritten by other kernels: whatever an earlier sequence's decode left in the q4_0 persistent kernel's
+    // scale records (token_kernel.h tk_qsc; tagged by position only) must not pass for "the position before" of the decode that follows
+    HIPCHK(tk_qsc_clear(c, c->stream));
+    HIPCHK(hipEventRecord(c->pf_start, c->stream));
+    HIPCHK(hipStreamWaitEvent(c->pf[1].stream, c->pf_start, 0));
+    int k = 0;
+    for (int i = 0; i < n; i += PF_TMAX, ++k) {
+        // batch k runs on lane k % 2; its lane's previous batch (k - 2) is ordered by the stream, batch k - 1 by the KV events
+        const bool last = i + PF_TMAX >= n;
+        const hipError_t pe = pf_batch(c, c->pf[k & 1], k > 0 ? &c->pf[(k - 1) & 1] : nullptr, c->pf_tok + i, std::min(PF_TMAX, n - i), pos0 + i, last, sj, i);
+        if (pe != hipSuccess) {   // nothing of this call may still be running (on either lane) when it returns
+            hipStreamSynchronize(c->pf[1].stream);
+            hipStreamSynchronize(c->stream);
+            return LLMK_E_HIP + (int)pe;
+        }
+    }
+    // what follows runs on the ctx stream (= lane 0's): after everything lane 1 was given, too
+    if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->pf[1].done, 0));
+    unsigned* h_flag = &c->host_words()->pf_flag;
+    *h_flag = 0;
+    if (c->pf_hm) HIPCHK(hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    return LLMK_OK;
+}
+// did the synchronised call's batched pass raise the f16-range flag?
+bool pf_flagged(const llmk_ctx* c) { return c->pf_hm && c->host_words()->pf_flag != 0; }
+
+// The f16-range flag of a batched call (prefill.h pf_gemm_h_kernel, pf_low_check) came back raised.
+// bit 0: an activation of this prompt does not fit an f16 (|x| >= 65504, or not finite): this context's GEMMs go back to
+// the f32 matrix instruction for good.  Bit 1 alone: a position whose whole row is below 2^-7 (the lo piece of the split
+// is an f16 subnormal there): THIS call is redone on the f32 instruction, the next one tries the f16 one again (advisor,
+// round 4: a BOS or early-layer row with genuinely small values must not cost the context the fast path).
+// Either way the call is redone (again(): the K/V rows it wrote are rewritten) and the first event says so once.
+template <class F>
+int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
+    const bool for_good = (c->host_words()->pf_flag & 1u) != 0;
+    if (!*told) {
+        *told = true;
+        fprintf(stderr, "llmk: %s met %s; %s\n", who, for_good ? "an activation beyond the f16 range" : "a position whose activations are all below 2^-7",
+                for_good ? "this context's prompt GEMMs run on the f32 matrix instruction from now on" : "this call is redone on the f32 matrix instruction");
+    }
+    HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    pf_teardown(c);
+    c->pf_hm = false;
+    int rc = pf_setup(c);
+    if (rc) return rc;
+    rc = again();
+    if (!for_good) pf_teardown(c);          // (pf_ready = false: the next call sets the f16 instruction up again)
+    return rc;
 }
 
 }  // namespace
@@ -1333,19 +1400,18 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(dev_alloc(&c->d_xb, (size_t)E * sizeof(float)));
     CK(dev_alloc(&c->d_hb, (size_t)H * sizeof(float)));
     CK(dev_alloc(&c->d_part, (size_t)E * sizeof(float)));
-    // [V] = sticky device error word; behind it (at V + 4) the two candidate buffers of the pipelined greedy decode, and behind
-    // those (at V + 4 + 4 * TK_NCU) the sampling parameters (d_sample_params), the truncated sampler's (d_filter_params, 8 words)
-    // and the two words its kernel leaves for verification (d_filter_out)
-    CK(dev_alloc(&c->d_logits, ((size_t)V + 24 + 4 * TK_NCU) * sizeof(float)));
+    // the logits, then the device's scratch words (scratch_layout.h TkDevWords: the sticky error word first)
+    const size_t logits_bytes = (size_t)V * sizeof(float) + sizeof(TkDevWords);
+    CK(dev_alloc(&c->d_logits, logits_bytes));
     CK(dev_alloc(&c->d_rope, (size_t)(hs / 2) * sizeof(float)));
     CK(dev_alloc(&c->d_tokpos, 4 * sizeof(int)));
     CK(dev_alloc(&c->d_next, 2 * sizeof(int)));
     CK(hipHostMalloc(&c->h_tokpos, 4 * sizeof(int), hipHostMallocDefault));
-    // [V] = the error word as the host sees it; behind it (at V + 4) the ids of llmk_decode_greedy, S ints
-    CK(hipHostMalloc(&c->h_logits, ((size_t)V + 4 + S) * sizeof(float), hipHostMallocMapped));
+    // the logits, then the host's scratch words (TkHostWords) and the S ids of the pipelined decode
+    CK(hipHostMalloc(&c->h_logits, (size_t)V * sizeof(float) + sizeof(TkHostWords) + (size_t)S * sizeof(int), hipHostMallocMapped));
     CK(hipHostGetDevicePointer((void**)&c->h_logits_dev, c->h_logits, 0));
     c->tk_direct = !(getenv("LLMK_TK_DIRECT") && getenv("LLMK_TK_DIRECT")[0] == '0');
-    CK(hipHostMalloc(&c->h_next, 4 * sizeof(int), hipHostMallocDefault));      // id, error word; rows kept, tau bits (llmk_sample_logits)
+    CK(hipHostMalloc(&c->h_next, sizeof(TkNext), hipHostMallocDefault));
     CK(hipHostMalloc(&c->h_samp, sizeof(llmk_sample_params), hipHostMallocDefault));
     CK(hipHostMalloc(&c->h_filt, sizeof(llmk_filter_params), hipHostMallocDefault));
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -1365,7 +1431,7 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
         else CK(pe);
     }
     if (rc == LLMK_OK) {
-        CK(hipMemset(c->d_logits, 0, ((size_t)V + 24 + 4 * TK_NCU) * sizeof(float)));
+        CK(hipMemset(c->d_logits, 0, logits_bytes));
         c->h_tokpos[0] = 0; c->h_tokpos[1] = 0; c->h_tokpos[2] = 0; c->h_tokpos[3] = 0;
         CK(hipMemset(c->d_kc, 0, kvn * sizeof(float)));  // s%key_cache(:,:,:) = 0   llama2.f90:317
         CK(hipMemset(c->d_vc, 0, kvn * sizeof(float)));
@@ -1726,27 +1792,6 @@ int llmk_forward(llmk_ctx* c, int token, int pos, float* logits_out) {
     return LLMK_OK;
 }
 
-// The f16-range flag of a batched call (prefill.h pf_gemm_h_kernel, pf_low_check) came back raised.
-// bit 0: an activation of this prompt does not fit an f16 (|x| >= 65504, or not finite): this context's GEMMs go back to
-// the f32 matrix instruction for good.  Bit 1 alone: a position whose whole row is below 2^-7 (the lo piece of the split
-// is an f16 subnormal there): THIS call is redone on the f32 instruction, the next one tries the f16 one again (advisor,
-// round 4: a BOS or early-layer row with genuinely small values must not cost the context the fast path).
-// Either way the caller redoes the call (the K/V rows it wrote are rewritten) and the first event says so once.
-static int pf_redo_setup(llmk_ctx* c, unsigned flag, const char* who, bool* told, bool* for_good_out) {
-    const bool for_good = (flag & 1u) != 0;
-    if (!*told) {
-        *told = true;
-        fprintf(stderr, "llmk: %s met %s; %s\n", who, for_good ? "an activation beyond the f16 range" : "a position whose activations are all below 2^-7",
-                for_good ? "this context's prompt GEMMs run on the f32 matrix instruction from now on" : "this call is redone on the f32 matrix instruction");
-    }
-    HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    pf_teardown(c);
-    c->pf_hm = false;
-    *for_good_out = for_good;
-    return pf_setup(c);
-}
-
 // The prompt loop of llama2.f90:376-402 as ONE call: tokens[0..n) (1-based ids) sit at positions pos0 .. pos0+n-1,
 // the KV cache rows of those positions are written, and logits_out receives the logits of the LAST position --
 // exactly what n llmk_forward calls leave behind.  f32 single-GPU contexts run the batched MFMA path (prefill.h);
@@ -1757,9 +1802,7 @@ int llmk_prefill(llmk_ctx* c, const int* tokens, int n, int pos0, float* logits_
     if (rc) return rc;
     for (int i = 0; i < n; ++i)
         if (tokens[i] < 1 || tokens[i] > c->V) return LLMK_E_ARG;
-    const int pf_step = PF_KSTEP;
-    const bool batched = c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0 && !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
-    if (!batched) {
+    if (!pf_eligible(c)) {
         for (int i = 0; i < n; ++i) {
             rc = run_token(c, tokens[i], pos0 + i, TAIL_LOGITS);
             if (rc) return rc;
@@ -1770,43 +1813,14 @@ int llmk_prefill(llmk_ctx* c, const int* tokens, int n, int pos0, float* logits_
     HIPCHK(hipSetDevice(c->cfg.device));
     rc = pf_setup(c, true);
     if (rc) return rc;
-    std::vector<int> tok0(tokens, tokens + n);
-    for (int& t : tok0) --t;
-    HIPCHK(hipMemcpyAsync(c->pf_tok, tok0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    // these positions are being rewritten by other kernels: whatever an earlier sequence's decode left in the q4_0 persistent kernel's
-    // scale records (token_kernel.h tk_qsc; tagged by position only) must not pass for "the position before" of the decode that follows
-    if (c->d_gran && c->tk_ngran)
-        HIPCHK(hipMemsetAsync(c->d_gran + c->tk_ngran - 4 * TK_QSC_LMAX, 0, 4 * TK_QSC_LMAX * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipEventRecord(c->pf_start, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->pf[1].stream, c->pf_start, 0));
-    int k = 0;
-    for (int i = 0; i < n; i += PF_TMAX, ++k) {
-        // batch k runs on lane k % 2; its lane's previous batch (k - 2) is ordered by the stream, batch k - 1 by the KV events
-        const bool last = i + PF_TMAX >= n;
-        const hipError_t pe = pf_batch(c, c->pf[k & 1], k > 0 ? &c->pf[(k - 1) & 1] : nullptr, c->pf_tok + i, std::min(PF_TMAX, n - i), pos0 + i, last);
-        if (pe != hipSuccess) {   // nothing of this call may still be running (on either lane) when it returns
-            hipStreamSynchronize(c->pf[1].stream);
-            hipStreamSynchronize(c->stream);
-            return LLMK_E_HIP + (int)pe;
-        }
-    }
-    // the classifier runs on the ctx stream (= lane 0's): after everything lane 1 was given, too -- nothing of this call is
-    // still running when it returns
-    if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->pf[1].done, 0));
+    rc = pf_run(c, tokens, n, pos0, nullptr);
+    if (rc) return rc;
     HIPCHK(launch_cls(c));                          // final rmsnorm + classifier of the last position   :627-636
     HIPCHK(hipMemcpyAsync(c->h_logits, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    unsigned* h_flag = reinterpret_cast<unsigned*>(c->h_logits + c->V + 1);
-    *h_flag = 0;
-    if (c->pf_hm) HIPCHK(hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->pf_hm && *h_flag) {
-        bool for_good;
+    if (pf_flagged(c)) {
         static bool told = false;           // (each entry point reports its own first event)
-        rc = pf_redo_setup(c, *h_flag, "llmk_prefill", &told, &for_good);
-        if (rc) return rc;
-        rc = llmk_prefill(c, tokens, n, pos0, logits_out);
-        if (!for_good) pf_teardown(c);          // (pf_ready = false: the next call sets the f16 instruction up again)
-        return rc;
+        return pf_redo(c, "llmk_prefill", &told, [&] { return llmk_prefill(c, tokens, n, pos0, logits_out); });
     }
     memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
     return LLMK_OK;
@@ -1825,9 +1839,9 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
     HIPCHK(hipSetDevice(c->cfg.device));
     rc = sc_setup(c);
     if (rc) return rc;
-    const int V = c->V, pf_step = PF_KSTEP;
+    const int V = c->V;
     ScoreJob sj{logprob_out != nullptr, logits_out != nullptr, n, ScPlan{0, 0, 0}};
-    bool batched = c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0 && !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
+    bool batched = pf_eligible(c);
     if (batched) {
         rc = pf_setup(c, true);
         if (rc) return rc;
@@ -1858,9 +1872,6 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
         for (int& t : tg0) --t;                                  // 0-based; -1 = no target here
         HIPCHK(hipMemcpyAsync(c->sc_targets, tg0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
-    unsigned* h_flag = reinterpret_cast<unsigned*>(c->h_logits + V + 1);
-    *h_flag = 0;
-    std::vector<int> tok0;
     if (!batched) {
         // tensor-parallel ranks, shapes off the 64-column step, LLMK_PREFILL=0: token by token; the pass leaves the position's logits in
         // the pinned vector (as for llmk_forward), one workgroup row of pf_score_kernel reads them from there
@@ -1881,37 +1892,15 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
             HIPCHK(hipStreamSynchronize(c->stream));             // (the next pass overwrites the pinned vector)
         }
     } else {
-        tok0.assign(tokens, tokens + n);
-        for (int& t : tok0) --t;
-        HIPCHK(hipMemcpyAsync(c->pf_tok, tok0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        if (c->d_gran && c->tk_ngran)        // (as llmk_prefill: the q4_0 persistent kernel's scale records of these positions)
-            HIPCHK(hipMemsetAsync(c->d_gran + c->tk_ngran - 4 * TK_QSC_LMAX, 0, 4 * TK_QSC_LMAX * sizeof(unsigned long long), c->stream));
-        HIPCHK(hipEventRecord(c->pf_start, c->stream));
-        HIPCHK(hipStreamWaitEvent(c->pf[1].stream, c->pf_start, 0));
-        int k = 0;
-        for (int i = 0; i < n; i += PF_TMAX, ++k) {
-            const bool last = i + PF_TMAX >= n;
-            const hipError_t pe = pf_batch(c, c->pf[k & 1], k > 0 ? &c->pf[(k - 1) & 1] : nullptr, c->pf_tok + i, std::min(PF_TMAX, n - i), pos0 + i, last, &sj, i);
-            if (pe != hipSuccess) {
-                hipStreamSynchronize(c->pf[1].stream);
-                hipStreamSynchronize(c->stream);
-                return LLMK_E_HIP + (int)pe;
-            }
-        }
-        if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->pf[1].done, 0));
-        if (c->pf_hm) HIPCHK(hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        rc = pf_run(c, tokens, n, pos0, &sj);
+        if (rc) return rc;
     }
     // the results: one copy, n floats and n ints
     HIPCHK(hipMemcpyAsync(c->h_sc, c->sc_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (batched && c->pf_hm && *h_flag) {
-        bool for_good;
+    if (batched && pf_flagged(c)) {
         static bool told = false;
-        rc = pf_redo_setup(c, *h_flag, "llmk_score", &told, &for_good);
-        if (rc) return rc;
-        rc = llmk_score(c, tokens, n, pos0, targets, logprob_out, argmax_out, logits_out);
-        if (!for_good) pf_teardown(c);
-        return rc;
+        return pf_redo(c, "llmk_score", &told, [&] { return llmk_score(c, tokens, n, pos0, targets, logprob_out, argmax_out, logits_out); });
     }
     const int* ids = reinterpret_cast<const int*>(c->h_sc + n);
     for (int i = 0; i < n; ++i)
@@ -1928,8 +1917,8 @@ int token_out(llmk_ctx* c, int token, int pos, TailMode tail, int* next_token) {
     if (rc) return rc;
     // the device argmax answers 0 ("no token") when no logit is finite (a damaged upload, an overflow): an error, not an id --
     // a host that indexes its vocabulary with it reads out of bounds (advisor, round 4)
-    if (*c->h_next < 1 || *c->h_next > c->V) return LLMK_E_NONFINITE;
-    *next_token = *c->h_next;
+    if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;
+    *next_token = c->h_next->id;
     return LLMK_OK;
 }
 int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
@@ -1937,7 +1926,7 @@ int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
     return token_out(c, token, pos, TAIL_GREEDY, next_token);
 }
 
-// invT = f32(1 / T), rounded once; the pinned words every sampling pass copies to the device (d_sample_params)
+// invT = f32(1 / T), rounded once; the pinned words every sampling pass copies to the device (TkDevWords::samp)
 int set_sample_params(llmk_ctx* c, float temperature, uint64_t seed) {
     if (!(temperature > 0.f) || !isfinite(temperature)) return LLMK_E_ARG;      // (NaN fails the first test)
     const float invT = 1.0f / temperature;
@@ -1966,25 +1955,25 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         // n launches enqueued back to back: launch i takes its token from launch i-1's candidates (device memory) and leaves
         // its own; ids reach the host through mapped memory as CU 0 of the NEXT launch resolves them
         HIPCHK(hipSetDevice(c->cfg.device));
-        int* h_ids = reinterpret_cast<int*>(c->h_logits + c->V + 4);
-        int* h_ids_dev = reinterpret_cast<int*>(c->h_logits_dev + c->V + 4);
-        float2* d_cand = reinterpret_cast<float2*>(c->d_logits + c->V + 4);
+        int* h_ids = c->host_words()->ids();
+        int* h_ids_dev = c->host_words_dev()->ids();
+        TkDevWords* dw = c->dev_words();
         memset(h_ids, 0, (size_t)n * sizeof(int));
-        reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
+        c->host_words()->err = 0;
         // the GR launches score their classifier rows with these parameters (token_kernel.h tk_sample_params); invT = 0 is greedy
         // (TAIL_FILTER: greedy words -- the cheap tail -- and sample_filter_kernel behind every launch, which replaces the launch's
         // candidates by its own single winner: the next launch's fold and cand_resolve_kernel pick that up like any other candidate)
         const llmk_sample_params want = tail == TAIL_SAMPLE ? *c->h_samp : llmk_sample_params{};
         if (tail == TAIL_FILTER && !(c->filt_known && memcmp(c->h_filt, &c->filt_dev, sizeof(llmk_filter_params)) == 0)) {
-            HIPCHK(hipMemcpyAsync(d_filter_params(c), c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
             c->filt_dev = *c->h_filt;
             c->filt_known = true;
         }
         if (memcmp(&want, &c->samp_dev, sizeof(want)) != 0) {
             if (tail == TAIL_SAMPLE)
-                HIPCHK(hipMemcpyAsync(d_sample_params(c), c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
+                HIPCHK(hipMemcpyAsync(&dw->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
             else
-                HIPCHK(hipMemsetAsync(d_sample_params(c), 0, sizeof(llmk_sample_params), c->stream));
+                HIPCHK(hipMemsetAsync(&dw->samp, 0, sizeof(llmk_sample_params), c->stream));
             c->samp_dev = want;
         }
         for (int i = 0; i < n; ++i) {
@@ -1999,14 +1988,13 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             HIPCHK(launch_token_kernel(c, false, g));
             if (tail == TAIL_FILTER) {
                 hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos0 + i,
-                                   d_filter_params(c), c->d_next, d_cand + (size_t)((pos0 + i) & 1) * TK_NCU, TK_NCU, d_filter_out(c));
+                                   &dw->filt, c->d_next, dw->cand[(pos0 + i) & 1], TK_NCU, dw->filter_out);
                 HIPCHK(hipGetLastError());
             }
         }
-        hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, d_cand + (size_t)((pos0 + n - 1) & 1) * TK_NCU,
-                           h_ids_dev + (n - 1), c->d_next, reinterpret_cast<unsigned*>(c->d_logits + c->V), c->V);
+        hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, dw->cand[(pos0 + n - 1) & 1], h_ids_dev + (n - 1), c->d_next, &dw->err, c->V);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c->h_next + 1, c->d_logits + c->V, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&c->h_next->err, &dw->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         // drain: ids are 1-based, 0 = not resolved yet
         volatile int* ids = h_ids;
         while (done < n) {
@@ -2025,7 +2013,7 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             ids_out[done] = ids[done];
             if (on_token) on_token(done, ids_out[done], user);
         }
-        const unsigned err = (unsigned)c->h_next[1];
+        const unsigned err = c->h_next->err;
         if (err == 0 && done == n) return LLMK_OK;
         // a timed-out exchange: every later launch drained on the sticky word.  Retire the token kernel and redo the rest,
         // from the first position whose id never arrived, on the multi-kernel path (it rewrites those KV rows).
@@ -2039,8 +2027,8 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
     for (int i = done; i < n; ++i) {
         rc = run_token(c, token, pos0 + i, tail);
         if (rc) return rc;
-        if (*c->h_next < 1 || *c->h_next > c->V) return LLMK_E_NONFINITE;      // (before the callback sees it)
-        token = ids_out[i] = *c->h_next;
+        if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;      // (before the callback sees it)
+        token = ids_out[i] = c->h_next->id;
         if (on_token) on_token(i, token, user);
     }
     return LLMK_OK;
@@ -2101,19 +2089,19 @@ int llmk_sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sam
     HIPCHK(hipSetDevice(c->cfg.device));
     c->filt_known = false;
     HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_filter_params(c), c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, d_filter_params(c),
-                       c->d_next, (float2*)nullptr, 0, d_filter_out(c));
+    HIPCHK(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, &c->dev_words()->filt,
+                       c->d_next, (float2*)nullptr, 0, c->dev_words()->filter_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_next, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_next + 2, d_filter_out(c), 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&c->h_next->kept, c->dev_words()->filter_out, sizeof(TkDevWords::filter_out), hipMemcpyDeviceToHost, c->stream));      // kept, tau
     HIPCHK(hipStreamSynchronize(c->stream));
     c->filt_dev = *c->h_filt;
     c->filt_known = true;
-    if (kept_out) *kept_out = c->h_next[2];
-    if (tau_out) memcpy(tau_out, c->h_next + 3, sizeof(float));
-    if (*c->h_next < 1 || *c->h_next > c->V) return LLMK_E_NONFINITE;
-    *token_out_ = *c->h_next;
+    if (kept_out) *kept_out = c->h_next->kept;
+    if (tau_out) *tau_out = c->h_next->tau;
+    if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;
+    *token_out_ = c->h_next->id;
     return LLMK_OK;
 }
 
@@ -2123,12 +2111,11 @@ int llmk_reset(llmk_ctx* c) {
     const size_t kvn = (size_t)c->L * c->S * c->KVl * sizeof(float);
     HIPCHK(hipMemsetAsync(c->d_kc, 0, kvn, c->stream));
     HIPCHK(hipMemsetAsync(c->d_vc, 0, kvn, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_logits + c->V, 0, sizeof(float), c->stream));   // the token kernel's sticky error word
-    if (c->d_gran && c->tk_ngran)      // a new sequence: no position before it (the q4_0 kernels' scale records, token_kernel.h tk_qsc)
-        HIPCHK(hipMemsetAsync(c->d_gran + c->tk_ngran - 4 * TK_QSC_LMAX, 0, 4 * TK_QSC_LMAX * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(&c->dev_words()->err, 0, sizeof(unsigned), c->stream));   // the token kernel's sticky error word
+    HIPCHK(tk_qsc_clear(c, c->stream));      // a new sequence: no position before it (the q4_0 kernels' scale records, token_kernel.h tk_qsc)
     HIPCHK(hipStreamSynchronize(c->stream));
-    reinterpret_cast<unsigned*>(c->h_logits)[c->V] = 0;
-    c->h_next[1] = 0;
+    c->host_words()->err = 0;
+    c->h_next->err = 0;
     for (int i = 0; i < 5; ++i) c->times[i] = 0.f;
     return LLMK_OK;
 }
@@ -2293,10 +2280,13 @@ int llmk_peek(llmk_ctx* c, int which, int layer, int pos, float* out, int n) {
 #ifdef LLMK_PF_TRACE
         case 7: src = c->pf[0].HB; len = PF_TMAX * c->H; break;
 #endif
-        case 8:  // the q4_0 persistent kernels' per-layer scale records (token_kernel.h tk_qsc): [2 buffers][TK_QSC_LMAX] x {|xb|, |hb|, pos, pos}
-            if (!c->d_gran || !c->tk_ngran) return LLMK_E_ARG;
-            src = reinterpret_cast<const float*>(c->d_gran + c->tk_ngran - 4 * TK_QSC_LMAX); len = 8 * TK_QSC_LMAX;
+        case 8: {  // the q4_0 persistent kernels' per-layer scale records (token_kernel.h tk_qsc): [2 buffers][TK_QSC_LMAX] x {|xb|, |hb|, pos, pos}
+            size_t ng;
+            src = reinterpret_cast<const float*>(tk_qsc_records(c, &ng));
+            if (!src) return LLMK_E_ARG;
+            len = (int)(2 * ng);
             break;
+        }
         case 6:  // debug: raw trace stamps reinterpret as floats (2 per stamp)
             if (!c->d_trace) return LLMK_E_ARG;
             src = (const float*)c->d_trace; len = TK_NCU * TK_TRACE_N * 2;
@@ -2461,14 +2451,14 @@ static int tp_selftest_run(llmk_ctx* c, int iters, unsigned jseed) {
     if (rc == LLMK_OK) {
         hipError_t e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&err, c->d_logits + c->V, sizeof(err), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&err, &c->dev_words()->err, sizeof(err), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = LLMK_E_HIP + (int)e;
         else if (err) rc = LLMK_E_TIMEOUT;
         else if (bad) rc = LLMK_E_COMM;
     }
     // leave the ctx as a fresh one: x, the logits and the sticky word
     hipMemsetAsync(c->d_x, 0, (size_t)c->E * sizeof(float), c->stream);
-    hipMemsetAsync(c->d_logits, 0, ((size_t)c->V + 4) * sizeof(float), c->stream);
+    hipMemsetAsync(c->d_logits, 0, (size_t)c->V * sizeof(float) + offsetof(TkDevWords, cand), c->stream);
     hipStreamSynchronize(c->stream);
     if (rc != LLMK_OK) {
         char what[160];

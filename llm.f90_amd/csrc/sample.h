@@ -68,7 +68,7 @@ LLMK_HD float llmk_sample_score(float logit, float invT, uint64_t seed, int pos,
     return s + g;
 }
 
-// The sampling parameters in device memory (behind the candidate buffers of the pipelined decode, llmk.hip): invT == 0 is greedy
+// The sampling parameters in device memory (behind the candidate buffers of the pipelined decode: scratch_layout.h TkDevWords::samp): invT == 0 is greedy
 struct llmk_sample_params {
     float invT;
     uint32_t seed_lo, seed_hi;

@@ -32,7 +32,7 @@
 #define LLMK_HD static inline
 #endif
 
-// The sampler as the device reads it (behind llmk_sample_params in device memory, llmk.hip d_filter_params)
+// The sampler as the device reads it (behind llmk_sample_params in device memory: scratch_layout.h TkDevWords::filt)
 struct llmk_filter_params {
     float invT;
     uint32_t seed_lo, seed_hi;

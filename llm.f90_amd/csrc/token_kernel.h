@@ -151,8 +151,12 @@ constexpr bool TK_EXP_NODOT = false;
 #endif
 
 namespace llmk {
-
 constexpr int TK_NCU = 256;               // one workgroup per CU
+}  // namespace llmk
+#include "scratch_layout.h"               // (the words behind the logits vectors: per-CU candidates among them, so behind TK_NCU)
+
+namespace llmk {
+
 constexpr int TK_WAVES = 8;               // 7 streaming + 1 service (2 waves/SIMD: 256 VGPRs each)
 // register tiles a streaming wave keeps requested ahead: TkShape::NB (5 x 8 KB for f32, 4 for f16; q4_0: 4 units of 9 KB)
 constexpr int TK_NS = TK_WAVES - 1;
@@ -203,8 +207,8 @@ struct TokenArgs {
     // trip.  Every CU leaves the first maximum of ITS classifier rows in cand_out[c] = {logit, 0-based row}; the NEXT launch
     // (ordered behind this one by the stream) starts by folding the 256 candidates of cand_in -- 2 KB, first maximum wins --
     // on every CU that needs the embedding row, so the token never leaves the device and no exchange is added.
-    // The candidates live behind the error word (err + 4: two buffers of TK_NCU float2, alternating by launch parity) and
-    // the resolved ids behind the host error word (herr + 4: ints) -- no further pointer arguments: the kernel is at its
+    // The candidates live behind the error word (TkDevWords::cand: two buffers of TK_NCU float2, alternating by launch parity) and
+    // the resolved ids behind the host error word (TkHostWords::ids) -- no further pointer arguments: the kernel is at its
     // SGPR ceiling, and three more pointers cost the f32 instantiation 36 bytes of scratch.
     // The flags share the word of the debug build's "do not wait" switch, and with TKG_CAND_IN the unused tok_imm carries
     // the index of the id to store: the argument block is exactly as large as before.
@@ -225,11 +229,12 @@ constexpr int TKG_CAND_IN = 4;     // the token is the fold of the previous posi
 constexpr int TKG_ID = 8;
 constexpr int TKG_NOSYNC = 32;     // debug build only: do not wait for exchange tags (wrong results; measures the pure streaming rate)
 __device__ __forceinline__ float2* tk_cand(const TokenArgs& a, int buf) {
-    return reinterpret_cast<float2*>(a.err + 4) + buf * TK_NCU;
+    // (buf * TK_NCU from the first buffer, not cand[buf]: the index arithmetic the kernels were tuned with, instruction for instruction)
+    return &reinterpret_cast<TkDevWords*>(a.err)->cand[0][0] + buf * TK_NCU;
 }
 // behind the two candidate buffers: the sampling parameters of the pipelined decode (invT == 0: greedy, llmk_decode_greedy)
 __device__ __forceinline__ const llmk_sample_params* tk_sample_params(const TokenArgs& a) {
-    return reinterpret_cast<const llmk_sample_params*>(a.err + 4 + 4 * TK_NCU);
+    return &reinterpret_cast<const TkDevWords*>(a.err)->samp;
 }
 // first-maximum-wins fold of {value, index-as-float-bits} pairs over a wave; every lane ends with the winner
 __device__ __forceinline__ void tk_wave_argmax(float& v, int& i) {
@@ -561,9 +566,16 @@ __device__ __forceinline__ float tk_scale_for(float amax, float fallback) {
 // record of layer l: {largest |xb|, largest |hb|, position that wrote .x, position that wrote .y} (positions as int bits).  Two
 // buffers by position parity: a launch reads the one the position before wrote and writes its own -- no workgroup can meet a record
 // of its own launch, however late it starts (the choice of scale must not depend on timing: reruns are bit-identical)
+constexpr size_t TK_QSC_GRANULES = 4 * (size_t)TK_QSC_LMAX;      // both buffers, two 8-byte granules per record
+// the exchange granules in front of the records, for shape SH: qkv | xb | xa | hb | x | per head the (PMAX - 1) other attention parts
+// (TkAttPlan<SH>::PMAX, declared further down: tk_setup in llmk.hip asserts that this is that number)
+template <class SH>
+constexpr size_t tk_qsc_front() {
+    return (size_t)SH::QKV + 3 * (size_t)SH::E + SH::H + (size_t)SH::NH * ((TK_NCU / SH::NH < 8 ? TK_NCU / SH::NH : 8) - 1) * (SH::HS + 2);
+}
 template <class SH>
 __device__ __forceinline__ float4* tk_qsc(const TokenArgs& a, int pos) {
-    constexpr size_t NG = (size_t)SH::QKV + 3 * (size_t)SH::E + SH::H + (size_t)SH::NH * ((TK_NCU / SH::NH < 8 ? TK_NCU / SH::NH : 8) - 1) * (SH::HS + 2);
+    constexpr size_t NG = tk_qsc_front<SH>();
     return reinterpret_cast<float4*>(a.g_qkv + NG) + (pos & 1) * TK_QSC_LMAX;
 }
 // Two predictions of the next image's largest |element|: this token's vector of the layer before (`now`), the same layer's vector

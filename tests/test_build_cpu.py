@@ -68,3 +68,18 @@ def test_every_included_header_is_a_prerequisite_of_the_libraries():
     assert not missing, f"not prerequisites of libllmk.so: {missing}"
     mk = open(os.path.join(pkg, "Makefile")).read()
     assert re.search(r"^csrc/libllmk\.so: \$\(LIB_DEPS\)$", mk, re.M) and re.search(r"^csrc/libllmk_debug\.so: \$\(LIB_DEPS\)$", mk, re.M)
+
+
+def test_scratch_words_are_addressed_through_their_structs():
+    """The words behind the logits vectors, the pinned next-token block and the q4_0 scale records have ONE definition
+    (csrc/scratch_layout.h, token_kernel.h tk_qsc_front / TK_QSC_GRANULES; its static_asserts hold the bytes in place at build time).
+    No hand-computed offset may come back into the shim or the token kernel: outside comments, neither file spells
+    `d_logits + V`, `[c->V]`, `h_next[1]`, `h_next + 2` ... or `tk_ngran - 4 * ...` again."""
+    raw = re.compile(r"(h_logits(_dev)?|d_logits) \+ (c->)?V\b|\[(c->)?V\]|h_next \+ \d|h_next\[\d\]|tk_ngran - 4")
+    hits = []
+    for name in ("llmk.hip", "token_kernel.h"):
+        for n, line in enumerate(open(os.path.join(ROOT, "llm.f90_amd", "csrc", name)), 1):
+            code = line.split("//", 1)[0]
+            if raw.search(code):
+                hits.append(f"{name}:{n}: {line.strip()}")
+    assert not hits, "\n".join(hits)
