@@ -281,7 +281,58 @@ int llmk_decode_sample_ex(llmk_ctx *ctx, int token, int pos0, int n, const llmk_
 int llmk_sample_logits(llmk_ctx *ctx, const float *logits, int pos, const llmk_sampler *sampler, int *token_out, int *kept_out,
                        float *tau_out);
 
-/* Zero the KV cache (new sequence), as llama2.f90:316-318. */
+/* The same three with what stock llama.cpp files are further sampled with: the repetition, frequency and presence penalties over a
+ * window of the tokens fed so far, and a logit bias (llm.f90_amd/csrc/sample_penalty.h holds the rule).  With z
+ * the logits of position pos, r = repeat, inv_r = f32(1 / r) rounded once, f = frequency, p = presence, W = the tokens fed at positions
+ * max(1, pos - last_n + 1) .. pos according to the context's token record (below; entries 0 = "none" are skipped) and c[t] = how often
+ * token t occurs in W, each product, sum and difference rounded to f32:
+ *   1. bias:       z[t] <- z[t] + b for every entry (t, b) of the bias list; b = -inf bans the token;
+ *   2. penalties:  for every t with c[t] > 0:  z[t] <- (z[t] > 0 ? z[t] * inv_r : z[t] * r), then z[t] <- z[t] - ((float)c[t] * f + p);
+ *                  a NaN row stays NaN, a -inf row stays -inf, -0.0 takes the `<= 0` branch;
+ *   3. the adjusted vector goes through the rule of llmk_*_sample_ex unchanged (filters, Gumbel-max, first maximum wins, the same
+ *      stateless noise keyed by (seed, pos, row)).
+ * Bias comes before the penalties on a row that gets both (llama.cpp's order).  The product with inv_r instead of llama.cpp's division
+ * by r is deliberate: the adjusted logits are a bit-exact function that float32 arithmetic reproduces anywhere; they differ from
+ * llama.cpp's by at most 1 ulp.  top_k = 1 is the greedy form: the maximum of the adjusted logits.  Temperature 0 stays LLMK_E_ARG,
+ * as in the _ex functions.
+ *
+ * The token record: S = seq_len ints on the device, hist[q-1] = the 1-based token fed at position q, 0 = none; zero when it is
+ * allocated (by the first call that needs it: a context that never uses these functions allocates nothing) and after llmk_reset.  It is
+ * indexed by position: a redone position rewrites its own entry.  llmk_forward, llmk_prefill, llmk_score, the greedy functions and
+ * the _ex functions do NOT maintain it: the caller records the prompt once with llmk_set_history (tokens fed at pos0 .. pos0+n-1, 0
+ * allowed = none), and llmk_forward_sample_pen / llmk_decode_sample_pen record every token they are fed from there (the pipelined
+ * decode on the device, from the id the sampler left there).  llmk_get_history reads it back (verification).
+ *
+ * Out of range -- last_n < 0 or > seq_len; repeat not finite, <= 0 or with 1/repeat beyond the normal f32 range; frequency or
+ * presence not finite; n_bias outside [0, LLMK_MAX_LOGIT_BIAS]; a bias that is NaN or +inf; a bias id outside [1, vocab_size] or given
+ * twice: LLMK_E_ARG before anything runs.  The sampler is checked as in the _ex functions.  With nothing on (n_bias == 0, and last_n ==
+ * 0 or repeat == 1, frequency == 0, presence == 0) the two functions ARE llmk_forward_sample_ex / llmk_decode_sample_ex: same code
+ * path, same ids, and the record is NOT maintained.  Otherwise one more one-workgroup kernel (sample_penalty_kernel) runs per position
+ * in front of the filter kernel, which then always runs; the pipelined decode stays pipelined, and every path -- the pipelined
+ * launches, the per-position pass, LLMK_FLAG_MULTI_KERNEL, a redone position -- runs the same two kernels, so the ids are
+ * bit-identical across them.  The context's logits buffer holds the ADJUSTED logits afterwards.  A tensor-parallel context gets what
+ * the _ex functions give it.
+ * llmk_sample_logits_pen is the verification hook, with the limits of llmk_sample_logits (whole-model contexts only; the logits buffer
+ * is overwritten, here with the adjusted vector): it READS the window from the record, positions up to and including `pos` (so pos <=
+ * seq_len), and does not write the record.  adjusted_out (optional): the vocab_size adjusted logits. */
+#define LLMK_MAX_LOGIT_BIAS 256
+typedef struct llmk_logit_bias { int32_t token; float bias; } llmk_logit_bias;   /* token 1-based */
+typedef struct llmk_penalties {
+    int32_t last_n;      /* window in positions, 0 = penalties off, at most seq_len */
+    float repeat;        /* 1 = off; finite, > 0, 1/repeat a normal f32 */
+    float frequency;     /* 0 = off; finite */
+    float presence;      /* 0 = off; finite */
+    const llmk_logit_bias *bias; int32_t n_bias;   /* 0..LLMK_MAX_LOGIT_BIAS; bias finite or -inf; token ids distinct, in [1, V] */
+} llmk_penalties;
+int llmk_set_history(llmk_ctx *ctx, const int *tokens, int n, int pos0);
+int llmk_get_history(llmk_ctx *ctx, int *tokens_out, int n, int pos0);
+int llmk_forward_sample_pen(llmk_ctx *ctx, int token, int pos, const llmk_sampler *sampler, const llmk_penalties *penalties, int *next_token);
+int llmk_decode_sample_pen(llmk_ctx *ctx, int token, int pos0, int n, const llmk_sampler *sampler, const llmk_penalties *penalties,
+                           int *ids_out, llmk_token_fn on_token, void *user);
+int llmk_sample_logits_pen(llmk_ctx *ctx, const float *logits, int pos, const llmk_sampler *sampler, const llmk_penalties *penalties,
+                           int *token_out, int *kept_out, float *tau_out, float *adjusted_out);
+
+/* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 
 /* The reference's five section timers s%times(1:5) (llama2.f90:538,561,599,622,638), accumulated

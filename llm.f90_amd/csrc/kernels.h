@@ -14,6 +14,7 @@
 
 #include "sample.h"
 #include "sample_filter.h"
+#include "sample_penalty.h"
 
 namespace llmk {
 
@@ -1020,6 +1021,59 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* 
     if (cand)
         for (int j = tid; j < ncand; j += SF_THREADS)
             cand[j] = (j == 0 && have) ? make_float2(best, __int_as_float(idx)) : make_float2(-INFINITY, __int_as_float(0x7fffffff));
+}
+
+// The penalties and the logit bias of sample_penalty.h by ONE workgroup, in place on the position's logits, in front of
+// sample_filter_kernel.  It touches at most last_n + n_bias rows:
+//   (a) hist[pos - 1] <- the token fed at this position: tokpos[0] + 1 behind a token pass of its own (tokpos not null); in a launch
+//       of the pipelined decode (tokpos null) what the previous position's sample_filter_kernel left in next_in[0], or tok_imm at the
+//       call's first position (next_in null).  No token (0, or an id out of range): 0 is recorded and nothing is adjusted.
+//       hist_out null (llmk_sample_logits_pen): the record is read, not written;
+//   (b) the bias list, one entry per thread (the ids are distinct: no two threads meet on a row); then a barrier;
+//   (c) the window, one position per thread and round: every slot adds 1 to cnt[token] (integer atomics on a V-int array in device
+//       memory that is all zero between launches), a barrier, then every slot exchanges cnt[token] for 0 -- the one slot that gets
+//       the non-zero count owns the row and applies the penalty, and the array is zero again for the next position.  No result
+//       depends on the order of anything.
+// pos: tokpos[1], or pos_imm when tokpos is null.
+constexpr int SP_THREADS = 256;
+__global__ __launch_bounds__(SP_THREADS) void sample_penalty_kernel(float* __restrict__ logits, int n, const int* __restrict__ tokpos,
+                                                                    int pos_imm, int tok_imm, const int* __restrict__ next_in,
+                                                                    const llmk_penalty_params* __restrict__ pp, const int* hist,
+                                                                    int* hist_out, int* __restrict__ cnt) {
+    const int tid = threadIdx.x;
+    const int pos = tokpos ? tokpos[1] : pos_imm;
+    int tok = tokpos ? tokpos[0] + 1 : next_in ? next_in[0] : tok_imm;
+    if (tok < 1 || tok > n) tok = 0;
+    if (hist_out) {
+        if (tid == 0) hist_out[pos - 1] = tok;
+        if (tok == 0) return;
+    }
+    const int n_bias = pp->n_bias < LLMK_PENALTY_MAX_BIAS ? pp->n_bias : LLMK_PENALTY_MAX_BIAS;
+    for (int j = tid; j < n_bias; j += SP_THREADS) {
+        const int t = pp->bias[j].token;
+        if (t >= 1 && t <= n) logits[t - 1] = llmk_penalty_bias_row(logits[t - 1], pp->bias[j].bias);
+    }
+    const int last_n = pp->last_n;
+    if (last_n <= 0) return;
+    __syncthreads();
+    const float r = pp->repeat, inv_r = pp->inv_repeat, f = pp->frequency, p = pp->presence;
+    const int lo = llmk_penalty_window_lo(pos, last_n);
+    // the slot of this very position is the token just recorded (its store need not have landed for the other waves)
+    auto slot = [&](int q) -> int {
+        const int t = (hist_out && q == pos) ? tok : hist[q - 1];
+        return (t >= 1 && t <= n) ? t : 0;
+    };
+    for (int q = lo + tid; q <= pos; q += SP_THREADS) {
+        const int t = slot(q);
+        if (t) atomicAdd(&cnt[t - 1], 1);
+    }
+    __syncthreads();
+    for (int q = lo + tid; q <= pos; q += SP_THREADS) {
+        const int t = slot(q);
+        if (!t) continue;
+        const int c = atomicExch(&cnt[t - 1], 0);
+        if (c > 0) logits[t - 1] = llmk_penalty_row(logits[t - 1], c, r, inv_r, f, p);
+    }
 }
 
 // q4_0 re-pack on upload: ggml blocks {f16 d; u8 qs[16]} (18 B, 2-byte aligned), bpr per row -> device rows of

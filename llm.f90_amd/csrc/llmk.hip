@@ -122,6 +122,14 @@ struct llmk_ctx {
     llmk_filter_params* h_filt = nullptr;
     llmk_filter_params filt_dev = {};
     bool filt_known = false;
+    // penalties and logit bias (llmk_*_sample_pen, sample_penalty.h), allocated by the first call that needs them (pen_setup): the
+    // token record (S ints: hist[q - 1] = the 1-based token fed at position q, 0 = none), the V counts of sample_penalty_kernel (all
+    // zero between launches), the parameters on the device and the pinned words they are copied from
+    int* d_hist = nullptr;
+    int* d_pen_cnt = nullptr;
+    llmk_penalty_params* d_pen = nullptr;
+    llmk_penalty_params* h_pen = nullptr;
+    hipGraphExec_t graph_pen = nullptr;
     hipEvent_t ev[8] = {};
     float times[5] = {0, 0, 0, 0, 0};
     int n_cu = 256;
@@ -536,9 +544,9 @@ int tk_setup_all(llmk_ctx* c) {
 __global__ void bump_serial_kernel(int* tokpos) { tokpos[2] += 1; }
 
 // What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
-// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h); the last three leave the 1-based id in h_next->id and
-// the sticky error word in h_next->err
-enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE, TAIL_FILTER };
+// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h; TAIL_PENALTY: the same behind the penalties and the
+// logit bias of sample_penalty.h); all but the first leave the 1-based id in h_next->id and the sticky error word in h_next->err
+enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE, TAIL_FILTER, TAIL_PENALTY };
 // the q4_0 persistent kernels' per-layer scale records (token_kernel.h tk_qsc): the last *n granules of d_gran; null on a context
 // that has none
 unsigned long long* tk_qsc_records(const llmk_ctx* c, size_t* n) {
@@ -552,7 +560,15 @@ hipError_t tk_qsc_clear(llmk_ctx* c, hipStream_t st) {
 }
 hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
     if (tail != TAIL_LOGITS) {
-        if (tail == TAIL_FILTER) {
+        if (tail == TAIL_FILTER || tail == TAIL_PENALTY) {
+            if (tail == TAIL_PENALTY) {
+                // the penalties travel like the filter's parameters; token and position come from the pass's device words, and the
+                // logits are adjusted in place before the filter reads them
+                HIPRET(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
+                hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, 0,
+                                   (const int*)nullptr, c->d_pen, c->d_hist, c->d_hist, c->d_pen_cnt);
+                HIPRET(hipGetLastError());
+            }
             // the same kernel as behind a launch of the pipelined decode (decode_run), with the position from the pass's device word
             HIPRET(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, &c->dev_words()->filt,
@@ -724,6 +740,7 @@ int tk_retire(llmk_ctx* c, unsigned code, int pos) {
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
     if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
+    if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
     for (int i = 0; i < LLMK_N_TENSORS; ++i)       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
         if (c->q16[i]) { hipFree(c->q16[i]); c->q16[i] = nullptr; }
     c->q16_dirty = true;
@@ -772,7 +789,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
             c->host_words()->err = 0;
             HIPCHK(launch_token_kernel(c, true));
         } else {
-            hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : tail == TAIL_FILTER ? &c->graph_filter : &c->graph_logits;
+            hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : tail == TAIL_FILTER ? &c->graph_filter : tail == TAIL_PENALTY ? &c->graph_pen : &c->graph_logits;
             if (!*g) {
                 rc = build_graph(c, tail, g);
                 if (rc) return rc;
@@ -812,7 +829,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
     return LLMK_E_TIMEOUT;
 }
 int run_token(llmk_ctx* c, int token, int pos, TailMode tail) {
-    if (tail == TAIL_FILTER) {               // (its tail copies h_filt to the device in the same way)
+    if (tail == TAIL_FILTER || tail == TAIL_PENALTY) {               // (both tails copy h_filt to the device in the same way)
         c->filt_known = false;
         const int rc = run_token_pass(c, token, pos, tail);
         if (rc == LLMK_OK) { c->filt_dev = *c->h_filt; c->filt_known = true; }
@@ -1285,7 +1302,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 400; }
+int llmk_version(void) { return 401; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -1751,6 +1768,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
         if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
         if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
         if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
+        if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
     }
     // the persistent kernel again, if one is instantiated for this shape with a classifier of this type (round 6: q6_K rows beside
     // q4_0 matrices -- a stock llama.cpp q4_0 file keeps the fast path); otherwise the multi-kernel path
@@ -1774,6 +1792,7 @@ int llmk_set_rms_eps(llmk_ctx* c, float eps) {
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
     if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
+    if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
     return LLMK_OK;
 }
 
@@ -1962,9 +1981,13 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         c->host_words()->err = 0;
         // the GR launches score their classifier rows with these parameters (token_kernel.h tk_sample_params); invT = 0 is greedy
         // (TAIL_FILTER: greedy words -- the cheap tail -- and sample_filter_kernel behind every launch, which replaces the launch's
-        // candidates by its own single winner: the next launch's fold and cand_resolve_kernel pick that up like any other candidate)
+        // candidates by its own single winner: the next launch's fold and cand_resolve_kernel pick that up like any other candidate;
+        // TAIL_PENALTY: sample_penalty_kernel in between, which records the token the launch was fed -- the host's at the first
+        // position, afterwards the id the filter kernel of the position before left in d_next -- and adjusts the launch's logits)
+        const bool filter_tail = tail == TAIL_FILTER || tail == TAIL_PENALTY;
+        if (tail == TAIL_PENALTY) HIPCHK(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
         const llmk_sample_params want = tail == TAIL_SAMPLE ? *c->h_samp : llmk_sample_params{};
-        if (tail == TAIL_FILTER && !(c->filt_known && memcmp(c->h_filt, &c->filt_dev, sizeof(llmk_filter_params)) == 0)) {
+        if (filter_tail && !(c->filt_known && memcmp(c->h_filt, &c->filt_dev, sizeof(llmk_filter_params)) == 0)) {
             HIPCHK(hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
             c->filt_dev = *c->h_filt;
             c->filt_known = true;
@@ -1986,7 +2009,12 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             // debug library only: this launch one workgroup short, so its peers really time out INSIDE the pipeline
             c->tk_short_grid = TK_DEBUG && getenv("LLMK_TK_INJECT_TIMEOUT") && atoi(getenv("LLMK_TK_INJECT_TIMEOUT")) == pos0 + i;
             HIPCHK(launch_token_kernel(c, false, g));
-            if (tail == TAIL_FILTER) {
+            if (tail == TAIL_PENALTY) {
+                hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos0 + i,
+                                   token, i ? (const int*)c->d_next : (const int*)nullptr, c->d_pen, c->d_hist, c->d_hist, c->d_pen_cnt);
+                HIPCHK(hipGetLastError());
+            }
+            if (filter_tail) {
                 hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos0 + i,
                                    &dw->filt, c->d_next, dw->cand[(pos0 + i) & 1], TK_NCU, dw->filter_out);
                 HIPCHK(hipGetLastError());
@@ -2105,6 +2133,133 @@ int llmk_sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sam
     return LLMK_OK;
 }
 
+// ---- penalties and logit bias (sample_penalty.h) -------------------------------------------------------------------------------
+static_assert(LLMK_PENALTY_MAX_BIAS == LLMK_MAX_LOGIT_BIAS, "sample_penalty.h and llmk.h agree on the length of the bias list");
+// the record, the counts and the parameter words: allocated (and zeroed) by the first call that needs them
+static int pen_setup(llmk_ctx* c) {
+    if (c->d_hist && c->d_pen_cnt && c->d_pen && c->h_pen) return LLMK_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (!c->d_hist) {
+        HIPCHK(dev_alloc(&c->d_hist, (size_t)c->S * sizeof(int)));
+        HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)c->S * sizeof(int), c->stream));
+    }
+    if (!c->d_pen_cnt) {
+        HIPCHK(dev_alloc(&c->d_pen_cnt, (size_t)c->V * sizeof(int)));
+        HIPCHK(hipMemsetAsync(c->d_pen_cnt, 0, (size_t)c->V * sizeof(int), c->stream));
+    }
+    if (!c->d_pen) {
+        HIPCHK(dev_alloc(&c->d_pen, sizeof(llmk_penalty_params)));
+        HIPCHK(hipMemsetAsync(c->d_pen, 0, sizeof(llmk_penalty_params), c->stream));
+    }
+    if (!c->h_pen) {
+        HIPCHK(hipHostMalloc(&c->h_pen, sizeof(llmk_penalty_params), hipHostMallocDefault));
+        memset(c->h_pen, 0, sizeof(llmk_penalty_params));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+// Checks, then the pinned words of sample_penalty.h.  *active = a penalty or a bias is on (none: the _pen functions ARE the _ex ones).
+// inv_r = f32(1 / r), rounded once, as invT is.
+static int set_penalty_params(llmk_ctx* c, const llmk_penalties* pn, bool* active) {
+    if (!pn) return LLMK_E_ARG;
+    if (pn->last_n < 0 || pn->last_n > c->S) return LLMK_E_ARG;
+    if (!(pn->repeat > 0.f) || !isfinite(pn->repeat) || !isfinite(pn->frequency) || !isfinite(pn->presence)) return LLMK_E_ARG;      // (NaN fails)
+    const float inv_r = 1.0f / pn->repeat;
+    if (!isfinite(inv_r) || !(inv_r >= FLT_MIN)) return LLMK_E_ARG;
+    if (pn->n_bias < 0 || pn->n_bias > LLMK_MAX_LOGIT_BIAS || (pn->n_bias > 0 && !pn->bias)) return LLMK_E_ARG;
+    for (int j = 0; j < pn->n_bias; ++j) {
+        const llmk_logit_bias& b = pn->bias[j];
+        if (b.token < 1 || b.token > c->V || !(isfinite(b.bias) || b.bias == -INFINITY)) return LLMK_E_ARG;      // (NaN and +inf fail)
+        for (int k = 0; k < j; ++k)
+            if (pn->bias[k].token == b.token) return LLMK_E_ARG;
+    }
+    const bool pen_on = pn->last_n > 0 && (pn->repeat != 1.f || pn->frequency != 0.f || pn->presence != 0.f);
+    *active = pen_on || pn->n_bias > 0;
+    if (!*active) return LLMK_OK;
+    const int rc = pen_setup(c);
+    if (rc) return rc;
+    llmk_penalty_params* h = c->h_pen;
+    memset(h, 0, sizeof(*h));
+    h->repeat = pn->repeat;
+    h->inv_repeat = inv_r;
+    h->frequency = pn->frequency;
+    h->presence = pn->presence;
+    h->last_n = pen_on ? pn->last_n : 0;
+    h->n_bias = pn->n_bias;
+    for (int j = 0; j < pn->n_bias; ++j) { h->bias[j].token = pn->bias[j].token; h->bias[j].bias = pn->bias[j].bias; }
+    return LLMK_OK;
+}
+int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
+    if (!c || !tokens || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (tokens[i] < 0 || tokens[i] > c->V) return LLMK_E_ARG;
+    const int rc = pen_setup(c);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_hist + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
+    if (!c || !tokens_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
+    const int rc = pen_setup(c);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(tokens_out, c->d_hist + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+int llmk_forward_sample_pen(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* next_token) {
+    if (!c || !next_token || token < 1 || token > c->V || pos < 1 || pos > c->S) return LLMK_E_ARG;      // (before pen_setup allocates)
+    bool filtered = false, active = false;
+    int rc = set_filter_params(c, sp, &filtered);
+    if (rc) return rc;
+    if ((rc = set_penalty_params(c, pn, &active)) != LLMK_OK) return rc;
+    return token_out(c, token, pos, active ? TAIL_PENALTY : filtered ? TAIL_FILTER : TAIL_SAMPLE, next_token);
+}
+int llmk_decode_sample_pen(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, const llmk_penalties* pn, int* ids_out,
+                           llmk_token_fn on_token, void* user) {
+    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
+    bool filtered = false, active = false;
+    int rc = set_filter_params(c, sp, &filtered);
+    if (rc) return rc;
+    if ((rc = set_penalty_params(c, pn, &active)) != LLMK_OK) return rc;
+    return decode_run(c, token, pos0, n, active ? TAIL_PENALTY : filtered ? TAIL_FILTER : TAIL_SAMPLE, ids_out, on_token, user);
+}
+// Verification hook: llmk_sample_logits with sample_penalty_kernel in front, as every path runs the two.  The window is read from
+// the record (positions up to and including `pos`, so pos <= seq_len); the record is not written.
+int llmk_sample_logits_pen(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* token_out_,
+                           int* kept_out, float* tau_out, float* adjusted_out) {
+    if (!c || !logits || !token_out_ || pos < 1 || pos > c->S || c->tp_size != 1) return LLMK_E_ARG;
+    bool filtered = false, active = false;
+    int rc = set_filter_params(c, sp, &filtered);
+    if (rc) return rc;
+    if ((rc = set_penalty_params(c, pn, &active)) != LLMK_OK) return rc;
+    if ((rc = check_ready(c)) != LLMK_OK) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    c->filt_known = false;
+    HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (active) {
+        HIPCHK(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, 0,
+                           (const int*)nullptr, c->d_pen, c->d_hist, (int*)nullptr, c->d_pen_cnt);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, &c->dev_words()->filt,
+                       c->d_next, (float2*)nullptr, 0, c->dev_words()->filter_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&c->h_next->kept, c->dev_words()->filter_out, sizeof(TkDevWords::filter_out), hipMemcpyDeviceToHost, c->stream));      // kept, tau
+    if (adjusted_out) HIPCHK(hipMemcpyAsync(adjusted_out, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->filt_dev = *c->h_filt;
+    c->filt_known = true;
+    if (kept_out) *kept_out = c->h_next->kept;
+    if (tau_out) *tau_out = c->h_next->tau;
+    if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;
+    *token_out_ = c->h_next->id;
+    return LLMK_OK;
+}
+
 int llmk_reset(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -2113,6 +2268,10 @@ int llmk_reset(llmk_ctx* c) {
     HIPCHK(hipMemsetAsync(c->d_vc, 0, kvn, c->stream));
     HIPCHK(hipMemsetAsync(&c->dev_words()->err, 0, sizeof(unsigned), c->stream));   // the token kernel's sticky error word
     HIPCHK(tk_qsc_clear(c, c->stream));      // a new sequence: no position before it (the q4_0 kernels' scale records, token_kernel.h tk_qsc)
+    if (c->d_hist) {                         // ... and no token fed yet (the record of the penalties; their counts are zero between launches anyway)
+        HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)c->S * sizeof(int), c->stream));
+        HIPCHK(hipMemsetAsync(c->d_pen_cnt, 0, (size_t)c->V * sizeof(int), c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->host_words()->err = 0;
     c->h_next->err = 0;
@@ -2485,6 +2644,7 @@ int llmk_tp_p2p_disable(llmk_ctx* c) {
     if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
     if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
     if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
+    if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
     return LLMK_OK;
 }
 
@@ -2625,13 +2785,14 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->graph_greedy) hipGraphExecDestroy(c->graph_greedy);
     if (c->graph_sample) hipGraphExecDestroy(c->graph_sample);
     if (c->graph_filter) hipGraphExecDestroy(c->graph_filter);
+    if (c->graph_pen) hipGraphExecDestroy(c->graph_pen);
     for (int i = 0; i < LLMK_N_TENSORS; ++i) {
         if (c->t[i].data && !c->t[i].alias) hipFree(c->t[i].data);
     }
     pf_teardown(c);
     sc_teardown(c);
     void* dev[] = {c->d_kc, c->d_vc, c->d_x, c->d_q, c->d_xb, c->d_hb, c->d_logits, c->d_rope, c->d_tokpos, c->d_next,
-                   c->d_gran, c->d_zeros, c->d_trace, c->d_part};
+                   c->d_gran, c->d_zeros, c->d_trace, c->d_part, c->d_hist, c->d_pen_cnt, c->d_pen};
     for (void* p : dev)
         if (p) hipFree(p);
     for (int b = 0; b < 2; ++b) {
@@ -2647,6 +2808,7 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->h_next) hipHostFree(c->h_next);
     if (c->h_samp) hipHostFree(c->h_samp);
     if (c->h_filt) hipHostFree(c->h_filt);
+    if (c->h_pen) hipHostFree(c->h_pen);
     for (int i = 0; i < 8; ++i)
         if (c->ev[i]) hipEventDestroy(c->ev[i]);
     if (c->stream) hipStreamDestroy(c->stream);

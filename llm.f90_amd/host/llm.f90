@@ -8,6 +8,7 @@
 !   ./llm -m model.gguf [-p prompt] [-n tokens] [-t temperature] [-s tokenizer.bin] [-v]
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
+!         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
 !         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score]
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
@@ -30,6 +31,12 @@ module arg_parse
      logical :: device_sample     ! extension: temperature sampling on the GPU (-t > 0; the Gumbel-max rule of include/llmk.h)
      integer :: top_k             ! extension: truncated sampling on the GPU (llmk_decode_sample_ex); any of the three with -t > 0
      real :: top_p, min_p         !   selects the device sampler.  0, 1, 0 = off
+     real :: repeat_penalty       ! extension: llama.cpp's penalties over the last repeat_last_n tokens (-1 = the whole context) and
+     integer :: repeat_last_n     !   --logit-bias ID:B (repeatable; ID 1-based as --encode prints it, B may be -inf), all in the device
+     real :: presence_penalty, frequency_penalty   ! sampler (llmk_decode_sample_pen); any of them with -t > 0 selects it.  1, 64, 0, 0 = off
+     integer :: n_bias
+     integer :: bias_id(256)      ! (LLMK_MAX_LOGIT_BIAS entries)
+     real :: bias_val(256)
      logical :: prefill           ! extension: the prompt goes through the model as ONE batched pass (llmk_prefill)
      logical :: stream_load       ! extension: matrices go from the file to the device tensor by tensor (always with --ngpu)
      logical :: timings           ! extension: fill the five "Timings" lines from hipEvent section timers (slow path)
@@ -65,6 +72,11 @@ contains
     a%top_k = 0
     a%top_p = 1
     a%min_p = 0
+    a%repeat_penalty = 1
+    a%repeat_last_n = 64
+    a%presence_penalty = 0
+    a%frequency_penalty = 0
+    a%n_bias = 0
     a%prefill = .false.
     a%stream_load = .false.
     a%timings = .false.
@@ -99,6 +111,11 @@ contains
        case ("--top-k");             read (val, *) a%top_k;       i = i + 2
        case ("--top-p");             read (val, *) a%top_p;       i = i + 2
        case ("--min-p");             read (val, *) a%min_p;       i = i + 2
+       case ("--repeat-penalty");    read (val, *) a%repeat_penalty;    i = i + 2
+       case ("--repeat-last-n");     read (val, *) a%repeat_last_n;     i = i + 2
+       case ("--presence-penalty");  read (val, *) a%presence_penalty;  i = i + 2
+       case ("--frequency-penalty"); read (val, *) a%frequency_penalty; i = i + 2
+       case ("--logit-bias");        call parse_bias(a, trim(val));     i = i + 2
        case ("--prefill");           a%prefill = .true.;       i = i + 1
        case ("--stream-load");       a%stream_load = .true.;   i = i + 1
        case ("--timings");           a%timings = .true.;       i = i + 1
@@ -117,6 +134,32 @@ contains
        end select
     end do
   end subroutine parse_args
+
+  ! --logit-bias ID:B -- B a number, or -inf (also -infinity) to ban the token
+  subroutine parse_bias(a, val)
+    use, intrinsic :: ieee_arithmetic, only: ieee_value, ieee_negative_inf
+    type(args), intent(inout) :: a
+    character(len=*), intent(in) :: val
+    integer :: k, ios
+    k = index(val, ":")
+    ios = 1
+    if (k > 1 .and. k < len(val) .and. a%n_bias < size(a%bias_id)) then
+       a%n_bias = a%n_bias + 1
+       read (val(1:k - 1), *, iostat=ios) a%bias_id(a%n_bias)
+       if (ios == 0) then
+          select case (val(k + 1:))
+          case ("-inf", "-Inf", "-INF", "-infinity", "-Infinity")
+             a%bias_val(a%n_bias) = ieee_value(1.0, ieee_negative_inf)
+          case default
+             read (val(k + 1:), *, iostat=ios) a%bias_val(a%n_bias)
+          end select
+       end if
+    end if
+    if (ios /= 0) then
+       print *, "--logit-bias takes ID:B (at most 256 of them; B a number or -inf):", val
+       stop 1
+    end if
+  end subroutine parse_bias
 
 end module arg_parse
 
@@ -195,6 +238,10 @@ program llm
   logical :: dsample                                ! --device-sample in its case: -t > 0 on one GPU
   integer(c_int64_t) :: dseed                       ! its seed: --seed N, or the clock's
   logical :: filtered                               ! --top-k / --top-p / --min-p given
+  logical :: penalised                              ! a penalty or a --logit-bias given: llmk_*_sample_pen
+  type(llmk_penalties) :: pens
+  type(llmk_logit_bias), allocatable, target :: bias_list(:)
+  integer(c_int), allocatable :: hist_tokens(:)
   type(llmk_sampler) :: sampler
   integer(c_int) :: dnext
   integer(c_int), allocatable, target :: sc_targets(:)   ! --score: the prompt's tokens, each the target of the position before it
@@ -346,7 +393,19 @@ program llm
   if (filtered .and. opts%temperature > 0 .and. opts%ngpu /= 1 .and. lead) &
        write (0, '(A)') "llm: --top-k / --top-p / --min-p are ignored with --ngpu > 1 (the device sampler runs on one GPU, " // &
        "the host sampler does not truncate)"
-  dsample = (opts%device_sample .or. filtered) .and. opts%temperature > 0 .and. opts%ngpu == 1
+  ! --repeat-penalty / --presence-penalty / --frequency-penalty / --logit-bias: likewise (they need the tokens chosen so far, which
+  ! stay on the device)
+  if (opts%repeat_last_n < 0) opts%repeat_last_n = conf%seq_len
+  opts%repeat_last_n = min(opts%repeat_last_n, conf%seq_len)
+  penalised = opts%n_bias > 0 .or. (opts%repeat_last_n > 0 .and. &
+       (opts%repeat_penalty /= 1 .or. opts%presence_penalty /= 0 .or. opts%frequency_penalty /= 0))
+  if (penalised .and. opts%temperature == 0 .and. lead) &
+       write (0, '(A)') "llm: the penalties and --logit-bias are ignored at temperature 0 (they live in the device sampler; " // &
+       "-t with --top-k 1 is its greedy form)"
+  if (penalised .and. opts%temperature > 0 .and. opts%ngpu /= 1 .and. lead) &
+       write (0, '(A)') "llm: the penalties and --logit-bias are ignored with --ngpu > 1 (the device sampler runs on one GPU)"
+  dsample = (opts%device_sample .or. filtered .or. penalised) .and. opts%temperature > 0 .and. opts%ngpu == 1
+  penalised = penalised .and. dsample
   if (dsample) then
      if (opts%seed >= 0) then
         dseed = int(opts%seed, c_int64_t)
@@ -361,6 +420,25 @@ program llm
      sampler%seed = dseed
      if (opts%verbose_ext .and. lead) print '(A,F8.4,A,I0,A,F8.5,A,F8.5)', " device sampler: temperature", opts%temperature, &
           " top_k ", opts%top_k, " top_p", opts%top_p, " min_p", opts%min_p
+     allocate(bias_list(max(1, opts%n_bias)))
+     do k = 1, opts%n_bias
+        bias_list(k)%token = int(opts%bias_id(k), c_int32_t)
+        bias_list(k)%bias = real(opts%bias_val(k), c_float)
+     end do
+     pens%last_n = int(opts%repeat_last_n, c_int32_t)
+     pens%repeat = real(opts%repeat_penalty, c_float)
+     pens%frequency = real(opts%frequency_penalty, c_float)
+     pens%presence = real(opts%presence_penalty, c_float)
+     pens%bias = c_loc(bias_list)
+     pens%n_bias = int(opts%n_bias, c_int32_t)
+     if (penalised .and. opts%verbose_ext .and. lead) then
+        print '(A,F8.4,A,I0,A,F8.4,A,F8.4,A,I0,A)', " device sampler: repeat penalty", opts%repeat_penalty, " over the last ", &
+             opts%repeat_last_n, " tokens, frequency", opts%frequency_penalty, " presence", opts%presence_penalty, ", ", opts%n_bias, &
+             " logit bias entries"
+        do k = 1, opts%n_bias
+           print '(A,I0,A,ES12.4)', "   logit bias: token ", opts%bias_id(k), " ", opts%bias_val(k)
+        end do
+     end if
   end if
 
   ! ---- generation loop (llama2.f90:376-402) -------------------------------------------------------
@@ -413,12 +491,22 @@ program llm
   ! tokens by what follows, so that token is produced, and the clock started, before the pipelined launches are enqueued
   ! (started at the first streamed id instead, several tokens had already completed: the printed rate was slightly high).
   loop_end = seq_len
-  ! --device-sample likewise, with llmk_forward_sample_ex / llmk_decode_sample_ex (all filters off: llmk_forward_sample / llmk_decode_sample)
+  ! the penalties read the context's token record: BOS and the prompt (the tokens fed at positions 1 .. k+1; the last of them is
+  ! recorded again by the first sampled position, which is fed it) go in once, before the first sampled position
+  if (penalised) then
+     k = min(size(prompt_tokens), conf%seq_len - 1)
+     allocate(hist_tokens(k + 1))
+     hist_tokens(1) = 2
+     hist_tokens(2:) = int(prompt_tokens(1:k), c_int)
+     call llmk_check(llmk_set_history(ctx, hist_tokens, int(k + 1, c_int), 1_c_int), "llmk_set_history")
+  end if
+  ! --device-sample likewise, with llmk_forward_sample_pen / llmk_decode_sample_pen (no penalty and no bias: llmk_forward_sample_ex /
+  ! llmk_decode_sample_ex; all filters off as well: llmk_forward_sample / llmk_decode_sample)
   if ((opts%device_argmax .and. opts%temperature == 0 .and. opts%ngpu == 1) .or. dsample) &
        loop_end = min(seq_len, max(size(prompt_tokens), pos0))
   do pos = pos0, loop_end
      if (dsample .and. pos > size(prompt_tokens)) then
-        call llmk_check(llmk_forward_sample_ex(ctx, int(token, c_int), int(pos, c_int), sampler, dnext), "llmk_forward_sample_ex")
+        call llmk_check(llmk_forward_sample_pen(ctx, int(token, c_int), int(pos, c_int), sampler, pens, dnext), "llmk_forward_sample_pen")
         next_tok = dnext
         token = next_tok
         if (lead) write (*, fmt="(A)", advance="no") vocab(token)(1:vocab_len(token))
@@ -444,8 +532,8 @@ program llm
      ts_len = vocab_len
      ts_print = lead
      if (dsample) then
-        call llmk_check(llmk_decode_sample_ex(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
-             sampler, stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample_ex")
+        call llmk_check(llmk_decode_sample_pen(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
+             sampler, pens, stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample_pen")
      else
         call llmk_check(llmk_decode_greedy(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
              stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_greedy")

@@ -24,6 +24,20 @@ module llmk_binding
      integer(c_int64_t) :: seed
   end type llmk_sampler
 
+  ! penalties and logit bias of llmk_forward_sample_pen / llmk_decode_sample_pen: last_n = 0, repeat = 1, frequency = 0,
+  ! presence = 0, n_bias = 0 are "off"; bias = c_loc of an array of n_bias llmk_logit_bias (token 1-based), or c_null_ptr
+  integer(c_int), parameter :: LLMK_MAX_LOGIT_BIAS = 256
+  type, bind(C) :: llmk_logit_bias
+     integer(c_int32_t) :: token
+     real(c_float) :: bias
+  end type llmk_logit_bias
+  type, bind(C) :: llmk_penalties
+     integer(c_int32_t) :: last_n
+     real(c_float) :: repeat, frequency, presence
+     type(c_ptr) :: bias
+     integer(c_int32_t) :: n_bias
+  end type llmk_penalties
+
   interface
      integer(c_int) function llmk_create(cfg, ctx) bind(C, name="llmk_create")
        import :: c_int, c_ptr, llmk_config
@@ -184,6 +198,53 @@ module llmk_binding
        type(llmk_sampler), intent(in) :: sampler
        integer(c_int), intent(out) :: token_out, kept_out
        real(c_float), intent(out) :: tau_out
+     end function
+     ! ... and behind the repetition / frequency / presence penalties and the logit bias (include/llmk.h; nothing on: the _ex two).
+     ! The penalties read the context's token record: llmk_set_history records the prompt (tokens fed at pos0 .. pos0+n-1) once,
+     ! the two _pen functions record what they are fed from there
+     integer(c_int) function llmk_set_history(ctx, tokens, n, pos0) bind(C, name="llmk_set_history")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(in) :: tokens(*)
+       integer(c_int), value :: n, pos0
+     end function
+     integer(c_int) function llmk_get_history(ctx, tokens_out, n, pos0) bind(C, name="llmk_get_history")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: tokens_out(*)
+       integer(c_int), value :: n, pos0
+     end function
+     integer(c_int) function llmk_forward_sample_pen(ctx, token, pos, sampler, penalties, next_token) bind(C, name="llmk_forward_sample_pen")
+       import :: c_int, c_ptr, llmk_sampler, llmk_penalties
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos
+       type(llmk_sampler), intent(in) :: sampler
+       type(llmk_penalties), intent(in) :: penalties
+       integer(c_int), intent(out) :: next_token
+     end function
+     integer(c_int) function llmk_decode_sample_pen(ctx, token, pos0, n, sampler, penalties, ids_out, on_token, user) &
+          bind(C, name="llmk_decode_sample_pen")
+       import :: c_int, c_ptr, c_funptr, llmk_sampler, llmk_penalties
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos0, n
+       type(llmk_sampler), intent(in) :: sampler
+       type(llmk_penalties), intent(in) :: penalties
+       integer(c_int), intent(out) :: ids_out(*)
+       type(c_funptr), value :: on_token
+       type(c_ptr), value :: user
+     end function
+     ! verification hook: the two sampler kernels on caller-supplied logits; adjusted_out = c_loc of vocab_size floats, or c_null_ptr
+     integer(c_int) function llmk_sample_logits_pen(ctx, logits, pos, sampler, penalties, token_out, kept_out, tau_out, adjusted_out) &
+          bind(C, name="llmk_sample_logits_pen")
+       import :: c_int, c_ptr, c_float, llmk_sampler, llmk_penalties
+       type(c_ptr), value :: ctx
+       real(c_float), intent(in) :: logits(*)
+       integer(c_int), value :: pos
+       type(llmk_sampler), intent(in) :: sampler
+       type(llmk_penalties), intent(in) :: penalties
+       integer(c_int), intent(out) :: token_out, kept_out
+       real(c_float), intent(out) :: tau_out
+       type(c_ptr), value :: adjusted_out
      end function
      integer(c_int) function llmk_path(ctx) bind(C, name="llmk_path")
        import :: c_int, c_ptr

@@ -25,7 +25,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_tp_p2p_connect_local", "llmk_tp_p2p_selftest", "llmk_tp_p2p_stress", "llmk_tp_p2p_disable", "llmk_tp_begin", "llmk_tp_segment",
            "llmk_tp_read_partial", "llmk_tp_write_partial", "llmk_tp_read_logits", "llmk_upload", "llmk_upload_rows",
            "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
-           "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_score", "llmk_reset", "llmk_timings",
+           "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_set_history", "llmk_get_history",
+           "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_score", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -53,6 +54,29 @@ class Sampler(C.Structure):
 
 def sampler(temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0) -> Sampler:
     return Sampler(temperature, top_k, top_p, min_p, seed & 0xFFFFFFFFFFFFFFFF)
+
+
+MAX_LOGIT_BIAS = 256
+
+
+class LogitBias(C.Structure):
+    """llmk_logit_bias: a 1-based token id and what is added to its logit (-inf bans the token)"""
+    _fields_ = [("token", C.c_int32), ("bias", C.c_float)]
+
+
+class Penalties(C.Structure):
+    """llmk_penalties: last_n = 0, repeat = 1, frequency = 0, presence = 0, no bias are "off" (include/llmk.h)"""
+    _fields_ = [("last_n", C.c_int32), ("repeat", C.c_float), ("frequency", C.c_float), ("presence", C.c_float),
+                ("bias", C.POINTER(LogitBias)), ("n_bias", C.c_int32)]
+
+
+def penalties(last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, presence: float = 0.0, bias=()) -> Penalties:
+    """bias: [(1-based token, bias)] or {token: bias}.  The entries live in an array the returned struct keeps alive."""
+    items = list(bias.items()) if isinstance(bias, dict) else list(bias)
+    arr = (LogitBias * max(1, len(items)))(*[LogitBias(int(t), float(b)) for t, b in items])
+    pn = Penalties(last_n, repeat, frequency, presence, C.cast(arr, C.POINTER(LogitBias)), len(items))
+    pn._entries = arr
+    return pn
 
 
 def build_lib(force: bool = False) -> str:
@@ -103,6 +127,12 @@ def lib():
             L.llmk_forward_sample_ex.argtypes = [vp, ci, ci, C.POINTER(Sampler), C.POINTER(ci)]
             L.llmk_decode_sample_ex.argtypes = [vp, ci, ci, ci, C.POINTER(Sampler), C.POINTER(ci), vp, vp]
             L.llmk_sample_logits.argtypes = [vp, cf, ci, C.POINTER(Sampler), C.POINTER(ci), C.POINTER(ci), cf]
+        if hasattr(L, "llmk_sample_logits_pen"):
+            L.llmk_set_history.argtypes = [vp, C.POINTER(ci), ci, ci]
+            L.llmk_get_history.argtypes = [vp, C.POINTER(ci), ci, ci]
+            L.llmk_forward_sample_pen.argtypes = [vp, ci, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(ci)]
+            L.llmk_decode_sample_pen.argtypes = [vp, ci, ci, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(ci), vp, vp]
+            L.llmk_sample_logits_pen.argtypes = [vp, cf, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(ci), C.POINTER(ci), cf, cf]
         if hasattr(L, "llmk_score"):
             L.llmk_score.argtypes = [vp, C.POINTER(ci), ci, ci, C.POINTER(ci), cf, C.POINTER(ci), cf]
         L.llmk_reset.argtypes = [vp]
@@ -296,6 +326,55 @@ class Llmk:
         _ck(lib().llmk_sample_logits(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, C.byref(sp), C.byref(tok), C.byref(kept),
                                      C.byref(tau)))
         return tok.value, kept.value, tau.value
+
+    def set_history(self, tokens, pos0: int = 1):
+        """record `tokens` (1-based ids, 0 = none) as fed at positions pos0.. (llmk_set_history): the prompt, once, before the
+        first *_sample_pen call"""
+        t = np.ascontiguousarray(tokens, np.int32)
+        _ck(lib().llmk_set_history(self._h, t.ctypes.data_as(C.POINTER(C.c_int)), len(t), pos0))
+
+    def get_history(self, n: int, pos0: int = 1) -> np.ndarray:
+        """the token record of positions pos0 .. pos0+n-1 (llmk_get_history)"""
+        out = np.zeros(n, np.int32)
+        _ck(lib().llmk_get_history(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), n, pos0))
+        return out
+
+    def forward_sample_pen(self, token: int, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
+                           min_p: float = 0.0, last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, presence: float = 0.0,
+                           bias=()) -> int:
+        """forward_sample_ex behind the penalties and the logit bias of sample_penalty.h (llmk_forward_sample_pen)"""
+        nxt = C.c_int(0)
+        sp = sampler(temperature, seed, top_k, top_p, min_p)
+        pn = penalties(last_n, repeat, frequency, presence, bias)
+        _ck(lib().llmk_forward_sample_pen(self._h, token, pos, C.byref(sp), C.byref(pn), C.byref(nxt)))
+        return nxt.value
+
+    def decode_sample_pen(self, token: int, pos0: int, n: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
+                          min_p: float = 0.0, last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, presence: float = 0.0,
+                          bias=(), on_token=None) -> np.ndarray:
+        """decode_sample_ex behind the penalties and the logit bias (llmk_decode_sample_pen); returns the n ids"""
+        ids = np.zeros(n, np.int32)
+        cb = TOKEN_FN(on_token) if on_token else None
+        sp = sampler(temperature, seed, top_k, top_p, min_p)
+        pn = penalties(last_n, repeat, frequency, presence, bias)
+        _ck(lib().llmk_decode_sample_pen(self._h, token, pos0, n, C.byref(sp), C.byref(pn), ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                         C.cast(cb, C.c_void_p) if cb else None, None))
+        return ids
+
+    def sample_logits_pen(self, logits, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+                          last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, presence: float = 0.0, bias=()):
+        """The two sampler kernels on caller-supplied logits, the window read from the token record (llmk_sample_logits_pen):
+        (1-based token, rows kept, tau, the V adjusted logits)"""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.shape != (self.V,):
+            raise ValueError("one logit per vocabulary row")
+        tok, kept, tau = C.c_int(0), C.c_int(0), C.c_float(0)
+        adj = np.empty(self.V, np.float32)
+        sp = sampler(temperature, seed, top_k, top_p, min_p)
+        pn = penalties(last_n, repeat, frequency, presence, bias)
+        _ck(lib().llmk_sample_logits_pen(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, C.byref(sp), C.byref(pn), C.byref(tok),
+                                         C.byref(kept), C.byref(tau), adj.ctypes.data_as(C.POINTER(C.c_float))))
+        return tok.value, kept.value, tau.value, adj
 
     def generate(self, n: int, prompt=(), want_logits: bool = True, greedy_on_device: bool = False):
         """The reference generation loop at temperature 0 (llama2.f90:376-402)."""
