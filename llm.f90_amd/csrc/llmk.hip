@@ -79,6 +79,28 @@ struct DevTensor {
     bool alias = false;      // `data` points into another tensor's allocation (the rmsnorm gains share one): never freed itself
 };
 
+// What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
+// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h; TAIL_PENALTY: the same behind the penalties and the
+// logit bias of sample_penalty.h); all but the first leave the 1-based id in h_next->id and the sticky error word in h_next->err.
+// enqueue_sampler has what the last two enqueue.
+enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE, TAIL_FILTER, TAIL_PENALTY, TAIL_COUNT };
+
+// What the device's copy of a set of parameter words holds once the stream has drained, as far as the host knows
+template <class T>
+struct DevShadow {
+    T value = {};
+    bool known = false;
+    void invalidate() { known = false; }                        // a pass is about to copy words the host cannot vouch for yet
+    void confirm(const T& v) { value = v; known = true; }      // ... and has copied v
+    template <class F>
+    hipError_t push(const T& want, F copy) {                    // copy() enqueues the write of `want`: only where the device holds something else
+        if (known && memcmp(&want, &value, sizeof(T)) == 0) return hipSuccess;
+        const hipError_t e = copy();
+        if (e == hipSuccess) confirm(want);
+        return e;
+    }
+};
+
 }  // namespace
 
 struct llmk_ctx {
@@ -112,16 +134,15 @@ struct llmk_ctx {
     TkHostWords* host_words() const { return tk_words_behind<TkHostWords>(h_logits, V); }
     TkHostWords* host_words_dev() const { return tk_words_behind<TkHostWords>(h_logits_dev, V); }
     hipStream_t stream = nullptr;
-    hipGraphExec_t graph_logits = nullptr, graph_greedy = nullptr, graph_sample = nullptr, graph_filter = nullptr;
-    llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current llmk_forward_sample / llmk_decode_sample call
-    // what the device's copy of them (TkDevWords::samp) holds once the stream has drained: zeros from llmk_create on; pad = 1 while
-    // unknown.  A pipelined decode writes them only when they differ, so a greedy one on a ctx that never sampled enqueues nothing new
-    llmk_sample_params samp_dev = {};
-    // the same pair for the truncated sampler (llmk_*_sample_ex with a filter on): its parameters sit behind the sampling words
-    // (TkDevWords::filt); filt_known = filt_dev is what the device holds
+    hipGraphExec_t graph[TAIL_COUNT] = {};      // the token pass with each tail, captured at first use (drop_graphs)
+    llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current sampling call
+    // the device's copy of them (TkDevWords::samp): zeros from llmk_create on.  A pipelined decode writes them only when they differ,
+    // so a greedy one on a ctx that never sampled enqueues nothing new
+    DevShadow<llmk_sample_params> samp_dev = {{}, true};
+    // the same pair for the truncated sampler (a filter, a penalty or a bias on): its parameters sit behind the sampling words
+    // (TkDevWords::filt)
     llmk_filter_params* h_filt = nullptr;
-    llmk_filter_params filt_dev = {};
-    bool filt_known = false;
+    DevShadow<llmk_filter_params> filt_dev;
     // penalties and logit bias (llmk_*_sample_pen, sample_penalty.h), allocated by the first call that needs them (pen_setup): the
     // token record (S ints: hist[q - 1] = the 1-based token fed at position q, 0 = none), the V counts of sample_penalty_kernel (all
     // zero between launches), the parameters on the device and the pinned words they are copied from
@@ -129,7 +150,6 @@ struct llmk_ctx {
     int* d_pen_cnt = nullptr;
     llmk_penalty_params* d_pen = nullptr;
     llmk_penalty_params* h_pen = nullptr;
-    hipGraphExec_t graph_pen = nullptr;
     hipEvent_t ev[8] = {};
     float times[5] = {0, 0, 0, 0, 0};
     int n_cu = 256;
@@ -543,10 +563,6 @@ int tk_setup_all(llmk_ctx* c) {
 
 __global__ void bump_serial_kernel(int* tokpos) { tokpos[2] += 1; }
 
-// What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
-// (llmk_forward_sample; TAIL_FILTER: the truncated one of sample_filter.h; TAIL_PENALTY: the same behind the penalties and the
-// logit bias of sample_penalty.h); all but the first leave the 1-based id in h_next->id and the sticky error word in h_next->err
-enum TailMode { TAIL_LOGITS, TAIL_GREEDY, TAIL_SAMPLE, TAIL_FILTER, TAIL_PENALTY };
 // the q4_0 persistent kernels' per-layer scale records (token_kernel.h tk_qsc): the last *n granules of d_gran; null on a context
 // that has none
 unsigned long long* tk_qsc_records(const llmk_ctx* c, size_t* n) {
@@ -558,21 +574,43 @@ hipError_t tk_qsc_clear(llmk_ctx* c, hipStream_t st) {
     unsigned long long* rec = tk_qsc_records(c, &n);
     return rec ? hipMemsetAsync(rec, 0, n * sizeof(unsigned long long), st) : hipSuccess;
 }
+
+// The two sampler kernels on the logits in d_logits, as EVERY site enqueues them -- the tail of a token pass (enqueue_tail), behind
+// each launch of the pipelined decode (decode_run), the verification hooks (sample_logits) -- so that all of them pick one id from
+// one vector.  With `penalty`, sample_penalty_kernel first: it records the fed token (where the site has a record to write), then
+// adjusts the logits in place by the words in d_pen.  Then sample_filter_kernel, by the words in TkDevWords::filt: it leaves its
+// single winner in d_next and, behind a launch of the pipelined decode, in place of that launch's candidates, where the next
+// launch's fold and cand_resolve_kernel pick it up like any other candidate (those launches score their classifier rows with the
+// greedy words, invT = 0: the cheap tail).  The parameter words travel like token and position: copies out of pinned memory, read
+// when a graph replays them.  What differs from site to site:
+struct SamplerSite {
+    const int* tokpos;      // position and fed token are the pass's device words ...
+    int pos, token;         // ... or, without them, these (token 0: none) ...
+    const int* prev;        // ... with the id the filter kernel of the position before left on the device in place of `token`
+    int* record;            // where the fed token is recorded (d_hist), null: the record is read only
+    float2* cand;           // the launch's candidates, replaced by the winner; null and 0: none
+    int ncand;
+    bool copy_pen, copy_filt;      // the parameter words are copied in front of their kernel (the penalties' at every call; the
+                                   // filter's here, or before by the site itself: DevShadow)
+};
+hipError_t enqueue_sampler(llmk_ctx* c, bool penalty, const SamplerSite& s) {
+    TkDevWords* dw = c->dev_words();
+    if (penalty) {
+        if (s.copy_pen) HIPRET(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, s.tokpos, s.pos, s.token, s.prev,
+                           c->d_pen, c->d_hist, s.record, c->d_pen_cnt);
+        HIPRET(hipGetLastError());
+    }
+    if (s.copy_filt) HIPRET(hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, s.tokpos, s.pos, &dw->filt, c->d_next,
+                       s.cand, s.ncand, dw->filter_out);
+    return hipGetLastError();
+}
+
 hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
     if (tail != TAIL_LOGITS) {
         if (tail == TAIL_FILTER || tail == TAIL_PENALTY) {
-            if (tail == TAIL_PENALTY) {
-                // the penalties travel like the filter's parameters; token and position come from the pass's device words, and the
-                // logits are adjusted in place before the filter reads them
-                HIPRET(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, 0,
-                                   (const int*)nullptr, c->d_pen, c->d_hist, c->d_hist, c->d_pen_cnt);
-                HIPRET(hipGetLastError());
-            }
-            // the same kernel as behind a launch of the pipelined decode (decode_run), with the position from the pass's device word
-            HIPRET(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, c->d_tokpos, 0, &c->dev_words()->filt,
-                               c->d_next, (float2*)nullptr, 0, c->dev_words()->filter_out);
+            HIPRET(enqueue_sampler(c, tail == TAIL_PENALTY, {c->d_tokpos, 0, 0, nullptr, c->d_hist, nullptr, 0, true, true}));
         } else if (tail == TAIL_SAMPLE) {
             // invT and the seed travel like token and position: a copy out of pinned memory, read when the graph replays it
             HIPRET(hipMemcpyAsync(&c->dev_words()->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
@@ -696,6 +734,11 @@ hipError_t enqueue_token(llmk_ctx* c, TailMode tail, bool timed) {
     return enqueue_tail(c, tail);
 }
 
+// (the graphs bake in kernel arguments, the path and the tensor types: whatever changes one of those drops them all)
+void drop_graphs(llmk_ctx* c) {
+    for (hipGraphExec_t& g : c->graph)
+        if (g) { hipGraphExecDestroy(g); g = nullptr; }
+}
 int build_graph(llmk_ctx* c, TailMode tail, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -722,6 +765,12 @@ int check_ready(llmk_ctx* c) {
 // token kernel for this context and tell the user once.  The caller re-runs the SAME position on the multi-kernel path,
 // which rewrites that position's KV rows and recomputes x from the embedding: nothing of the failed launch survives.
 constexpr int TK_RANGE_LIMIT = 4;
+// debug library only (LLMK_TK_INJECT_TIMEOUT=pos): the token kernel is launched one workgroup short at this position, so its peers
+// really time out
+bool tk_inject_timeout(int pos) {
+    const char* at = TK_DEBUG ? getenv("LLMK_TK_INJECT_TIMEOUT") : nullptr;
+    return at && atoi(at) == pos;
+}
 int tk_clear_err(llmk_ctx* c) {
     HIPCHK(hipMemsetAsync(&c->dev_words()->err, 0, sizeof(unsigned), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -736,11 +785,7 @@ int tk_retire(llmk_ctx* c, unsigned code, int pos) {
     if (rc) return rc;
     c->use_tk = false;
     c->tk_retired = true;
-    if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
-    if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
-    if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
-    if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
-    if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
+    drop_graphs(c);
     for (int i = 0; i < LLMK_N_TENSORS; ++i)       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
         if (c->q16[i]) { hipFree(c->q16[i]); c->q16[i] = nullptr; }
     c->q16_dirty = true;
@@ -777,8 +822,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
     const bool timed = (c->cfg.flags & LLMK_FLAG_TIMINGS) != 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         c->h_tokpos[2] += 1;  // token serial: makes every exchange epoch of this pass unique
-        // debug library only: launch the token kernel one workgroup short at this position, so its peers really time out
-        c->tk_short_grid = TK_DEBUG && c->use_tk && getenv("LLMK_TK_INJECT_TIMEOUT") && atoi(getenv("LLMK_TK_INJECT_TIMEOUT")) == pos;
+        c->tk_short_grid = c->use_tk && tk_inject_timeout(pos);
         if ((c->tp_size > 1 || c->comm) && !c->p2p) {   // tensor-parallel over RCCL: eager launches with the collectives in between
             rc = enqueue_token_tp(c);
             if (rc) return rc;
@@ -789,7 +833,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
             c->host_words()->err = 0;
             HIPCHK(launch_token_kernel(c, true));
         } else {
-            hipGraphExec_t* g = tail == TAIL_GREEDY ? &c->graph_greedy : tail == TAIL_SAMPLE ? &c->graph_sample : tail == TAIL_FILTER ? &c->graph_filter : tail == TAIL_PENALTY ? &c->graph_pen : &c->graph_logits;
+            hipGraphExec_t* g = &c->graph[tail];
             if (!*g) {
                 rc = build_graph(c, tail, g);
                 if (rc) return rc;
@@ -828,17 +872,14 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
     }
     return LLMK_E_TIMEOUT;
 }
+// ... and the shadows of the words its tail copies to the device: known again once the pass is through
 int run_token(llmk_ctx* c, int token, int pos, TailMode tail) {
-    if (tail == TAIL_FILTER || tail == TAIL_PENALTY) {               // (both tails copy h_filt to the device in the same way)
-        c->filt_known = false;
-        const int rc = run_token_pass(c, token, pos, tail);
-        if (rc == LLMK_OK) { c->filt_dev = *c->h_filt; c->filt_known = true; }
-        return rc;
-    }
-    if (tail != TAIL_SAMPLE) return run_token_pass(c, token, pos, tail);
-    c->samp_dev.pad = 1;                     // (the sampling tail copies h_samp to the device: known again once the pass is through)
+    const bool filt = tail == TAIL_FILTER || tail == TAIL_PENALTY, samp = tail == TAIL_SAMPLE;
+    if (filt) c->filt_dev.invalidate();
+    if (samp) c->samp_dev.invalidate();
     const int rc = run_token_pass(c, token, pos, tail);
-    if (rc == LLMK_OK) c->samp_dev = *c->h_samp;
+    if (rc == LLMK_OK && filt) c->filt_dev.confirm(*c->h_filt);
+    if (rc == LLMK_OK && samp) c->samp_dev.confirm(*c->h_samp);
     return rc;
 }
 
@@ -1764,11 +1805,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
     c->q16_dirty = true;
     if (c->use_tk) {
         c->use_tk = false;
-        if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
-        if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
-        if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
-        if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
-        if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
+        drop_graphs(c);
     }
     // the persistent kernel again, if one is instantiated for this shape with a classifier of this type (round 6: q6_K rows beside
     // q4_0 matrices -- a stock llama.cpp q4_0 file keeps the fast path); otherwise the multi-kernel path
@@ -1788,11 +1825,7 @@ int llmk_set_rms_eps(llmk_ctx* c, float eps) {
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->eps = eps;
-    if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }   // kernel arguments are baked in
-    if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
-    if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
-    if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
-    if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
+    drop_graphs(c);   // kernel arguments are baked in
     return LLMK_OK;
 }
 
@@ -1930,7 +1963,7 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
     return LLMK_OK;
 }
 
-// the id a TAIL_GREEDY / TAIL_SAMPLE pass left in h_next
+// the id a pass with any tail but TAIL_LOGITS left in h_next
 int token_out(llmk_ctx* c, int token, int pos, TailMode tail, int* next_token) {
     int rc = run_token(c, token, pos, tail);
     if (rc) return rc;
@@ -1940,31 +1973,85 @@ int token_out(llmk_ctx* c, int token, int pos, TailMode tail, int* next_token) {
     *next_token = c->h_next->id;
     return LLMK_OK;
 }
-int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
-    if (!c || !next_token) return LLMK_E_ARG;
-    return token_out(c, token, pos, TAIL_GREEDY, next_token);
-}
 
-// invT = f32(1 / T), rounded once; the pinned words every sampling pass copies to the device (TkDevWords::samp)
-int set_sample_params(llmk_ctx* c, float temperature, uint64_t seed) {
-    if (!(temperature > 0.f) || !isfinite(temperature)) return LLMK_E_ARG;      // (NaN fails the first test)
-    const float invT = 1.0f / temperature;
-    if (!isfinite(invT) || !(invT >= FLT_MIN)) return LLMK_E_ARG;              // 1/T beyond the normal f32 range
-    c->h_samp->invT = invT;
-    c->h_samp->seed_lo = (uint32_t)seed;
-    c->h_samp->seed_hi = (uint32_t)(seed >> 32);
-    c->h_samp->pad = 0;
+// ---- the device sampler (sample.h, sample_filter.h, sample_penalty.h): one request, three bodies ------------------------------------
+static_assert(LLMK_PENALTY_MAX_BIAS == LLMK_MAX_LOGIT_BIAS, "sample_penalty.h and llmk.h agree on the length of the bias list");
+// the record, the counts and the parameter words: allocated (and zeroed) by the first call that needs them
+static int pen_setup(llmk_ctx* c) {
+    if (c->d_hist && c->d_pen_cnt && c->d_pen && c->h_pen) return LLMK_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (!c->d_hist) {
+        HIPCHK(dev_alloc(&c->d_hist, (size_t)c->S * sizeof(int)));
+        HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)c->S * sizeof(int), c->stream));
+    }
+    if (!c->d_pen_cnt) {
+        HIPCHK(dev_alloc(&c->d_pen_cnt, (size_t)c->V * sizeof(int)));
+        HIPCHK(hipMemsetAsync(c->d_pen_cnt, 0, (size_t)c->V * sizeof(int), c->stream));
+    }
+    if (!c->d_pen) {
+        HIPCHK(dev_alloc(&c->d_pen, sizeof(llmk_penalty_params)));
+        HIPCHK(hipMemsetAsync(c->d_pen, 0, sizeof(llmk_penalty_params), c->stream));
+    }
+    if (!c->h_pen) {
+        HIPCHK(hipHostMalloc(&c->h_pen, sizeof(llmk_penalty_params), hipHostMallocDefault));
+        memset(c->h_pen, 0, sizeof(llmk_penalty_params));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
 }
-int llmk_forward_sample(llmk_ctx* c, int token, int pos, float temperature, uint64_t seed, int* next_token) {
-    if (!c || !next_token) return LLMK_E_ARG;
-    const int rc = set_sample_params(c, temperature, seed);
+// What a sampling call asks for: checked, then put into the pinned words that the passes copy to the device -- h_samp (invT = f32(1 / T),
+// rounded once), h_filt and, with a penalty or a bias on, h_pen (inv_r = f32(1 / r), as invT is).  pn == null: an entry point WITHOUT a
+// penalties argument (the _pen functions reject a null one themselves).  *tail: TAIL_PENALTY with a penalty or a bias on, else
+// TAIL_FILTER with a filter on, else TAIL_SAMPLE -- so with nothing on the _pen functions ARE the _ex ones, and those the plain ones.
+// Nothing is allocated (pen_setup) before every check has passed, and nothing at all for a request that needs no record.
+static int sampler_request(llmk_ctx* c, const llmk_sampler* sp, const llmk_penalties* pn, TailMode* tail) {
+    if (!sp) return LLMK_E_ARG;
+    if (sp->top_k < 0 || !(sp->top_p > 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f)) return LLMK_E_ARG;      // (NaN fails)
+    if (!(sp->temperature > 0.f) || !isfinite(sp->temperature)) return LLMK_E_ARG;      // (NaN fails the first test)
+    const float invT = 1.0f / sp->temperature;
+    if (!isfinite(invT) || !(invT >= FLT_MIN)) return LLMK_E_ARG;              // 1/T beyond the normal f32 range
+    float inv_r = 1.f;
+    bool pen_on = false, active = false;
+    if (pn) {
+        if (pn->last_n < 0 || pn->last_n > c->S) return LLMK_E_ARG;
+        if (!(pn->repeat > 0.f) || !isfinite(pn->repeat) || !isfinite(pn->frequency) || !isfinite(pn->presence)) return LLMK_E_ARG;      // (NaN fails)
+        inv_r = 1.0f / pn->repeat;
+        if (!isfinite(inv_r) || !(inv_r >= FLT_MIN)) return LLMK_E_ARG;
+        if (pn->n_bias < 0 || pn->n_bias > LLMK_MAX_LOGIT_BIAS || (pn->n_bias > 0 && !pn->bias)) return LLMK_E_ARG;
+        for (int j = 0; j < pn->n_bias; ++j) {
+            const llmk_logit_bias& b = pn->bias[j];
+            if (b.token < 1 || b.token > c->V || !(isfinite(b.bias) || b.bias == -INFINITY)) return LLMK_E_ARG;      // (NaN and +inf fail)
+            for (int k = 0; k < j; ++k)
+                if (pn->bias[k].token == b.token) return LLMK_E_ARG;
+        }
+        pen_on = pn->last_n > 0 && (pn->repeat != 1.f || pn->frequency != 0.f || pn->presence != 0.f);
+        active = pen_on || pn->n_bias > 0;
+    }
+    const uint32_t seed_lo = (uint32_t)sp->seed, seed_hi = (uint32_t)(sp->seed >> 32);
+    *c->h_samp = llmk_sample_params{invT, seed_lo, seed_hi, 0};
+    *c->h_filt = llmk_filter_params{invT, seed_lo, seed_hi, sp->top_k, sp->top_p, sp->min_p, {0, 0}};
+    *tail = sp->top_k != 0 || sp->top_p != 1.f || sp->min_p != 0.f ? TAIL_FILTER : TAIL_SAMPLE;
+    if (!active) return LLMK_OK;
+    const int rc = pen_setup(c);
     if (rc) return rc;
-    return token_out(c, token, pos, TAIL_SAMPLE, next_token);
+    *c->h_pen = llmk_penalty_params{pn->repeat, inv_r, pn->frequency, pn->presence, pen_on ? pn->last_n : 0, pn->n_bias, {0, 0}, {}};
+    for (int j = 0; j < pn->n_bias; ++j) c->h_pen->bias[j] = llmk_penalty_bias{pn->bias[j].token, pn->bias[j].bias};
+    *tail = TAIL_PENALTY;
+    return LLMK_OK;
 }
 
+// One position, the next token drawn on the device
+static int sample_forward(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* next_token) {
+    TailMode tail;
+    const int rc = sampler_request(c, sp, pn, &tail);
+    return rc ? rc : token_out(c, token, pos, tail, next_token);
+}
+
+static bool decode_args_ok(const llmk_ctx* c, int token, int pos0, int n, const int* ids_out) {
+    return c && ids_out && n >= 1 && pos0 >= 1 && pos0 + n - 1 <= c->S && token >= 1 && token <= c->V;
+}
 // The generation loop of llama2.f90:379-396 for n positions with no host round trip between them: at temperature 0
-// (TAIL_GREEDY, the argmax) or by the sampling rule of sample.h (TAIL_SAMPLE, parameters already in c->h_samp).
+// (TAIL_GREEDY, the argmax) or by the request in the pinned words (sampler_request)
 int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_out, llmk_token_fn on_token, void* user) {
     int rc = check_ready(c);
     if (rc) return rc;
@@ -1979,26 +2066,17 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         TkDevWords* dw = c->dev_words();
         memset(h_ids, 0, (size_t)n * sizeof(int));
         c->host_words()->err = 0;
-        // the GR launches score their classifier rows with these parameters (token_kernel.h tk_sample_params); invT = 0 is greedy
-        // (TAIL_FILTER: greedy words -- the cheap tail -- and sample_filter_kernel behind every launch, which replaces the launch's
-        // candidates by its own single winner: the next launch's fold and cand_resolve_kernel pick that up like any other candidate;
-        // TAIL_PENALTY: sample_penalty_kernel in between, which records the token the launch was fed -- the host's at the first
-        // position, afterwards the id the filter kernel of the position before left in d_next -- and adjusts the launch's logits)
+        // the GR launches score their classifier rows with the sampling words (token_kernel.h tk_sample_params): the request's, or
+        // zeros -- invT = 0 is greedy, which is also what the sampler kernels run behind (enqueue_sampler).  Those words and the
+        // filter's are written only where the device holds others
         const bool filter_tail = tail == TAIL_FILTER || tail == TAIL_PENALTY;
-        if (tail == TAIL_PENALTY) HIPCHK(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
         const llmk_sample_params want = tail == TAIL_SAMPLE ? *c->h_samp : llmk_sample_params{};
-        if (filter_tail && !(c->filt_known && memcmp(c->h_filt, &c->filt_dev, sizeof(llmk_filter_params)) == 0)) {
-            HIPCHK(hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
-            c->filt_dev = *c->h_filt;
-            c->filt_known = true;
-        }
-        if (memcmp(&want, &c->samp_dev, sizeof(want)) != 0) {
-            if (tail == TAIL_SAMPLE)
-                HIPCHK(hipMemcpyAsync(&dw->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
-            else
-                HIPCHK(hipMemsetAsync(&dw->samp, 0, sizeof(llmk_sample_params), c->stream));
-            c->samp_dev = want;
-        }
+        if (filter_tail)
+            HIPCHK(c->filt_dev.push(*c->h_filt, [&] { return hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream); }));
+        HIPCHK(c->samp_dev.push(want, [&] {
+            return tail == TAIL_SAMPLE ? hipMemcpyAsync(&dw->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream)
+                                       : hipMemsetAsync(&dw->samp, 0, sizeof(llmk_sample_params), c->stream);
+        }));
         for (int i = 0; i < n; ++i) {
             c->h_tokpos[0] = token - 1;
             c->h_tokpos[1] = pos0 + i;
@@ -2006,19 +2084,12 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             TkGreedy g;
             g.gflags = TKG_GREEDY | (i ? TKG_CAND_IN | TKG_ID : 0);
             g.id_index = i - 1;
-            // debug library only: this launch one workgroup short, so its peers really time out INSIDE the pipeline
-            c->tk_short_grid = TK_DEBUG && getenv("LLMK_TK_INJECT_TIMEOUT") && atoi(getenv("LLMK_TK_INJECT_TIMEOUT")) == pos0 + i;
+            c->tk_short_grid = tk_inject_timeout(pos0 + i);      // (INSIDE the pipeline)
             HIPCHK(launch_token_kernel(c, false, g));
-            if (tail == TAIL_PENALTY) {
-                hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos0 + i,
-                                   token, i ? (const int*)c->d_next : (const int*)nullptr, c->d_pen, c->d_hist, c->d_hist, c->d_pen_cnt);
-                HIPCHK(hipGetLastError());
-            }
-            if (filter_tail) {
-                hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos0 + i,
-                                   &dw->filt, c->d_next, dw->cand[(pos0 + i) & 1], TK_NCU, dw->filter_out);
-                HIPCHK(hipGetLastError());
-            }
+            // the fed token: the host's at the first position, afterwards the id the filter kernel of the position before left in d_next
+            if (filter_tail)
+                HIPCHK(enqueue_sampler(c, tail == TAIL_PENALTY, {nullptr, pos0 + i, token, i ? c->d_next : nullptr, c->d_hist,
+                                                                 dw->cand[(pos0 + i) & 1], TK_NCU, i == 0, false}));
         }
         hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, dw->cand[(pos0 + n - 1) & 1], h_ids_dev + (n - 1), c->d_next, &dw->err, c->V);
         HIPCHK(hipGetLastError());
@@ -2061,71 +2132,32 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
     }
     return LLMK_OK;
 }
-int llmk_decode_greedy(llmk_ctx* c, int token, int pos0, int n, int* ids_out, llmk_token_fn on_token, void* user) {
-    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
-    return decode_run(c, token, pos0, n, TAIL_GREEDY, ids_out, on_token, user);
-}
-int llmk_decode_sample(llmk_ctx* c, int token, int pos0, int n, float temperature, uint64_t seed, int* ids_out,
-                       llmk_token_fn on_token, void* user) {
-    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
-    const int rc = set_sample_params(c, temperature, seed);
-    if (rc) return rc;
-    return decode_run(c, token, pos0, n, TAIL_SAMPLE, ids_out, on_token, user);
+
+static int sample_decode(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, const llmk_penalties* pn, int* ids_out,
+                         llmk_token_fn on_token, void* user) {
+    TailMode tail;
+    const int rc = sampler_request(c, sp, pn, &tail);
+    return rc ? rc : decode_run(c, token, pos0, n, tail, ids_out, on_token, user);
 }
 
-// The truncated sampler: checks, then the pinned words of sample_filter.h.  *filtered = a filter is on (none: the _ex functions ARE
-// llmk_forward_sample / llmk_decode_sample)
-int set_filter_params(llmk_ctx* c, const llmk_sampler* sp, bool* filtered) {
-    if (!sp) return LLMK_E_ARG;
-    if (sp->top_k < 0 || !(sp->top_p > 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f)) return LLMK_E_ARG;      // (NaN fails)
-    const int rc = set_sample_params(c, sp->temperature, sp->seed);
-    if (rc) return rc;
-    llmk_filter_params f = {};
-    f.invT = c->h_samp->invT;
-    f.seed_lo = c->h_samp->seed_lo;
-    f.seed_hi = c->h_samp->seed_hi;
-    f.top_k = sp->top_k;
-    f.top_p = sp->top_p;
-    f.min_p = sp->min_p;
-    *c->h_filt = f;
-    *filtered = sp->top_k != 0 || sp->top_p != 1.f || sp->min_p != 0.f;
-    return LLMK_OK;
-}
-int llmk_forward_sample_ex(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, int* next_token) {
-    if (!c || !next_token) return LLMK_E_ARG;
-    bool filtered = false;
-    const int rc = set_filter_params(c, sp, &filtered);
-    if (rc) return rc;
-    return token_out(c, token, pos, filtered ? TAIL_FILTER : TAIL_SAMPLE, next_token);
-}
-int llmk_decode_sample_ex(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, int* ids_out, llmk_token_fn on_token, void* user) {
-    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
-    bool filtered = false;
-    const int rc = set_filter_params(c, sp, &filtered);
-    if (rc) return rc;
-    return decode_run(c, token, pos0, n, filtered ? TAIL_FILTER : TAIL_SAMPLE, ids_out, on_token, user);
-}
-// Verification hook: the rule on the caller's logits, by the kernel every path runs (no token pass; the ctx's own logits buffer
-// is overwritten, nothing else -- the sticky error word behind it included).  Whole-model contexts only: a TP rank's classifier
-// owns a slice of the vocabulary, and its logits buffer belongs to the collective.
-int llmk_sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, int* token_out_, int* kept_out, float* tau_out) {
-    if (!c || !logits || !token_out_ || pos < 1 || c->tp_size != 1) return LLMK_E_ARG;
-    bool filtered = false;
-    int rc = set_filter_params(c, sp, &filtered);
+// Verification hook: the rule on the caller's logits as if they were those of position `pos`, by the kernels every path runs (no
+// token pass; the ctx's own logits buffer is overwritten, nothing else -- the sticky error word behind it included).  The filter
+// kernel runs with all filters off too; the penalty kernel's window is read from the record, which is not written.
+static int sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* token_out_,
+                         int* kept_out, float* tau_out, float* adjusted_out) {
+    TailMode tail;
+    int rc = sampler_request(c, sp, pn, &tail);
     if (rc) return rc;
     if ((rc = check_ready(c)) != LLMK_OK) return rc;
     HIPCHK(hipSetDevice(c->cfg.device));
-    c->filt_known = false;
+    c->filt_dev.invalidate();
     HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, &c->dev_words()->filt,
-                       c->d_next, (float2*)nullptr, 0, c->dev_words()->filter_out);
-    HIPCHK(hipGetLastError());
+    HIPCHK(enqueue_sampler(c, tail == TAIL_PENALTY, {nullptr, pos, 0, nullptr, nullptr, nullptr, 0, true, true}));
     HIPCHK(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(&c->h_next->kept, c->dev_words()->filter_out, sizeof(TkDevWords::filter_out), hipMemcpyDeviceToHost, c->stream));      // kept, tau
+    if (adjusted_out) HIPCHK(hipMemcpyAsync(adjusted_out, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->filt_dev = *c->h_filt;
-    c->filt_known = true;
+    c->filt_dev.confirm(*c->h_filt);
     if (kept_out) *kept_out = c->h_next->kept;
     if (tau_out) *tau_out = c->h_next->tau;
     if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;
@@ -2133,61 +2165,53 @@ int llmk_sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sam
     return LLMK_OK;
 }
 
-// ---- penalties and logit bias (sample_penalty.h) -------------------------------------------------------------------------------
-static_assert(LLMK_PENALTY_MAX_BIAS == LLMK_MAX_LOGIT_BIAS, "sample_penalty.h and llmk.h agree on the length of the bias list");
-// the record, the counts and the parameter words: allocated (and zeroed) by the first call that needs them
-static int pen_setup(llmk_ctx* c) {
-    if (c->d_hist && c->d_pen_cnt && c->d_pen && c->h_pen) return LLMK_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (!c->d_hist) {
-        HIPCHK(dev_alloc(&c->d_hist, (size_t)c->S * sizeof(int)));
-        HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)c->S * sizeof(int), c->stream));
-    }
-    if (!c->d_pen_cnt) {
-        HIPCHK(dev_alloc(&c->d_pen_cnt, (size_t)c->V * sizeof(int)));
-        HIPCHK(hipMemsetAsync(c->d_pen_cnt, 0, (size_t)c->V * sizeof(int), c->stream));
-    }
-    if (!c->d_pen) {
-        HIPCHK(dev_alloc(&c->d_pen, sizeof(llmk_penalty_params)));
-        HIPCHK(hipMemsetAsync(c->d_pen, 0, sizeof(llmk_penalty_params), c->stream));
-    }
-    if (!c->h_pen) {
-        HIPCHK(hipHostMalloc(&c->h_pen, sizeof(llmk_penalty_params), hipHostMallocDefault));
-        memset(c->h_pen, 0, sizeof(llmk_penalty_params));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return LLMK_OK;
+// The entry points: their own pointer and range checks, then one of the bodies above
+int llmk_forward_greedy(llmk_ctx* c, int token, int pos, int* next_token) {
+    if (!c || !next_token) return LLMK_E_ARG;
+    return token_out(c, token, pos, TAIL_GREEDY, next_token);
 }
-// Checks, then the pinned words of sample_penalty.h.  *active = a penalty or a bias is on (none: the _pen functions ARE the _ex ones).
-// inv_r = f32(1 / r), rounded once, as invT is.
-static int set_penalty_params(llmk_ctx* c, const llmk_penalties* pn, bool* active) {
-    if (!pn) return LLMK_E_ARG;
-    if (pn->last_n < 0 || pn->last_n > c->S) return LLMK_E_ARG;
-    if (!(pn->repeat > 0.f) || !isfinite(pn->repeat) || !isfinite(pn->frequency) || !isfinite(pn->presence)) return LLMK_E_ARG;      // (NaN fails)
-    const float inv_r = 1.0f / pn->repeat;
-    if (!isfinite(inv_r) || !(inv_r >= FLT_MIN)) return LLMK_E_ARG;
-    if (pn->n_bias < 0 || pn->n_bias > LLMK_MAX_LOGIT_BIAS || (pn->n_bias > 0 && !pn->bias)) return LLMK_E_ARG;
-    for (int j = 0; j < pn->n_bias; ++j) {
-        const llmk_logit_bias& b = pn->bias[j];
-        if (b.token < 1 || b.token > c->V || !(isfinite(b.bias) || b.bias == -INFINITY)) return LLMK_E_ARG;      // (NaN and +inf fail)
-        for (int k = 0; k < j; ++k)
-            if (pn->bias[k].token == b.token) return LLMK_E_ARG;
-    }
-    const bool pen_on = pn->last_n > 0 && (pn->repeat != 1.f || pn->frequency != 0.f || pn->presence != 0.f);
-    *active = pen_on || pn->n_bias > 0;
-    if (!*active) return LLMK_OK;
-    const int rc = pen_setup(c);
-    if (rc) return rc;
-    llmk_penalty_params* h = c->h_pen;
-    memset(h, 0, sizeof(*h));
-    h->repeat = pn->repeat;
-    h->inv_repeat = inv_r;
-    h->frequency = pn->frequency;
-    h->presence = pn->presence;
-    h->last_n = pen_on ? pn->last_n : 0;
-    h->n_bias = pn->n_bias;
-    for (int j = 0; j < pn->n_bias; ++j) { h->bias[j].token = pn->bias[j].token; h->bias[j].bias = pn->bias[j].bias; }
-    return LLMK_OK;
+int llmk_forward_sample(llmk_ctx* c, int token, int pos, float temperature, uint64_t seed, int* next_token) {
+    if (!c || !next_token) return LLMK_E_ARG;
+    const llmk_sampler sp = {temperature, 0, 1.f, 0.f, seed};      // (no filter)
+    return sample_forward(c, token, pos, &sp, nullptr, next_token);
+}
+int llmk_forward_sample_ex(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, int* next_token) {
+    if (!c || !next_token) return LLMK_E_ARG;
+    return sample_forward(c, token, pos, sp, nullptr, next_token);
+}
+int llmk_forward_sample_pen(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* next_token) {
+    if (!c || !next_token || !pn || token < 1 || token > c->V || pos < 1 || pos > c->S) return LLMK_E_ARG;      // (before pen_setup allocates)
+    return sample_forward(c, token, pos, sp, pn, next_token);
+}
+int llmk_decode_greedy(llmk_ctx* c, int token, int pos0, int n, int* ids_out, llmk_token_fn on_token, void* user) {
+    if (!decode_args_ok(c, token, pos0, n, ids_out)) return LLMK_E_ARG;
+    return decode_run(c, token, pos0, n, TAIL_GREEDY, ids_out, on_token, user);
+}
+int llmk_decode_sample(llmk_ctx* c, int token, int pos0, int n, float temperature, uint64_t seed, int* ids_out,
+                       llmk_token_fn on_token, void* user) {
+    if (!decode_args_ok(c, token, pos0, n, ids_out)) return LLMK_E_ARG;
+    const llmk_sampler sp = {temperature, 0, 1.f, 0.f, seed};      // (no filter)
+    return sample_decode(c, token, pos0, n, &sp, nullptr, ids_out, on_token, user);
+}
+int llmk_decode_sample_ex(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, int* ids_out, llmk_token_fn on_token, void* user) {
+    if (!decode_args_ok(c, token, pos0, n, ids_out)) return LLMK_E_ARG;
+    return sample_decode(c, token, pos0, n, sp, nullptr, ids_out, on_token, user);
+}
+int llmk_decode_sample_pen(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, const llmk_penalties* pn, int* ids_out,
+                           llmk_token_fn on_token, void* user) {
+    if (!decode_args_ok(c, token, pos0, n, ids_out) || !pn) return LLMK_E_ARG;
+    return sample_decode(c, token, pos0, n, sp, pn, ids_out, on_token, user);
+}
+// (whole-model contexts only: a TP rank's classifier owns a slice of the vocabulary, and its logits buffer belongs to the collective.
+// The _pen hook's window ends at `pos`, so pos <= seq_len there)
+int llmk_sample_logits(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, int* token_out_, int* kept_out, float* tau_out) {
+    if (!c || !logits || !token_out_ || pos < 1 || c->tp_size != 1) return LLMK_E_ARG;
+    return sample_logits(c, logits, pos, sp, nullptr, token_out_, kept_out, tau_out, nullptr);
+}
+int llmk_sample_logits_pen(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* token_out_,
+                           int* kept_out, float* tau_out, float* adjusted_out) {
+    if (!c || !logits || !token_out_ || !pn || pos < 1 || pos > c->S || c->tp_size != 1) return LLMK_E_ARG;
+    return sample_logits(c, logits, pos, sp, pn, token_out_, kept_out, tau_out, adjusted_out);
 }
 int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
     if (!c || !tokens || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
@@ -2205,58 +2229,6 @@ int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(tokens_out, c->d_hist + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return LLMK_OK;
-}
-int llmk_forward_sample_pen(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* next_token) {
-    if (!c || !next_token || token < 1 || token > c->V || pos < 1 || pos > c->S) return LLMK_E_ARG;      // (before pen_setup allocates)
-    bool filtered = false, active = false;
-    int rc = set_filter_params(c, sp, &filtered);
-    if (rc) return rc;
-    if ((rc = set_penalty_params(c, pn, &active)) != LLMK_OK) return rc;
-    return token_out(c, token, pos, active ? TAIL_PENALTY : filtered ? TAIL_FILTER : TAIL_SAMPLE, next_token);
-}
-int llmk_decode_sample_pen(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, const llmk_penalties* pn, int* ids_out,
-                           llmk_token_fn on_token, void* user) {
-    if (!c || !ids_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S || token < 1 || token > c->V) return LLMK_E_ARG;
-    bool filtered = false, active = false;
-    int rc = set_filter_params(c, sp, &filtered);
-    if (rc) return rc;
-    if ((rc = set_penalty_params(c, pn, &active)) != LLMK_OK) return rc;
-    return decode_run(c, token, pos0, n, active ? TAIL_PENALTY : filtered ? TAIL_FILTER : TAIL_SAMPLE, ids_out, on_token, user);
-}
-// Verification hook: llmk_sample_logits with sample_penalty_kernel in front, as every path runs the two.  The window is read from
-// the record (positions up to and including `pos`, so pos <= seq_len); the record is not written.
-int llmk_sample_logits_pen(llmk_ctx* c, const float* logits, int pos, const llmk_sampler* sp, const llmk_penalties* pn, int* token_out_,
-                           int* kept_out, float* tau_out, float* adjusted_out) {
-    if (!c || !logits || !token_out_ || pos < 1 || pos > c->S || c->tp_size != 1) return LLMK_E_ARG;
-    bool filtered = false, active = false;
-    int rc = set_filter_params(c, sp, &filtered);
-    if (rc) return rc;
-    if ((rc = set_penalty_params(c, pn, &active)) != LLMK_OK) return rc;
-    if ((rc = check_ready(c)) != LLMK_OK) return rc;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    c->filt_known = false;
-    HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (active) {
-        HIPCHK(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, 0,
-                           (const int*)nullptr, c->d_pen, c->d_hist, (int*)nullptr, c->d_pen_cnt);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(&c->dev_words()->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, (const int*)nullptr, pos, &c->dev_words()->filt,
-                       c->d_next, (float2*)nullptr, 0, c->dev_words()->filter_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&c->h_next->kept, c->dev_words()->filter_out, sizeof(TkDevWords::filter_out), hipMemcpyDeviceToHost, c->stream));      // kept, tau
-    if (adjusted_out) HIPCHK(hipMemcpyAsync(adjusted_out, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->filt_dev = *c->h_filt;
-    c->filt_known = true;
-    if (kept_out) *kept_out = c->h_next->kept;
-    if (tau_out) *tau_out = c->h_next->tau;
-    if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;
-    *token_out_ = c->h_next->id;
     return LLMK_OK;
 }
 
@@ -2640,11 +2612,7 @@ int llmk_tp_p2p_disable(llmk_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->p2p = false;
-    if (c->graph_logits) { hipGraphExecDestroy(c->graph_logits); c->graph_logits = nullptr; }
-    if (c->graph_greedy) { hipGraphExecDestroy(c->graph_greedy); c->graph_greedy = nullptr; }
-    if (c->graph_sample) { hipGraphExecDestroy(c->graph_sample); c->graph_sample = nullptr; }
-    if (c->graph_filter) { hipGraphExecDestroy(c->graph_filter); c->graph_filter = nullptr; }
-    if (c->graph_pen) { hipGraphExecDestroy(c->graph_pen); c->graph_pen = nullptr; }
+    drop_graphs(c);
     return LLMK_OK;
 }
 
@@ -2781,11 +2749,7 @@ int llmk_destroy(llmk_ctx* c) {
         if (c->ipc_mapped[r]) hipIpcCloseMemHandle(c->ipc_mapped[r]);
     if (c->d_inbox) hipFree(c->d_inbox);
     if (c->d_tp_bad) hipFree(c->d_tp_bad);
-    if (c->graph_logits) hipGraphExecDestroy(c->graph_logits);
-    if (c->graph_greedy) hipGraphExecDestroy(c->graph_greedy);
-    if (c->graph_sample) hipGraphExecDestroy(c->graph_sample);
-    if (c->graph_filter) hipGraphExecDestroy(c->graph_filter);
-    if (c->graph_pen) hipGraphExecDestroy(c->graph_pen);
+    drop_graphs(c);
     for (int i = 0; i < LLMK_N_TENSORS; ++i) {
         if (c->t[i].data && !c->t[i].alias) hipFree(c->t[i].data);
     }

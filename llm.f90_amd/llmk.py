@@ -79,6 +79,11 @@ def penalties(last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, pres
     return pn
 
 
+def _request(temperature, seed, top_k, top_p, min_p, *pen):
+    """a sampling wrapper's keyword arguments as what the C entry points take: (byref(Sampler), byref(Penalties))"""
+    return C.byref(sampler(temperature, seed, top_k, top_p, min_p)), C.byref(penalties(*pen))
+
+
 def build_lib(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 -> csrc/libllmk.so (cross-compiles without a GPU)."""
     subprocess.run(["make", "-s", "-C", _HERE, "lib"] + (["-B"] if force else []), check=True)
@@ -275,13 +280,16 @@ class Llmk:
         _ck(lib().llmk_forward_greedy(self._h, token, pos, C.byref(nxt)))
         return nxt.value
 
-    def decode_greedy(self, token: int, pos0: int, n: int, on_token=None) -> np.ndarray:
-        """n positions from pos0 at temperature 0 with the argmax on the device (llmk_decode_greedy); returns the n ids."""
+    def _decode(self, fn, token: int, pos0: int, n: int, on_token, *request) -> np.ndarray:
+        """a llmk_decode_* call: fn(ctx, token, pos0, n, *request, ids_out, on_token, user); returns the n ids"""
         ids = np.zeros(n, np.int32)
         cb = TOKEN_FN(on_token) if on_token else None
-        _ck(lib().llmk_decode_greedy(self._h, token, pos0, n, ids.ctypes.data_as(C.POINTER(C.c_int)),
-                                     C.cast(cb, C.c_void_p) if cb else None, None))
+        _ck(fn(self._h, token, pos0, n, *request, ids.ctypes.data_as(C.POINTER(C.c_int)), C.cast(cb, C.c_void_p) if cb else None, None))
         return ids
+
+    def decode_greedy(self, token: int, pos0: int, n: int, on_token=None) -> np.ndarray:
+        """n positions from pos0 at temperature 0 with the argmax on the device (llmk_decode_greedy); returns the n ids."""
+        return self._decode(lib().llmk_decode_greedy, token, pos0, n, on_token)
 
     def forward_sample(self, token: int, pos: int, temperature: float, seed: int) -> int:
         """One position; the next token drawn on the device at temperature T > 0 (llmk_forward_sample, the rule of sample.h)."""
@@ -291,29 +299,21 @@ class Llmk:
 
     def decode_sample(self, token: int, pos0: int, n: int, temperature: float, seed: int, on_token=None) -> np.ndarray:
         """n positions from pos0 at temperature T > 0 with the draw on the device (llmk_decode_sample); returns the n ids."""
-        ids = np.zeros(n, np.int32)
-        cb = TOKEN_FN(on_token) if on_token else None
-        _ck(lib().llmk_decode_sample(self._h, token, pos0, n, temperature, seed & 0xFFFFFFFFFFFFFFFF,
-                                     ids.ctypes.data_as(C.POINTER(C.c_int)), C.cast(cb, C.c_void_p) if cb else None, None))
-        return ids
+        return self._decode(lib().llmk_decode_sample, token, pos0, n, on_token, temperature, seed & 0xFFFFFFFFFFFFFFFF)
 
     def forward_sample_ex(self, token: int, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
                           min_p: float = 0.0) -> int:
         """forward_sample with top-k / top-p / min-p truncation in front of the draw (llmk_forward_sample_ex, sample_filter.h)."""
         nxt = C.c_int(0)
-        sp = sampler(temperature, seed, top_k, top_p, min_p)
-        _ck(lib().llmk_forward_sample_ex(self._h, token, pos, C.byref(sp), C.byref(nxt)))
+        sp, _ = _request(temperature, seed, top_k, top_p, min_p)
+        _ck(lib().llmk_forward_sample_ex(self._h, token, pos, sp, C.byref(nxt)))
         return nxt.value
 
     def decode_sample_ex(self, token: int, pos0: int, n: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
                          min_p: float = 0.0, on_token=None) -> np.ndarray:
         """decode_sample with top-k / top-p / min-p truncation (llmk_decode_sample_ex); returns the n ids."""
-        ids = np.zeros(n, np.int32)
-        cb = TOKEN_FN(on_token) if on_token else None
-        sp = sampler(temperature, seed, top_k, top_p, min_p)
-        _ck(lib().llmk_decode_sample_ex(self._h, token, pos0, n, C.byref(sp), ids.ctypes.data_as(C.POINTER(C.c_int)),
-                                        C.cast(cb, C.c_void_p) if cb else None, None))
-        return ids
+        sp, _ = _request(temperature, seed, top_k, top_p, min_p)
+        return self._decode(lib().llmk_decode_sample_ex, token, pos0, n, on_token, sp)
 
     def sample_logits(self, logits, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0):
         """The device sampler's rule on caller-supplied logits (V floats), no token pass (llmk_sample_logits):
@@ -322,9 +322,8 @@ class Llmk:
         if lg.shape != (self.V,):
             raise ValueError("one logit per vocabulary row")
         tok, kept, tau = C.c_int(0), C.c_int(0), C.c_float(0)
-        sp = sampler(temperature, seed, top_k, top_p, min_p)
-        _ck(lib().llmk_sample_logits(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, C.byref(sp), C.byref(tok), C.byref(kept),
-                                     C.byref(tau)))
+        sp, _ = _request(temperature, seed, top_k, top_p, min_p)
+        _ck(lib().llmk_sample_logits(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, sp, C.byref(tok), C.byref(kept), C.byref(tau)))
         return tok.value, kept.value, tau.value
 
     def set_history(self, tokens, pos0: int = 1):
@@ -344,22 +343,16 @@ class Llmk:
                            bias=()) -> int:
         """forward_sample_ex behind the penalties and the logit bias of sample_penalty.h (llmk_forward_sample_pen)"""
         nxt = C.c_int(0)
-        sp = sampler(temperature, seed, top_k, top_p, min_p)
-        pn = penalties(last_n, repeat, frequency, presence, bias)
-        _ck(lib().llmk_forward_sample_pen(self._h, token, pos, C.byref(sp), C.byref(pn), C.byref(nxt)))
+        sp, pn = _request(temperature, seed, top_k, top_p, min_p, last_n, repeat, frequency, presence, bias)
+        _ck(lib().llmk_forward_sample_pen(self._h, token, pos, sp, pn, C.byref(nxt)))
         return nxt.value
 
     def decode_sample_pen(self, token: int, pos0: int, n: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0,
                           min_p: float = 0.0, last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, presence: float = 0.0,
                           bias=(), on_token=None) -> np.ndarray:
         """decode_sample_ex behind the penalties and the logit bias (llmk_decode_sample_pen); returns the n ids"""
-        ids = np.zeros(n, np.int32)
-        cb = TOKEN_FN(on_token) if on_token else None
-        sp = sampler(temperature, seed, top_k, top_p, min_p)
-        pn = penalties(last_n, repeat, frequency, presence, bias)
-        _ck(lib().llmk_decode_sample_pen(self._h, token, pos0, n, C.byref(sp), C.byref(pn), ids.ctypes.data_as(C.POINTER(C.c_int)),
-                                         C.cast(cb, C.c_void_p) if cb else None, None))
-        return ids
+        sp, pn = _request(temperature, seed, top_k, top_p, min_p, last_n, repeat, frequency, presence, bias)
+        return self._decode(lib().llmk_decode_sample_pen, token, pos0, n, on_token, sp, pn)
 
     def sample_logits_pen(self, logits, pos: int, temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
                           last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, presence: float = 0.0, bias=()):
@@ -370,10 +363,9 @@ class Llmk:
             raise ValueError("one logit per vocabulary row")
         tok, kept, tau = C.c_int(0), C.c_int(0), C.c_float(0)
         adj = np.empty(self.V, np.float32)
-        sp = sampler(temperature, seed, top_k, top_p, min_p)
-        pn = penalties(last_n, repeat, frequency, presence, bias)
-        _ck(lib().llmk_sample_logits_pen(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, C.byref(sp), C.byref(pn), C.byref(tok),
-                                         C.byref(kept), C.byref(tau), adj.ctypes.data_as(C.POINTER(C.c_float))))
+        sp, pn = _request(temperature, seed, top_k, top_p, min_p, last_n, repeat, frequency, presence, bias)
+        _ck(lib().llmk_sample_logits_pen(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, sp, pn, C.byref(tok), C.byref(kept), C.byref(tau),
+                                         adj.ctypes.data_as(C.POINTER(C.c_float))))
         return tok.value, kept.value, tau.value, adj
 
     def generate(self, n: int, prompt=(), want_logits: bool = True, greedy_on_device: bool = False):
