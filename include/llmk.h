@@ -332,6 +332,44 @@ int llmk_decode_sample_pen(llmk_ctx *ctx, int token, int pos0, int n, const llmk
 int llmk_sample_logits_pen(llmk_ctx *ctx, const float *logits, int pos, const llmk_sampler *sampler, const llmk_penalties *penalties,
                            int *token_out, int *kept_out, float *tau_out, float *adjusted_out);
 
+/* Decode log-probs: what the model thought of the tokens a sampling call returned (llama.cpp's --n-probs, the `logprobs` /
+ * `top_logprobs` of the serving APIs), computed on the device behind the kernel that picked each token (csrc/logprob.h,
+ * sample_logprob_kernel).  With z the vocab_size RAW logits of a position -- what the classifier wrote, before
+ * bias, penalties, temperature and truncation, i.e. what llmk_score reports for the same tokens -- and L their log-sum-exp:
+ *   token_logprob[i]         = z[id - 1] - L for the id returned for position i;
+ *   top_tokens[i*top_n + j],
+ *   top_logprobs[i*top_n + j] = the j-th row in the order z descending, then index ascending (-0.0 and +0.0 tie), over the rows with
+ *                              z > -inf that are not NaN: {1-based id, z - L}; {0, -inf} where fewer than top_n such rows exist.
+ * A +inf or NaN logit adds no error of its own: L and the values are then what the arithmetic of csrc/score.h gives in the kernel's
+ * order -- NaN, except that a NaN which is the first row of a thread's chain is dropped (an empty log-sum-exp state ignores what it
+ * holds), so at vocab_size <= 1024 NaN rows do not reach L at all; the ids are defined either way.  LLMK_E_NONFINITE stays what the
+ * greedy and sampling functions make of it.
+ *
+ * sampler == NULL is the greedy form -- the rule of llmk_forward_greedy / llmk_decode_greedy, first maximum wins; penalties must then
+ * be NULL as well.  Otherwise sampler and the optional penalties (NULL = none) mean exactly what they mean to the _pen functions, and
+ * the ids ARE the ids those return for the same arguments: same kernels, same noise, the token record kept by the same rule.
+ * LLMK_E_ARG before anything runs or is allocated: logprobs == NULL; top_n outside [0, LLMK_MAX_TOP_LOGPROBS]; nothing asked for (top_n
+ * == 0 and token_logprob == NULL); a NULL array that top_n needs; a tensor-parallel context.  The arrays (n = 1 for
+ * llmk_forward_sample_lp) are complete when the call returns; on_token keeps its signature and its timing; on any error the arrays are
+ * unspecified.  The pipelined decode stays pipelined: one more one-workgroup kernel per position, the records read back in one copy
+ * at the end of the call.  Under penalties the context's logits buffer still holds the ADJUSTED vector afterwards.
+ * llmk_logprob_logits is the verification hook, with the limits of llmk_sample_logits (whole-model contexts only; the context's logits
+ * buffer is overwritten; no token pass): the same kernel on the caller's logits, for `token` in [0, vocab_size] (0: none,
+ * *token_logprob = 0.0f).  token_logprob may be NULL when top_n > 0. */
+#define LLMK_MAX_TOP_LOGPROBS 20
+typedef struct llmk_logprobs {
+    int32_t top_n;          /* 0..LLMK_MAX_TOP_LOGPROBS alternatives per position */
+    float *token_logprob;   /* n floats, or NULL */
+    int32_t *top_tokens;    /* n * top_n ints (1-based, 0 = none); NULL iff top_n == 0 */
+    float *top_logprobs;    /* n * top_n floats; NULL iff top_n == 0 */
+} llmk_logprobs;
+int llmk_forward_sample_lp(llmk_ctx *ctx, int token, int pos, const llmk_sampler *sampler, const llmk_penalties *penalties,
+                           const llmk_logprobs *logprobs, int *next_token);
+int llmk_decode_sample_lp(llmk_ctx *ctx, int token, int pos0, int n, const llmk_sampler *sampler, const llmk_penalties *penalties,
+                          const llmk_logprobs *logprobs, int *ids_out, llmk_token_fn on_token, void *user);
+int llmk_logprob_logits(llmk_ctx *ctx, const float *logits, int token, int top_n, float *token_logprob, int32_t *top_tokens,
+                        float *top_logprobs);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

@@ -15,6 +15,7 @@
 #include "sample.h"
 #include "sample_filter.h"
 #include "sample_penalty.h"
+#include "logprob.h"
 
 namespace llmk {
 
@@ -812,6 +813,93 @@ __device__ __forceinline__ unsigned long long sf_shfl_down_u64(unsigned long lon
     const unsigned lo = __shfl_down((unsigned)v, o, 64), hi = __shfl_down((unsigned)(v >> 32), o, 64);
     return ((unsigned long long)hi << 32) | lo;
 }
+// One level of a radix descent by the whole workgroup (sample_filter_kernel, sample_logprob_kernel): bins <- the non-NaN rows under
+// `prefix` (all of them at level 0); with_minp: also the smallest key with e >= min_p (wk: 16 words of scratch).  WITH_SUM = false
+// counts only: no e, no Q, hs unused (null), the sums of `bins` are zero.  Every thread returns the same value.
+template <bool WITH_SUM>
+__device__ __forceinline__ unsigned sf_fill(const float* __restrict__ logits, int n, float invT, float m, float min_p, int level, unsigned prefix,
+                                            bool with_hist, bool with_minp, unsigned long long* hs, unsigned* hc, llmk_filter_bins& bins,
+                                            llmk_filter_bins& bins0, unsigned* wk) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int shift = 24 - 8 * level;
+    if (with_hist) {
+        for (int j = tid; j < 256 * SF_COPIES; j += SF_THREADS) { hc[j] = 0u; if (WITH_SUM) hs[j] = 0ull; }
+        __syncthreads();
+    }
+    unsigned kmin = 0xffffffffu;
+    for (int i = tid; i < n; i += SF_THREADS) {
+        const float z = logits[i];
+        if (z != z) continue;
+        const unsigned key = llmk_filter_key(z);
+        if (level > 0 && (key >> (shift + 8)) != prefix) continue;
+        const float e = WITH_SUM ? llmk_filter_e(z, invT, m) : 0.f;
+        if (with_minp && e >= min_p) kmin = key < kmin ? key : kmin;
+        if (with_hist) {
+            const int slot = (int)((key >> shift) & 255u) * SF_COPIES + (lane & (SF_COPIES - 1));
+            atomicAdd(&hc[slot], 1u);
+            if (WITH_SUM) atomicAdd(&hs[slot], (unsigned long long)llmk_filter_q(e));
+        }
+    }
+    if (with_minp) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned ok = __shfl_xor(kmin, o, 64); kmin = ok < kmin ? ok : kmin; }
+        if (lane == 0) wk[wid] = kmin;
+    }
+    __syncthreads();
+    if (with_hist && tid < 256) {      // (the copies read rotated by the bin: 64 lanes, 64 banks)
+        unsigned c = 0;
+        unsigned long long s = 0;
+#pragma unroll
+        for (int k = 0; k < SF_COPIES; ++k) {
+            const int slot = tid * SF_COPIES + ((k + tid) & (SF_COPIES - 1));
+            c += hc[slot];
+            if (WITH_SUM) s += hs[slot];
+        }
+        bins.cnt[tid] = c;
+        bins.sum[tid] = s;
+        if (level == 0) { bins0.cnt[tid] = c; bins0.sum[tid] = s; }
+    }
+    if (with_minp) { kmin = wk[0]; for (int w = 1; w < 16; ++w) kmin = wk[w] < kmin ? wk[w] : kmin; }
+    __syncthreads();
+    return kmin;
+}
+// wave 0 walks the bins from the top, four per lane: what lies above each lane's bins is a suffix sum over the lanes.  Leaves the
+// digit to descend into, and what lies above it, in `walk` (behind a barrier)
+__device__ __forceinline__ void sf_walk_bins(const llmk_filter_bins& b, unsigned cnt_above, unsigned long long sum_above, bool by_count, unsigned k,
+                                             double target, llmk_filter_walk& walk) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (wid == 0) {
+        unsigned c[4], ct = 0;
+        unsigned long long s[4], st = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = b.cnt[4 * lane + j]; s[j] = b.sum[4 * lane + j]; ct += c[j]; st += s[j]; }
+        unsigned ca = ct;
+        unsigned long long sa = st;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned oc = __shfl_down(ca, o, 64);
+            const unsigned long long os = sf_shfl_down_u64(sa, o);
+            if (lane + o < 64) { ca += oc; sa += os; }
+        }
+        ca = ca - ct + cnt_above;      // above this lane's four bins
+        sa = sa - st + sum_above;
+        int digit = 256;
+        unsigned dca = 0;
+        unsigned long long dsa = 0;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {      // from the lane's top bin down: the LOWEST qualifying bin stays
+            const bool q = c[j] != 0 && (by_count ? (ca < k && ca + c[j] >= k) : ((double)sa < target));
+            if (q) { digit = 4 * lane + j; dca = ca; dsa = sa; }
+            ca += c[j];
+            sa += s[j];
+        }
+        int low = digit;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const int od = __shfl_xor(low, o, 64); low = od < low ? od : low; }
+        if (digit == low && digit < 256) { walk.digit = digit; walk.cnt_above = dca; walk.sum_above = dsa; }
+    }
+    __syncthreads();
+}
 __global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* __restrict__ logits, int n, const int* __restrict__ tokpos,
                                                                    int pos_imm, const llmk_filter_params* __restrict__ fp,
                                                                    int* __restrict__ next, float2* __restrict__ cand, int ncand,
@@ -851,83 +939,12 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* 
     const float m = llmk_filter_m(zmax, invT);
     unsigned tau = LLMK_FILTER_KEY_NINF;
 
-    // one level of a descent: bins <- the rows under `prefix` (all rows at level 0); with_minp: also the smallest key with e >= min_p
+    // one level of a descent / one walk over its bins (sf_fill, sf_walk_bins)
     auto fill = [&](int level, unsigned prefix, bool with_hist, bool with_minp) -> unsigned {
-        const int shift = 24 - 8 * level;
-        if (with_hist) {
-            for (int j = tid; j < 256 * SF_COPIES; j += SF_THREADS) { hc[j] = 0u; hs[j] = 0ull; }
-            __syncthreads();
-        }
-        unsigned kmin = 0xffffffffu;
-        for (int i = tid; i < n; i += SF_THREADS) {
-            const float z = logits[i];
-            if (z != z) continue;
-            const unsigned key = llmk_filter_key(z);
-            if (level > 0 && (key >> (shift + 8)) != prefix) continue;
-            const float e = llmk_filter_e(z, invT, m);
-            if (with_minp && e >= min_p) kmin = key < kmin ? key : kmin;
-            if (with_hist) {
-                const int slot = (int)((key >> shift) & 255u) * SF_COPIES + (lane & (SF_COPIES - 1));
-                atomicAdd(&hc[slot], 1u);
-                atomicAdd(&hs[slot], (unsigned long long)llmk_filter_q(e));
-            }
-        }
-        if (with_minp) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { const unsigned ok = __shfl_xor(kmin, o, 64); kmin = ok < kmin ? ok : kmin; }
-            if (lane == 0) wk[wid] = kmin;
-        }
-        __syncthreads();
-        if (with_hist && tid < 256) {      // (the copies read rotated by the bin: 64 lanes, 64 banks)
-            unsigned c = 0;
-            unsigned long long s = 0;
-#pragma unroll
-            for (int k = 0; k < SF_COPIES; ++k) {
-                const int slot = tid * SF_COPIES + ((k + tid) & (SF_COPIES - 1));
-                c += hc[slot];
-                s += hs[slot];
-            }
-            bins.cnt[tid] = c;
-            bins.sum[tid] = s;
-            if (level == 0) { bins0.cnt[tid] = c; bins0.sum[tid] = s; }
-        }
-        if (with_minp) { kmin = wk[0]; for (int w = 1; w < 16; ++w) kmin = wk[w] < kmin ? wk[w] : kmin; }
-        __syncthreads();
-        return kmin;
+        return sf_fill<true>(logits, n, invT, m, min_p, level, prefix, with_hist, with_minp, hs, hc, bins, bins0, wk);
     };
-    // wave 0 walks the bins from the top, four per lane: what lies above each lane's bins is a suffix sum over the lanes
     auto walk_bins = [&](const llmk_filter_bins& b, unsigned cnt_above, unsigned long long sum_above, bool by_count, unsigned k, double target) {
-        if (wid == 0) {
-            unsigned c[4], ct = 0;
-            unsigned long long s[4], st = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { c[j] = b.cnt[4 * lane + j]; s[j] = b.sum[4 * lane + j]; ct += c[j]; st += s[j]; }
-            unsigned ca = ct;
-            unsigned long long sa = st;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned oc = __shfl_down(ca, o, 64);
-                const unsigned long long os = sf_shfl_down_u64(sa, o);
-                if (lane + o < 64) { ca += oc; sa += os; }
-            }
-            ca = ca - ct + cnt_above;      // above this lane's four bins
-            sa = sa - st + sum_above;
-            int digit = 256;
-            unsigned dca = 0;
-            unsigned long long dsa = 0;
-#pragma unroll
-            for (int j = 3; j >= 0; --j) {      // from the lane's top bin down: the LOWEST qualifying bin stays
-                const bool q = c[j] != 0 && (by_count ? (ca < k && ca + c[j] >= k) : ((double)sa < target));
-                if (q) { digit = 4 * lane + j; dca = ca; dsa = sa; }
-                ca += c[j];
-                sa += s[j];
-            }
-            int low = digit;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { const int od = __shfl_xor(low, o, 64); low = od < low ? od : low; }
-            if (digit == low && digit < 256) { walk.digit = digit; walk.cnt_above = dca; walk.sum_above = dsa; }
-        }
-        __syncthreads();
+        sf_walk_bins(b, cnt_above, sum_above, by_count, k, target, walk);
     };
 
     if (!none) {
@@ -1073,6 +1090,160 @@ __global__ __launch_bounds__(SP_THREADS) void sample_penalty_kernel(float* __res
         if (!t) continue;
         const int c = atomicExch(&cnt[t - 1], 0);
         if (c > 0) logits[t - 1] = llmk_penalty_row(logits[t - 1], c, r, inv_r, f, p);
+    }
+}
+
+// The fold of the ncand candidates {value, row as int bits} a launch of the pipelined decode leaves, by ONE wave: the largest value,
+// the lowest row among equals (what the next launch makes of them: token_kernel.h tk_token); every lane returns the winner.  Shared by
+// cand_resolve_kernel (llmk.hip) and sample_logprob_kernel, so that both name the id the next launch is fed.
+__device__ __forceinline__ void cand_fold(const float2* __restrict__ cand, int ncand, float& bv, int& bi) {
+    bv = -INFINITY;
+    bi = 0x7fffffff;
+    for (int k = threadIdx.x & 63; k < ncand; k += 64) {
+        const float2 cd = cand[k];
+        const int ci = __float_as_int(cd.y);
+        if (cd.x > bv || (cd.x == bv && ci < bi)) { bv = cd.x; bi = ci; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+}
+
+// The log-prob record of a position by the rule of logprob.h: ONE workgroup of 1,024 threads behind whatever picked the position's
+// token.  `logits` are the RAW logits (under penalties: the copy taken in front of sample_penalty_kernel); they stay where they lie
+// (L2), and the number of passes over them does not depend on top_n:
+//   pass 1      the log-sum-exp state in the rule's order, and the number of listable rows;
+//   passes 2-5  the count descent of sample_filter_kernel (sf_fill without sums, sf_walk_bins by count): the key K of the
+//               min(top_n, listable)-th largest row and the number of rows above it;
+//   pass 6      every wave takes a contiguous range of rows, 64 at a time in ascending order: the rows above K go to one list in any
+//               order (an integer LDS counter; fewer than top_n of them), the wave's first rows EQUAL to K to the wave's own list in
+//               index order (a ballot and a running count); the waves' lists in wave order are the equal rows in ascending index order;
+//   then wave 0 rank-sorts the 20 entries or fewer (llmk_logprob_before) and writes the record.
+// The id: id_ptr[0] where a kernel left one (argmax_kernel / sample_kernel / sample_filter_kernel: d_next); else the fold of the
+// ncand candidates of a pipelined launch, by the rule of the next launch and cand_resolve_kernel (largest value, lowest row); else
+// id_imm (llmk_logprob_logits).  No id (0 / out of range): token_logprob = 0.  top_n is a device word, so a graph serves every top_n.
+__global__ __launch_bounds__(SF_THREADS) void sample_logprob_kernel(const float* __restrict__ logits, int n, const int* __restrict__ id_ptr,
+                                                                    const float2* __restrict__ cand, int ncand, int id_imm,
+                                                                    const unsigned* __restrict__ top_n_ptr, llmk_logprob_record* __restrict__ out) {
+    constexpr int MAXN = LLMK_LOGPROB_MAX_TOP;
+    __shared__ unsigned hc[256 * SF_COPIES];                // the level's counts, SF_COPIES copies per bin
+    __shared__ llmk_filter_bins bins;
+    __shared__ llmk_filter_walk walk;
+    __shared__ unsigned wk[16], wc[16];
+    __shared__ float wm[16], ws[16];
+    __shared__ int above[MAXN], equal[16][MAXN];
+    __shared__ unsigned n_above, n_equal[16];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid == 0) n_above = 0u;
+
+    // ---- pass 1: L and the number of listable rows
+    llmk_lse st = llmk_lse_empty();
+    unsigned listable = 0;
+    for (int i = tid; i < n; i += SF_THREADS) {
+        const float z = logits[i];
+        st = llmk_lse_step(st, z);
+        listable += llmk_logprob_listable(z) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        llmk_lse other;
+        other.m = __shfl_xor(st.m, o, 64);
+        other.s = __shfl_xor(st.s, o, 64);
+        st = llmk_lse_merge(st, other);
+        listable += __shfl_xor(listable, o, 64);
+    }
+    if (lane == 0) { wm[wid] = st.m; ws[wid] = st.s; wc[wid] = listable; }
+    __syncthreads();
+    st.m = wm[0];
+    st.s = ws[0];
+    listable = wc[0];
+    for (int w = 1; w < 16; ++w) {
+        llmk_lse other;
+        other.m = wm[w];
+        other.s = ws[w];
+        st = llmk_lse_merge(st, other);
+        listable += wc[w];
+    }
+    const float L = llmk_lse_value(st);
+    const unsigned want = top_n_ptr[0] < (unsigned)MAXN ? top_n_ptr[0] : (unsigned)MAXN;
+    const unsigned k = want < listable ? want : listable;
+
+    if (k > 0) {      // (uniform)
+        // ---- passes 2-5: the key of the k-th largest row (-inf rows are binned too: they lie below every listable row)
+        unsigned K = 0, ca = 0;
+        for (int level = 0; level < 4; ++level) {
+            sf_fill<false>(logits, n, 0.f, 0.f, 0.f, level, K, true, false, nullptr, hc, bins, bins, wk);
+            sf_walk_bins(bins, ca, 0ull, true, k, 0.0, walk);
+            K = (K << 8) | (unsigned)walk.digit;
+            ca = walk.cnt_above;
+            __syncthreads();      // (walk and bins are rewritten by the next level)
+        }
+        // ---- pass 6: collect
+        const int per_wave = (((n + 15) >> 4) + 63) & ~63;
+        const int lo = wid * per_wave, hi = lo + per_wave < n ? lo + per_wave : n;
+        unsigned run = 0;
+        for (int r = lo; r < hi; r += 64) {
+            const int i = r + lane;
+            const float z = i < hi ? logits[i] : -INFINITY;
+            const bool ok = llmk_logprob_listable(z);
+            const unsigned key = ok ? llmk_filter_key(z) : 0u;
+            if (ok && key > K) {
+                const unsigned slot = atomicAdd(&n_above, 1u);
+                if (slot < (unsigned)MAXN) above[slot] = i;
+            }
+            const bool eq = ok && key == K;
+            const unsigned long long b = __ballot(eq);
+            if (eq) {
+                const unsigned ord = run + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+                if (ord < (unsigned)MAXN) equal[wid][ord] = i;
+            }
+            run += (unsigned)__popcll(b);
+        }
+        if (lane == 0) n_equal[wid] = run < (unsigned)MAXN ? run : (unsigned)MAXN;
+        __syncthreads();
+        // ---- the list, ordered
+        if (wid == 0) {
+            int idx = 0x7fffffff;
+            float z = -INFINITY;
+            if ((unsigned)lane < k) {
+                if ((unsigned)lane < ca) {
+                    idx = above[lane];
+                } else {
+                    unsigned e = (unsigned)lane - ca;
+                    for (int w = 0; w < 16; ++w) {
+                        if (e < n_equal[w]) { idx = equal[w][e]; break; }
+                        e -= n_equal[w];
+                    }
+                }
+                if ((unsigned)idx < (unsigned)n) z = logits[idx];
+            }
+            int rank = 0;
+            for (unsigned e = 0; e < k; ++e) {
+                const float ze = __shfl(z, (int)e, 64);
+                const int ie = __shfl(idx, (int)e, 64);
+                rank += llmk_logprob_before(ze, ie, z, idx) ? 1 : 0;
+            }
+            if ((unsigned)lane < k && rank < MAXN) {
+                out->top_tokens[rank] = (unsigned)idx < (unsigned)n ? idx + 1 : 0;
+                out->top_logprobs[rank] = llmk_logprob_value(z, L);
+            }
+        }
+    }
+    if (wid == 0) {
+        if ((unsigned)lane >= k && lane < MAXN) { out->top_tokens[lane] = 0; out->top_logprobs[lane] = -INFINITY; }
+        int id = id_imm;
+        if (id_ptr) {
+            id = id_ptr[0];
+        } else if (cand) {
+            float bv;
+            int bi;
+            cand_fold(cand, ncand, bv, bi);
+            id = (unsigned)bi < (unsigned)n ? bi + 1 : 0;
+        }
+        if (lane == 0) out->token_logprob = (id >= 1 && id <= n) ? llmk_logprob_value(logits[id - 1], L) : 0.f;
     }
 }
 

@@ -134,7 +134,7 @@ struct llmk_ctx {
     TkHostWords* host_words() const { return tk_words_behind<TkHostWords>(h_logits, V); }
     TkHostWords* host_words_dev() const { return tk_words_behind<TkHostWords>(h_logits_dev, V); }
     hipStream_t stream = nullptr;
-    hipGraphExec_t graph[TAIL_COUNT] = {};      // the token pass with each tail, captured at first use (drop_graphs)
+    hipGraphExec_t graph[TAIL_COUNT][2] = {};   // the token pass with each tail, without / with the log-prob record, captured at first use (drop_graphs)
     llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current sampling call
     // the device's copy of them (TkDevWords::samp): zeros from llmk_create on.  A pipelined decode writes them only when they differ,
     // so a greedy one on a ctx that never sampled enqueues nothing new
@@ -150,6 +150,13 @@ struct llmk_ctx {
     int* d_pen_cnt = nullptr;
     llmk_penalty_params* d_pen = nullptr;
     llmk_penalty_params* h_pen = nullptr;
+    // decode log-probs (llmk_*_sample_lp, logprob.h), allocated by the first call that asks for them (lp_setup): S + 1 records on the
+    // device and in pinned memory -- [q - 1]: position q of a pipelined decode; [S]: what the tail of a token pass, or the hook, leaves
+    // -- the pinned top_n word, and the V raw logits that are set aside in front of sample_penalty_kernel
+    llmk_logprob_record *d_lp = nullptr, *h_lp = nullptr;
+    unsigned* h_lp_top = nullptr;
+    float* d_lp_raw = nullptr;
+    int lp_top_n = -1;      // the running call's request (logprob_request .. LpScope), -1: none -- every site enqueues what it always did
     hipEvent_t ev[8] = {};
     float times[5] = {0, 0, 0, 0, 0};
     int n_cu = 256;
@@ -496,14 +503,9 @@ hipError_t launch_token_kernel(llmk_ctx* c, bool direct = false, const TkGreedy&
 // adds 0x2000 only to a clear word: behind a range event (0x4000) the drained launches leave candidates that need not be finite,
 // and 0x2000 on top would make the host retire the kernel instead of redoing the one position (tk_range_only)
 __global__ __launch_bounds__(64) void cand_resolve_kernel(const float2* __restrict__ cand, int* id_out, int* next, unsigned* err, int V) {
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int k = threadIdx.x; k < TK_NCU; k += 64) {
-        const float2 cd = cand[k];
-        const int ci = __float_as_int(cd.y);
-        if (cd.x > bv || (cd.x == bv && ci < bi)) { bv = cd.x; bi = ci; }
-    }
-    tk_wave_argmax(bv, bi);
+    float bv;
+    int bi;
+    cand_fold(cand, TK_NCU, bv, bi);
     if (threadIdx.x == 0) {
         const bool none = (unsigned)bi >= (unsigned)V;
         const unsigned e = *err;
@@ -592,10 +594,22 @@ struct SamplerSite {
     int ncand;
     bool copy_pen, copy_filt;      // the parameter words are copied in front of their kernel (the penalties' at every call; the
                                    // filter's here, or before by the site itself: DevShadow)
+    llmk_logprob_record* lp;       // where the position's log-prob record goes (null: none): the raw logits are set aside in front of
+                                   // the penalties, and sample_logprob_kernel runs behind the filter kernel on the id in d_next
 };
+// sample_logprob_kernel behind whatever picked the token: the id in id_ptr, or folded from the candidates, or `id`
+hipError_t enqueue_logprob(llmk_ctx* c, const float* logits, const int* id_ptr, const float2* cand, int ncand, int id, llmk_logprob_record* out) {
+    hipLaunchKernelGGL(sample_logprob_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, logits, c->V, id_ptr, cand, ncand, id,
+                       &c->dev_words()->lp_top_n, out);
+    return hipGetLastError();
+}
+hipError_t copy_logprob_top(llmk_ctx* c) {      // (top_n travels like token and position: a copy out of pinned memory)
+    return hipMemcpyAsync(&c->dev_words()->lp_top_n, c->h_lp_top, sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
+}
 hipError_t enqueue_sampler(llmk_ctx* c, bool penalty, const SamplerSite& s) {
     TkDevWords* dw = c->dev_words();
     if (penalty) {
+        if (s.lp) HIPRET(hipMemcpyAsync(c->d_lp_raw, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         if (s.copy_pen) HIPRET(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, s.tokpos, s.pos, s.token, s.prev,
                            c->d_pen, c->d_hist, s.record, c->d_pen_cnt);
@@ -604,13 +618,17 @@ hipError_t enqueue_sampler(llmk_ctx* c, bool penalty, const SamplerSite& s) {
     if (s.copy_filt) HIPRET(hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, s.tokpos, s.pos, &dw->filt, c->d_next,
                        s.cand, s.ncand, dw->filter_out);
-    return hipGetLastError();
+    HIPRET(hipGetLastError());
+    return s.lp ? enqueue_logprob(c, penalty ? c->d_lp_raw : c->d_logits, c->d_next, nullptr, 0, 0, s.lp) : hipSuccess;
 }
 
 hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
     if (tail != TAIL_LOGITS) {
+        llmk_logprob_record* lp = c->lp_top_n >= 0 ? c->d_lp + c->S : nullptr;
+        if (lp) HIPRET(copy_logprob_top(c));
         if (tail == TAIL_FILTER || tail == TAIL_PENALTY) {
-            HIPRET(enqueue_sampler(c, tail == TAIL_PENALTY, {c->d_tokpos, 0, 0, nullptr, c->d_hist, nullptr, 0, true, true}));
+            HIPRET(enqueue_sampler(c, tail == TAIL_PENALTY, {c->d_tokpos, 0, 0, nullptr, c->d_hist, nullptr, 0, true, true, lp}));
+            lp = nullptr;      // (enqueued)
         } else if (tail == TAIL_SAMPLE) {
             // invT and the seed travel like token and position: a copy out of pinned memory, read when the graph replays it
             HIPRET(hipMemcpyAsync(&c->dev_words()->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream));
@@ -619,6 +637,8 @@ hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
             hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_logits, c->V, c->d_next);
         }
         HIPRET(hipGetLastError());
+        if (lp) HIPRET(enqueue_logprob(c, c->d_logits, c->d_next, nullptr, 0, 0, lp));
+        if (c->lp_top_n >= 0) HIPRET(hipMemcpyAsync(c->h_lp + c->S, c->d_lp + c->S, sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
         HIPRET(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPRET(hipMemcpyAsync(&c->h_next->err, &c->dev_words()->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     } else {      // the logits and, behind them, the error word: TkDevWords::err lands in TkHostWords::err
@@ -736,8 +756,9 @@ hipError_t enqueue_token(llmk_ctx* c, TailMode tail, bool timed) {
 
 // (the graphs bake in kernel arguments, the path and the tensor types: whatever changes one of those drops them all)
 void drop_graphs(llmk_ctx* c) {
-    for (hipGraphExec_t& g : c->graph)
-        if (g) { hipGraphExecDestroy(g); g = nullptr; }
+    for (auto& per_tail : c->graph)
+        for (hipGraphExec_t& g : per_tail)
+            if (g) { hipGraphExecDestroy(g); g = nullptr; }
 }
 int build_graph(llmk_ctx* c, TailMode tail, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
@@ -833,7 +854,7 @@ int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
             c->host_words()->err = 0;
             HIPCHK(launch_token_kernel(c, true));
         } else {
-            hipGraphExec_t* g = &c->graph[tail];
+            hipGraphExec_t* g = &c->graph[tail][c->lp_top_n >= 0 ? 1 : 0];
             if (!*g) {
                 rc = build_graph(c, tail, g);
                 if (rc) return rc;
@@ -1343,7 +1364,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 401; }
+int llmk_version(void) { return 402; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -1999,12 +2020,65 @@ static int pen_setup(llmk_ctx* c) {
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
 }
+// ---- decode log-probs (logprob.h) ----
+static_assert(LLMK_LOGPROB_MAX_TOP == LLMK_MAX_TOP_LOGPROBS, "logprob.h and llmk.h agree on the length of the list");
+// the checks of a log-prob request: nothing runs and nothing is allocated here
+static bool logprob_args_ok(const llmk_ctx* c, const llmk_logprobs* lp) {
+    if (!c || !lp || lp->top_n < 0 || lp->top_n > LLMK_MAX_TOP_LOGPROBS) return false;
+    if (lp->top_n == 0 && !lp->token_logprob) return false;
+    if (lp->top_n > 0 && (!lp->top_tokens || !lp->top_logprobs)) return false;
+    return c->tp_size == 1 && !c->comm && !c->p2p;
+}
+// the records, the pinned top_n word and, under penalties, the raw logits: allocated by the first call that needs them
+static int lp_setup(llmk_ctx* c, bool raw) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t bytes = ((size_t)c->S + 1) * sizeof(llmk_logprob_record);
+    if (!c->d_lp) {
+        HIPCHK(dev_alloc(&c->d_lp, bytes));
+        HIPCHK(hipMemsetAsync(c->d_lp, 0, bytes, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (!c->h_lp) {
+        HIPCHK(hipHostMalloc(&c->h_lp, bytes, hipHostMallocDefault));
+        memset(c->h_lp, 0, bytes);
+    }
+    if (!c->h_lp_top) {
+        HIPCHK(hipHostMalloc(&c->h_lp_top, sizeof(unsigned), hipHostMallocDefault));
+        *c->h_lp_top = 0u;
+    }
+    if (raw && !c->d_lp_raw) HIPCHK(dev_alloc(&c->d_lp_raw, (size_t)c->V * sizeof(float)));
+    return LLMK_OK;
+}
+// a checked request becomes the running call's (every site reads c->lp_top_n); LpScope ends it
+static int logprob_request(llmk_ctx* c, const llmk_logprobs* lp, bool raw) {
+    const int rc = lp_setup(c, raw);
+    if (rc) return rc;
+    *c->h_lp_top = (unsigned)lp->top_n;
+    c->lp_top_n = lp->top_n;
+    return LLMK_OK;
+}
+struct LpScope {
+    llmk_ctx* c;
+    ~LpScope() { c->lp_top_n = -1; }
+};
+// record `from` of the pinned block into entry i of the caller's arrays
+static void logprob_deliver(const llmk_ctx* c, const llmk_logprobs* lp, int i, int from) {
+    const llmk_logprob_record& r = c->h_lp[from];
+    if (lp->token_logprob) lp->token_logprob[i] = r.token_logprob;
+    for (int j = 0; j < lp->top_n; ++j) {
+        lp->top_tokens[(size_t)i * lp->top_n + j] = r.top_tokens[j];
+        lp->top_logprobs[(size_t)i * lp->top_n + j] = r.top_logprobs[j];
+    }
+}
+
 // What a sampling call asks for: checked, then put into the pinned words that the passes copy to the device -- h_samp (invT = f32(1 / T),
 // rounded once), h_filt and, with a penalty or a bias on, h_pen (inv_r = f32(1 / r), as invT is).  pn == null: an entry point WITHOUT a
 // penalties argument (the _pen functions reject a null one themselves).  *tail: TAIL_PENALTY with a penalty or a bias on, else
 // TAIL_FILTER with a filter on, else TAIL_SAMPLE -- so with nothing on the _pen functions ARE the _ex ones, and those the plain ones.
 // Nothing is allocated (pen_setup) before every check has passed, and nothing at all for a request that needs no record.
-static int sampler_request(llmk_ctx* c, const llmk_sampler* sp, const llmk_penalties* pn, TailMode* tail) {
+// lp: the log-prob request of the _lp functions (null: none), checked first and granted last (logprob_request).
+static int sampler_request(llmk_ctx* c, const llmk_sampler* sp, const llmk_penalties* pn, TailMode* tail, const llmk_logprobs* lp = nullptr) {
+    if (lp && !logprob_args_ok(c, lp)) return LLMK_E_ARG;
     if (!sp) return LLMK_E_ARG;
     if (sp->top_k < 0 || !(sp->top_p > 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f)) return LLMK_E_ARG;      // (NaN fails)
     if (!(sp->temperature > 0.f) || !isfinite(sp->temperature)) return LLMK_E_ARG;      // (NaN fails the first test)
@@ -2031,9 +2105,10 @@ static int sampler_request(llmk_ctx* c, const llmk_sampler* sp, const llmk_penal
     *c->h_samp = llmk_sample_params{invT, seed_lo, seed_hi, 0};
     *c->h_filt = llmk_filter_params{invT, seed_lo, seed_hi, sp->top_k, sp->top_p, sp->min_p, {0, 0}};
     *tail = sp->top_k != 0 || sp->top_p != 1.f || sp->min_p != 0.f ? TAIL_FILTER : TAIL_SAMPLE;
-    if (!active) return LLMK_OK;
-    const int rc = pen_setup(c);
+    if (!active) return lp ? logprob_request(c, lp, false) : LLMK_OK;
+    int rc = pen_setup(c);
     if (rc) return rc;
+    if (lp && (rc = logprob_request(c, lp, true)) != LLMK_OK) return rc;
     *c->h_pen = llmk_penalty_params{pn->repeat, inv_r, pn->frequency, pn->presence, pen_on ? pn->last_n : 0, pn->n_bias, {0, 0}, {}};
     for (int j = 0; j < pn->n_bias; ++j) c->h_pen->bias[j] = llmk_penalty_bias{pn->bias[j].token, pn->bias[j].bias};
     *tail = TAIL_PENALTY;
@@ -2052,7 +2127,9 @@ static bool decode_args_ok(const llmk_ctx* c, int token, int pos0, int n, const 
 }
 // The generation loop of llama2.f90:379-396 for n positions with no host round trip between them: at temperature 0
 // (TAIL_GREEDY, the argmax) or by the request in the pinned words (sampler_request)
-int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_out, llmk_token_fn on_token, void* user) {
+// lp: where the log-prob records of a running request (c->lp_top_n >= 0) are delivered once every id is there
+int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_out, llmk_token_fn on_token, void* user,
+               const llmk_logprobs* lp = nullptr) {
     int rc = check_ready(c);
     if (rc) return rc;
     const bool timed = (c->cfg.flags & (LLMK_FLAG_TIMINGS | LLMK_FLAG_NO_GRAPH)) != 0;
@@ -2077,6 +2154,7 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             return tail == TAIL_SAMPLE ? hipMemcpyAsync(&dw->samp, c->h_samp, sizeof(llmk_sample_params), hipMemcpyHostToDevice, c->stream)
                                        : hipMemsetAsync(&dw->samp, 0, sizeof(llmk_sample_params), c->stream);
         }));
+        if (lp) HIPCHK(copy_logprob_top(c));
         for (int i = 0; i < n; ++i) {
             c->h_tokpos[0] = token - 1;
             c->h_tokpos[1] = pos0 + i;
@@ -2089,8 +2167,13 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             // the fed token: the host's at the first position, afterwards the id the filter kernel of the position before left in d_next
             if (filter_tail)
                 HIPCHK(enqueue_sampler(c, tail == TAIL_PENALTY, {nullptr, pos0 + i, token, i ? c->d_next : nullptr, c->d_hist,
-                                                                 dw->cand[(pos0 + i) & 1], TK_NCU, i == 0, false}));
+                                                                 dw->cand[(pos0 + i) & 1], TK_NCU, i == 0, false,
+                                                                 lp ? c->d_lp + (pos0 + i - 1) : nullptr}));
+            else if (lp)      // the id: the fold of this launch's candidates, as the next launch (or cand_resolve_kernel) takes it
+                HIPCHK(enqueue_logprob(c, c->d_logits, nullptr, dw->cand[(pos0 + i) & 1], TK_NCU, 0, c->d_lp + (pos0 + i - 1)));
         }
+        if (lp)      // the records of the whole call, in one copy
+            HIPCHK(hipMemcpyAsync(c->h_lp + (pos0 - 1), c->d_lp + (pos0 - 1), (size_t)n * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
         hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, dw->cand[(pos0 + n - 1) & 1], h_ids_dev + (n - 1), c->d_next, &dw->err, c->V);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&c->h_next->err, &dw->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -2113,7 +2196,10 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             if (on_token) on_token(done, ids_out[done], user);
         }
         const unsigned err = c->h_next->err;
-        if (err == 0 && done == n) return LLMK_OK;
+        if (err == 0 && done == n) {
+            for (int i = 0; lp && i < n; ++i) logprob_deliver(c, lp, i, pos0 + i - 1);
+            return LLMK_OK;
+        }
         // a timed-out exchange: every later launch drained on the sticky word.  Retire the token kernel and redo the rest,
         // from the first position whose id never arrived, on the multi-kernel path (it rewrites those KV rows).
         // (0x4000 alone -- an activation beyond the q4_0 kernel's f16 image at ONE position: the rest of the call goes position by
@@ -2128,8 +2214,10 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         if (rc) return rc;
         if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;      // (before the callback sees it)
         token = ids_out[i] = c->h_next->id;
+        if (lp) c->h_lp[pos0 + i - 1] = c->h_lp[c->S];      // (a redone position rewrites its record)
         if (on_token) on_token(i, token, user);
     }
+    for (int i = 0; lp && i < n; ++i) logprob_deliver(c, lp, i, pos0 + i - 1);
     return LLMK_OK;
 }
 
@@ -2212,6 +2300,45 @@ int llmk_sample_logits_pen(llmk_ctx* c, const float* logits, int pos, const llmk
                            int* kept_out, float* tau_out, float* adjusted_out) {
     if (!c || !logits || !token_out_ || !pn || pos < 1 || pos > c->S || c->tp_size != 1) return LLMK_E_ARG;
     return sample_logits(c, logits, pos, sp, pn, token_out_, kept_out, tau_out, adjusted_out);
+}
+// The _lp functions: the request of the _pen functions (penalties optional), or the greedy form (no sampler), plus the record
+int llmk_forward_sample_lp(llmk_ctx* c, int token, int pos, const llmk_sampler* sp, const llmk_penalties* pn, const llmk_logprobs* lp,
+                           int* next_token) {
+    if (!c || !next_token || !logprob_args_ok(c, lp) || (!sp && pn) || token < 1 || token > c->V || pos < 1 || pos > c->S) return LLMK_E_ARG;
+    int rc = check_ready(c);      // (before logprob_request allocates)
+    if (rc) return rc;
+    LpScope scope{c};
+    TailMode tail = TAIL_GREEDY;
+    rc = sp ? sampler_request(c, sp, pn, &tail, lp) : logprob_request(c, lp, false);
+    if (rc == LLMK_OK) rc = token_out(c, token, pos, tail, next_token);
+    if (rc == LLMK_OK) logprob_deliver(c, lp, 0, c->S);
+    return rc;
+}
+int llmk_decode_sample_lp(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, const llmk_penalties* pn, const llmk_logprobs* lp,
+                          int* ids_out, llmk_token_fn on_token, void* user) {
+    if (!decode_args_ok(c, token, pos0, n, ids_out) || !logprob_args_ok(c, lp) || (!sp && pn)) return LLMK_E_ARG;
+    int rc = check_ready(c);      // (before logprob_request allocates)
+    if (rc) return rc;
+    LpScope scope{c};
+    TailMode tail = TAIL_GREEDY;
+    rc = sp ? sampler_request(c, sp, pn, &tail, lp) : logprob_request(c, lp, false);
+    return rc ? rc : decode_run(c, token, pos0, n, tail, ids_out, on_token, user, lp);
+}
+// (the hook: sample_logprob_kernel on the caller's logits, the id given)
+int llmk_logprob_logits(llmk_ctx* c, const float* logits, int token, int top_n, float* token_logprob, int32_t* top_tokens, float* top_logprobs) {
+    const llmk_logprobs lp = {top_n, token_logprob, top_tokens, top_logprobs};
+    if (!c || !logits || !logprob_args_ok(c, &lp) || token < 0 || token > c->V) return LLMK_E_ARG;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if ((rc = lp_setup(c, false)) != LLMK_OK) return rc;      // (no site reads a running request here: the kernel is enqueued below)
+    *c->h_lp_top = (unsigned)top_n;
+    HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(copy_logprob_top(c));
+    HIPCHK(enqueue_logprob(c, c->d_logits, nullptr, nullptr, 0, token, c->d_lp + c->S));
+    HIPCHK(hipMemcpyAsync(c->h_lp + c->S, c->d_lp + c->S, sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    logprob_deliver(c, &lp, 0, c->S);
+    return LLMK_OK;
 }
 int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
     if (!c || !tokens || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
@@ -2756,7 +2883,7 @@ int llmk_destroy(llmk_ctx* c) {
     pf_teardown(c);
     sc_teardown(c);
     void* dev[] = {c->d_kc, c->d_vc, c->d_x, c->d_q, c->d_xb, c->d_hb, c->d_logits, c->d_rope, c->d_tokpos, c->d_next,
-                   c->d_gran, c->d_zeros, c->d_trace, c->d_part, c->d_hist, c->d_pen_cnt, c->d_pen};
+                   c->d_gran, c->d_zeros, c->d_trace, c->d_part, c->d_hist, c->d_pen_cnt, c->d_pen, c->d_lp, c->d_lp_raw};
     for (void* p : dev)
         if (p) hipFree(p);
     for (int b = 0; b < 2; ++b) {
@@ -2773,6 +2900,8 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->h_samp) hipHostFree(c->h_samp);
     if (c->h_filt) hipHostFree(c->h_filt);
     if (c->h_pen) hipHostFree(c->h_pen);
+    if (c->h_lp) hipHostFree(c->h_lp);
+    if (c->h_lp_top) hipHostFree(c->h_lp_top);
     for (int i = 0; i < 8; ++i)
         if (c->ev[i]) hipEventDestroy(c->ev[i]);
     if (c->stream) hipStreamDestroy(c->stream);

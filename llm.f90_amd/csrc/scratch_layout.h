@@ -21,11 +21,12 @@ struct TkDevWords {
     llmk_sample_params samp;        // sampling parameters of the pass / the pipelined decode (invT == 0: greedy)
     llmk_filter_params filt;        // the truncated sampler's parameters (sample_filter_kernel)
     unsigned filter_out[2];         // what sample_filter_kernel leaves for verification: rows kept, tau bits
-    unsigned pad1[6];
+    unsigned lp_top_n;              // the log-prob request's top_n as sample_logprob_kernel reads it (one graph serves every top_n)
+    unsigned pad1[5];
 };
 static_assert(offsetof(TkDevWords, err) == 0 && offsetof(TkDevWords, cand) == 16, "scratch layout");
 static_assert(offsetof(TkDevWords, samp) == 16 + 16 * TK_NCU && offsetof(TkDevWords, filt) == 32 + 16 * TK_NCU, "scratch layout");
-static_assert(offsetof(TkDevWords, filter_out) == 64 + 16 * TK_NCU, "scratch layout");
+static_assert(offsetof(TkDevWords, filter_out) == 64 + 16 * TK_NCU && offsetof(TkDevWords, lp_top_n) == 72 + 16 * TK_NCU, "scratch layout");
 static_assert(sizeof(TkDevWords) == (24 + 4 * TK_NCU) * 4 && alignof(TkDevWords) == 8, "scratch layout");
 
 // Host words behind the V logits of the pinned, device-mapped h_logits; ids() follow: the S ids of the pipelined decode

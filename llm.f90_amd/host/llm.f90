@@ -9,7 +9,7 @@
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
 !         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N]
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
 ! (one process per GPU, devices d..d+N-1), every rank loads the file and keeps its shard, the ranks meet through a
@@ -48,6 +48,8 @@ module arg_parse
      logical :: gguf_eps, gguf_rope_base   ! extension: honour the file's rms epsilon / RoPE base (the reference hard-codes
                                            ! 1e-5 and 10000, llama2.f90:454,545)
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
+     integer :: logprobs          ! extension: --logprobs N (0 .. 20): the log-prob of every generated token and its N most likely
+                                  ! alternatives, from the device (llmk_*_sample_lp); -1 = off
      logical :: score             ! extension: score the prompt instead of continuing it (llmk_score): log-prob per token, perplexity
   end type args
 
@@ -89,6 +91,7 @@ contains
     a%gguf_rope_base = .false.
     a%encode_only = .false.
     a%score = .false.
+    a%logprobs = -1
 
     nargs = command_argument_count()
     i = 1
@@ -128,6 +131,13 @@ contains
        case ("--gguf-rope-base");    a%gguf_rope_base = .true.; i = i + 1
        case ("--encode");            a%encode_only = .true.;   i = i + 1
        case ("--score");             a%score = .true.;         i = i + 1
+       case ("--logprobs")
+          read (val, *) a%logprobs
+          if (a%logprobs < 0 .or. a%logprobs > 20) then
+             print *, "--logprobs takes N in 0 .. 20"
+             stop 1
+          end if
+          i = i + 2
        case default
           print *, "Unrecognized option:", trim(opt)
           stop
@@ -247,6 +257,14 @@ program llm
   integer(c_int), allocatable, target :: sc_targets(:)   ! --score: the prompt's tokens, each the target of the position before it
   real(c_float), allocatable, target :: sc_logprob(:)
   real(kind=wp) :: sc_sum
+  logical :: lp_on                                  ! --logprobs N on one GPU: the device consumer with the log-prob record
+  type(llmk_sampler), target :: lp_sampler
+  type(llmk_penalties), target :: lp_pens
+  type(c_ptr) :: lp_sp, lp_pn                       ! their addresses, or c_null_ptr (greedy form; no penalties)
+  integer(c_int), allocatable :: lp_ids(:)          ! the generated tokens, in order
+  real(c_float), allocatable, target :: lp_token(:), lp_top(:)
+  integer(c_int32_t), allocatable, target :: lp_top_ids(:)
+  integer :: lp_n, lp_w
 
   call parse_args(opts)
   lead = opts%tp_rank == 0
@@ -404,7 +422,12 @@ program llm
        "-t with --top-k 1 is its greedy form)"
   if (penalised .and. opts%temperature > 0 .and. opts%ngpu /= 1 .and. lead) &
        write (0, '(A)') "llm: the penalties and --logit-bias are ignored with --ngpu > 1 (the device sampler runs on one GPU)"
-  dsample = (opts%device_sample .or. filtered .or. penalised) .and. opts%temperature > 0 .and. opts%ngpu == 1
+  ! --logprobs N: the records come from the device consumer, so the flag selects it as the filter flags do -- the sampler at -t > 0,
+  ! the greedy form (llmk_decode_greedy's rule) at -t 0
+  lp_on = opts%logprobs >= 0 .and. opts%ngpu == 1
+  if (opts%logprobs >= 0 .and. opts%ngpu /= 1 .and. lead) &
+       write (0, '(A)') "llm: --logprobs is ignored with --ngpu > 1 (the log-prob kernel runs on one GPU)"
+  dsample = (opts%device_sample .or. filtered .or. penalised .or. lp_on) .and. opts%temperature > 0 .and. opts%ngpu == 1
   penalised = penalised .and. dsample
   if (dsample) then
      if (opts%seed >= 0) then
@@ -441,13 +464,29 @@ program llm
      end if
   end if
 
+  if (lp_on) then
+     lp_w = opts%logprobs
+     allocate(lp_ids(conf%seq_len), lp_token(conf%seq_len), lp_top(max(1, lp_w * conf%seq_len)), lp_top_ids(max(1, lp_w * conf%seq_len)))
+     lp_n = 0
+     lp_sp = c_null_ptr
+     lp_pn = c_null_ptr
+     if (dsample) then
+        lp_sampler = sampler
+        lp_sp = c_loc(lp_sampler)
+        if (penalised) then
+           lp_pens = pens
+           lp_pn = c_loc(lp_pens)
+        end if
+     end if
+  end if
+
   ! ---- generation loop (llama2.f90:376-402) -------------------------------------------------------
   t_start = 0
   token = 2                                          ! BOS: 1-based index of <s>
   pos0 = 1
-  if (dsample .and. opts%prefill .and. size(prompt_tokens) > 0 .and. size(prompt_tokens) < seq_len) then
+  if ((dsample .or. lp_on) .and. opts%prefill .and. size(prompt_tokens) > 0 .and. size(prompt_tokens) < seq_len) then
      ! positions 1 .. k (BOS, then the first k-1 prompt tokens) in one call; the last prompt token goes through the loop below,
-     ! whose llmk_forward_sample draws the first id on the device
+     ! whose llmk_forward_sample draws the first id on the device (--logprobs at -t 0 too: the first generated token gets its record)
      k = size(prompt_tokens)
      allocate(batch(k))
      batch(1) = 2
@@ -502,9 +541,19 @@ program llm
   end if
   ! --device-sample likewise, with llmk_forward_sample_pen / llmk_decode_sample_pen (no penalty and no bias: llmk_forward_sample_ex /
   ! llmk_decode_sample_ex; all filters off as well: llmk_forward_sample / llmk_decode_sample)
-  if ((opts%device_argmax .and. opts%temperature == 0 .and. opts%ngpu == 1) .or. dsample) &
+  if ((opts%device_argmax .and. opts%temperature == 0 .and. opts%ngpu == 1) .or. dsample .or. lp_on) &
        loop_end = min(seq_len, max(size(prompt_tokens), pos0))
   do pos = pos0, loop_end
+     if (lp_on .and. pos > size(prompt_tokens)) then
+        call llmk_check(llmk_forward_sample_lp(ctx, int(token, c_int), int(pos, c_int), lp_sp, lp_pn, lp_request(lp_n, 1), dnext), &
+             "llmk_forward_sample_lp")
+        lp_n = lp_n + 1
+        lp_ids(lp_n) = dnext
+        token = dnext
+        if (lead) write (*, fmt="(A)", advance="no") vocab(token)(1:vocab_len(token))
+        if (t_start == 0) t_start = clock_ticks()
+        cycle
+     end if
      if (dsample .and. pos > size(prompt_tokens)) then
         call llmk_check(llmk_forward_sample_pen(ctx, int(token, c_int), int(pos, c_int), sampler, pens, dnext), "llmk_forward_sample_pen")
         next_tok = dnext
@@ -531,7 +580,12 @@ program llm
      ts_vocab = vocab
      ts_len = vocab_len
      ts_print = lead
-     if (dsample) then
+     if (lp_on) then
+        call llmk_check(llmk_decode_sample_lp(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
+             lp_sp, lp_pn, lp_request(lp_n, seq_len - loop_end), stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample_lp")
+        lp_ids(lp_n + 1:lp_n + size(stream_ids)) = stream_ids
+        lp_n = lp_n + size(stream_ids)
+     else if (dsample) then
         call llmk_check(llmk_decode_sample_pen(ctx, int(token, c_int), int(loop_end + 1, c_int), int(seq_len - loop_end, c_int), &
              sampler, pens, stream_ids, c_funloc(ts_on_token), c_null_ptr), "llmk_decode_sample_pen")
      else
@@ -546,6 +600,23 @@ program llm
 
   call llmk_check(llmk_timings(ctx, ktimes), "llmk_timings")
   s%times = ktimes
+  ! --logprobs: after the generated text and a newline, in the formats of --score: one line per generated token -- index, id,
+  ! log-prob, then the N alternatives as id:log-prob -- and the three totals
+  if (lp_on .and. lead) then
+     print '(A)', ""
+     sc_sum = 0
+     do pos = 1, lp_n
+        write (*, '(I0,1X,I0,1X,ES15.8)', advance="no") pos, lp_ids(pos), lp_token(pos)
+        do j = 1, lp_w
+           write (*, '(1X,I0,A,ES15.8)', advance="no") lp_top_ids((pos - 1) * lp_w + j), ":", lp_top((pos - 1) * lp_w + j)
+        end do
+        print '(A)', ""
+        sc_sum = sc_sum + lp_token(pos)
+     end do
+     print '(A,1X,I0)', "tokens", lp_n
+     print '(A,1X,ES15.8)', "sum logprob", sc_sum
+     if (lp_n > 0) print '(A,1X,ES15.8)', "perplexity", exp(-sc_sum / lp_n)
+  end if
   if (lead) then
      print *, ""
      print *, "Inference time: ", dt_ms / 1000, " seconds"
@@ -559,6 +630,20 @@ program llm
   rc = llmk_destroy(ctx)
 
 contains
+
+  ! the request for the next n positions: the records go behind the `done` already there
+  function lp_request(done, n) result(r)
+    integer, intent(in) :: done, n
+    type(llmk_logprobs) :: r
+    r%top_n = int(lp_w, c_int32_t)
+    r%token_logprob = c_loc(lp_token(done + 1))
+    r%top_tokens = c_null_ptr
+    r%top_logprobs = c_null_ptr
+    if (lp_w > 0 .and. n > 0) then
+       r%top_tokens = c_loc(lp_top_ids(done * lp_w + 1))
+       r%top_logprobs = c_loc(lp_top(done * lp_w + 1))
+    end if
+  end function lp_request
 
   subroutine upload_weights()
     integer(c_size_t) :: f4

@@ -38,6 +38,15 @@ module llmk_binding
      integer(c_int32_t) :: n_bias
   end type llmk_penalties
 
+  ! the log-prob request of llmk_forward_sample_lp / llmk_decode_sample_lp: top_n in 0 .. LLMK_MAX_TOP_LOGPROBS alternatives per
+  ! position; token_logprob = c_loc of n floats or c_null_ptr; top_tokens / top_logprobs = c_loc of n * top_n values (c_null_ptr
+  ! at top_n = 0)
+  integer(c_int), parameter :: LLMK_MAX_TOP_LOGPROBS = 20
+  type, bind(C) :: llmk_logprobs
+     integer(c_int32_t) :: top_n
+     type(c_ptr) :: token_logprob, top_tokens, top_logprobs
+  end type llmk_logprobs
+
   interface
      integer(c_int) function llmk_create(cfg, ctx) bind(C, name="llmk_create")
        import :: c_int, c_ptr, llmk_config
@@ -213,6 +222,37 @@ module llmk_binding
        type(c_ptr), value :: ctx
        integer(c_int), intent(out) :: tokens_out(*)
        integer(c_int), value :: n, pos0
+     end function
+     ! the same two with the log-prob record of every position (include/llmk.h).  sampler and penalties travel as C addresses:
+     ! c_loc of a `target` llmk_sampler / llmk_penalties, or c_null_ptr -- no sampler is the greedy form, no penalties is none
+     integer(c_int) function llmk_forward_sample_lp(ctx, token, pos, sampler, penalties, logprobs, next_token) &
+          bind(C, name="llmk_forward_sample_lp")
+       import :: c_int, c_ptr, llmk_logprobs
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos
+       type(c_ptr), value :: sampler, penalties
+       type(llmk_logprobs), intent(in) :: logprobs
+       integer(c_int), intent(out) :: next_token
+     end function
+     integer(c_int) function llmk_decode_sample_lp(ctx, token, pos0, n, sampler, penalties, logprobs, ids_out, on_token, user) &
+          bind(C, name="llmk_decode_sample_lp")
+       import :: c_int, c_ptr, c_funptr, llmk_logprobs
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: token, pos0, n
+       type(c_ptr), value :: sampler, penalties
+       type(llmk_logprobs), intent(in) :: logprobs
+       integer(c_int), intent(out) :: ids_out(*)
+       type(c_funptr), value :: on_token
+       type(c_ptr), value :: user
+     end function
+     ! verification hook: the log-prob kernel on caller-supplied logits (vocab_size floats) for `token` (0 = none), no token pass
+     integer(c_int) function llmk_logprob_logits(ctx, logits, token, top_n, token_logprob, top_tokens, top_logprobs) &
+          bind(C, name="llmk_logprob_logits")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: ctx
+       real(c_float), intent(in) :: logits(*)
+       integer(c_int), value :: token, top_n
+       type(c_ptr), value :: token_logprob, top_tokens, top_logprobs
      end function
      integer(c_int) function llmk_forward_sample_pen(ctx, token, pos, sampler, penalties, next_token) bind(C, name="llmk_forward_sample_pen")
        import :: c_int, c_ptr, llmk_sampler, llmk_penalties

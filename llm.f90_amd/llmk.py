@@ -26,7 +26,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_tp_read_partial", "llmk_tp_write_partial", "llmk_tp_read_logits", "llmk_upload", "llmk_upload_rows",
            "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
            "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_set_history", "llmk_get_history",
-           "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_score", "llmk_reset", "llmk_timings",
+           "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
+           "llmk_logprob_logits", "llmk_score", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -77,6 +78,29 @@ def penalties(last_n: int = 0, repeat: float = 1.0, frequency: float = 0.0, pres
     pn = Penalties(last_n, repeat, frequency, presence, C.cast(arr, C.POINTER(LogitBias)), len(items))
     pn._entries = arr
     return pn
+
+
+MAX_TOP_LOGPROBS = 20
+
+
+class Logprobs(C.Structure):
+    """llmk_logprobs: top_n alternatives per position and where the records go (include/llmk.h)"""
+    _fields_ = [("top_n", C.c_int32), ("token_logprob", C.POINTER(C.c_float)), ("top_tokens", C.POINTER(C.c_int32)),
+                ("top_logprobs", C.POINTER(C.c_float))]
+
+
+def logprobs(n: int, top_n: int, want_token: bool = True) -> Logprobs:
+    """A request for n positions; the arrays (token_logprob [n], top_tokens and top_logprobs [n][top_n]) live in the returned struct."""
+    lp = Logprobs(top_n, None, None, None)
+    lp.token = np.zeros(n, np.float32) if want_token else None
+    lp.tokens = np.zeros((n, max(top_n, 0)), np.int32)
+    lp.values = np.zeros((n, max(top_n, 0)), np.float32)
+    if want_token:
+        lp.token_logprob = lp.token.ctypes.data_as(C.POINTER(C.c_float))
+    if top_n > 0:
+        lp.top_tokens = lp.tokens.ctypes.data_as(C.POINTER(C.c_int32))
+        lp.top_logprobs = lp.values.ctypes.data_as(C.POINTER(C.c_float))
+    return lp
 
 
 def _request(temperature, seed, top_k, top_p, min_p, *pen):
@@ -138,6 +162,10 @@ def lib():
             L.llmk_forward_sample_pen.argtypes = [vp, ci, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(ci)]
             L.llmk_decode_sample_pen.argtypes = [vp, ci, ci, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(ci), vp, vp]
             L.llmk_sample_logits_pen.argtypes = [vp, cf, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(ci), C.POINTER(ci), cf, cf]
+        if hasattr(L, "llmk_logprob_logits"):
+            L.llmk_forward_sample_lp.argtypes = [vp, ci, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(Logprobs), C.POINTER(ci)]
+            L.llmk_decode_sample_lp.argtypes = [vp, ci, ci, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(Logprobs), C.POINTER(ci), vp, vp]
+            L.llmk_logprob_logits.argtypes = [vp, cf, ci, ci, cf, C.POINTER(C.c_int32), cf]
         if hasattr(L, "llmk_score"):
             L.llmk_score.argtypes = [vp, C.POINTER(ci), ci, ci, C.POINTER(ci), cf, C.POINTER(ci), cf]
         L.llmk_reset.argtypes = [vp]
@@ -367,6 +395,45 @@ class Llmk:
         _ck(lib().llmk_sample_logits_pen(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), pos, sp, pn, C.byref(tok), C.byref(kept), C.byref(tau),
                                          adj.ctypes.data_as(C.POINTER(C.c_float))))
         return tok.value, kept.value, tau.value, adj
+
+    @staticmethod
+    def _lp_request(temperature, seed, top_k, top_p, min_p, pen):
+        """(sampler, penalties) of a *_sample_lp call: temperature None is the greedy form (both null); no penalty keyword, no penalties"""
+        if temperature is None:
+            if pen or top_k or top_p != 1.0 or min_p:
+                raise ValueError("the greedy form takes no sampler settings")
+            return None, None
+        return C.byref(sampler(temperature, seed, top_k, top_p, min_p)), (C.byref(penalties(**pen)) if pen else None)
+
+    def forward_sample_lp(self, token: int, pos: int, top_n: int, temperature=None, seed: int = 0, top_k: int = 0, top_p: float = 1.0,
+                          min_p: float = 0.0, **pen):
+        """One position with its log-prob record (llmk_forward_sample_lp): temperature None = greedy, else forward_sample_pen's
+        request (pen: last_n, repeat, frequency, presence, bias).  Returns (id, token_logprob, top_tokens [top_n], top_logprobs [top_n])."""
+        nxt = C.c_int(0)
+        sp, pn = self._lp_request(temperature, seed, top_k, top_p, min_p, pen)
+        lp = logprobs(1, top_n)
+        _ck(lib().llmk_forward_sample_lp(self._h, token, pos, sp, pn, C.byref(lp), C.byref(nxt)))
+        return nxt.value, float(lp.token[0]), lp.tokens[0], lp.values[0]
+
+    def decode_sample_lp(self, token: int, pos0: int, n: int, top_n: int, temperature=None, seed: int = 0, top_k: int = 0,
+                         top_p: float = 1.0, min_p: float = 0.0, on_token=None, **pen):
+        """n positions with their log-prob records (llmk_decode_sample_lp): temperature None = decode_greedy's ids, else
+        decode_sample_pen's.  Returns (ids [n], token_logprob [n], top_tokens [n][top_n], top_logprobs [n][top_n])."""
+        sp, pn = self._lp_request(temperature, seed, top_k, top_p, min_p, pen)
+        lp = logprobs(n, top_n)
+        ids = self._decode(lib().llmk_decode_sample_lp, token, pos0, n, on_token, sp, pn, C.byref(lp))
+        return ids, lp.token, lp.tokens, lp.values
+
+    def logprob_logits(self, logits, token: int, top_n: int):
+        """The log-prob kernel on caller-supplied logits (V floats), no token pass (llmk_logprob_logits): (token_logprob of the
+        1-based `token` (0: none, 0.0), top_tokens [top_n], top_logprobs [top_n])."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.shape != (self.V,):
+            raise ValueError("one logit per vocabulary row")
+        lp = logprobs(1, top_n)
+        _ck(lib().llmk_logprob_logits(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), token, top_n, lp.token_logprob, lp.top_tokens,
+                                      lp.top_logprobs))
+        return float(lp.token[0]), lp.tokens[0], lp.values[0]
 
     def generate(self, n: int, prompt=(), want_logits: bool = True, greedy_on_device: bool = False):
         """The reference generation loop at temperature 0 (llama2.f90:376-402)."""
