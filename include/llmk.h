@@ -370,6 +370,47 @@ int llmk_decode_sample_lp(llmk_ctx *ctx, int token, int pos0, int n, const llmk_
 int llmk_logprob_logits(llmk_ctx *ctx, const float *logits, int token, int top_n, float *token_logprob, int32_t *top_tokens,
                         float *top_logprobs);
 
+/* Batched decode: several sequences go through ONE pass over the weights.  A batch belongs to a context and
+ * runs on its weights (nothing is uploaded twice); it owns K/V caches [n_layers][n_slots][seq_len][kv_dim] (f32, zeroed) for n_slots
+ * sequences ("slots", numbered from 0).  The context's own sequence and every other entry point are untouched.  A pass runs on the
+ * context's stream through the context's prefill workspaces: calls on a batch and calls on its context must be serialised by the
+ * caller, as all calls on a context already are.  The layers' weights and an f32 / f16 / q4_0 classifier cross HBM once per pass; a
+ * q6_K classifier (a stock llama.cpp q4_0 file's output.weight) has no batched form and is read once per ROW of the pass.
+ *
+ * create:  n_slots in [1, LLMK_MAX_BATCH], seq_len in [1, the context's seq_len], else LLMK_E_ARG.  LLMK_E_SHAPE for a context the
+ *          batched pass does not serve -- tensor-parallel, emb_dim or hidden_dim not a multiple of 64, kv_dim not a multiple of 16,
+ *          more than 16 query heads per kv head, a classifier no row chunk of which fits the pass's workspace.  There is NO
+ *          token-by-token fallback (LLMK_PREFILL=0 does not apply).  LLMK_E_STATE before all tensors are uploaded, whatever the
+ *          shape.  llmk_destroy of a context with live batches is LLMK_E_STATE: destroy the batches first.
+ * fork:    copies the K/V rows of positions 1..n_pos of every layer from the CONTEXT's own cache (filled by llmk_prefill /
+ *          llmk_forward) into `slot`; n_pos in [0, min(batch seq_len, context seq_len)], 0 empties the slot.  N completions of one
+ *          prompt: prefill once, fork N times.
+ * forward: one pass.  Row i feeds tokens[i] (1-based) at position pos[i] (1-based, <= the batch's seq_len) of slot slots[i]: that
+ *          slot's K/V row pos[i] is written and the row attends over the slot's rows 1..pos[i].  n in [1, n_slots], slots distinct,
+ *          else LLMK_E_ARG before anything runs; the rows' positions are unrelated.  logits_out [n][vocab_size] in row order,
+ *          argmax_out [n] the 1-based first maximum (the rule of llmk_forward_greedy); either may be NULL, both NULL is LLMK_E_ARG.
+ *          A row with no finite logit: LLMK_E_NONFINITE.  The f16-range rule of llmk_prefill applies (the call is redone on the f32
+ *          matrix instruction, its K/V rows rewritten).
+ * decode:  `steps` passes with no host round trip between them: ids_out[i*steps + s] is the id picked for row i after position
+ *          pos0[i]+s, fed to that row at pos0[i]+s+1 from device memory.  pos0[i]+steps-1 <= seq_len and everything forward checks,
+ *          up front.  samplers NULL: greedy.  Else samplers[i] is row i's own llmk_sampler -- temperature, seed, top_k, top_p, min_p,
+ *          with the meaning and the checks of llmk_forward_sample_ex -- and the pick is DEFINED as what llmk_sample_logits answers for that
+ *          row's logits, that position and that sampler: the same kernel reads the same bits.  Penalties, logit bias and log-prob
+ *          records are out of scope for a batch.
+ * time:    measurement hook: average milliseconds of one full pass (classifier and greedy pick included) of n rows, slots 0..n-1,
+ *          all at position pos.  It OVERWRITES those slots' row pos: fork or refill the slots afterwards.
+ * The same call on the same state returns bit-identical outputs.  A row's logits are within the 1e-4 parity bar of llmk_forward's on
+ * that sequence alone, and across different batch compositions (the GEMM tiling follows the row count), not bit-identical. */
+typedef struct llmk_batch llmk_batch;
+#define LLMK_MAX_BATCH 128            /* rows of one pass */
+int llmk_batch_create(llmk_ctx *ctx, int n_slots, int seq_len, llmk_batch **out);
+int llmk_batch_destroy(llmk_batch *b);
+int llmk_batch_fork(llmk_batch *b, int slot, int n_pos);
+int llmk_batch_forward(llmk_batch *b, int n, const int *slots, const int *tokens, const int *pos, float *logits_out, int *argmax_out);
+int llmk_batch_decode(llmk_batch *b, int n, const int *slots, const int *tokens, const int *pos0, int steps,
+                      const llmk_sampler *samplers, int *ids_out);
+int llmk_batch_time(llmk_batch *b, int n, int pos, int iters, float *avg_ms);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

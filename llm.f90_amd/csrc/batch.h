@@ -1,0 +1,251 @@
+// Batched decode (llmk_batch_*): up to PF_TMAX ROWS -- one position each of DIFFERENT sequences -- go through every
+// layer together, so the weights cross HBM once per pass instead of once per token per sequence (a q6_K classifier excepted: sc_batch
+// runs its decode kernel per row).  The GEMMs, the residual and SwiGLU epilogues and the classifier are the prefill's (prefill.h); what a
+// row's POSITION touches is here:
+//   row words      {slot, pos} per row (pos 1-based): which of the batch's K/V caches the row lives in, and where
+//   bd_epi_qkv     pf_epi_qkv_pair's arithmetic with the position and the cache base taken from the row words
+//   bd_attn        decode attention over many caches: one workgroup per (kv head, row, part of the row's timesteps)
+//   bd_attn_merge  the parts of a row folded in part order
+//   bd_advance     llmk_batch_decode: the picked id becomes the row's next token, its position moves on -- on the device
+// The caches are [L][n_slots][seq_len][KV] f32.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "prefill.h"
+
+namespace llmk {
+
+constexpr int BD_TILE = 16;          // cache rows per MFMA tile (the A operand's 16 rows)
+constexpr int BD_WAVES = 8;          // waves of an attention workgroup: tiles of a part go round robin
+constexpr int BD_MAX_PARTS = 8;      // workgroups a row's timesteps are split over, at most
+constexpr int BD_MAX_GROUP = 16;     // query heads per kv head, at most (the B operand's 16 columns)
+
+// The split rule.  A pass has n * n_kv_heads (row, kv head) pairs; with fewer of them than CUs a row's tiles are split over `parts`
+// workgroups, as long as every part still has a tile for each of its waves.  tiles per part (tpp) is ONE value for the pass, from its
+// longest row: part p of a row of `pos` timesteps takes tiles [p * tpp, min((p + 1) * tpp, ceil(pos / BD_TILE))) -- possibly none.
+__host__ __device__ inline int bd_parts(int n, int n_kv_heads, int max_pos, int n_cu) {
+    const int ntile = (max_pos + BD_TILE - 1) / BD_TILE;
+    int parts = n_cu / (n * n_kv_heads);
+    parts = parts < (ntile + BD_WAVES - 1) / BD_WAVES ? parts : (ntile + BD_WAVES - 1) / BD_WAVES;
+    parts = parts < BD_MAX_PARTS ? parts : BD_MAX_PARTS;
+    return parts < 1 ? 1 : parts;
+}
+__host__ __device__ inline int bd_tiles_per_part(int max_pos, int parts) {
+    const int ntile = (max_pos + BD_TILE - 1) / BD_TILE;
+    return (ntile + parts - 1) / parts;
+}
+
+struct BdRow { int slot, pos; };      // pos 1-based; {slot, pos} is read as tokpos[1] = pos by the sampler kernels
+static_assert(sizeof(BdRow) == 2 * sizeof(int) && offsetof(BdRow, pos) == sizeof(int), "the sampler kernels read a row's words as int tokpos[2]");
+
+// where the rows live: a layer's caches are kc + slot * slot_stride, seq_len rows of KV floats each
+struct BdCaches {
+    const BdRow* rows;
+    size_t slot_stride;      // seq_len * KV
+    int n_slots, seq_len;
+};
+__device__ __forceinline__ bool bd_row_ok(const BdCaches& bc, const BdRow& r) {
+    return (unsigned)r.slot < (unsigned)bc.n_slots && r.pos >= 1 && r.pos <= bc.seq_len;
+}
+
+// RoPE + K/V write of pf_epi_qkv_kernel; row t's position and cache come from its row words.  The arithmetic IS pf_epi_qkv_pair:
+// it is handed the same arguments with pos0 + t = the row's position and the slot's caches.
+__global__ void bd_epi_qkv_kernel(PfEpiArgs a, BdCaches bc) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    if (p4 >= a.rows / 4) return;
+    const BdRow r = bc.rows[t];
+    if (!bd_row_ok(bc, r)) return;       // (the host checks every row before a pass; a decode cannot run past seq_len)
+    const float4 s4 = pf_sum4(a, t, 4 * p4);
+    a.pos0 = r.pos - t;
+    a.kc += (size_t)r.slot * bc.slot_stride;
+    a.vc += (size_t)r.slot * bc.slot_stride;
+    pf_epi_qkv_pair(a, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
+    pf_epi_qkv_pair(a, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
+}
+
+// ---- decode attention over many caches                                                      llama2.f90:572-598 ------------
+// pf_attn_kernel's layout with the 16 MFMA query columns holding the kv_mul QUERY HEADS OF ONE KV GROUP (padded by repeating the
+// last) instead of 16 prompt positions: row b's K/V rows 0 .. pos_b-1 of slot_b cross L2 once for the whole group.  One workgroup
+// per (kv head, row, part); its 8 waves take the part's 16-row tiles round robin, each with a running softmax, and merge through LDS.
+// parts == 1: the normalised output goes to `out`.  Otherwise the part leaves its state -- the maximum M, the sum L and the
+// unnormalised output relative to M, per query head -- in po / pml, and bd_attn_merge_kernel folds a row's parts in part order.
+// An empty part (a short row next to a long one) leaves M = -inf, L = 0.
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* __restrict__ Q, const float* __restrict__ kc,
+                                                                  const float* __restrict__ vc, float* __restrict__ out,
+                                                                  float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                  int KV, int kv_mul, int E, int tpp) {
+    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
+    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
+    float* so = reinterpret_cast<float*>(pf_smem);   // [NW][16][HS]
+    float* sm = so + NW * 16 * HS;                    // [NW][16]
+    float* sl = sm + NW * 16;                         // [NW][16]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, b = blockIdx.y, part = blockIdx.z, parts = gridDim.z, nkv = gridDim.x;
+    const BdRow row = bc.rows[b];
+    if (!bd_row_ok(bc, row)) return;                  // whole workgroup: no barrier is pending
+    const int nrows = row.pos;                        // cache rows 0 .. nrows-1 are visible
+    const int h = kvh * kv_mul + min(li, kv_mul - 1); // this lane's query head
+    const float scale = sqrtf((float)HS);
+    float qf[DG];
+    {
+        const float* qp = Q + (size_t)b * E + (size_t)h * HS + g * DG;
+#pragma unroll
+        for (int m = 0; m < DG; m += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(qp + m);
+            qf[m] = v.x; qf[m + 1] = v.y; qf[m + 2] = v.z; qf[m + 3] = v.w;
+        }
+    }
+    float m_run = -INFINITY, l_run = 0.f;
+    pf_v4f O[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
+    const float* kb = kc + (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS + g * DG;
+    const float* vb = vc + (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS + NT * li;
+    const int ntile = (nrows + BD_TILE - 1) / BD_TILE;
+    const int t0 = part * tpp, t1 = min(t0 + tpp, ntile);
+    // K / V fragments of a tile are requested one tile ahead (unconditional loads of a clamped row index)
+    float kn[DG], vn[4][NT];
+#define BD_ATT_LOAD(R0_)                                                                                  \
+    do {                                                                                                  \
+        const float* kp_ = kb + (size_t)min((R0_) + li, nrows - 1) * KV;                                  \
+        _Pragma("unroll") for (int m = 0; m < DG; m += 4) {                                               \
+            const float4 v_ = *reinterpret_cast<const float4*>(kp_ + m);                                  \
+            kn[m] = v_.x; kn[m + 1] = v_.y; kn[m + 2] = v_.z; kn[m + 3] = v_.w;                           \
+        }                                                                                                 \
+        _Pragma("unroll") for (int v = 0; v < 4; ++v) {                                                   \
+            const float* vp_ = vb + (size_t)min((R0_) + 4 * g + v, nrows - 1) * KV;                       \
+            if constexpr (NT % 4 == 0) {                                                                  \
+                _Pragma("unroll") for (int t = 0; t < NT; t += 4) {                                       \
+                    const float4 x_ = *reinterpret_cast<const float4*>(vp_ + t);                          \
+                    vn[v][t] = x_.x; vn[v][t + 1] = x_.y; vn[v][t + 2] = x_.z; vn[v][t + 3] = x_.w;       \
+                }                                                                                         \
+            } else if constexpr (NT == 2) {                                                               \
+                const float2 x_ = *reinterpret_cast<const float2*>(vp_);                                  \
+                vn[v][0] = x_.x; vn[v][1] = x_.y;                                                         \
+            } else {                                                                                      \
+                vn[v][0] = vp_[0];                                                                        \
+            }                                                                                             \
+        }                                                                                                 \
+    } while (0)
+    BD_ATT_LOAD(min(t0 + wid, ntile - 1) * BD_TILE);
+    for (int kt = t0 + wid; kt < t1; kt += NW) {
+        const int r0 = kt * BD_TILE;
+        float kf[DG], vf[4][NT];
+#pragma unroll
+        for (int m = 0; m < DG; ++m) kf[m] = kn[m];
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
+        BD_ATT_LOAD(min(kt + NW, ntile - 1) * BD_TILE);
+        pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int m = 0; m < DG; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[m], qf[m], acc, 0, 0, 0);
+        float sc[4], mx = -INFINITY;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const bool vis = r0 + 4 * g + v < nrows;
+            sc[v] = vis ? acc[v] / scale : -INFINITY;
+            mx = fmaxf(mx, sc[v]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const bool any = m_new != -INFINITY;
+        const float alpha = !any ? 1.f : (m_run == -INFINITY ? 0.f : expf(m_run - m_new));
+        float p[4], rs = 0.f;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            p[v] = (any && sc[v] != -INFINITY) ? expf(sc[v] - m_new) : 0.f;
+            rs += p[v];
+        }
+        rs += __shfl_xor(rs, 16, 64);
+        rs += __shfl_xor(rs, 32, 64);
+        l_run = l_run * alpha + rs;
+        m_run = m_new;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float ar = __shfl(alpha, 4 * g + r, 64);                     // O rows are query heads 4g+r
+#pragma unroll
+            for (int t = 0; t < NT; ++t) O[t][r] *= ar;
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) O[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(p[v], vf[v][t], O[t], 0, 0, 0);
+    }
+#undef BD_ATT_LOAD
+    if (g == 0) {
+        sm[wid * 16 + li] = m_run;
+        sl[wid * 16 + li] = l_run;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) so[(size_t)(wid * 16 + 4 * g + r) * HS + NT * li + t] = O[t][r];
+    __syncthreads();
+    const size_t pbase = ((size_t)b * nkv + kvh) * parts + part;      // this part's state: po [.][BD_MAX_GROUP][HS], pml [.][BD_MAX_GROUP]
+    for (int idx = tid; idx < kv_mul * HS; idx += NW * WAVE) {
+        const int q = idx / HS, d = idx % HS;
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[w * 16 + q]);
+        float L = 0.f, val = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = sm[w * 16 + q];
+            const float e = mw == -INFINITY ? 0.f : expf(mw - M);
+            L += sl[w * 16 + q] * e;
+            val += so[(size_t)(w * 16 + q) * HS + d] * e;
+        }
+        if (parts == 1) {
+            out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+        } else {
+            po[(pbase * BD_MAX_GROUP + q) * HS + d] = val;
+            if (d == 0) pml[pbase * BD_MAX_GROUP + q] = make_float2(M, L);
+        }
+    }
+}
+
+// the parts of (row, kv head) in part order: out = sum_p O_p e^(M_p - M) / sum_p L_p e^(M_p - M); part 0 is never empty
+template <int HS>
+__global__ __launch_bounds__(256) void bd_attn_merge_kernel(const float* __restrict__ po, const float2* __restrict__ pml,
+                                                            float* __restrict__ out, BdCaches bc, int kv_mul, int E, int parts) {
+    const int kvh = blockIdx.x, b = blockIdx.y, nkv = gridDim.x;
+    if (!bd_row_ok(bc, bc.rows[b])) return;
+    const size_t pbase = ((size_t)b * nkv + kvh) * parts;
+    for (int idx = threadIdx.x; idx < kv_mul * HS; idx += 256) {
+        const int q = idx / HS, d = idx % HS;
+        float M = -INFINITY;
+        for (int p = 0; p < parts; ++p) M = fmaxf(M, pml[(pbase + p) * BD_MAX_GROUP + q].x);
+        float L = 0.f, val = 0.f;
+        for (int p = 0; p < parts; ++p) {
+            const float2 ml = pml[(pbase + p) * BD_MAX_GROUP + q];
+            const float e = ml.x == -INFINITY ? 0.f : expf(ml.x - M);
+            L += ml.y * e;
+            val += po[((pbase + p) * BD_MAX_GROUP + q) * HS + d] * e;
+        }
+        out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+    }
+}
+
+// llmk_batch_decode, between two passes: row i's pick (1-based; greedy: the classifier's first maximum, else what the sampler left)
+// is recorded, becomes the token the row feeds next (0-based, as pf_embed_kernel reads it) and the row moves one position on.
+// No pick (no finite logit): the error word is raised and the row feeds token 0 -- the call answers LLMK_E_NONFINITE.
+__global__ void bd_advance_kernel(const int* __restrict__ picked, int n, int V, int step, int steps, int* __restrict__ ids,
+                                  int* __restrict__ tok0, BdRow* __restrict__ rows, unsigned* __restrict__ err) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int id = picked[i];
+    const bool ok = id >= 1 && id <= V;
+    if (!ok) atomicOr(err, 1u);
+    ids[(size_t)i * steps + step] = ok ? id : 0;
+    tok0[i] = ok ? id - 1 : 0;
+    rows[i].pos += 1;
+}
+
+}  // namespace llmk

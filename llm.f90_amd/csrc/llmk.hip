@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "token_kernel.h"
 #include "prefill.h"
+#include "batch.h"
 #include "tp_p2p.h"
 
 #include <rccl/rccl.h>
@@ -218,8 +219,36 @@ struct llmk_ctx {
     float* sc_logits = nullptr;            // [sc_logits_cap][V]
     size_t sc_logits_cap = 0;
     bool sc_ready = false;
+    int n_batches = 0;                     // live llmk_batch objects on this context (llmk_destroy refuses while there are any)
 };
 typedef llmk_ctx::PfLane PfLane;
+
+// Batched decode (batch.h): K/V caches of its own for n_slots sequences on the context's weights.  A pass runs on
+// the context's stream through lane 0 of its prefill workspaces and the scoring partials (calls on a batch and on its context are
+// serialised by the caller, as all calls on a context are); what a pass needs beyond them is here.
+struct llmk_batch {
+    llmk_ctx* ctx = nullptr;
+    int n_slots = 0, seq_len = 0;
+    float *d_kc = nullptr, *d_vc = nullptr;      // [L][n_slots][seq_len][KV]
+    BdRow* d_rows = nullptr;                     // [LLMK_MAX_BATCH] row words
+    int* d_tok = nullptr;                        // [LLMK_MAX_BATCH] 0-based fed ids
+    float* d_out = nullptr;                      // [2 * LLMK_MAX_BATCH]: (unused log-probs), then the rows' first maxima (1-based ints)
+    float* d_logits = nullptr;                   // [n_slots][V]
+    float* d_po = nullptr;                       // attention parts: [n_cu][BD_MAX_GROUP][hs] unnormalised outputs ...
+    float2* d_pml = nullptr;                     // ... and [n_cu][BD_MAX_GROUP] {M, L}
+    int* d_next = nullptr;                       // [LLMK_MAX_BATCH] the samplers' picks
+    llmk_filter_params* d_filt = nullptr;        // [LLMK_MAX_BATCH] row i's sampler
+    unsigned* d_out2 = nullptr;                  // [LLMK_MAX_BATCH][2] sample_filter_kernel's {kept, tau}
+    unsigned* d_err = nullptr;                   // a decode step had no finite logit in some row
+    int* d_ids = nullptr;                        // [ids_cap] a decode's ids, row-major
+    size_t ids_cap = 0;
+    // pinned: what a call uploads (rows, tokens, samplers) and reads back (first maxima, error word)
+    BdRow* h_rows = nullptr;
+    int* h_tok = nullptr;
+    llmk_filter_params* h_filt = nullptr;
+    float* h_out = nullptr;
+    unsigned* h_err = nullptr;
+};
 
 namespace {
 
@@ -1126,6 +1155,8 @@ struct ScoreJob {
     bool want_lp, want_logits;
     int n;                   // positions of the call
     ScPlan sp;               // the classifier's row chunks: sc_plan, once per call (it depends on the context and its matrix instruction only)
+    float* out = nullptr;    // where the log-probs and ids go instead of sc_out, and the logits instead of sc_logits (a batch's own: llmk_batch_*)
+    float* logits = nullptr;
 };
 // The classifier GEMM runs in chunks of R rows (a multiple of 128, or all V rows) whose partial tiles fit the workspace the layers'
 // GEMMs already have: V is 2.8x the largest row count that one is sized for (2H; Llama-3: 9x), and a context that scores allocates
@@ -1191,7 +1222,7 @@ int sc_setup(llmk_ctx* c) {
 // the merge of a batch's partials: log-probs and ids of positions i0 .. i0+T-1 of the call
 hipError_t sc_merge(llmk_ctx* c, int lane, hipStream_t st, const ScoreJob& sj, int nparts, int T, int i0) {
     hipLaunchKernelGGL(pf_score_merge_kernel, dim3(T), dim3(64), 0, st, c->sc_part[lane], nparts, sj.want_lp ? c->sc_targets + i0 : nullptr,
-                       c->sc_tgt[lane], c->sc_out + i0, reinterpret_cast<int*>(c->sc_out + sj.n) + i0);
+                       c->sc_tgt[lane], (sj.out ? sj.out : c->sc_out) + i0, reinterpret_cast<int*>((sj.out ? sj.out : c->sc_out) + sj.n) + i0);
     return hipGetLastError();
 }
 // after the last layer of a batch (w.Xs = x * final gains, w.xn: pf_epi_resid_norm_kernel): positions i0 .. i0+T-1 of the call
@@ -1199,13 +1230,14 @@ hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const 
     const DevTensor& ct = c->t[LLMK_WCLS];
     const int V = c->V, E = c->E;
     const ScPlan& sp = sj.sp;
+    float* const logits = sj.logits ? sj.logits : c->sc_logits;
     PfScoreArgs s;
     memset(&s, 0, sizeof(s));
     s.zp = (size_t)V; s.V = V; s.nparts = sp.nparts; s.part = c->sc_part[lane];
     s.targets = sj.want_lp ? c->sc_targets + i0 : nullptr; s.tgt = c->sc_tgt[lane];
     if (ct.type == LLMK_TYPE_Q6_K) {
         // no batched q6_K GEMM: the decode classifier (final rmsnorm inside, q6k.h) on each of the batch's rows
-        float* Z = sj.want_logits ? c->sc_logits + (size_t)i0 * V : c->sc_z[lane];
+        float* Z = sj.want_logits ? logits + (size_t)i0 * V : c->sc_z[lane];
         const size_t smem = 16 + (size_t)E * sizeof(float);
         const int blocks = (V + GEMV_WAVES * Q6K_RPW - 1) / (GEMV_WAVES * Q6K_RPW);
         for (int t = 0; t < T; ++t) {
@@ -1223,22 +1255,24 @@ hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const 
         HIPRET(pf_gemm(c, w, (const char*)ct.data + (size_t)r0 * ct.row_bytes, (int)ct.row_bytes, w.Xs, rows, E, T, &e, ct.type));
         e.rows = rows; e.out = nullptr;
         s.r0 = r0; s.part0 = k * ((sp.R + PF_SC_ROWS - 1) / PF_SC_ROWS);
-        s.zout = sj.want_logits ? c->sc_logits + (size_t)i0 * V + r0 : nullptr;
+        s.zout = sj.want_logits ? logits + (size_t)i0 * V + r0 : nullptr;
         hipLaunchKernelGGL((pf_score_kernel<true>), dim3((rows + PF_SC_ROWS - 1) / PF_SC_ROWS, T), dim3(256), 0, w.stream, e, s);
         HIPRET(hipGetLastError());
     }
     return sc_merge(c, lane, w.stream, sj, sp.nparts, T, i0);
 }
 
-// one batch of T <= PF_TMAX prompt positions pos0 .. pos0+T-1 (1-based) through all layers; X[T-1] ends up in d_x
-// `prev`: the lane of the batch before this one (null for the first batch of a call); `last`: this batch ends the prompt
-// `sj` (llmk_score): the final rmsnorm, the classifier and the log-softmax of all T positions follow; i0 = the batch's first position in the call
-hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, int T, int pos0, bool last, const ScoreJob* sj = nullptr, int i0 = 0) {
+// The layers of one pass, shared by the prefill (pf_batch) and the batched decode (bd_pass): T <= PF_TMAX rows, the ids in `tok` (0-based,
+// device memory), through the embedding and every layer on the lane's stream; X ends up in w.X.  What a row's POSITION touches is the
+// caller's: qkv_attn(l, e) follows layer l's QKV GEMM (e.rows / e.out are set for its epilogue) and enqueues RoPE, the K/V write and
+// the attention into w.XB.  final_gains: the gains the last residual's kernel normalises w.Xs with (null: none).  `e` is left as the
+// classifier's epilogue needs it.
+template <class QkvAttn>
+hipError_t pf_layers(llmk_ctx* c, PfLane& w, const int* tok, int T, int pos0, const float* final_gains, PfEpiArgs& e, QkvAttn&& qkv_attn) {
     const int E = c->E, H = c->H, KV = c->KV, QKV = E + 2 * KV, Tp = (T + 15) / 16 * 16;
     const float* emb = (const float*)c->t[LLMK_TOKEN_EMBEDDING_TABLE].data;
     hipLaunchKernelGGL(pf_embed_kernel, dim3((E + 255) / 256, T), dim3(256), 0, w.stream, emb, tok, w.X, E);
     HIPRET(hipGetLastError());
-    PfEpiArgs e;
     memset(&e, 0, sizeof(e));
     e.P = w.P; e.xn = w.xn; e.rope = c->d_rope; e.Tp = Tp; e.T = T; e.pos0 = pos0;
     e.E = E; e.KV = KV; e.hs = c->hs; e.H = H;
@@ -1249,8 +1283,6 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
             const char* wt = (const char*)dt.data + (size_t)l * rows_per_layer * dt.row_bytes;
             return pf_gemm(c, w, wt, (int)dt.row_bytes, X, rows_per_layer, K, T, &e);
         };
-        float* kc = c->d_kc + (size_t)l * c->S * KV;
-        float* vc = c->d_vc + (size_t)l * c->S * KV;
         // rmsnorm (layer 0 here, later layers in the previous residual's kernel) + QKV + RoPE + KV write   llama2.f90:527-565
         if (l == 0) {
             hipLaunchKernelGGL(pf_norm_kernel, dim3(T), dim3(256), 0, w.stream, w.X,
@@ -1258,18 +1290,8 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
             HIPRET(hipGetLastError());
         }
         HIPRET(gemm(LLMK_WQKV, QKV, w.Xs, E));
-        e.rows = QKV; e.out = w.Q; e.kc = kc; e.vc = vc;
-        hipLaunchKernelGGL(pf_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, e);
-        HIPRET(hipGetLastError());
-        if (!last) HIPRET(hipEventRecord(w.kv[l], w.stream));             // the next batch's attention reads these rows
-        if (prev) HIPRET(hipStreamWaitEvent(w.stream, prev->kv[l], 0));   // ... as this one reads the previous batch's
-        // causal attention: position pos0+t sees cache rows 0 .. pos0+t-1                 :572-598
-        HIPRET(with_head_size(c->hs, [&](auto hs) {
-            constexpr int HS = decltype(hs)::value;
-            hipLaunchKernelGGL((pf_attn_kernel<HS>), dim3(c->nh, (T + 15) / 16), dim3(PF_ATT_WAVES * WAVE), pf_attn_smem(HS), w.stream,
-                               w.Q, kc, vc, w.XB, KV, c->kv_mul, pos0, T, E);
-            return hipGetLastError();
-        }));
+        e.rows = QKV; e.out = w.Q;
+        HIPRET(qkv_attn(l, e));                                                         // :572-598
         // x += wo . xb                                                                    :603-605
         HIPRET(gemm(LLMK_WO, E, w.XB, E));
         e.rows = E; e.out = w.X;
@@ -1285,21 +1307,49 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
         HIPRET(gemm(LLMK_W2, E, w.HB, H));
         e.rows = E; e.out = w.X;
         hipLaunchKernelGGL(pf_epi_resid_norm_kernel, dim3(T), dim3(1024), 0, w.stream, e,
-                           l + 1 < c->L ? (const float*)c->t[LLMK_RMS_ATT_WEIGHT].data + (size_t)(l + 1) * E
-                           : sj ? (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data : nullptr, w.Xs,      // (scoring: the FINAL rmsnorm of every row)
-                           w.xn, c->eps);
+                           l + 1 < c->L ? (const float*)c->t[LLMK_RMS_ATT_WEIGHT].data + (size_t)(l + 1) * E : final_gains, w.Xs, w.xn, c->eps);
         HIPRET(hipGetLastError());
     }
+    return hipSuccess;
+}
+
+// one batch of T <= PF_TMAX prompt positions pos0 .. pos0+T-1 (1-based) through all layers; X[T-1] ends up in d_x
+// `prev`: the lane of the batch before this one (null for the first batch of a call); `last`: this batch ends the prompt
+// `sj` (llmk_score): the final rmsnorm, the classifier and the log-softmax of all T positions follow; i0 = the batch's first position in the call
+hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, int T, int pos0, bool last, const ScoreJob* sj = nullptr, int i0 = 0) {
+    const int E = c->E, KV = c->KV, QKV = E + 2 * KV;
+    PfEpiArgs e;
+    // (scoring: the FINAL rmsnorm of every row)
+    HIPRET(pf_layers(c, w, tok, T, pos0, sj ? (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data : nullptr, e, [&](int l, PfEpiArgs& a) -> hipError_t {
+        float* kc = c->d_kc + (size_t)l * c->S * KV;
+        float* vc = c->d_vc + (size_t)l * c->S * KV;
+        a.kc = kc; a.vc = vc;
+        hipLaunchKernelGGL(pf_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a);
+        HIPRET(hipGetLastError());
+        if (!last) HIPRET(hipEventRecord(w.kv[l], w.stream));             // the next batch's attention reads these rows
+        if (prev) HIPRET(hipStreamWaitEvent(w.stream, prev->kv[l], 0));   // ... as this one reads the previous batch's
+        // causal attention: position pos0+t sees cache rows 0 .. pos0+t-1
+        return with_head_size(c->hs, [&](auto hs) {
+            constexpr int HS = decltype(hs)::value;
+            hipLaunchKernelGGL((pf_attn_kernel<HS>), dim3(c->nh, (T + 15) / 16), dim3(PF_ATT_WAVES * WAVE), pf_attn_smem(HS), w.stream,
+                               w.Q, kc, vc, w.XB, KV, c->kv_mul, pos0, T, E);
+            return hipGetLastError();
+        });
+    }));
     if (sj) HIPRET(sc_batch(c, w, &w == &c->pf[1] ? 1 : 0, e, *sj, T, i0));
     if (last) HIPRET(hipMemcpyAsync(c->d_x, w.X + (size_t)(T - 1) * E, (size_t)E * sizeof(float), hipMemcpyDeviceToDevice, w.stream));
     return hipEventRecord(w.done, w.stream);
 }
 
-// May this context take the batched pass (llmk_prefill, llmk_score)?  Single GPU, shapes on the GEMMs' 64-column step, not switched off
-bool pf_eligible(const llmk_ctx* c) {
+// Can this context's shape take the batched pass at all?  Single GPU, shapes on the GEMMs' 64-column step
+bool pf_shape_ok(const llmk_ctx* c) {
     const int pf_step = PF_KSTEP;
-    return c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0 &&
-           !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
+    return c->tp_size == 1 && !c->comm && c->E % pf_step == 0 && c->H % pf_step == 0 && c->KV % 16 == 0;
+}
+// May this context take the batched pass (llmk_prefill, llmk_score)?  A shape that can, and not switched off (the batched decode has
+// no token-by-token form to be switched to: it asks pf_shape_ok)
+bool pf_eligible(const llmk_ctx* c) {
+    return pf_shape_ok(c) && !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
 }
 // The batched pass of llmk_prefill and (sj: with the classifier and log-softmax of every position) llmk_score, ENQUEUED: tokens[0..n)
 // (1-based ids) at positions pos0 .. pos0+n-1 in batches of PF_TMAX that alternate between the two lanes, then the f16-range flag on
@@ -1364,7 +1414,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 402; }
+int llmk_version(void) { return 403; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2359,6 +2409,270 @@ int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
     return LLMK_OK;
 }
 
+// ---- batched decode (batch.h) -----------------------------------------------------------------------------------
+static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
+constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 * BD_WAVES * 16) * sizeof(float); }
+
+static void batch_free(llmk_batch* b) {
+    void* dev[] = {b->d_kc, b->d_vc, b->d_rows, b->d_tok, b->d_out, b->d_logits, b->d_po, b->d_pml, b->d_next, b->d_filt, b->d_out2, b->d_err, b->d_ids};
+    for (void* p : dev)
+        if (p) hipFree(p);
+    void* host[] = {b->h_rows, b->h_tok, b->h_filt, b->h_out, b->h_err};
+    for (void* p : host)
+        if (p) hipHostFree(p);
+    delete b;
+}
+
+// One pass, ENQUEUED on the context's stream: the n rows in d_rows / d_tok through every layer, the classifier and the per-row first
+// maximum (into d_out + n); the logits of every row into d_logits when asked for.  max_pos: the longest row (the attention's split rule).
+static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp) {
+    llmk_ctx* c = b->ctx;
+    PfLane& w = c->pf[0];
+    const int E = c->E, KV = c->KV, QKV = E + 2 * KV, T = n;
+    const BdCaches bc{b->d_rows, (size_t)b->seq_len * KV, b->n_slots, b->seq_len};
+    const int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
+    PfEpiArgs e;
+    // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
+    HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
+        float* kc = b->d_kc + (size_t)l * b->n_slots * bc.slot_stride;
+        float* vc = b->d_vc + (size_t)l * b->n_slots * bc.slot_stride;
+        a.kc = kc; a.vc = vc;
+        hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc);
+        HIPRET(hipGetLastError());
+        return with_head_size(c->hs, [&](auto hs) {
+            constexpr int HS = decltype(hs)::value;
+            hipLaunchKernelGGL((bd_attn_kernel<HS>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                               w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
+            HIPRET(hipGetLastError());
+            if (parts > 1) hipLaunchKernelGGL((bd_attn_merge_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, c->kv_mul, E, parts);
+            return hipGetLastError();
+        });
+    }));
+    ScoreJob sj{false, want_logits, n, sp};
+    sj.out = b->d_out;
+    sj.logits = b->d_logits;
+    return sc_batch(c, w, 0, e, sj, T, 0);
+}
+
+// the context's side of a pass: workspaces, the classifier's kernels and its row chunks (they follow the matrix instruction in use)
+static int bd_ready(llmk_batch* b, ScPlan* sp) {
+    llmk_ctx* c = b->ctx;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if ((rc = sc_setup(c)) != LLMK_OK) return rc;
+    if ((rc = pf_setup(c, true)) != LLMK_OK) return rc;
+    const int ct = c->t[LLMK_WCLS].type;
+    if (ct != LLMK_TYPE_Q6_K && ct != c->cfg.weight_type) HIPCHK(pf_prepare_type(ct));
+    *sp = sc_plan(c);
+    if (ct != LLMK_TYPE_Q6_K && sp->R == 0) return LLMK_E_SHAPE;      // no chunk of the classifier fits the workspace: there is no token-by-token form
+    return LLMK_OK;
+}
+// rows of a call: n in [1, n_slots], distinct slots, ids and positions in range (last_pos: the last position the call writes)
+static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos, int span) {
+    if (!slots || !tokens || !pos || n < 1 || n > b->n_slots || span < 1) return false;
+    bool seen[LLMK_MAX_BATCH] = {};
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= b->n_slots || seen[slots[i]]) return false;
+        seen[slots[i]] = true;
+        if (tokens[i] < 1 || tokens[i] > b->ctx->V) return false;
+        if (pos[i] < 1 || pos[i] > b->seq_len || span - 1 > b->seq_len - pos[i]) return false;
+    }
+    return true;
+}
+static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos) {
+    for (int i = 0; i < n; ++i) {
+        b->h_rows[i] = BdRow{slots[i], pos[i]};
+        b->h_tok[i] = tokens[i] - 1;
+    }
+    hipStream_t st = b->ctx->stream;
+    HIPRET(hipMemcpyAsync(b->d_rows, b->h_rows, (size_t)n * sizeof(BdRow), hipMemcpyHostToDevice, st));
+    return hipMemcpyAsync(b->d_tok, b->h_tok, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
+}
+// the f16-range flag on its way to the host (as pf_run leaves it)
+static hipError_t bd_fetch_flag(llmk_ctx* c) {
+    unsigned* h_flag = &c->host_words()->pf_flag;
+    *h_flag = 0;
+    return c->pf_hm ? hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
+int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) {
+    if (!c || !out || n_slots < 1 || n_slots > LLMK_MAX_BATCH || seq_len < 1 || seq_len > c->S) return LLMK_E_ARG;
+    *out = nullptr;
+    int rc = check_ready(c);      // (an incomplete context is LLMK_E_STATE whatever its shape)
+    if (rc) return rc;
+    if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    llmk_batch* b = new llmk_batch;
+    b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len;
+    ScPlan sp;
+    if ((rc = bd_ready(b, &sp)) != LLMK_OK) { delete b; return rc; }
+    const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV * sizeof(float), nb = LLMK_MAX_BATCH;
+    auto alloc = [&]() -> int {
+        HIPCHK(dev_alloc(&b->d_kc, cache));
+        HIPCHK(dev_alloc(&b->d_vc, cache));
+        HIPCHK(hipMemsetAsync(b->d_kc, 0, cache, c->stream));
+        HIPCHK(hipMemsetAsync(b->d_vc, 0, cache, c->stream));
+        HIPCHK(dev_alloc(&b->d_rows, nb * sizeof(BdRow)));
+        HIPCHK(dev_alloc(&b->d_tok, nb * sizeof(int)));
+        HIPCHK(dev_alloc(&b->d_out, 2 * nb * sizeof(float)));
+        HIPCHK(dev_alloc(&b->d_logits, (size_t)n_slots * c->V * sizeof(float)));
+        // parts > 1 only while rows x kv heads x parts <= n_cu (bd_parts)
+        HIPCHK(dev_alloc(&b->d_po, (size_t)c->n_cu * BD_MAX_GROUP * c->hs * sizeof(float)));
+        HIPCHK(dev_alloc(&b->d_pml, (size_t)c->n_cu * BD_MAX_GROUP * sizeof(float2)));
+        HIPCHK(dev_alloc(&b->d_next, nb * sizeof(int)));
+        HIPCHK(dev_alloc(&b->d_filt, nb * sizeof(llmk_filter_params)));
+        HIPCHK(dev_alloc(&b->d_out2, 2 * nb * sizeof(unsigned)));
+        HIPCHK(dev_alloc(&b->d_err, sizeof(unsigned)));
+        HIPCHK(hipHostMalloc(&b->h_rows, nb * sizeof(BdRow), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc(&b->h_tok, nb * sizeof(int), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc(&b->h_filt, nb * sizeof(llmk_filter_params), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc(&b->h_out, 2 * nb * sizeof(float), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc(&b->h_err, sizeof(unsigned), hipHostMallocDefault));
+        HIPCHK(with_head_size(c->hs, [](auto hs) {
+            constexpr int HS = decltype(hs)::value;
+            return hipFuncSetAttribute((const void*)bd_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+        }));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return LLMK_OK;
+    };
+    if ((rc = alloc()) != LLMK_OK) { batch_free(b); return rc; }
+    ++c->n_batches;
+    *out = b;
+    return LLMK_OK;
+}
+
+int llmk_batch_destroy(llmk_batch* b) {
+    if (!b) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    hipSetDevice(c->cfg.device);
+    hipStreamSynchronize(c->stream);
+    --c->n_batches;
+    batch_free(b);
+    return LLMK_OK;
+}
+
+int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
+    if (!b || slot < 0 || slot >= b->n_slots || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S)) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t row = (size_t)c->KV, slot_rows = (size_t)b->seq_len * row;
+    float* caches[2][2] = {{b->d_kc, c->d_kc}, {b->d_vc, c->d_vc}};
+    for (auto& p : caches)
+        for (int l = 0; l < c->L; ++l) {
+            float* dst = p[0] + ((size_t)l * b->n_slots + slot) * slot_rows;
+            if ((size_t)n_pos < (size_t)b->seq_len)      // rows beyond n_pos: as in a fresh slot
+                HIPCHK(hipMemsetAsync(dst + (size_t)n_pos * row, 0, (slot_rows - (size_t)n_pos * row) * sizeof(float), c->stream));
+            if (n_pos > 0)
+                HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+
+int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos, float* logits_out, int* argmax_out) {
+    if (!b || (!logits_out && !argmax_out) || !bd_rows_ok(b, n, slots, tokens, pos, 1)) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    ScPlan sp;
+    int rc = bd_ready(b, &sp);
+    if (rc) return rc;
+    HIPCHK(bd_upload_rows(b, n, slots, tokens, pos));
+    HIPCHK(bd_pass(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp));
+    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(bd_fetch_flag(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pf_flagged(c)) {
+        static bool told = false;
+        return pf_redo(c, "llmk_batch_forward", &told, [&] { return llmk_batch_forward(b, n, slots, tokens, pos, logits_out, argmax_out); });
+    }
+    const int* ids = reinterpret_cast<const int*>(b->h_out + n);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 1 || ids[i] > c->V) return LLMK_E_NONFINITE;
+    if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
+    if (logits_out) HIPCHK(hipMemcpy(logits_out, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost));
+    return LLMK_OK;
+}
+
+int llmk_batch_decode(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos0, int steps, const llmk_sampler* samplers, int* ids_out) {
+    if (!b || !ids_out || steps < 1 || !bd_rows_ok(b, n, slots, tokens, pos0, steps)) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    if (samplers) {
+        for (int i = 0; i < n; ++i) {      // llmk_forward_sample_ex's checks (sampler_request)
+            const llmk_sampler& sp = samplers[i];
+            if (sp.top_k < 0 || !(sp.top_p > 0.f && sp.top_p <= 1.f) || !(sp.min_p >= 0.f && sp.min_p <= 1.f)) return LLMK_E_ARG;
+            if (!(sp.temperature > 0.f) || !isfinite(sp.temperature)) return LLMK_E_ARG;
+            const float invT = 1.0f / sp.temperature;
+            if (!isfinite(invT) || !(invT >= FLT_MIN)) return LLMK_E_ARG;
+            b->h_filt[i] = llmk_filter_params{invT, (uint32_t)sp.seed, (uint32_t)(sp.seed >> 32), sp.top_k, sp.top_p, sp.min_p, {0, 0}};
+        }
+    }
+    ScPlan sp;
+    int rc = bd_ready(b, &sp);
+    if (rc) return rc;
+    const size_t nids = (size_t)n * steps;
+    if (b->ids_cap < nids) {
+        if (b->d_ids) { hipFree(b->d_ids); b->d_ids = nullptr; b->ids_cap = 0; }
+        HIPCHK(dev_alloc(&b->d_ids, nids * sizeof(int)));
+        b->ids_cap = nids;
+    }
+    HIPCHK(bd_upload_rows(b, n, slots, tokens, pos0));
+    if (samplers) HIPCHK(hipMemcpyAsync(b->d_filt, b->h_filt, (size_t)n * sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(b->d_err, 0, sizeof(unsigned), c->stream));
+    const int max_pos0 = *std::max_element(pos0, pos0 + n);
+    for (int s = 0; s < steps; ++s) {
+        HIPCHK(bd_pass(b, n, max_pos0 + s, samplers != nullptr, sp));
+        const int* picked = reinterpret_cast<const int*>(b->d_out + n);
+        if (samplers) {
+            // row i's draw: the kernel llmk_sample_logits runs, on the row's logits, position (the row words: tokpos[1] = pos) and sampler
+            for (int i = 0; i < n; ++i)
+                hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, b->d_logits + (size_t)i * c->V, c->V,
+                                   reinterpret_cast<const int*>(b->d_rows + i), 0, b->d_filt + i, b->d_next + i, (float2*)nullptr, 0, b->d_out2 + 2 * i);
+            HIPCHK(hipGetLastError());
+            picked = b->d_next;
+        }
+        hipLaunchKernelGGL(bd_advance_kernel, dim3(1), dim3(LLMK_MAX_BATCH), 0, c->stream, picked, n, c->V, s, steps, b->d_ids, b->d_tok, b->d_rows, b->d_err);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(b->h_err, b->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(bd_fetch_flag(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pf_flagged(c)) {
+        static bool told = false;
+        return pf_redo(c, "llmk_batch_decode", &told, [&] { return llmk_batch_decode(b, n, slots, tokens, pos0, steps, samplers, ids_out); });
+    }
+    HIPCHK(hipMemcpy(ids_out, b->d_ids, nids * sizeof(int), hipMemcpyDeviceToHost));
+    return *b->h_err ? LLMK_E_NONFINITE : LLMK_OK;
+}
+
+int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
+    if (!b || !avg_ms || n < 1 || n > b->n_slots || pos < 1 || pos > b->seq_len || iters < 1) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    ScPlan sp;
+    int rc = bd_ready(b, &sp);
+    if (rc) return rc;
+    int slots[LLMK_MAX_BATCH], tokens[LLMK_MAX_BATCH], posv[LLMK_MAX_BATCH];
+    for (int i = 0; i < n; ++i) { slots[i] = i; tokens[i] = 1; posv[i] = pos; }
+    HIPCHK(bd_upload_rows(b, n, slots, tokens, posv));
+    HIPCHK(bd_pass(b, n, pos, false, sp));      // warm-up
+    HIPCHK(hipStreamSynchronize(c->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    hipError_t pe = hipEventCreate(&e1);
+    if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
+    for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, pos, false, sp);
+    if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
+    if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
+    float ms = 0.f;
+    if (pe == hipSuccess) pe = hipEventElapsedTime(&ms, e0, e1);
+    hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pe != hipSuccess) return LLMK_E_HIP + (int)pe;
+    *avg_ms = ms / (float)iters;
+    return LLMK_OK;
+}
+
 int llmk_reset(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -2869,6 +3183,7 @@ int llmk_tp_ranks_seen(llmk_ctx* c) {
 
 int llmk_destroy(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
+    if (c->n_batches > 0) return LLMK_E_STATE;      // its batches go first (llmk_batch_destroy): they run on this context's weights and stream
     hipSetDevice(c->cfg.device);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->comm) ncclCommDestroy(c->comm);

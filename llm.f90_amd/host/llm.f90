@@ -9,7 +9,11 @@
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
 !         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N]
+!
+! --parallel N (1 .. 128, one GPU): N completions of the prompt decoded TOGETHER (llmk_batch_*, DESIGN.md section 3i) -- the prompt is
+! prefilled once and forked into N slots, every pass over the weights serves all N; seeds seed, seed+1, ... at -t > 0 (the filter
+! flags apply), greedy at -t 0 (N equal texts).  The completions are printed after generation, each under a line [k], k = 0 .. N-1.
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
 ! (one process per GPU, devices d..d+N-1), every rank loads the file and keeps its shard, the ranks meet through a
@@ -48,6 +52,7 @@ module arg_parse
      logical :: gguf_eps, gguf_rope_base   ! extension: honour the file's rms epsilon / RoPE base (the reference hard-codes
                                            ! 1e-5 and 10000, llama2.f90:454,545)
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
+     integer :: parallel          ! extension: --parallel N (0 = off): N completions decoded together on one GPU (llmk_batch_*)
      integer :: logprobs          ! extension: --logprobs N (0 .. 20): the log-prob of every generated token and its N most likely
                                   ! alternatives, from the device (llmk_*_sample_lp); -1 = off
      logical :: score             ! extension: score the prompt instead of continuing it (llmk_score): log-prob per token, perplexity
@@ -92,6 +97,7 @@ contains
     a%encode_only = .false.
     a%score = .false.
     a%logprobs = -1
+    a%parallel = 0
 
     nargs = command_argument_count()
     i = 1
@@ -131,6 +137,13 @@ contains
        case ("--gguf-rope-base");    a%gguf_rope_base = .true.; i = i + 1
        case ("--encode");            a%encode_only = .true.;   i = i + 1
        case ("--score");             a%score = .true.;         i = i + 1
+       case ("--parallel")
+          read (val, *) a%parallel
+          if (a%parallel < 1 .or. a%parallel > 128) then
+             print *, "--parallel takes N in 1 .. 128"
+             stop 1
+          end if
+          i = i + 2
        case ("--logprobs")
           read (val, *) a%logprobs
           if (a%logprobs < 0 .or. a%logprobs > 20) then
@@ -265,8 +278,37 @@ program llm
   real(c_float), allocatable, target :: lp_token(:), lp_top(:)
   integer(c_int32_t), allocatable, target :: lp_top_ids(:)
   integer :: lp_n, lp_w
+  type(c_ptr) :: pbatch                             ! --parallel N: the batch, its rows and samplers, the ids [row][step]
+  integer(c_int), allocatable :: par_slots(:), par_tokens(:), par_pos(:), par_ids(:)
+  type(llmk_sampler), allocatable, target :: par_samplers(:)
+  type(c_ptr) :: par_sp
+  integer :: par_steps
 
   call parse_args(opts)
+  ! --parallel N: what a batch does not do is said and stops here (include/llmk.h: penalties, logit bias and log-prob records are out
+  ! of scope for a batch; a batch lives on one GPU; --score continues nothing)
+  if (opts%parallel > 0) then
+     if (opts%ngpu > 1) then
+        print *, "--parallel: the completions are decoded together on one GPU (no tensor-parallel batches): drop --ngpu"
+        stop 1
+     end if
+     if (opts%score) then
+        print *, "--parallel: --score scores the prompt and continues nothing: drop one of the two"
+        stop 1
+     end if
+     if (opts%logprobs >= 0) then
+        print *, "--parallel: --logprobs is not available for completions decoded together (llmk_batch_decode keeps no log-prob records)"
+        stop 1
+     end if
+     if (opts%n_bias > 0) then
+        print *, "--parallel: --logit-bias is not available for completions decoded together (llmk_batch_decode applies no logit bias)"
+        stop 1
+     end if
+     if (opts%repeat_penalty /= 1 .or. opts%presence_penalty /= 0 .or. opts%frequency_penalty /= 0) then
+        print *, "--parallel: the penalties are not available for completions decoded together (llmk_batch_decode applies none)"
+        stop 1
+     end if
+  end if
   lead = opts%tp_rank == 0
   if (opts%ngpu > 1) call tp_launch_workers()
   if (opts%ak) then
@@ -398,6 +440,76 @@ program llm
      print '(A,1X,ES15.8)', "sum logprob", sc_sum
      print '(A,1X,ES15.8)', "perplexity", exp(-sc_sum / k)
      print *, 1000 * k / dt_ms, "positions/second"
+     rc = llmk_destroy(ctx)
+     stop
+  end if
+
+  ! --parallel N: positions 1 .. k (BOS and the first k-1 prompt tokens) are prefilled ONCE on the context and forked into N slots;
+  ! the last prompt token (BOS without a prompt) is fed to all N rows at position k+1 and llmk_batch_decode runs positions
+  ! k+1 .. seq_len for all of them, every id drawn on the device: row i by the sampler (temperature, filters, seed + i), or the first
+  ! maximum at -t 0.  Nothing is printed before the call returns; then the completions, one after another
+  if (opts%parallel > 0) then
+     k = size(prompt_tokens)
+     if (k >= seq_len) then
+        print *, "--parallel: the prompt (", k, "tokens ) leaves no position to generate within -n", seq_len
+        stop 1
+     end if
+     rc = llmk_batch_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), pbatch)
+     if (rc == 2) then                               ! LLMK_E_SHAPE
+        print *, "--parallel: this model's shape has no batched pass (emb_dim and hidden_dim must be multiples of 64, kv_dim of 16, " // &
+             "at most 16 query heads per kv head)"
+        stop 1
+     end if
+     call llmk_check(rc, "llmk_batch_create")
+     t_start = clock_ticks()
+     token = 2
+     if (k > 0) then
+        allocate(batch(k))
+        batch(1) = 2
+        batch(2:) = int(prompt_tokens(1:k - 1), c_int)
+        call llmk_check(llmk_prefill(ctx, batch, int(k, c_int), 1_c_int, logits), "llmk_prefill")
+        token = prompt_tokens(k)
+     end if
+     par_steps = seq_len - k
+     allocate(par_slots(opts%parallel), par_tokens(opts%parallel), par_pos(opts%parallel), par_ids(opts%parallel * par_steps))
+     allocate(par_samplers(opts%parallel))
+     par_sp = c_null_ptr
+     dseed = 0
+     if (opts%temperature > 0) then
+        if (opts%seed >= 0) then
+           dseed = int(opts%seed, c_int64_t)
+        else
+           call system_clock(dseed)
+        end if
+        if (opts%verbose) print *, "device sampler seed:", dseed
+        par_sp = c_loc(par_samplers)
+     end if
+     do j = 1, opts%parallel
+        call llmk_check(llmk_batch_fork(pbatch, int(j - 1, c_int), int(k, c_int)), "llmk_batch_fork")
+        par_slots(j) = int(j - 1, c_int)
+        par_tokens(j) = int(token, c_int)
+        par_pos(j) = int(k + 1, c_int)
+        par_samplers(j)%temperature = real(opts%temperature, c_float)
+        par_samplers(j)%top_k = int(opts%top_k, c_int32_t)
+        par_samplers(j)%top_p = real(opts%top_p, c_float)
+        par_samplers(j)%min_p = real(opts%min_p, c_float)
+        par_samplers(j)%seed = dseed + int(j - 1, c_int64_t)
+     end do
+     call llmk_check(llmk_batch_decode(pbatch, int(opts%parallel, c_int), par_slots, par_tokens, par_pos, int(par_steps, c_int), &
+          par_sp, par_ids), "llmk_batch_decode")
+     t_end = clock_ticks()
+     dt_ms = elapsed_ms(t_start, t_end)
+     do j = 1, opts%parallel
+        print '(A,I0,A)', "[", j - 1, "]"
+        do pos = 1, par_steps
+           l = par_ids((j - 1) * par_steps + pos)
+           write (*, fmt="(A)", advance="no") vocab(l)(1:vocab_len(l))
+        end do
+        print '(A)', ""
+     end do
+     print *, "Inference time: ", dt_ms / 1000, " seconds"
+     print *, 1000 * real(opts%parallel, wp) * par_steps / dt_ms, "tokens/second (", opts%parallel, "completions together )"
+     rc = llmk_batch_destroy(pbatch)
      rc = llmk_destroy(ctx)
      stop
   end if

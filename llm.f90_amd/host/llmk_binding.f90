@@ -286,6 +286,31 @@ module llmk_binding
        real(c_float), intent(out) :: tau_out
        type(c_ptr), value :: adjusted_out
      end function
+     ! batched decode (include/llmk.h, DESIGN.md section 3i): `--parallel N`.  samplers = c_loc of a `target` array of n
+     ! llmk_sampler, or c_null_ptr = greedy
+     integer(c_int) function llmk_batch_create(ctx, n_slots, seq_len, batch) bind(C, name="llmk_batch_create")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: n_slots, seq_len
+       type(c_ptr), intent(out) :: batch
+     end function
+     integer(c_int) function llmk_batch_destroy(batch) bind(C, name="llmk_batch_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+     end function
+     integer(c_int) function llmk_batch_fork(batch, slot, n_pos) bind(C, name="llmk_batch_fork")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot, n_pos
+     end function
+     integer(c_int) function llmk_batch_decode(batch, n, slots, tokens, pos0, steps, samplers, ids_out) bind(C, name="llmk_batch_decode")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n, steps
+       integer(c_int), intent(in) :: slots(*), tokens(*), pos0(*)
+       type(c_ptr), value :: samplers
+       integer(c_int), intent(out) :: ids_out(*)
+     end function
      integer(c_int) function llmk_path(ctx) bind(C, name="llmk_path")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

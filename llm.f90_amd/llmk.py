@@ -27,7 +27,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
            "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_set_history", "llmk_get_history",
            "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
-           "llmk_logprob_logits", "llmk_score", "llmk_reset", "llmk_timings",
+           "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
+           "llmk_batch_decode", "llmk_batch_time", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -58,6 +59,7 @@ def sampler(temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, m
 
 
 MAX_LOGIT_BIAS = 256
+MAX_BATCH = 128
 
 
 class LogitBias(C.Structure):
@@ -168,6 +170,13 @@ def lib():
             L.llmk_logprob_logits.argtypes = [vp, cf, ci, ci, cf, C.POINTER(C.c_int32), cf]
         if hasattr(L, "llmk_score"):
             L.llmk_score.argtypes = [vp, C.POINTER(ci), ci, ci, C.POINTER(ci), cf, C.POINTER(ci), cf]
+        if hasattr(L, "llmk_batch_create"):
+            L.llmk_batch_create.argtypes = [vp, ci, ci, C.POINTER(vp)]
+            L.llmk_batch_destroy.argtypes = [vp]
+            L.llmk_batch_fork.argtypes = [vp, ci, ci]
+            L.llmk_batch_forward.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), cf, C.POINTER(ci)]
+            L.llmk_batch_decode.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(Sampler), C.POINTER(ci)]
+            L.llmk_batch_time.argtypes = [vp, ci, ci, ci, cf]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -547,6 +556,70 @@ class Llmk:
     def close(self):
         if self._h:
             lib().llmk_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Batch:
+    """Batched decode (llmk_batch_*): n_slots sequences with K/V caches of their own on the weights of the
+    Llmk context `model`; every pass takes one position of up to n_slots of them.  Slots count from 0; tokens and positions are
+    1-based.  Calls on a batch and on its context must not overlap.  Close the batch before its context."""
+
+    def __init__(self, model: Llmk, n_slots: int, seq_len: int | None = None):
+        self.model, self.n_slots, self.V = model, n_slots, model.V
+        self._h = C.c_void_p()
+        _ck(lib().llmk_batch_create(model._h, n_slots, seq_len or model.shape.seq_len, C.byref(self._h)))
+
+    @staticmethod
+    def _rows(slots, tokens, pos):
+        a = [np.ascontiguousarray(x, np.int32) for x in (slots, tokens, pos)]
+        if not (a[0].ndim == 1 and a[0].shape == a[1].shape == a[2].shape):
+            raise ValueError("one slot, one token and one position per row")
+        return a, [x.ctypes.data_as(C.POINTER(C.c_int)) for x in a]
+
+    def fork(self, slot: int, n_pos: int):
+        """the context's K/V rows of positions 1..n_pos into `slot` (llmk_batch_fork); n_pos = 0 empties the slot"""
+        _ck(lib().llmk_batch_fork(self._h, slot, n_pos))
+
+    def forward(self, slots, tokens, pos, want_logits: bool = True, want_argmax: bool = True):
+        """one pass (llmk_batch_forward): (logits [n][V], argmax [n] 1-based), or the one that was asked for"""
+        a, p = self._rows(slots, tokens, pos)
+        n = len(a[0])
+        lg = np.empty((n, self.V), np.float32) if want_logits else None
+        am = np.empty(n, np.int32) if want_argmax else None
+        _ck(lib().llmk_batch_forward(self._h, n, *p, lg.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None,
+                                     am.ctypes.data_as(C.POINTER(C.c_int)) if want_argmax else None))
+        out = [x for x in (lg, am) if x is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def decode(self, slots, tokens, pos0, steps: int, samplers=None) -> np.ndarray:
+        """`steps` passes, the picks fed back on the device (llmk_batch_decode): ids [n][steps].  samplers: None = greedy, else one
+        Sampler (llmk.sampler(...)) per row"""
+        a, p = self._rows(slots, tokens, pos0)
+        n = len(a[0])
+        sp = None
+        if samplers is not None:
+            if len(samplers) != n:
+                raise ValueError("one sampler per row")
+            sp = (Sampler * max(1, n))(*samplers)
+        ids = np.zeros((n, max(steps, 0)), np.int32)
+        _ck(lib().llmk_batch_decode(self._h, n, *p, steps, sp, ids.ctypes.data_as(C.POINTER(C.c_int))))
+        return ids
+
+    def time(self, n: int, pos: int, iters: int) -> float:
+        """average ms of one full pass of n rows at position pos (llmk_batch_time); overwrites slot state"""
+        ms = C.c_float(0)
+        _ck(lib().llmk_batch_time(self._h, n, pos, iters, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self._h:
+            lib().llmk_batch_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

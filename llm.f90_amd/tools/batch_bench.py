@@ -1,0 +1,128 @@
+"""Batched decode against the single-stream decode of the same context, in one process.
+
+    python -m llm_f90_amd.tools.batch_bench --shape tinyllama --type f32
+    python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k
+
+For n = 1, 2, 4, ... 128 rows and positions 25 and 1024: llmk_batch_time's milliseconds per full pass (every layer, the classifier and a
+greedy pick for every row) and the aggregate tokens per second n / pass; then llmk_decode_greedy's tokens per second on the same
+context (one sequence on the persistent kernel, or whatever path the shape gets).  Every figure is the median of --repeats
+measurements behind a warm-up, with the spread (max - min) / median beside it.  Weights are bench.py's synthetic ones (same seed).
+Prints a table on stdout and, with --json, one JSON line."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+import llm_f90_amd  # noqa: E402,F401
+from llm_f90_amd import llmk  # noqa: E402
+from llm_f90_amd.tools import gguf  # noqa: E402
+
+ROWS = (1, 2, 4, 8, 16, 32, 64, 128)
+POSITIONS = (25, 1024)
+
+
+def med_spread(xs):
+    m = statistics.median(xs)
+    return m, (max(xs) - min(xs)) / m if m else 0.0
+
+
+def build(shape_name: str, type_name: str, cls_q6k: bool):
+    """the context bench.py builds for --shape / --type / --cls-q6k"""
+    import bench
+    shape = gguf.SHAPES[shape_name]
+    wtype = {"f32": 0, "f16": 1, "q4_0": 2}[type_name]
+    big = shape.matmul_params() > 3e9
+    if big and wtype == 0:
+        raise SystemExit("the 7B/70B shapes are benchmarked as q4_0 or f16")
+    if cls_q6k and (wtype == 0 or shape.emb_dim % 256):
+        raise SystemExit("--cls-q6k: a q6_K classifier beside f16 / q4_0 matrices, emb_dim a multiple of 256")
+    fw = None if big else gguf.synth_fused(shape, bench.SEED, wtype)
+    if cls_q6k and fw is not None:
+        fw = gguf.with_q6k_classifier(fw)
+    if big:
+        return bench.build_streamed(shape, wtype, fw, 0, 0, 0, 1, None, cls_q6k=cls_q6k), shape
+    return llmk.Llmk(fw), shape
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shape", default="tinyllama", choices=sorted(gguf.SHAPES))
+    ap.add_argument("--type", default="f32", choices=["f32", "f16", "q4_0"])
+    ap.add_argument("--cls-q6k", action="store_true")
+    ap.add_argument("--iters", type=int, default=20, help="passes per measurement")
+    ap.add_argument("--repeats", type=int, default=5, help="measurements per figure (the median is reported)")
+    ap.add_argument("--decode-steps", type=int, default=248, help="positions of one llmk_decode_greedy measurement (behind 8 warm-up positions)")
+    ap.add_argument("--single-only", action="store_true",
+                    help="only the llmk_decode_greedy figures: the baseline of another build of the library selected with LLMK_LIB")
+    ap.add_argument("--json", action="store_true")
+    a = ap.parse_args()
+
+    m, shape = build(a.shape, a.type, a.cls_q6k)
+    positions = [p for p in POSITIONS if p <= shape.seq_len]
+    out = {"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "path": m.path_name(), "batch": [], "decode_greedy": {}}
+
+    # single stream first: llmk_decode_greedy, the library's fastest decode, at the positions the batch rows sit at
+    for pos in positions:
+        steps = min(a.decode_steps, shape.seq_len - pos + 1)
+        rates = []
+        for r in range(a.repeats + 1):
+            m.reset()
+            m.decode_greedy(2, max(1, pos - 8), 8)              # warm-up (the first call also captures the graphs)
+            t0 = time.perf_counter()
+            m.decode_greedy(2, pos, steps)
+            dt = time.perf_counter() - t0
+            if r:
+                rates.append(steps / dt)
+        med, spread = med_spread(rates)
+        out["decode_greedy"][str(pos)] = {"tok_s": med, "spread": spread, "steps": steps}
+
+    if a.single_only:
+        positions_b = []
+    else:
+        positions_b = positions
+    # one batch per position, its caches no longer than the position needs (128 slots x 1,024 positions of a 7B model are 137 GB of
+    # f32 K/V rows); where even that does not fit beside the weights, the row counts that do
+    for pos in positions_b:
+        slots, b = max(ROWS), None
+        while b is None:
+            try:
+                b = llmk.Batch(m, slots, pos)
+            except llmk.LlmkError as e:
+                if slots == 1:
+                    raise
+                print(f"# pos {pos}: no room for {slots} slots ({e}); trying {slots // 2}", file=sys.stderr)
+                slots //= 2
+        for n in ROWS:
+            if n > slots:
+                continue
+            b.time(n, pos, 3)                                   # warm-up at this row count (its GEMM instantiation, its plan)
+            ms = [b.time(n, pos, a.iters) for _ in range(a.repeats)]
+            med, spread = med_spread(ms)
+            out["batch"].append({"n": n, "pos": pos, "ms_per_pass": med, "spread": spread, "tok_s": n / med * 1e3})
+        b.close()
+    m.close()
+
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# batched decode, {a.shape} {out['type']}: llmk_batch_time, median of {a.repeats} x {a.iters} passes (spread = (max - min) / median)")
+    print(f"# single stream on the same context ({out['path']}): llmk_decode_greedy, median of {a.repeats} runs")
+    for pos in positions:
+        d = out["decode_greedy"][str(pos)]
+        print(f"pos {pos:5d}   decode_greedy {d['tok_s']:10.1f} tok/s  (spread {d['spread']:.3f}, {d['steps']} positions, {1e3 / d['tok_s']:.3f} ms/token)")
+        if not a.single_only:
+            print(f"{'n':>5} {'ms/pass':>10} {'spread':>8} {'tok/s':>12} {'x single':>9}")
+        for row in out["batch"]:
+            if row["pos"] == pos:
+                print(f"{row['n']:5d} {row['ms_per_pass']:10.3f} {row['spread']:8.3f} {row['tok_s']:12.1f} {row['tok_s'] / d['tok_s']:9.2f}")
+    if a.json:
+        print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

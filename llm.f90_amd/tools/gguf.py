@@ -85,6 +85,10 @@ SHAPES: Dict[str, LlamaShape] = {
     # (persistent kernel and attn_kernel<64>: 256 timesteps per tile; attn_kernel<128>: 128)
     "tk-small-long": LlamaShape(256, 768, 2, 4, 2, 1024, 704),
     "tiny-hs128-long": LlamaShape(512, 1376, 2, 4, 4, 640, 320),
+    # the same with hidden_dim on the batched GEMMs' 64-column step (1376 = 21.5 x 64 is not): head size 128 with one query head per
+    # kv head on the passes that have no token-by-token form (llmk_batch_*)
+    "tiny-hs128w": LlamaShape(512, 1408, 2, 4, 4, 640, 40),
+    "tiny-hs128w-long": LlamaShape(512, 1408, 2, 4, 4, 640, 320),
 }
 
 
