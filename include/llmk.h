@@ -203,9 +203,14 @@ int llmk_prefill(llmk_ctx* ctx, const int* tokens, int n, int pos0, float* logit
  * Each of the three outputs may be NULL (what is not asked for is not copied); all three NULL is LLMK_E_ARG.  A position none of
  * whose logits is finite: LLMK_E_NONFINITE (on any error the contents of the outputs are unspecified).  All arithmetic is f32 in a fixed reduction order (llm.f90_amd/csrc/score.h): two
  * calls with the same input on the same context return bit-identical outputs, whichever outputs are asked for.  Contexts that
- * take llmk_prefill's batched path run the classifier as a GEMM over each batch of 128 positions (a q6_K classifier: the decode
- * classifier per position); the others -- and a vocab_size that is not a multiple of 4 (said once on stderr) -- go token by token inside.  The logits are within the parity bar of llmk_forward's, not
- * bit-identical to them. */
+ * take llmk_prefill's batched path run the classifier as a GEMM over each batch of 128 positions.
+ *   An f32, f16 or q4_0 classifier whose vocab_size is not a multiple of 4: the whole call goes token by token inside (said once on stderr).
+ *   A q6_K classifier never goes token by token.  It takes the GEMM too, except in three cases, in which the decode classifier runs once
+ *   per row of the batch instead: on the f32 matrix instruction (LLMK_PF_F32_MFMA=1, or after an f16-range flag); with a vocab_size that
+ *   is not a multiple of 4; in a batch of fewer rows than the crossover.  llmk_cls_form tells which form a batch takes.
+ *   The f16-range flag covers the q6_K weights as well: a weight of magnitude >= 65504 or a non-finite super-block scale d raises it, the
+ *   call is redone on the f32 instruction, and the note on stderr is the one for activations ("an activation beyond the f16 range").
+ * The logits are within the parity bar of llmk_forward's, not bit-identical to them. */
 int llmk_score(llmk_ctx *ctx, const int *tokens, int n, int pos0, const int *targets, float *logprob_out, int *argmax_out,
                float *logits_out);
 
@@ -374,8 +379,10 @@ int llmk_logprob_logits(llmk_ctx *ctx, const float *logits, int token, int top_n
  * runs on its weights (nothing is uploaded twice); it owns K/V caches [n_layers][n_slots][seq_len][kv_dim] (f32, zeroed) for n_slots
  * sequences ("slots", numbered from 0).  The context's own sequence and every other entry point are untouched.  A pass runs on the
  * context's stream through the context's prefill workspaces: calls on a batch and calls on its context must be serialised by the
- * caller, as all calls on a context already are.  The layers' weights and an f32 / f16 / q4_0 classifier cross HBM once per pass; a
- * q6_K classifier (a stock llama.cpp q4_0 file's output.weight) has no batched form and is read once per ROW of the pass.
+ * caller, as all calls on a context already are.  The layers' weights and the classifier cross HBM once per pass.  A q6_K classifier
+ * (a stock llama.cpp q4_0 file's output.weight) is read once per ROW of the pass in three cases only: on the f32 matrix instruction
+ * (LLMK_PF_F32_MFMA=1, or after an f16-range flag), with a vocab_size that is not a multiple of 4, and in a pass of fewer rows than the
+ * crossover where the per-row form is the faster one (llmk_cls_form tells which form a pass takes).
  *
  * create:  n_slots in [1, LLMK_MAX_BATCH], seq_len in [1, the context's seq_len], else LLMK_E_ARG.  LLMK_E_SHAPE for a context the
  *          batched pass does not serve -- tensor-parallel, emb_dim or hidden_dim not a multiple of 64, kv_dim not a multiple of 16,
@@ -425,12 +432,23 @@ int llmk_timings(llmk_ctx *ctx, float ms[5]);
  * (LLMK_E_ARG when the ctx runs the multi-kernel path), 7..10 the w1|w3, wqkv, wo, w2 GEMMs of llmk_prefill at 128 positions
  * (bytes = that matrix of one layer; flop = 2 * 128 * rows * K), 11 the five per-layer kernels of the multi-kernel path (a
  * tensor-parallel rank's too, without its exchanges) for all layers as one hipGraph: milliseconds and bytes per LAYER,
- * 12 the classifier GEMM of llmk_score at 128 positions (all its row chunks, without the scoring epilogue; bytes = wcls;
- * LLMK_E_ARG for a q6_K classifier, which has no GEMM).
+ * 12 the classifier GEMM of llmk_score at 128 positions (all its row chunks, without the scoring epilogue; bytes = wcls -- q6_K rows as they lie
+ * on the device: 210 bytes per 256 weights, rounded up to 16 per row; LLMK_E_ARG where the context has no classifier GEMM:
+ * llmk_cls_form(ctx, 128) != LLMK_CLS_GEMM).
  * STATE: a measurement hook, not part of the generation path.  Kernels 0..6 and 11 run real kernels of the pass at the ctx's
  * current position (position 1 if none was run yet): they overwrite x, that position's K/V rows and the exchange state, kernel 11
  * for every layer; kernels 7..10 and 12 overwrite the prefill workspaces.  Call llmk_reset before generating on the ctx again. */
 int llmk_time_kernel(llmk_ctx *ctx, int kernel, int iters, float *avg_ms, double *bytes_per_launch);
+
+/* Which form the classifier of a batched pass (llmk_score's batches, llmk_batch_*) of `rows` rows (1..LLMK_MAX_BATCH, else
+ * LLMK_E_ARG) takes on this context RIGHT NOW; like llmk_path the answer can change (an f16-range flag moves the context to the f32
+ * matrix instruction, where q6_K rows have no GEMM), and like llmk_time_kernel the call may set up the prefill workspaces.  The answer
+ * describes the batched pass itself: LLMK_PREFILL=0, which makes llmk_score go token by token and leaves llmk_batch_* as it is, does not
+ * change it. */
+#define LLMK_CLS_NONE 0   /* this context has no batched pass with `rows` rows (llmk_score goes token by token, llmk_batch_create refuses) */
+#define LLMK_CLS_GEMM 1   /* the classifier crosses HBM once per pass (f32 / f16 / q4_0 / q6_K) */
+#define LLMK_CLS_ROWS 2   /* q6_K only: the decode classifier once per row of the pass */
+int llmk_cls_form(llmk_ctx *ctx, int rows);   /* a negative LLMK_E_* code on error (-LLMK_E_ARG for a NULL context), as llmk_path */
 
 /* Debug/verification: copy internal device vectors to the host. which: 0 = x (residual stream, E),
  * 1 = q (E), 2 = xb (attention output, E), 3 = hb (H), 4 = key_cache row [layer][pos-1] (KV),

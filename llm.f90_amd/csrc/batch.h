@@ -1,6 +1,6 @@
 // Batched decode (llmk_batch_*): up to PF_TMAX ROWS -- one position each of DIFFERENT sequences -- go through every
-// layer together, so the weights cross HBM once per pass instead of once per token per sequence (a q6_K classifier excepted: sc_batch
-// runs its decode kernel per row).  The GEMMs, the residual and SwiGLU epilogues and the classifier are the prefill's (prefill.h); what a
+// layer together, so the weights cross HBM once per pass instead of once per token per sequence (q6_K classifier rows too, through the
+// GEMM of prefill.h; sc_batch runs the decode classifier per row only where llmk.hip sc_plan says so).  The GEMMs, the residual and SwiGLU epilogues and the classifier are the prefill's (prefill.h); what a
 // row's POSITION touches is here:
 //   row words      {slot, pos} per row (pos 1-based): which of the batch's K/V caches the row lives in, and where
 //   bd_epi_qkv     pf_epi_qkv_pair's arithmetic with the position and the cache base taken from the row words

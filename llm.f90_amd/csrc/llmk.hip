@@ -961,7 +961,13 @@ PfPlan pf_plan(const llmk_ctx* c, int rows, int K, int T = PF_TMAX, int wt = -1)
     static const double step_f32[2] = {2.45, 4.25}, step_h[2] = {LLMK_PF_H_STEP1, LLMK_PF_H_STEP2}, step_hq[2] = {LLMK_PF_HQ_STEP1, LLMK_PF_HQ_STEP2};
     // (f32 weights: three instructions per chunk, as q4_0; q4_0 at whole batches: the two-group strip runs on eight waves, pf_gemm_launch)
     static const double step_q8[2] = {LLMK_PF_HQ_STEP1, LLMK_PF_HQ_STEP2 * 0.925};
-    const double* step_us = !c->pf_hm ? step_f32 : wt == LLMK_TYPE_F16 ? step_h
+    // q6_K rows (the classifier of a stock q4_0 file, f16 instruction only): the same three instructions per chunk as q4_0 and ~1.3x its
+    // integer work per weight (two planes to merge); four waves at every batch length; see pf_gemm_h_kernel.  The factor 1.3 is an ESTIMATE
+    // from the instruction counts, not a pf_trace measurement: 2.5 us per step of two row groups, where kernel 12 on Llama-2-7B gives
+    // 140.9 us / 64 units = 2.2 us with ring fill and flush included (profiles/q6k_gemm.txt section 4); one row group was not timed alone
+    static const double step_q6[2] = {LLMK_PF_HQ_STEP1 * 1.3, LLMK_PF_HQ_STEP2 * 1.3};
+    const bool q6 = wt == LLMK_TYPE_Q6_K;
+    const double* step_us = !c->pf_hm ? step_f32 : wt == LLMK_TYPE_F16 ? step_h : q6 ? step_q6
                             : (wt == LLMK_TYPE_Q4_0 && (T + 15) / 16 == 8) ? step_q8 : step_hq;
     PfPlan best{};
     double best_t = 1e30;
@@ -977,6 +983,7 @@ PfPlan pf_plan(const llmk_ctx* c, int rows, int K, int T = PF_TMAX, int wt = -1)
         p.nk = K / PF_KSTEP;
         p.total = (rows + sr - 1) / sr * p.nk;
         p.U = (p.total + c->n_cu - 1) / c->n_cu;
+        if (q6) p.U = (p.U + 1) & ~1;       // a q6_K ring stage is a pair of steps: every block starts on an even step (total is a multiple of 4)
         p.grid = (p.total + p.U - 1) / p.U;
         // before the first step and after the last: the f16-instruction kernel's ring takes 2.8 / 4.6 us to fill and its last
         // step (the flush) runs 0.5 / 1.4 us over, one / two row groups (block timelines, round 3); the f32 kernel: ~4 us
@@ -1094,11 +1101,16 @@ hipError_t pf_prepare_type(int wt) {
     switch (wt) {
         case LLMK_TYPE_Q4_0: HIPRET(pf_gemm_prepare<WT_Q4_0>()); return pf_gemm_h_prepare<WT_Q4_0>();
         case LLMK_TYPE_F16: HIPRET(pf_gemm_prepare<WT_F16>()); return pf_gemm_h_prepare<WT_F16>();
+        case LLMK_TYPE_Q6_K: return pf_gemm_h_prepare<WT_Q6_K>();      // (classifier rows; no form on the f32 instruction: sc_plan)
         default: HIPRET(pf_gemm_prepare<WT_F32>()); return pf_gemm_h_prepare<WT_F32>();
     }
 }
 hipError_t pf_prepare(const llmk_ctx* c) {
     HIPRET(pf_prepare_type(c->cfg.weight_type));
+    // the classifier's own GEMM kernels (llmk_score, llmk_batch_*, llmk_time_kernel 12), where its type differs; llmk_set_tensor_type
+    // tears the workspaces down when that type changes, so the next setup comes through here again
+    const int ct = c->t[LLMK_WCLS].type;
+    if (ct != c->cfg.weight_type) HIPRET(pf_prepare_type(ct));
     return with_head_size(c->hs, [](auto hs) {
         constexpr int HS = decltype(hs)::value;
         return hipFuncSetAttribute((const void*)pf_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pf_attn_smem(HS));
@@ -1120,10 +1132,12 @@ hipError_t pf_gemm_launch(llmk_ctx* c, const PfLane& w, const PfGemmArgs& a, con
             }
         }
         if (wt == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q4_0>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
+        else if (wt == LLMK_TYPE_Q6_K) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q6_K>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
         else if (wt == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F16>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
         else hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F32>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
         return hipGetLastError();
     }
+    if (wt == LLMK_TYPE_Q6_K) return hipErrorInvalidValue;      // (sc_plan keeps q6_K rows off the f32 instruction)
     if (wt == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_Q4_0, NR>), grid, block, smem, w.stream, a);
     else if (wt == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_F16, NR>), grid, block, smem, w.stream, a);
     else hipLaunchKernelGGL((pf_gemm_kernel<NG, WT_F32, NR>), grid, block, smem, w.stream, a);
@@ -1154,18 +1168,26 @@ struct ScPlan { int R, nchunks, nparts; };
 struct ScoreJob {
     bool want_lp, want_logits;
     int n;                   // positions of the call
-    ScPlan sp;               // the classifier's row chunks: sc_plan, once per call (it depends on the context and its matrix instruction only)
+    ScPlan sp;               // the classifier's row chunks: sc_plan, once per call (it depends on the context and its matrix instruction; q6_K rows: and on the batch's rows, sc_batch)
     float* out = nullptr;    // where the log-probs and ids go instead of sc_out, and the logits instead of sc_logits (a batch's own: llmk_batch_*)
     float* logits = nullptr;
 };
 // The classifier GEMM runs in chunks of R rows (a multiple of 128, or all V rows) whose partial tiles fit the workspace the layers'
 // GEMMs already have: V is 2.8x the largest row count that one is sized for (2H; Llama-3: 9x), and a context that scores allocates
 // no partial-tile workspace beyond what a prefill needs.  R = 0: no chunk fits (or V is not whole 4-row vectors): the call
-// goes token by token.
-ScPlan sc_plan(const llmk_ctx* c) {
+// goes token by token -- or, with a q6_K classifier, the pass runs the decode classifier once per row (sc_batch), which is also what
+// a q6_K classifier does on the f32 matrix instruction (no GEMM there) and in a pass of fewer than SC_Q6K_GEMM_MIN_ROWS rows.
+// SC_Q6K_GEMM_MIN_ROWS: the row count from which a pass over q6_K classifier rows takes the GEMM.  One memory-bound launch per row
+// against a GEMM whose weight arithmetic does not shrink with the rows: profiles/q6k_gemm.txt has the table behind the number.
+#ifndef LLMK_Q6K_GEMM_MIN_ROWS
+#define LLMK_Q6K_GEMM_MIN_ROWS 3
+#endif
+constexpr int SC_Q6K_GEMM_MIN_ROWS = LLMK_Q6K_GEMM_MIN_ROWS;
+// rows: the rows of the pass (a q6_K classifier's answer depends on them; the chunks do not)
+ScPlan sc_plan(const llmk_ctx* c, int rows = PF_TMAX) {
     const int V = c->V, wt = c->t[LLMK_WCLS].type;
     ScPlan sp{0, 0, (V + PF_SC_ROWS - 1) / PF_SC_ROWS};
-    if (wt == LLMK_TYPE_Q6_K) return sp;         // (no GEMM: the decode classifier per position, one chunk of partials)
+    if (wt == LLMK_TYPE_Q6_K && (!c->pf_hm || rows < SC_Q6K_GEMM_MIN_ROWS)) return sp;      // (one chunk of partials)
     if (V % 4) return sp;
     auto need = [&](int rows) {
         size_t m = 0;
@@ -1229,14 +1251,15 @@ hipError_t sc_merge(llmk_ctx* c, int lane, hipStream_t st, const ScoreJob& sj, i
 hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const ScoreJob& sj, int T, int i0) {
     const DevTensor& ct = c->t[LLMK_WCLS];
     const int V = c->V, E = c->E;
-    const ScPlan& sp = sj.sp;
+    // (a q6_K classifier: the call's plan is that of a whole batch; a batch below the crossover -- the last one of a call -- has its own)
+    const ScPlan sp = ct.type == LLMK_TYPE_Q6_K && sj.sp.R > 0 && T < SC_Q6K_GEMM_MIN_ROWS ? sc_plan(c, T) : sj.sp;
     float* const logits = sj.logits ? sj.logits : c->sc_logits;
     PfScoreArgs s;
     memset(&s, 0, sizeof(s));
     s.zp = (size_t)V; s.V = V; s.nparts = sp.nparts; s.part = c->sc_part[lane];
     s.targets = sj.want_lp ? c->sc_targets + i0 : nullptr; s.tgt = c->sc_tgt[lane];
-    if (ct.type == LLMK_TYPE_Q6_K) {
-        // no batched q6_K GEMM: the decode classifier (final rmsnorm inside, q6k.h) on each of the batch's rows
+    if (ct.type == LLMK_TYPE_Q6_K && sp.R == 0) {
+        // q6_K rows without the GEMM (sc_plan): the decode classifier (final rmsnorm inside, q6k.h) on each of the batch's rows
         float* Z = sj.want_logits ? logits + (size_t)i0 * V : c->sc_z[lane];
         const size_t smem = 16 + (size_t)E * sizeof(float);
         const int blocks = (V + GEMV_WAVES * Q6K_RPW - 1) / (GEMV_WAVES * Q6K_RPW);
@@ -1252,6 +1275,12 @@ hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const 
     }
     for (int k = 0; k < sp.nchunks; ++k) {
         const int r0 = k * sp.R, rows = std::min(sp.R, V - r0);
+#ifdef LLMK_PF_TRACE
+        if (getenv("LLMK_PF_SHOW_PLAN")) {          // debug build: the plan each classifier chunk is launched with (tests/test_q6k_gemm_gpu.py quotes it)
+            const PfPlan p = pf_plan(c, rows, E, T, ct.type);
+            fprintf(stderr, "llmk: classifier chunk %d of %d: T %d rows %d nr %d U %d nk %d grid %d\n", k + 1, sp.nchunks, T, rows, p.nr, p.U, p.nk, p.grid);
+        }
+#endif
         HIPRET(pf_gemm(c, w, (const char*)ct.data + (size_t)r0 * ct.row_bytes, (int)ct.row_bytes, w.Xs, rows, E, T, &e, ct.type));
         e.rows = rows; e.out = nullptr;
         s.r0 = r0; s.part0 = k * ((sp.R + PF_SC_ROWS - 1) / PF_SC_ROWS);
@@ -1414,7 +1443,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 403; }
+int llmk_version(void) { return 404; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -1864,6 +1893,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (t.data) HIPCHK(hipFree(t.data));
+    if (c->pf_ready) pf_teardown(c);      // (the next setup prepares the new type's GEMM kernels: pf_prepare)
     t.data = nullptr;
     t.type = ggml_type;
     t.uploaded = false;
@@ -1968,11 +1998,8 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
     if (batched) {
         rc = pf_setup(c, true);
         if (rc) return rc;
-        const int ct = c->t[LLMK_WCLS].type;
-        if (ct != LLMK_TYPE_Q6_K) {
-            if (ct != c->cfg.weight_type) HIPCHK(pf_prepare_type(ct));      // the classifier's own GEMM kernels: dynamic-LDS limits
-        }
-        sj.sp = sc_plan(c);
+        const int ct = c->t[LLMK_WCLS].type;      // (the classifier's own GEMM kernels were prepared with the workspaces: pf_prepare)
+        sj.sp = sc_plan(c, std::min(n, (int)PF_TMAX));      // (R = 0 with a q6_K classifier: the decode classifier per row, not token by token)
         if (ct != LLMK_TYPE_Q6_K && sj.sp.R == 0) {
             batched = false;
             static bool told_slow = false;          // (a call some 30x slower than its neighbours must not be silent)
@@ -2455,7 +2482,7 @@ static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, c
 }
 
 // the context's side of a pass: workspaces, the classifier's kernels and its row chunks (they follow the matrix instruction in use)
-static int bd_ready(llmk_batch* b, ScPlan* sp) {
+static int bd_ready(llmk_batch* b, ScPlan* sp, int rows) {
     llmk_ctx* c = b->ctx;
     int rc = check_ready(c);
     if (rc) return rc;
@@ -2463,8 +2490,7 @@ static int bd_ready(llmk_batch* b, ScPlan* sp) {
     if ((rc = sc_setup(c)) != LLMK_OK) return rc;
     if ((rc = pf_setup(c, true)) != LLMK_OK) return rc;
     const int ct = c->t[LLMK_WCLS].type;
-    if (ct != LLMK_TYPE_Q6_K && ct != c->cfg.weight_type) HIPCHK(pf_prepare_type(ct));
-    *sp = sc_plan(c);
+    *sp = sc_plan(c, rows);
     if (ct != LLMK_TYPE_Q6_K && sp->R == 0) return LLMK_E_SHAPE;      // no chunk of the classifier fits the workspace: there is no token-by-token form
     return LLMK_OK;
 }
@@ -2506,7 +2532,7 @@ int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) {
     llmk_batch* b = new llmk_batch;
     b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len;
     ScPlan sp;
-    if ((rc = bd_ready(b, &sp)) != LLMK_OK) { delete b; return rc; }
+    if ((rc = bd_ready(b, &sp, n_slots)) != LLMK_OK) { delete b; return rc; }
     const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV * sizeof(float), nb = LLMK_MAX_BATCH;
     auto alloc = [&]() -> int {
         HIPCHK(dev_alloc(&b->d_kc, cache));
@@ -2574,7 +2600,7 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
     if (!b || (!logits_out && !argmax_out) || !bd_rows_ok(b, n, slots, tokens, pos, 1)) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
     ScPlan sp;
-    int rc = bd_ready(b, &sp);
+    int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos));
     HIPCHK(bd_pass(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp));
@@ -2607,7 +2633,7 @@ int llmk_batch_decode(llmk_batch* b, int n, const int* slots, const int* tokens,
         }
     }
     ScPlan sp;
-    int rc = bd_ready(b, &sp);
+    int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     const size_t nids = (size_t)n * steps;
     if (b->ids_cap < nids) {
@@ -2648,7 +2674,7 @@ int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     if (!b || !avg_ms || n < 1 || n > b->n_slots || pos < 1 || pos > b->seq_len || iters < 1) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
     ScPlan sp;
-    int rc = bd_ready(b, &sp);
+    int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     int slots[LLMK_MAX_BATCH], tokens[LLMK_MAX_BATCH], posv[LLMK_MAX_BATCH];
     for (int i = 0; i < n; ++i) { slots[i] = i; tokens[i] = 1; posv[i] = pos; }
@@ -2749,10 +2775,8 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
         if (c->tp_size != 1 || c->E % pf_step || c->H % pf_step) return LLMK_E_ARG;
         rc = pf_setup(c, true);
         if (rc) return rc;
-        if (kernel == 12) {   // llmk_score's classifier GEMM: all its row chunks, without the scoring epilogue (a q6_K classifier has no GEMM)
-            const int ct = c->t[LLMK_WCLS].type;
-            if (ct == LLMK_TYPE_Q6_K) return LLMK_E_ARG;
-            if (ct != c->cfg.weight_type) HIPCHK(pf_prepare_type(ct));
+        if (kernel == 12) {   // llmk_score's classifier GEMM: all its row chunks, without the scoring epilogue (R = 0: this context has no GEMM -- V % 4,
+                              // the workspace, or q6_K rows on the f32 instruction)
             sp = sc_plan(c);
             if (sp.R == 0) return LLMK_E_ARG;
         }
@@ -2826,11 +2850,28 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
             b = 2.0 * c->KV * 4.0 * c->h_tokpos[1];  // K and V rows 1..pos of one layer
         } else {
             const TensorDesc& d = c->desc[tids[kernel]];
-            b = (double)d.rows * (double)row_bytes_for(c->t[tids[kernel]].type, d.K);
+            const int type = c->t[tids[kernel]].type;      // (the q6_K GEMM reads the device rows, padding included)
+            b = (double)d.rows * (double)(kernel == 12 && type == LLMK_TYPE_Q6_K ? dev_row_bytes(type, d.K) : row_bytes_for(type, d.K));
         }
         *bytes_per_launch = b;
     }
     return LLMK_OK;
+}
+
+// (errors are NEGATIVE, as llmk_path's: the forms are small non-negative numbers).  The answer is that of the batched pass itself --
+// pf_shape_ok, not pf_eligible: LLMK_PREFILL=0 sends llmk_score token by token and leaves llmk_batch_* batched (include/llmk.h says so)
+int llmk_cls_form(llmk_ctx* c, int rows) {
+    if (!c || rows < 1 || rows > LLMK_MAX_BATCH) return -LLMK_E_ARG;
+    int rc = check_ready(c);
+    if (rc) return -rc;
+    if (!pf_shape_ok(c)) return LLMK_CLS_NONE;
+    auto setup = [&]() -> int {
+        HIPCHK(hipSetDevice(c->cfg.device));
+        return pf_setup(c, true);
+    };
+    if ((rc = setup()) != LLMK_OK) return -rc;
+    if (sc_plan(c, rows).R > 0) return LLMK_CLS_GEMM;
+    return c->t[LLMK_WCLS].type == LLMK_TYPE_Q6_K ? LLMK_CLS_ROWS : LLMK_CLS_NONE;
 }
 
 int llmk_peek(llmk_ctx* c, int which, int layer, int pos, float* out, int n) {

@@ -336,17 +336,39 @@ __device__ __forceinline__ void pf_ring(F& step, int s, int nsteps) {      // (N
         }
     }
 }
+// q6_K rows: a ring stage is a PAIR of steps (see pf_gemm_h_kernel); steps s+Q and s+Q+1 (Q even) multiply stage (Q / 2) % R, and
+// the even one refills the other stage with the next pair
+template <int Q, int N, int R, class F>
+__device__ __forceinline__ void pf_ring_pairs(F& step, int s, int nsteps) {
+    if constexpr (Q < N) {
+        if (s + Q < nsteps) {
+            step(s + Q, std::integral_constant<int, (Q / 2) % R>(), std::integral_constant<int, (Q / 2 + 1) % R>(), std::integral_constant<int, Q & 1>());
+            pf_ring_pairs<Q + 1, N, R>(step, s, nsteps);
+        }
+    }
+}
 // q4_0 weights (WT_Q4_0) on the same instruction: a 32-column chunk is one block; lane (row li, k group kg) takes the low
 // (kg < 2) or high nibbles of bytes 8 (kg & 1) .. + 7 of the block = its elements 16 (kg >> 1) + 8 (kg & 1) .. + 7 = the 8
 // consecutive columns of slot kg (the activation side is the f16 kernel's), turns them into the reference's f32 weights
 // (n - 8) d exactly (n - 8 as f16: byte n under 0x64 is the half 1024 + n, minus 1032; times the row's f16 block scale through
 // v_fma_mix_f32) and feeds each as two f16 pieces: see the step.
+// q6_K rows (WT_Q6_K; the classifier of a stock q4_0 file, as q6k_repack_kernel leaves them: planes A | B | C | scales | d, q6k.h).  Column
+// 256 sb + 128 n + 32 k + l of a row: the 64-column step s lies in super-block sb = s / 4, half n = (s / 2) & 1, and its chunk j is group
+// k = 2 (s & 1) + j.  Slot kg of a chunk is l = 8 kg .. + 7 = bytes 8 (kg & 1) .. + 7 of quad 4 sb + 2 n + (kg >> 1) = bytes 32 (s / 2) + 8 kg .. of
+// plane A (j = 0) or B (j = 1): low nibbles in an even step, high nibbles in an odd one; the same bytes of plane C carry the two high bits
+// of all four groups (bit pair 2 k), and the group's scale is byte 8 (s / 2) + (kg >> 1) + 2 k of the scale plane.  The steps 2 m and 2 m + 1
+// read the SAME bytes, so a ring stage holds a PAIR of steps (24 weight bytes, the 8 scale bytes of the half and d, per lane and row
+// group) and is requested once: every byte of the row crosses the memory path once per pass.  The host gives every block an even
+// number of units (llmk.hip pf_plan), and nk is a multiple of 4: a pair never straddles two blocks or two strips.
+// The weight d * scale * (q - 32) is formed as an f32 (q - 32 as f16: byte q under 0x64 is the half 1024 + q, minus 1056; times the f32
+// d * scale through v_fma_mix_f32: exact, 6 x 18 significand bits) and split into two f16 pieces as an f32 weight is.
 // NWV = waves per workgroup: 4 (one per SIMD), or 8 with NR = 1 -- the strip of the 4-wave NR = 2 form (same units, same partial tiles)
 // on two waves per SIMD; used for q4_0 weights (llmk.hip pf_gemm_launch)
 template <int NG, int NR, int WT = WT_F16, int NWV = PF_WAVES>
 __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, unsigned* __restrict__ flag, unsigned* __restrict__ lowcnt) {
     constexpr int NW = NWV, TP = NG * 16, NJ = 2, SR = 16 * NR * NW, NT = NW * WAVE;
-    constexpr bool Q4 = WT == WT_Q4_0, F32W = WT == WT_F32;
+    constexpr bool Q4 = WT == WT_Q4_0, F32W = WT == WT_F32, Q6 = WT == WT_Q6_K;
+    static_assert(!Q6 || NWV == PF_WAVES, "q6_K rows: the four-wave form only");
     // ring depth of the weight stages.  Round 5: SHALLOWER is faster -- six f16 stages left ~100 values parked in accumulation registers and
     // moved in and out inside the step (256 VGPRs + 170 AGPRs for 64 accumulators; three stages: 254 + 92), and what they bought in lead they lost
     // again (f16: six -> three stages +5.6 % prompt rate, f32 four / three -> two +1.8 %, q4_0 on eight waves
@@ -363,7 +385,7 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
 #ifndef LLMK_PF_ST_F16
 #define LLMK_PF_ST_F16 3
 #endif
-    constexpr int ST = Q4 ? (NWV == 8 ? LLMK_PF_ST_Q8 : LLMK_PF_ST_Q4) : F32W ? LLMK_PF_ST_F32 : LLMK_PF_ST_F16;
+    constexpr int ST = Q6 ? 2 : Q4 ? (NWV == 8 ? LLMK_PF_ST_Q8 : LLMK_PF_ST_Q4) : F32W ? LLMK_PF_ST_F32 : LLMK_PF_ST_F16;      // (q6_K: two PAIRS of steps)
     extern __shared__ __attribute__((aligned(16))) char pf_smem[];
     _Float16* xh = reinterpret_cast<_Float16*>(pf_smem);                                  // [2 buffers][hi, lo][TP][PF_HP]
     float* tb = reinterpret_cast<float*>(pf_smem + (size_t)4 * TP * PF_HP * sizeof(_Float16));   // [TP][SR + PF_TPAD]
@@ -371,9 +393,9 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
     const int u0 = blockIdx.x * a.U, nsteps = min(a.U, a.total - u0);
     if (nsteps <= 0) return;
     const int li = lane & 15, kg = lane >> 4;
-    const size_t rowb = Q4 ? (size_t)a.RS : (size_t)a.K * (F32W ? 4 : 2);
-    const char* wbase = static_cast<const char*>(a.W) + (Q4 ? (size_t)(kg & 1) * 8 : (size_t)kg * (F32W ? 32 : 16));
-    constexpr int STEPB = Q4 ? 32 : PF_KSTEP * (F32W ? 4 : 2);           // weight bytes per row per step
+    const size_t rowb = (Q4 || Q6) ? (size_t)a.RS : (size_t)a.K * (F32W ? 4 : 2);
+    const char* wbase = static_cast<const char*>(a.W) + (Q6 ? (size_t)kg * 8 : Q4 ? (size_t)(kg & 1) * 8 : (size_t)kg * (F32W ? 32 : 16));
+    constexpr int STEPB = Q6 ? 16 : Q4 ? 32 : PF_KSTEP * (F32W ? 4 : 2);           // weight bytes per row per step (q6_K: of each plane)
     int cs = u0 / a.nk, ck = u0 % a.nk;
     int ws = cs, wk = ck, wi = 0, xk = ck, xi = 0;
     const char* wp = wbase + (size_t)min(ws * SR + wid * (16 * NR) + li, a.rows - 1) * rowb + (size_t)wk * STEPB;
@@ -394,9 +416,13 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
         for (int g = 0; g < NG; ++g) acc[r][g] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
     // a stage: f16 -- 16 bytes per chunk and row group
     typedef unsigned pf_v2u __attribute__((ext_vector_type(2)));
-    float4 w[Q4 ? 1 : ST][Q4 ? 1 : NR * NJ * (F32W ? 2 : 1)];     // f32: a lane's 8 columns of a chunk are two 16-byte loads
+    float4 w[(Q4 || Q6) ? 1 : ST][(Q4 || Q6) ? 1 : NR * NJ * (F32W ? 2 : 1)];     // f32: a lane's 8 columns of a chunk are two 16-byte loads
     pf_v2u wq[Q4 ? ST : 1][Q4 ? NR * NJ : 1];        // q4_0: the lane's 8 nibble bytes per block and row group
     unsigned wd[Q4 ? ST : 1][Q4 ? NR : 1];          //       the row's two block scales (f16 pair)
+    // q6_K: a PAIR of steps per stage -- the lane's 8 bytes of planes A, B and C, the 8 scales of the (super-block, half), d
+    pf_v2u qa[Q6 ? ST : 1][Q6 ? NR : 1], qb[Q6 ? ST : 1][Q6 ? NR : 1], qc[Q6 ? ST : 1][Q6 ? NR : 1], qs[Q6 ? ST : 1][Q6 ? NR : 1];
+    unsigned qd[Q6 ? ST : 1][Q6 ? NR : 1];
+    bool wbad = false;                               //       a d that is not finite (v_max_f32 drops a NaN)
     // activations of two steps in flight: requested a whole step before they are published, published in the shadow of the
     // matrix instructions
     constexpr bool XR2 = true;
@@ -411,8 +437,22 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
 
     auto wload = [&](auto stage) {
         constexpr int Q = decltype(stage)::value;
+        if constexpr (Q6) {
+            // the pair of steps wk, wk + 1 (wk even): wp = the row + 8 kg + 16 wk; planes 16 nk bytes apart, then 4 nk scale bytes
+            const size_t pl = (size_t)a.nk * 16;
 #pragma unroll
-        for (int q = 0; q < NR * NJ; ++q) {
+            for (int r = 0; r < NR; ++r) {
+                const char* rp = wp + (size_t)r * 16 * rowb;
+                qa[Q][r] = __builtin_nontemporal_load(reinterpret_cast<const pf_v2u*>(rp));
+                qb[Q][r] = __builtin_nontemporal_load(reinterpret_cast<const pf_v2u*>(rp + pl));
+                qc[Q][r] = __builtin_nontemporal_load(reinterpret_cast<const pf_v2u*>(rp + 2 * pl));
+                const char* sp = rp - (size_t)kg * 8 - (size_t)wk * 16 + 3 * pl;
+                qs[Q][r] = *reinterpret_cast<const pf_v2u*>(sp + (size_t)wk * 4);
+                qd[Q][r] = *reinterpret_cast<const unsigned short*>(sp + (size_t)a.nk * 4 + (size_t)(wk >> 2) * 2);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NR * NJ; ++q) {      // (q6_K rows: nothing here, the loads above are the stage)
             if constexpr (Q4) {
                 const char* rp = wp + (size_t)(q / NJ) * 16 * rowb;
                 wq[Q][q] = __builtin_nontemporal_load(reinterpret_cast<const pf_v2u*>(rp + (q % NJ) * 16));
@@ -421,11 +461,12 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
             } else if constexpr (F32W) {
                 w[Q][2 * q] = ldg_nt(reinterpret_cast<const float4*>(wp + (size_t)(q / NJ) * 16 * rowb + (q % NJ) * 128));
                 w[Q][2 * q + 1] = ldg_nt(reinterpret_cast<const float4*>(wp + (size_t)(q / NJ) * 16 * rowb + (q % NJ) * 128 + 16));
-            } else {
+            } else if constexpr (!Q6) {
                 w[Q][q] = ldg_nt(reinterpret_cast<const float4*>(wp + (size_t)(q / NJ) * 16 * rowb + (q % NJ) * 64));
             }
         }
-        const int adv = wi < nsteps - 1 ? 1 : 0;
+        constexpr int SPS = Q6 ? 2 : 1;                  // steps per stage
+        const int adv = wi + SPS < nsteps ? SPS : 0;
         wi += adv;
         wk += adv;
         const bool wrap = wk == a.nk;
@@ -497,7 +538,7 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
         }
         pf_v8h B0[NG], B1[NG];
         bread(B0, buf, 0);
-        if constexpr (Q4 || F32W) {
+        if constexpr (Q4 || F32W || Q6) {
             // f32 weights: w = wh + wl, two f16 pieces (|w - wh - wl| <= 2^-20 |w|, as for the activations; a weight of
             // magnitude >= 65504 raises the same flag), three instructions per chunk: wh.xhi + wl.xhi + wh.xlo.
             // q4_0: the weight (n - 8) d is an exact f32 (4 x 11 significand bits) and splits EXACTLY into two f16 pieces,
@@ -518,6 +559,23 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
                     typedef __fp16 pf_g2 __attribute__((ext_vector_type(2)));
                     union { unsigned u[4]; pf_h2 h[4]; } t;
                     unsigned dp = 0;
+                    float dsc = 0.f;
+                    if constexpr (Q6) {
+                        const int k = 2 * PAR + j;              // the chunk's group of the (super-block, half)
+                        const pf_v2u av = j ? qb[CUR][r] : qa[CUR][r], cv = qc[CUR][r];
+#pragma unroll
+                        for (int d = 0; d < 2; ++d) {
+                            const unsigned a4 = d ? av.y : av.x, c2 = d ? cv.y : cv.x;
+                            const unsigned hb = k == 0 ? c2 << 4 : k == 1 ? c2 << 2 : k == 2 ? c2 : c2 >> 2;
+                            const unsigned q = ((PAR ? a4 >> 4 : a4) & 0x0F0F0F0Fu) | (hb & 0x30303030u);
+                            t.u[2 * d] = __builtin_amdgcn_perm(0x64646464u, q, 0x04010400u);        // halves 0x64qq = 1024 + q of bytes 0, 1
+                            t.u[2 * d + 1] = __builtin_amdgcn_perm(0x64646464u, q, 0x04030402u);    // ... of bytes 2, 3
+                        }
+                        // scale byte (kg >> 1) + 2 k of the half's eight: k < 2 in the low word, int8; d * scale is exact (11 x 7 bits)
+                        const unsigned sw = (PAR ? qs[CUR][r].y : qs[CUR][r].x) >> ((kg >> 1) * 8 + 16 * j);
+                        dsc = (float)(int)(signed char)(sw & 0xffu) * __half2float(__ushort_as_half((unsigned short)qd[CUR][r]));
+                        wbad = wbad || !(fabsf(dsc) <= 3.0e38f);
+                    }
                     if constexpr (Q4) {
                         const unsigned sh = (kg >> 1) * 4;
                         dp = wd[CUR][r];
@@ -536,6 +594,11 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
                             const float4& wv = w[CUR][2 * (r * NJ + j) + d / 2];
                             w0 = (d & 1) ? wv.z : wv.x;
                             w1 = (d & 1) ? wv.w : wv.y;
+                            wmax = fmaxf(fmaxf(wmax, fabsf(w0)), fabsf(w1));
+                        } else if constexpr (Q6) {
+                            t.h[d] = t.h[d] - (pf_h2){(_Float16)1056.0f, (_Float16)1056.0f};       // q - 32
+                            asm("v_fma_mix_f32 %0, %2, %3, 0 op_sel_hi:[1,0,0]\n\t"
+                                "v_fma_mix_f32 %1, %2, %3, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=&v"(w0), "=&v"(w1) : "v"(t.u[d]), "v"(dsc));
                             wmax = fmaxf(fmaxf(wmax, fabsf(w0)), fabsf(w1));
                         } else {
                         t.h[d] = t.h[d] - (pf_h2){(_Float16)1032.0f, (_Float16)1032.0f};       // n - 8
@@ -589,7 +652,7 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
                     for (int g = 0; g < NG; ++g) acc[r][g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[r], Bc[g], acc[r][g], 0, 0, 0);
             }
         }
-        wload(nxt);
+        if constexpr (!Q6 || PAR == 0) wload(nxt);          // (q6_K: the even step of a pair requests the next pair)
         if (++ck == a.nk || S == nsteps - 1) {
             const int slot = (int)blockIdx.x - pf_first_block(cs, a.nk, a.U);
 #pragma unroll
@@ -622,7 +685,11 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
     PF_STAMP(1);
     // two ring cycles per trip: the loop's back edge costs a drain of the weight prefetch (hipcc's waitcnt pass merges the
     // loop's two entries conservatively: s_waitcnt vmcnt(0) in the first step of a trip), and this path's GEMMs have <= 12 units per block
-    for (int s = 0; s < nsteps; s += 2 * ST) pf_ring<0, 2 * ST, ST>(step, s, nsteps);
+    if constexpr (Q6) {
+        for (int s = 0; s < nsteps; s += 2 * ST) pf_ring_pairs<0, 2 * ST, ST>(step, s, nsteps);
+    } else {
+        for (int s = 0; s < nsteps; s += 2 * ST) pf_ring<0, 2 * ST, ST>(step, s, nsteps);
+    }
     // Range checks of the two-piece split (advisor, round 3).  High end: an activation >= 65504 fits neither piece.  LOW end:
     // below 2^-3 the lo piece is an f16 subnormal and the pair's error is 2^-24 ABSOLUTE, not 2^-20 relative -- harmless for
     // the small elements of an O(1) row, but a position whose WHOLE row is small (attention output or SwiGLU output of a model
@@ -647,7 +714,7 @@ __global__ __launch_bounds__(NWV * WAVE) void pf_gemm_h_kernel(PfGemmArgs a, uns
             if (r > 0.f) atomicAdd(lowcnt + PF_TMAX + t, 1u);
         }
     }
-    if (__any(!(amax < 65504.0f)) && lane == 0) atomicOr(flag, 1u);     // (NaN counts)
+    if (__any(!(amax < 65504.0f) || wbad) && lane == 0) atomicOr(flag, 1u);     // (NaN counts)
 #ifdef LLMK_PF_TRACE
     if (tid == 0) { tr[17] = wall_clock64(); tr[19] = __builtin_readcyclecounter(); }
 #endif

@@ -315,6 +315,11 @@ module llmk_binding
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
      end function
+     integer(c_int) function llmk_cls_form(ctx, rows) bind(C, name="llmk_cls_form")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: rows
+     end function
      integer(c_int) function llmk_tk_shapes(buf, n) bind(C, name="llmk_tk_shapes")
        import :: c_int, c_char, c_size_t
        character(kind=c_char), intent(out) :: buf(*)

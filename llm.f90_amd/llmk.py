@@ -29,7 +29,7 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
            "llmk_batch_decode", "llmk_batch_time", "llmk_reset", "llmk_timings",
-           "llmk_time_kernel", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
+           "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
               3: "tensor-parallel rank: eager launches + RCCL collectives", 4: "tensor-parallel rank, collectives not connected"}
@@ -60,6 +60,7 @@ def sampler(temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, m
 
 MAX_LOGIT_BIAS = 256
 MAX_BATCH = 128
+CLS_NONE, CLS_GEMM, CLS_ROWS = 0, 1, 2      # llmk_cls_form: LLMK_CLS_*
 
 
 class LogitBias(C.Structure):
@@ -180,6 +181,8 @@ def lib():
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
+        if hasattr(L, "llmk_cls_form"):           # (as the groups above: absent from an older build selected with LLMK_LIB for an A/B)
+            L.llmk_cls_form.argtypes = [vp, ci]
         L.llmk_peek.argtypes = [vp, ci, ci, ci, cf, ci]
         L.llmk_destroy.argtypes = [vp]
         L.llmk_path.argtypes = [vp]
@@ -538,6 +541,13 @@ class Llmk:
         ms, b = C.c_float(0), C.c_double(0)
         _ck(lib().llmk_time_kernel(self._h, kernel, iters, C.byref(ms), C.byref(b)))
         return ms.value, b.value
+
+    def cls_form(self, rows: int) -> int:
+        """which form the classifier of a batched pass of `rows` rows takes right now: CLS_NONE, CLS_GEMM or CLS_ROWS"""
+        rc = lib().llmk_cls_form(self._h, rows)
+        if rc < 0:
+            _ck(-rc)
+        return rc
 
     def peek(self, which: int, n: int, layer: int = 0, pos: int = 1):
         out = np.empty(n, np.float32)
