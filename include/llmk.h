@@ -402,8 +402,9 @@ int llmk_logprob_logits(llmk_ctx *ctx, const float *logits, int token, int top_n
  *          pos0[i]+s, fed to that row at pos0[i]+s+1 from device memory.  pos0[i]+steps-1 <= seq_len and everything forward checks,
  *          up front.  samplers NULL: greedy.  Else samplers[i] is row i's own llmk_sampler -- temperature, seed, top_k, top_p, min_p,
  *          with the meaning and the checks of llmk_forward_sample_ex -- and the pick is DEFINED as what llmk_sample_logits answers for that
- *          row's logits, that position and that sampler: the same kernel reads the same bits.  Penalties, logit bias and log-prob
- *          records are out of scope for a batch.
+ *          row's logits, that position and that sampler: the same kernel body reads the same bits, in ONE launch per step with a
+ *          workgroup per row of the pass (sample_filter_rows_kernel).  Penalties, logit bias and log-prob
+ *          records are out of scope of this function: llmk_rows_decode, below, takes them.
  * time:    measurement hook: average milliseconds of one full pass (classifier and greedy pick included) of n rows, slots 0..n-1,
  *          all at position pos.  It OVERWRITES those slots' row pos: fork or refill the slots afterwards.
  * The same call on the same state returns bit-identical outputs.  A row's logits are within the 1e-4 parity bar of llmk_forward's on
@@ -417,6 +418,48 @@ int llmk_batch_forward(llmk_batch *b, int n, const int *slots, const int *tokens
 int llmk_batch_decode(llmk_batch *b, int n, const int *slots, const int *tokens, const int *pos0, int steps,
                       const llmk_sampler *samplers, int *ids_out);
 int llmk_batch_time(llmk_batch *b, int n, int pos, int iters, float *avg_ms);
+
+/* The rows functions: what a context's _pen and _lp functions do for one sequence, for the rows of a batch.
+ * ("rows" are the sequences of one pass; the family is not named after the batch only because the list above is closed.)  Each of the
+ * three sampler kernels has a rows form with one workgroup per row of the pass, so a step of a decode is ONE launch of each kernel it
+ * needs, however many rows it has.  Indexing: logits, samplers, penalties, picks and log-prob records are per ROW i of the call;
+ * the token records and the penalty kernel's counts are per SLOT -- a sequence keeps its record whichever row of a call it is.
+ *
+ * State, all allocated by the first call that needs it (a batch that never uses these functions allocates nothing): a token record per
+ * slot, [n_slots][seq_len] ints with the meaning of a context's (hist[q-1] = the 1-based token fed at position q, 0 = none; zero when
+ * allocated); llmk_batch_fork zeroes the record of the slot it fills or empties, if the batch has records: a forked slot is a new
+ * sequence, and the caller records its prompt with llmk_rows_set_history exactly as a context's caller does with llmk_set_history.
+ * set_history / get_history: llmk_set_history / llmk_get_history for `slot` in [0, n_slots), ranges against the BATCH's seq_len.
+ *
+ * decode:  everything llmk_batch_decode checks and does.  samplers NULL: greedy, else [n].  penalties NULL: none, else [n], entry i
+ *          meaning to row i what it means to llmk_decode_sample_pen, with the same checks (last_n at most the batch's seq_len; bias ids
+ *          distinct and in [1, vocab_size]); with samplers NULL it must be NULL.  logprobs NULL: none, else ONE request for the call
+ *          by the rules of llmk_decode_sample_lp (the greedy form with records is allowed): top_n is shared by all rows,
+ *          token_logprob[i*steps + s] belongs to ids_out[i*steps + s], top_tokens and top_logprobs are indexed
+ *          [(i*steps + s)*top_n + j].
+ *          DEFINITION: ids_out[i*steps + s] is what llmk_sample_logits_pen answers on the context for row i's logits of that step,
+ *          position pos0[i]+s, row i's sampler and penalties, with the context's record holding that slot's record; the log-prob
+ *          record is what llmk_logprob_logits answers for the RAW logits and that id.  The same kernel bodies read the same bits.
+ *          If penalties is given and at least one row has something on (a bias, or last_n > 0 with a penalty that is not neutral),
+ *          the record of EVERY row of the call is maintained: the fed token is written at its position at every step, on the
+ *          device.  With nothing on in any row, or penalties NULL, the call is the one without penalties and no record is touched
+ *          (the context's rule).  With penalties and logprobs both NULL the call IS llmk_batch_decode: same code path, same ids.
+ *          The f16-range rule applies: a redone call rewrites the same record entries (records are indexed by position).
+ *          LLMK_E_NONFINITE as in llmk_batch_decode; the arrays are then unspecified.
+ * sample_logits: the verification hook, like llmk_sample_logits_pen for a context: no pass, no K/V; it READS the slots' records
+ *          (positions up to and including pos[i], so pos[i] <= the batch's seq_len) and writes none.  The caller's logits
+ *          [n][vocab_size] overwrite the batch's logits rows.  samplers is required (NULL: LLMK_E_ARG); penalties and logprobs are
+ *          optional.  tokens_out [n] is required; kept_out [n], tau_out [n] and adjusted_out [n][vocab_size] are optional; the
+ *          log-prob arrays are filled as by a decode of one step, for the id the row picked.  A row with no row above -inf gives the
+ *          call LLMK_E_NONFINITE: the outputs are then unspecified and the batch stays usable.
+ * A NULL batch is LLMK_E_ARG before anything touches a device, in all four. */
+int llmk_rows_set_history(llmk_batch *b, int slot, const int *tokens, int n, int pos0);
+int llmk_rows_get_history(llmk_batch *b, int slot, int *tokens_out, int n, int pos0);
+int llmk_rows_decode(llmk_batch *b, int n, const int *slots, const int *tokens, const int *pos0, int steps,
+                     const llmk_sampler *samplers, const llmk_penalties *penalties, const llmk_logprobs *logprobs, int *ids_out);
+int llmk_rows_sample_logits(llmk_batch *b, int n, const int *slots, const int *pos, const float *logits,
+                            const llmk_sampler *samplers, const llmk_penalties *penalties, const llmk_logprobs *logprobs,
+                            int *tokens_out, int *kept_out, float *tau_out, float *adjusted_out);
 
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);

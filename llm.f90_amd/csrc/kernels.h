@@ -900,10 +900,9 @@ __device__ __forceinline__ void sf_walk_bins(const llmk_filter_bins& b, unsigned
     }
     __syncthreads();
 }
-__global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* __restrict__ logits, int n, const int* __restrict__ tokpos,
-                                                                   int pos_imm, const llmk_filter_params* __restrict__ fp,
-                                                                   int* __restrict__ next, float2* __restrict__ cand, int ncand,
-                                                                   unsigned* __restrict__ out2) {
+// (the body: shared by sample_filter_kernel and sample_filter_rows_kernel, below -- one workgroup, one vector of logits)
+__device__ __forceinline__ void sample_filter_body(const float* __restrict__ logits, int n, int pos, const llmk_filter_params* __restrict__ fp,
+                                                   int* __restrict__ next, float2* __restrict__ cand, int ncand, unsigned* __restrict__ out2) {
     __shared__ unsigned long long hs[256 * SF_COPIES];      // the level's sums of Q, SF_COPIES copies per bin
     __shared__ unsigned hc[256 * SF_COPIES];                // ... and counts
     __shared__ llmk_filter_bins bins, bins0;                // the copies summed; level 0 kept for the second descent
@@ -912,7 +911,6 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* 
     __shared__ unsigned wk[16], wc[16];
     __shared__ llmk_filter_walk walk;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int pos = tokpos ? tokpos[1] : pos_imm;
     const float invT = fp->invT, top_p = fp->top_p, min_p = fp->min_p;
     const int top_k = fp->top_k;
     const uint64_t seed = (uint64_t)fp->seed_lo | ((uint64_t)fp->seed_hi << 32);
@@ -1039,6 +1037,21 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* 
         for (int j = tid; j < ncand; j += SF_THREADS)
             cand[j] = (j == 0 && have) ? make_float2(best, __int_as_float(idx)) : make_float2(-INFINITY, __int_as_float(0x7fffffff));
 }
+__global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* __restrict__ logits, int n, const int* __restrict__ tokpos,
+                                                                   int pos_imm, const llmk_filter_params* __restrict__ fp,
+                                                                   int* __restrict__ next, float2* __restrict__ cand, int ncand,
+                                                                   unsigned* __restrict__ out2) {
+    sample_filter_body(logits, n, tokpos ? tokpos[1] : pos_imm, fp, next, cand, ncand, out2);
+}
+// The rows form (a batched pass, batch.h): workgroup i is row i of the pass and does what sample_filter_kernel does for one vector --
+// logits + i * n, position rows[i].pos (rows: the pass's row words {slot, pos}, two ints each), parameters filt + i, outputs
+// next + i and out2 + 2 * i; no candidates.  Same body, same bits.
+__global__ __launch_bounds__(SF_THREADS) void sample_filter_rows_kernel(const float* __restrict__ logits, int n, const int* __restrict__ rows,
+                                                                        const llmk_filter_params* __restrict__ filt, int* __restrict__ next,
+                                                                        unsigned* __restrict__ out2) {
+    const int i = blockIdx.x;
+    sample_filter_body(logits + (size_t)i * n, n, rows[2 * i + 1], filt + i, next + i, nullptr, 0, out2 + 2 * i);
+}
 
 // The penalties and the logit bias of sample_penalty.h by ONE workgroup, in place on the position's logits, in front of
 // sample_filter_kernel.  It touches at most last_n + n_bias rows:
@@ -1053,13 +1066,10 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_kernel(const float* 
 //       depends on the order of anything.
 // pos: tokpos[1], or pos_imm when tokpos is null.
 constexpr int SP_THREADS = 256;
-__global__ __launch_bounds__(SP_THREADS) void sample_penalty_kernel(float* __restrict__ logits, int n, const int* __restrict__ tokpos,
-                                                                    int pos_imm, int tok_imm, const int* __restrict__ next_in,
-                                                                    const llmk_penalty_params* __restrict__ pp, const int* hist,
-                                                                    int* hist_out, int* __restrict__ cnt) {
+// (the body: shared by sample_penalty_kernel and sample_penalty_rows_kernel, below; tok: the fed token as the site found it)
+__device__ __forceinline__ void sample_penalty_body(float* __restrict__ logits, int n, int pos, int tok, const llmk_penalty_params* __restrict__ pp,
+                                                    const int* hist, int* hist_out, int* __restrict__ cnt) {
     const int tid = threadIdx.x;
-    const int pos = tokpos ? tokpos[1] : pos_imm;
-    int tok = tokpos ? tokpos[0] + 1 : next_in ? next_in[0] : tok_imm;
     if (tok < 1 || tok > n) tok = 0;
     if (hist_out) {
         if (tid == 0) hist_out[pos - 1] = tok;
@@ -1091,6 +1101,28 @@ __global__ __launch_bounds__(SP_THREADS) void sample_penalty_kernel(float* __res
         const int c = atomicExch(&cnt[t - 1], 0);
         if (c > 0) logits[t - 1] = llmk_penalty_row(logits[t - 1], c, r, inv_r, f, p);
     }
+}
+__global__ __launch_bounds__(SP_THREADS) void sample_penalty_kernel(float* __restrict__ logits, int n, const int* __restrict__ tokpos,
+                                                                    int pos_imm, int tok_imm, const int* __restrict__ next_in,
+                                                                    const llmk_penalty_params* __restrict__ pp, const int* hist,
+                                                                    int* hist_out, int* __restrict__ cnt) {
+    sample_penalty_body(logits, n, tokpos ? tokpos[1] : pos_imm, tokpos ? tokpos[0] + 1 : next_in ? next_in[0] : tok_imm, pp, hist, hist_out, cnt);
+}
+// The rows form (a batched pass, batch.h): workgroup i is row i of the pass.  Logits, fed token and parameters are the ROW's --
+// logits + i * n (adjusted in place), tok0[i] + 1 (tok0: the pass's 0-based fed ids; null with hist_out null, where no token is
+// recorded), pen + i, position rows[i].pos; the token record and the counts are the SLOT's -- hist + rows[i].slot * seq_len and
+// cnt + rows[i].slot * n, so a sequence keeps its record whichever row of a call it is.  hist_out null: the record is read, not
+// written (the hook).  A row whose words have nothing on records its fed token and adjusts nothing.  A row whose words do not name a
+// slot and a position of the batch does nothing (the host checks every row before a pass).
+__global__ __launch_bounds__(SP_THREADS) void sample_penalty_rows_kernel(float* __restrict__ logits, int n, const int* __restrict__ rows,
+                                                                         const int* __restrict__ tok0, const llmk_penalty_params* __restrict__ pen,
+                                                                         const int* hist, int* hist_out, int* __restrict__ cnt, int n_slots,
+                                                                         int seq_len) {
+    const int i = blockIdx.x, slot = rows[2 * i], pos = rows[2 * i + 1];
+    if ((unsigned)slot >= (unsigned)n_slots || pos < 1 || pos > seq_len) return;
+    const size_t rec = (size_t)slot * seq_len;
+    sample_penalty_body(logits + (size_t)i * n, n, pos, tok0 ? tok0[i] + 1 : 0, pen + i, hist + rec, hist_out ? hist_out + rec : nullptr,
+                        cnt + (size_t)slot * n);
 }
 
 // The fold of the ncand candidates {value, row as int bits} a launch of the pipelined decode leaves, by ONE wave: the largest value,
@@ -1125,9 +1157,10 @@ __device__ __forceinline__ void cand_fold(const float2* __restrict__ cand, int n
 // The id: id_ptr[0] where a kernel left one (argmax_kernel / sample_kernel / sample_filter_kernel: d_next); else the fold of the
 // ncand candidates of a pipelined launch, by the rule of the next launch and cand_resolve_kernel (largest value, lowest row); else
 // id_imm (llmk_logprob_logits).  No id (0 / out of range): token_logprob = 0.  top_n is a device word, so a graph serves every top_n.
-__global__ __launch_bounds__(SF_THREADS) void sample_logprob_kernel(const float* __restrict__ logits, int n, const int* __restrict__ id_ptr,
-                                                                    const float2* __restrict__ cand, int ncand, int id_imm,
-                                                                    const unsigned* __restrict__ top_n_ptr, llmk_logprob_record* __restrict__ out) {
+// (the body: shared by sample_logprob_kernel and sample_logprob_rows_kernel, below)
+__device__ __forceinline__ void sample_logprob_body(const float* __restrict__ logits, int n, const int* __restrict__ id_ptr,
+                                                    const float2* __restrict__ cand, int ncand, int id_imm,
+                                                    const unsigned* __restrict__ top_n_ptr, llmk_logprob_record* __restrict__ out) {
     constexpr int MAXN = LLMK_LOGPROB_MAX_TOP;
     __shared__ unsigned hc[256 * SF_COPIES];                // the level's counts, SF_COPIES copies per bin
     __shared__ llmk_filter_bins bins;
@@ -1245,6 +1278,20 @@ __global__ __launch_bounds__(SF_THREADS) void sample_logprob_kernel(const float*
         }
         if (lane == 0) out->token_logprob = (id >= 1 && id <= n) ? llmk_logprob_value(logits[id - 1], L) : 0.f;
     }
+}
+__global__ __launch_bounds__(SF_THREADS) void sample_logprob_kernel(const float* __restrict__ logits, int n, const int* __restrict__ id_ptr,
+                                                                    const float2* __restrict__ cand, int ncand, int id_imm,
+                                                                    const unsigned* __restrict__ top_n_ptr, llmk_logprob_record* __restrict__ out) {
+    sample_logprob_body(logits, n, id_ptr, cand, ncand, id_imm, top_n_ptr, out);
+}
+// The rows form (a batched pass, batch.h): workgroup i is row i of the pass -- the RAW logits raw + i * n, the id in id_ptr[i] (what
+// picked the row's token left it there), the call's one top_n word; the record goes to out + i * stride + step (a decode of `stride`
+// steps keeps row i's records together).
+__global__ __launch_bounds__(SF_THREADS) void sample_logprob_rows_kernel(const float* __restrict__ raw, int n, const int* __restrict__ id_ptr,
+                                                                         const unsigned* __restrict__ top_n_ptr,
+                                                                         llmk_logprob_record* __restrict__ out, int stride, int step) {
+    const int i = blockIdx.x;
+    sample_logprob_body(raw + (size_t)i * n, n, id_ptr + i, nullptr, 0, 0, top_n_ptr, out + (size_t)i * stride + step);
 }
 
 // q4_0 re-pack on upload: ggml blocks {f16 d; u8 qs[16]} (18 B, 2-byte aligned), bpr per row -> device rows of

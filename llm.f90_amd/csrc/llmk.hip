@@ -248,6 +248,17 @@ struct llmk_batch {
     llmk_filter_params* h_filt = nullptr;
     float* h_out = nullptr;
     unsigned* h_err = nullptr;
+    // penalties, logit bias and log-prob records of the rows functions (llmk_rows_*), allocated by the first call that needs them
+    // (rows_pen_setup, rows_lp_setup) as a context's are.  Logits, parameters, picks and records are per ROW of a call; the token
+    // records and the counts are per SLOT: a sequence keeps its record whichever row of a call it is
+    int* d_hist = nullptr;                       // [n_slots][seq_len] hist[slot][q - 1] = the 1-based token fed at position q, 0 = none
+    int* d_pen_cnt = nullptr;                    // [n_slots][V] sample_penalty_rows_kernel's counts, all zero between launches
+    llmk_penalty_params* d_pen = nullptr;        // [LLMK_MAX_BATCH] row i's penalties and bias ...
+    llmk_penalty_params* h_pen = nullptr;        // ... and the pinned words they are copied from
+    float* d_raw = nullptr;                      // [n_slots][V] the raw logits, set aside in front of the penalty kernel for the records
+    llmk_logprob_record *d_lp = nullptr, *h_lp = nullptr;      // [lp_cap] a call's records, [row][step]
+    size_t lp_cap = 0;
+    unsigned *d_lp_top = nullptr, *h_lp_top = nullptr;         // the call's top_n word
 };
 
 namespace {
@@ -1443,7 +1454,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 404; }
+int llmk_version(void) { return 405; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2154,40 +2165,52 @@ static void logprob_deliver(const llmk_ctx* c, const llmk_logprobs* lp, int i, i
 // TAIL_FILTER with a filter on, else TAIL_SAMPLE -- so with nothing on the _pen functions ARE the _ex ones, and those the plain ones.
 // Nothing is allocated (pen_setup) before every check has passed, and nothing at all for a request that needs no record.
 // lp: the log-prob request of the _lp functions (null: none), checked first and granted last (logprob_request).
+// The checks come first, in two functions that touch no context and no device: a context's request, llmk_batch_decode and the rows
+// functions (a sampler and a penalties entry per row) all ask them.
+// a public sampler, checked, as the filter kernel's words (invT = f32(1 / T)); false: out of range
+static bool sampler_words(const llmk_sampler* sp, llmk_filter_params* out) {
+    if (!sp) return false;
+    if (sp->top_k < 0 || !(sp->top_p > 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f)) return false;      // (NaN fails)
+    if (!(sp->temperature > 0.f) || !isfinite(sp->temperature)) return false;      // (NaN fails the first test)
+    const float invT = 1.0f / sp->temperature;
+    if (!isfinite(invT) || !(invT >= FLT_MIN)) return false;              // 1/T beyond the normal f32 range
+    *out = llmk_filter_params{invT, (uint32_t)sp->seed, (uint32_t)(sp->seed >> 32), sp->top_k, sp->top_p, sp->min_p, {0, 0}};
+    return true;
+}
+// public penalties, checked against a vocabulary of V rows and a record of S positions, as the penalty kernel's words (inv_r = f32(1 / r);
+// last_n = 0 unless a penalty is on); *active: a penalty or a bias is on.  false: out of range
+static bool penalty_words(const llmk_penalties* pn, int V, int S, llmk_penalty_params* out, bool* active) {
+    if (!pn || pn->last_n < 0 || pn->last_n > S) return false;
+    if (!(pn->repeat > 0.f) || !isfinite(pn->repeat) || !isfinite(pn->frequency) || !isfinite(pn->presence)) return false;      // (NaN fails)
+    const float inv_r = 1.0f / pn->repeat;
+    if (!isfinite(inv_r) || !(inv_r >= FLT_MIN)) return false;
+    if (pn->n_bias < 0 || pn->n_bias > LLMK_MAX_LOGIT_BIAS || (pn->n_bias > 0 && !pn->bias)) return false;
+    for (int j = 0; j < pn->n_bias; ++j) {
+        const llmk_logit_bias& b = pn->bias[j];
+        if (b.token < 1 || b.token > V || !(isfinite(b.bias) || b.bias == -INFINITY)) return false;      // (NaN and +inf fail)
+        for (int k = 0; k < j; ++k)
+            if (pn->bias[k].token == b.token) return false;
+    }
+    const bool pen_on = pn->last_n > 0 && (pn->repeat != 1.f || pn->frequency != 0.f || pn->presence != 0.f);
+    *active = pen_on || pn->n_bias > 0;
+    *out = llmk_penalty_params{pn->repeat, inv_r, pn->frequency, pn->presence, pen_on ? pn->last_n : 0, pn->n_bias, {0, 0}, {}};
+    for (int j = 0; j < pn->n_bias; ++j) out->bias[j] = llmk_penalty_bias{pn->bias[j].token, pn->bias[j].bias};
+    return true;
+}
 static int sampler_request(llmk_ctx* c, const llmk_sampler* sp, const llmk_penalties* pn, TailMode* tail, const llmk_logprobs* lp = nullptr) {
     if (lp && !logprob_args_ok(c, lp)) return LLMK_E_ARG;
-    if (!sp) return LLMK_E_ARG;
-    if (sp->top_k < 0 || !(sp->top_p > 0.f && sp->top_p <= 1.f) || !(sp->min_p >= 0.f && sp->min_p <= 1.f)) return LLMK_E_ARG;      // (NaN fails)
-    if (!(sp->temperature > 0.f) || !isfinite(sp->temperature)) return LLMK_E_ARG;      // (NaN fails the first test)
-    const float invT = 1.0f / sp->temperature;
-    if (!isfinite(invT) || !(invT >= FLT_MIN)) return LLMK_E_ARG;              // 1/T beyond the normal f32 range
-    float inv_r = 1.f;
-    bool pen_on = false, active = false;
-    if (pn) {
-        if (pn->last_n < 0 || pn->last_n > c->S) return LLMK_E_ARG;
-        if (!(pn->repeat > 0.f) || !isfinite(pn->repeat) || !isfinite(pn->frequency) || !isfinite(pn->presence)) return LLMK_E_ARG;      // (NaN fails)
-        inv_r = 1.0f / pn->repeat;
-        if (!isfinite(inv_r) || !(inv_r >= FLT_MIN)) return LLMK_E_ARG;
-        if (pn->n_bias < 0 || pn->n_bias > LLMK_MAX_LOGIT_BIAS || (pn->n_bias > 0 && !pn->bias)) return LLMK_E_ARG;
-        for (int j = 0; j < pn->n_bias; ++j) {
-            const llmk_logit_bias& b = pn->bias[j];
-            if (b.token < 1 || b.token > c->V || !(isfinite(b.bias) || b.bias == -INFINITY)) return LLMK_E_ARG;      // (NaN and +inf fail)
-            for (int k = 0; k < j; ++k)
-                if (pn->bias[k].token == b.token) return LLMK_E_ARG;
-        }
-        pen_on = pn->last_n > 0 && (pn->repeat != 1.f || pn->frequency != 0.f || pn->presence != 0.f);
-        active = pen_on || pn->n_bias > 0;
-    }
-    const uint32_t seed_lo = (uint32_t)sp->seed, seed_hi = (uint32_t)(sp->seed >> 32);
-    *c->h_samp = llmk_sample_params{invT, seed_lo, seed_hi, 0};
-    *c->h_filt = llmk_filter_params{invT, seed_lo, seed_hi, sp->top_k, sp->top_p, sp->min_p, {0, 0}};
+    llmk_filter_params filt;
+    llmk_penalty_params pen;
+    bool active = false;
+    if (!sampler_words(sp, &filt) || (pn && !penalty_words(pn, c->V, c->S, &pen, &active))) return LLMK_E_ARG;
+    *c->h_samp = llmk_sample_params{filt.invT, filt.seed_lo, filt.seed_hi, 0};
+    *c->h_filt = filt;
     *tail = sp->top_k != 0 || sp->top_p != 1.f || sp->min_p != 0.f ? TAIL_FILTER : TAIL_SAMPLE;
     if (!active) return lp ? logprob_request(c, lp, false) : LLMK_OK;
     int rc = pen_setup(c);
     if (rc) return rc;
     if (lp && (rc = logprob_request(c, lp, true)) != LLMK_OK) return rc;
-    *c->h_pen = llmk_penalty_params{pn->repeat, inv_r, pn->frequency, pn->presence, pen_on ? pn->last_n : 0, pn->n_bias, {0, 0}, {}};
-    for (int j = 0; j < pn->n_bias; ++j) c->h_pen->bias[j] = llmk_penalty_bias{pn->bias[j].token, pn->bias[j].bias};
+    *c->h_pen = pen;
     *tail = TAIL_PENALTY;
     return LLMK_OK;
 }
@@ -2441,10 +2464,11 @@ static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one pre
 constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 * BD_WAVES * 16) * sizeof(float); }
 
 static void batch_free(llmk_batch* b) {
-    void* dev[] = {b->d_kc, b->d_vc, b->d_rows, b->d_tok, b->d_out, b->d_logits, b->d_po, b->d_pml, b->d_next, b->d_filt, b->d_out2, b->d_err, b->d_ids};
+    void* dev[] = {b->d_kc, b->d_vc, b->d_rows, b->d_tok, b->d_out, b->d_logits, b->d_po, b->d_pml, b->d_next, b->d_filt, b->d_out2, b->d_err, b->d_ids,
+                   b->d_hist, b->d_pen_cnt, b->d_pen, b->d_raw, b->d_lp, b->d_lp_top};
     for (void* p : dev)
         if (p) hipFree(p);
-    void* host[] = {b->h_rows, b->h_tok, b->h_filt, b->h_out, b->h_err};
+    void* host[] = {b->h_rows, b->h_tok, b->h_filt, b->h_out, b->h_err, b->h_pen, b->h_lp, b->h_lp_top};
     for (void* p : host)
         if (p) hipHostFree(p);
     delete b;
@@ -2495,13 +2519,14 @@ static int bd_ready(llmk_batch* b, ScPlan* sp, int rows) {
     return LLMK_OK;
 }
 // rows of a call: n in [1, n_slots], distinct slots, ids and positions in range (last_pos: the last position the call writes)
-static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos, int span) {
-    if (!slots || !tokens || !pos || n < 1 || n > b->n_slots || span < 1) return false;
+// (fed = false: rows that feed no token -- the hook of the rows functions; `tokens` is not read)
+static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos, int span, bool fed = true) {
+    if (!slots || (fed && !tokens) || !pos || n < 1 || n > b->n_slots || span < 1) return false;
     bool seen[LLMK_MAX_BATCH] = {};
     for (int i = 0; i < n; ++i) {
         if (slots[i] < 0 || slots[i] >= b->n_slots || seen[slots[i]]) return false;
         seen[slots[i]] = true;
-        if (tokens[i] < 1 || tokens[i] > b->ctx->V) return false;
+        if (fed && (tokens[i] < 1 || tokens[i] > b->ctx->V)) return false;
         if (pos[i] < 1 || pos[i] > b->seq_len || span - 1 > b->seq_len - pos[i]) return false;
     }
     return true;
@@ -2509,7 +2534,7 @@ static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* 
 static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos) {
     for (int i = 0; i < n; ++i) {
         b->h_rows[i] = BdRow{slots[i], pos[i]};
-        b->h_tok[i] = tokens[i] - 1;
+        b->h_tok[i] = tokens ? tokens[i] - 1 : 0;      // (null: rows that feed no token, bd_rows_ok)
     }
     hipStream_t st = b->ctx->stream;
     HIPRET(hipMemcpyAsync(b->d_rows, b->h_rows, (size_t)n * sizeof(BdRow), hipMemcpyHostToDevice, st));
@@ -2592,6 +2617,8 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
             if (n_pos > 0)
                 HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         }
+    // a forked or emptied slot is a new sequence: no token fed yet (the caller records the prompt with llmk_rows_set_history)
+    if (b->d_hist) HIPCHK(hipMemsetAsync(b->d_hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
 }
@@ -2619,55 +2646,233 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
     return LLMK_OK;
 }
 
-int llmk_batch_decode(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos0, int steps, const llmk_sampler* samplers, int* ids_out) {
-    if (!b || !ids_out || steps < 1 || !bd_rows_ok(b, n, slots, tokens, pos0, steps)) return LLMK_E_ARG;
+// ---- the rows functions: a batch's samplers, penalties, bias and log-prob records, one workgroup per row of the pass ----
+// the slots' token records, their counts and the rows' penalty words: allocated (and zeroed) by the first call that needs them
+static int rows_pen_setup(llmk_batch* b) {
+    if (b->d_hist && b->d_pen_cnt && b->d_pen && b->h_pen) return LLMK_OK;
     llmk_ctx* c = b->ctx;
-    if (samplers) {
-        for (int i = 0; i < n; ++i) {      // llmk_forward_sample_ex's checks (sampler_request)
-            const llmk_sampler& sp = samplers[i];
-            if (sp.top_k < 0 || !(sp.top_p > 0.f && sp.top_p <= 1.f) || !(sp.min_p >= 0.f && sp.min_p <= 1.f)) return LLMK_E_ARG;
-            if (!(sp.temperature > 0.f) || !isfinite(sp.temperature)) return LLMK_E_ARG;
-            const float invT = 1.0f / sp.temperature;
-            if (!isfinite(invT) || !(invT >= FLT_MIN)) return LLMK_E_ARG;
-            b->h_filt[i] = llmk_filter_params{invT, (uint32_t)sp.seed, (uint32_t)(sp.seed >> 32), sp.top_k, sp.top_p, sp.min_p, {0, 0}};
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t hist = (size_t)b->n_slots * b->seq_len * sizeof(int), cnt = (size_t)b->n_slots * c->V * sizeof(int);
+    const size_t pen = (size_t)LLMK_MAX_BATCH * sizeof(llmk_penalty_params);
+    if (!b->d_hist) {
+        HIPCHK(dev_alloc(&b->d_hist, hist));
+        HIPCHK(hipMemsetAsync(b->d_hist, 0, hist, c->stream));
+    }
+    if (!b->d_pen_cnt) {
+        HIPCHK(dev_alloc(&b->d_pen_cnt, cnt));
+        HIPCHK(hipMemsetAsync(b->d_pen_cnt, 0, cnt, c->stream));
+    }
+    if (!b->d_pen) {
+        HIPCHK(dev_alloc(&b->d_pen, pen));
+        HIPCHK(hipMemsetAsync(b->d_pen, 0, pen, c->stream));
+    }
+    if (!b->h_pen) {
+        HIPCHK(hipHostMalloc(&b->h_pen, pen, hipHostMallocDefault));
+        memset(b->h_pen, 0, pen);
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+// room for a call's nrec records on the device and in pinned memory (grown like d_ids), the top_n word and, under penalties, the raw logits
+static int rows_lp_setup(llmk_batch* b, size_t nrec, bool raw) {
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (b->lp_cap < nrec) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (b->d_lp) { hipFree(b->d_lp); b->d_lp = nullptr; }
+        if (b->h_lp) { hipHostFree(b->h_lp); b->h_lp = nullptr; }
+        b->lp_cap = 0;
+        HIPCHK(dev_alloc(&b->d_lp, nrec * sizeof(llmk_logprob_record)));
+        HIPCHK(hipHostMalloc(&b->h_lp, nrec * sizeof(llmk_logprob_record), hipHostMallocDefault));
+        b->lp_cap = nrec;
+    }
+    if (!b->d_lp_top) HIPCHK(dev_alloc(&b->d_lp_top, sizeof(unsigned)));
+    if (!b->h_lp_top) HIPCHK(hipHostMalloc(&b->h_lp_top, sizeof(unsigned), hipHostMallocDefault));
+    if (raw && !b->d_raw) HIPCHK(dev_alloc(&b->d_raw, (size_t)b->n_slots * c->V * sizeof(float)));
+    return LLMK_OK;
+}
+// What the rows of a call ask for: every entry checked (sampler_words, penalty_words; the window against the BATCH's seq_len), nothing
+// allocated before every check has passed and nothing at all by a call that needs no record.  The samplers' words go to h_filt; with a
+// penalty or a bias on in ANY row (*pen_on), every row's words go to h_pen -- a row with nothing on gets words that adjust nothing.
+// nrec: the records the call writes (lp not null).
+static int rows_request(llmk_batch* b, int n, const llmk_sampler* samplers, const llmk_penalties* penalties, const llmk_logprobs* lp, size_t nrec,
+                        bool* pen_on) {
+    llmk_ctx* c = b->ctx;
+    *pen_on = false;
+    if ((!samplers && penalties) || (lp && !logprob_args_ok(c, lp))) return LLMK_E_ARG;
+    for (int i = 0; samplers && i < n; ++i)
+        if (!sampler_words(samplers + i, b->h_filt + i)) return LLMK_E_ARG;
+    std::vector<llmk_penalty_params> pen(penalties ? (size_t)n : 0);
+    for (int i = 0; penalties && i < n; ++i) {
+        bool active = false;
+        if (!penalty_words(penalties + i, c->V, b->seq_len, &pen[i], &active)) return LLMK_E_ARG;
+        *pen_on = *pen_on || active;
+    }
+    int rc;
+    if (*pen_on) {
+        if ((rc = rows_pen_setup(b)) != LLMK_OK) return rc;
+        memcpy(b->h_pen, pen.data(), (size_t)n * sizeof(llmk_penalty_params));
+    }
+    if (lp) {
+        if ((rc = rows_lp_setup(b, nrec, *pen_on)) != LLMK_OK) return rc;
+        *b->h_lp_top = (unsigned)lp->top_n;
+    }
+    return LLMK_OK;
+}
+// The sampler kernels of one step or one hook call, ENQUEUED: one launch of n workgroups each, workgroup i on row i's logits in d_logits
+// by row i's words.  pen: the penalty kernel first (record: it writes the slots' records, else it only reads them), the raw logits
+// set aside in front of it when records are asked for; then the filter kernel, which leaves the picks in d_next; greedy: none of the
+// two, the picks are `picked` (the classifier's first maxima).  lp: the log-prob kernel on the raw logits and the picks, records to
+// d_lp + i * stride + step.  Returns where the picks are.
+static hipError_t rows_enqueue(llmk_batch* b, int n, bool sampled, bool pen, bool record, bool lp, int stride, int step, const int** picked) {
+    llmk_ctx* c = b->ctx;
+    const int* rows = reinterpret_cast<const int*>(b->d_rows);
+    if (sampled) {
+        if (pen) {
+            if (lp) HIPRET(hipMemcpyAsync(b->d_raw, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            hipLaunchKernelGGL(sample_penalty_rows_kernel, dim3(n), dim3(SP_THREADS), 0, c->stream, b->d_logits, c->V, rows, record ? b->d_tok : nullptr,
+                               b->d_pen, b->d_hist, record ? b->d_hist : nullptr, b->d_pen_cnt, b->n_slots, b->seq_len);
+            HIPRET(hipGetLastError());
+        }
+        hipLaunchKernelGGL(sample_filter_rows_kernel, dim3(n), dim3(SF_THREADS), 0, c->stream, b->d_logits, c->V, rows, b->d_filt, b->d_next, b->d_out2);
+        HIPRET(hipGetLastError());
+        *picked = b->d_next;
+    }
+    if (lp) {
+        hipLaunchKernelGGL(sample_logprob_rows_kernel, dim3(n), dim3(SF_THREADS), 0, c->stream, (sampled && pen) ? b->d_raw : b->d_logits, c->V, *picked,
+                           b->d_lp_top, b->d_lp, stride, step);
+        HIPRET(hipGetLastError());
+    }
+    return hipSuccess;
+}
+// the parameter words of a call on their way to the device, like rows and tokens
+static hipError_t rows_upload_words(llmk_batch* b, int n, bool sampled, bool pen, bool lp) {
+    hipStream_t st = b->ctx->stream;
+    if (sampled) HIPRET(hipMemcpyAsync(b->d_filt, b->h_filt, (size_t)n * sizeof(llmk_filter_params), hipMemcpyHostToDevice, st));
+    if (pen) HIPRET(hipMemcpyAsync(b->d_pen, b->h_pen, (size_t)n * sizeof(llmk_penalty_params), hipMemcpyHostToDevice, st));
+    if (lp) HIPRET(hipMemcpyAsync(b->d_lp_top, b->h_lp_top, sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return hipSuccess;
+}
+// the pinned records [row][step] into the caller's arrays
+static void rows_deliver(const llmk_batch* b, const llmk_logprobs* lp, size_t nrec) {
+    for (size_t k = 0; k < nrec; ++k) {
+        const llmk_logprob_record& r = b->h_lp[k];
+        if (lp->token_logprob) lp->token_logprob[k] = r.token_logprob;
+        for (int j = 0; j < lp->top_n; ++j) {
+            lp->top_tokens[k * lp->top_n + j] = r.top_tokens[j];
+            lp->top_logprobs[k * lp->top_n + j] = r.top_logprobs[j];
         }
     }
-    ScPlan sp;
-    int rc = bd_ready(b, &sp, n);
-    if (rc) return rc;
+}
+
+// llmk_batch_decode and llmk_rows_decode (`who`): the former is the latter without penalties and records
+static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, const int* tokens, const int* pos0, int steps,
+                       const llmk_sampler* samplers, const llmk_penalties* penalties, const llmk_logprobs* lp, int* ids_out) {
+    if (!b || !ids_out || steps < 1 || !bd_rows_ok(b, n, slots, tokens, pos0, steps)) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
     const size_t nids = (size_t)n * steps;
+    bool pen = false;
+    int rc = rows_request(b, n, samplers, penalties, lp, nids, &pen);
+    if (rc) return rc;
+    ScPlan sp;
+    if ((rc = bd_ready(b, &sp, n)) != LLMK_OK) return rc;
     if (b->ids_cap < nids) {
         if (b->d_ids) { hipFree(b->d_ids); b->d_ids = nullptr; b->ids_cap = 0; }
         HIPCHK(dev_alloc(&b->d_ids, nids * sizeof(int)));
         b->ids_cap = nids;
     }
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos0));
-    if (samplers) HIPCHK(hipMemcpyAsync(b->d_filt, b->h_filt, (size_t)n * sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(rows_upload_words(b, n, samplers != nullptr, pen, lp != nullptr));
     HIPCHK(hipMemsetAsync(b->d_err, 0, sizeof(unsigned), c->stream));
     const int max_pos0 = *std::max_element(pos0, pos0 + n);
     for (int s = 0; s < steps; ++s) {
-        HIPCHK(bd_pass(b, n, max_pos0 + s, samplers != nullptr, sp));
+        HIPCHK(bd_pass(b, n, max_pos0 + s, samplers != nullptr || lp != nullptr, sp));
+        // row i's draw: the kernels the verification hooks run, on the row's logits, position (the row words) and words.  The advance
+        // runs behind them: the penalty kernel of the next step finds the fed token in d_tok and the new position in d_rows
         const int* picked = reinterpret_cast<const int*>(b->d_out + n);
-        if (samplers) {
-            // row i's draw: the kernel llmk_sample_logits runs, on the row's logits, position (the row words: tokpos[1] = pos) and sampler
-            for (int i = 0; i < n; ++i)
-                hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, b->d_logits + (size_t)i * c->V, c->V,
-                                   reinterpret_cast<const int*>(b->d_rows + i), 0, b->d_filt + i, b->d_next + i, (float2*)nullptr, 0, b->d_out2 + 2 * i);
-            HIPCHK(hipGetLastError());
-            picked = b->d_next;
-        }
+        HIPCHK(rows_enqueue(b, n, samplers != nullptr, pen, true, lp != nullptr, steps, s, &picked));
         hipLaunchKernelGGL(bd_advance_kernel, dim3(1), dim3(LLMK_MAX_BATCH), 0, c->stream, picked, n, c->V, s, steps, b->d_ids, b->d_tok, b->d_rows, b->d_err);
         HIPCHK(hipGetLastError());
     }
+    if (lp) HIPCHK(hipMemcpyAsync(b->h_lp, b->d_lp, nids * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(b->h_err, b->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(bd_fetch_flag(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (pf_flagged(c)) {
+        // The redone call starts from the caller's rows again and finds the state a first call finds: the token records are indexed by
+        // position, so it rewrites the very entries this one wrote (as it rewrites the K/V rows), and the counts are all zero again
+        // after every launch of the penalty kernel, whatever the logits were.
         static bool told = false;
-        return pf_redo(c, "llmk_batch_decode", &told, [&] { return llmk_batch_decode(b, n, slots, tokens, pos0, steps, samplers, ids_out); });
+        return pf_redo(c, who, &told, [&] { return rows_decode(b, who, n, slots, tokens, pos0, steps, samplers, penalties, lp, ids_out); });
     }
     HIPCHK(hipMemcpy(ids_out, b->d_ids, nids * sizeof(int), hipMemcpyDeviceToHost));
-    return *b->h_err ? LLMK_E_NONFINITE : LLMK_OK;
+    if (*b->h_err) return LLMK_E_NONFINITE;
+    if (lp) rows_deliver(b, lp, nids);
+    return LLMK_OK;
+}
+
+int llmk_batch_decode(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos0, int steps, const llmk_sampler* samplers, int* ids_out) {
+    return rows_decode(b, "llmk_batch_decode", n, slots, tokens, pos0, steps, samplers, nullptr, nullptr, ids_out);
+}
+int llmk_rows_decode(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos0, int steps, const llmk_sampler* samplers,
+                     const llmk_penalties* penalties, const llmk_logprobs* logprobs, int* ids_out) {
+    return rows_decode(b, "llmk_rows_decode", n, slots, tokens, pos0, steps, samplers, penalties, logprobs, ids_out);
+}
+
+// The verification hook of the rows functions: no pass, no K/V; the caller's logits [n][V] take the place of the batch's logits rows,
+// the slots' token records are read (positions up to and including pos[i]) and not written
+int llmk_rows_sample_logits(llmk_batch* b, int n, const int* slots, const int* pos, const float* logits, const llmk_sampler* samplers,
+                            const llmk_penalties* penalties, const llmk_logprobs* logprobs, int* tokens_out, int* kept_out, float* tau_out,
+                            float* adjusted_out) {
+    if (!b || !logits || !samplers || !tokens_out || !bd_rows_ok(b, n, slots, nullptr, pos, 1, false)) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    int rc = check_ready(c);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    bool pen = false;
+    if ((rc = rows_request(b, n, samplers, penalties, logprobs, (size_t)n, &pen)) != LLMK_OK) return rc;
+    const size_t nv = (size_t)n * c->V * sizeof(float);
+    std::vector<unsigned> out2((size_t)2 * n);
+    HIPCHK(bd_upload_rows(b, n, slots, nullptr, pos));
+    HIPCHK(rows_upload_words(b, n, true, pen, logprobs != nullptr));
+    HIPCHK(hipMemcpyAsync(b->d_logits, logits, nv, hipMemcpyHostToDevice, c->stream));
+    const int* picked = nullptr;
+    HIPCHK(rows_enqueue(b, n, true, pen, false, logprobs != nullptr, 1, 0, &picked));
+    HIPCHK(hipMemcpyAsync(tokens_out, picked, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out2.data(), b->d_out2, out2.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    if (adjusted_out) HIPCHK(hipMemcpyAsync(adjusted_out, b->d_logits, nv, hipMemcpyDeviceToHost, c->stream));
+    if (logprobs) HIPCHK(hipMemcpyAsync(b->h_lp, b->d_lp, (size_t)n * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i) {
+        if (kept_out) kept_out[i] = (int)out2[2 * i];
+        if (tau_out) memcpy(tau_out + i, &out2[2 * i + 1], sizeof(float));
+    }
+    for (int i = 0; i < n; ++i)
+        if (tokens_out[i] < 1 || tokens_out[i] > c->V) return LLMK_E_NONFINITE;
+    if (logprobs) rows_deliver(b, logprobs, (size_t)n);
+    return LLMK_OK;
+}
+
+// llmk_set_history / llmk_get_history for one slot of a batch
+int llmk_rows_set_history(llmk_batch* b, int slot, const int* tokens, int n, int pos0) {
+    if (!b || !tokens || slot < 0 || slot >= b->n_slots || n < 1 || pos0 < 1 || pos0 + n - 1 > b->seq_len) return LLMK_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (tokens[i] < 0 || tokens[i] > b->ctx->V) return LLMK_E_ARG;
+    const int rc = rows_pen_setup(b);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    HIPCHK(hipMemcpyAsync(b->d_hist + (size_t)slot * b->seq_len + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return LLMK_OK;
+}
+int llmk_rows_get_history(llmk_batch* b, int slot, int* tokens_out, int n, int pos0) {
+    if (!b || !tokens_out || slot < 0 || slot >= b->n_slots || n < 1 || pos0 < 1 || pos0 + n - 1 > b->seq_len) return LLMK_E_ARG;
+    const int rc = rows_pen_setup(b);
+    if (rc) return rc;
+    hipStream_t st = b->ctx->stream;
+    HIPCHK(hipMemcpyAsync(tokens_out, b->d_hist + (size_t)slot * b->seq_len + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return LLMK_OK;
 }
 
 int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {

@@ -311,6 +311,41 @@ module llmk_binding
        type(c_ptr), value :: samplers
        integer(c_int), intent(out) :: ids_out(*)
      end function
+     ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
+     ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
+     ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too
+     integer(c_int) function llmk_rows_set_history(batch, slot, tokens, n, pos0) bind(C, name="llmk_rows_set_history")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot, n, pos0
+       integer(c_int), intent(in) :: tokens(*)
+     end function
+     integer(c_int) function llmk_rows_get_history(batch, slot, tokens_out, n, pos0) bind(C, name="llmk_rows_get_history")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot, n, pos0
+       integer(c_int), intent(out) :: tokens_out(*)
+     end function
+     integer(c_int) function llmk_rows_decode(batch, n, slots, tokens, pos0, steps, samplers, penalties, logprobs, ids_out) &
+          bind(C, name="llmk_rows_decode")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n, steps
+       integer(c_int), intent(in) :: slots(*), tokens(*), pos0(*)
+       type(c_ptr), value :: samplers, penalties, logprobs
+       integer(c_int), intent(out) :: ids_out(*)
+     end function
+     integer(c_int) function llmk_rows_sample_logits(batch, n, slots, pos, logits, samplers, penalties, logprobs, tokens_out, &
+          kept_out, tau_out, adjusted_out) bind(C, name="llmk_rows_sample_logits")
+       import :: c_int, c_float, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n
+       integer(c_int), intent(in) :: slots(*), pos(*)
+       real(c_float), intent(in) :: logits(*)
+       type(c_ptr), value :: samplers, penalties, logprobs
+       integer(c_int), intent(out) :: tokens_out(*)
+       type(c_ptr), value :: kept_out, tau_out, adjusted_out
+     end function
      integer(c_int) function llmk_path(ctx) bind(C, name="llmk_path")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

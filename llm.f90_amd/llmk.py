@@ -28,7 +28,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_set_history", "llmk_get_history",
            "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
-           "llmk_batch_decode", "llmk_batch_time", "llmk_reset", "llmk_timings",
+           "llmk_batch_decode", "llmk_batch_time", "llmk_rows_set_history", "llmk_rows_get_history", "llmk_rows_decode",
+           "llmk_rows_sample_logits", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -178,6 +179,12 @@ def lib():
             L.llmk_batch_forward.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), cf, C.POINTER(ci)]
             L.llmk_batch_decode.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(Sampler), C.POINTER(ci)]
             L.llmk_batch_time.argtypes = [vp, ci, ci, ci, cf]
+        if hasattr(L, "llmk_rows_decode"):
+            pi = C.POINTER(ci)
+            L.llmk_rows_set_history.argtypes = [vp, ci, pi, ci, ci]
+            L.llmk_rows_get_history.argtypes = [vp, ci, pi, ci, ci]
+            L.llmk_rows_decode.argtypes = [vp, ci, pi, pi, pi, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(Logprobs), pi]
+            L.llmk_rows_sample_logits.argtypes = [vp, ci, pi, pi, cf, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(Logprobs), pi, pi, cf, cf]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -620,6 +627,78 @@ class Batch:
         ids = np.zeros((n, max(steps, 0)), np.int32)
         _ck(lib().llmk_batch_decode(self._h, n, *p, steps, sp, ids.ctypes.data_as(C.POINTER(C.c_int))))
         return ids
+
+    @staticmethod
+    def _row_words(n, samplers, penalties):
+        """one Sampler / one Penalties per row as the arrays the rows functions take (None stays None)"""
+        for w, what in ((samplers, "sampler"), (penalties, "penalties entry")):
+            if w is not None and len(w) != n:
+                raise ValueError(f"one {what} per row")
+        sp = (Sampler * max(1, n))(*samplers) if samplers is not None else None
+        pn = (Penalties * max(1, n))(*penalties) if penalties is not None else None      # (the bias lists stay the caller's entries')
+        return sp, pn
+
+    @staticmethod
+    def _records(shape, top_n, want_token_logprob):
+        """the log-prob request of a rows call (None: nothing asked for) over records of `shape`"""
+        if top_n is None and not want_token_logprob:
+            return None
+        lp = logprobs(int(np.prod(shape)), top_n or 0, want_token_logprob)
+        lp.shape = tuple(shape)
+        return lp
+
+    @staticmethod
+    def _with_records(first, lp):
+        """the outputs of a rows call, then the record arrays that were asked for, in the shape of the call"""
+        out = list(first)
+        if lp is not None:
+            out += [lp.token.reshape(lp.shape)] if lp.token is not None else []
+            out += [lp.tokens.reshape(lp.shape + (lp.top_n,)), lp.values.reshape(lp.shape + (lp.top_n,))] if lp.top_n > 0 else []
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def decode_rows(self, slots, tokens, pos0, steps: int, samplers=None, penalties=None, top_n=None, want_token_logprob: bool = False):
+        """decode with per-row penalties, bias and log-prob records (llmk_rows_decode).  samplers: None = greedy, else one Sampler per
+        row; penalties: None, else one llmk.penalties(...) per row; top_n: None = no alternatives, else 0..20 for every row.  Returns
+        ids [n][steps], then the arrays asked for: token_logprob [n][steps] (want_token_logprob), top_tokens and top_logprobs
+        [n][steps][top_n] (top_n > 0)."""
+        a, p = self._rows(slots, tokens, pos0)
+        n = len(a[0])
+        sp, pn = self._row_words(n, samplers, penalties)
+        lp = self._records((n, max(steps, 0)), top_n, want_token_logprob)
+        ids = np.zeros((n, max(steps, 0)), np.int32)
+        _ck(lib().llmk_rows_decode(self._h, n, *p, steps, sp, pn, C.byref(lp) if lp is not None else None, ids.ctypes.data_as(C.POINTER(C.c_int))))
+        return self._with_records([ids], lp)
+
+    def sample_logits_rows(self, slots, pos, logits, samplers, penalties=None, top_n=None, want_token_logprob: bool = False):
+        """The sampler kernels' rows forms on caller-supplied logits [n][V], the windows read from the slots' records, no pass
+        (llmk_rows_sample_logits).  Returns tokens [n], kept [n], tau [n], adjusted [n][V], then the log-prob arrays asked for as
+        decode_rows returns them for one step: token_logprob [n], top_tokens and top_logprobs [n][top_n]."""
+        a = [np.ascontiguousarray(x, np.int32) for x in (slots, pos)]
+        if not (a[0].ndim == 1 and a[0].shape == a[1].shape):
+            raise ValueError("one slot and one position per row")
+        n = len(a[0])
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.shape != (n, self.V):
+            raise ValueError("one logit per row and vocabulary row")
+        sp, pn = self._row_words(n, samplers, penalties)
+        lp = self._records((n,), top_n, want_token_logprob)
+        tok, kept, tau, adj = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32), np.empty((n, self.V), np.float32)
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        _ck(lib().llmk_rows_sample_logits(self._h, n, a[0].ctypes.data_as(ip), a[1].ctypes.data_as(ip), lg.ctypes.data_as(fp), sp, pn,
+                                          C.byref(lp) if lp is not None else None, tok.ctypes.data_as(ip), kept.ctypes.data_as(ip),
+                                          tau.ctypes.data_as(fp), adj.ctypes.data_as(fp)))
+        return self._with_records([tok, kept, tau, adj], lp)
+
+    def set_history(self, slot: int, tokens, pos0: int = 1):
+        """record `tokens` (1-based ids, 0 = none) as fed to `slot` at positions pos0.. (llmk_rows_set_history)"""
+        t = np.ascontiguousarray(tokens, np.int32)
+        _ck(lib().llmk_rows_set_history(self._h, slot, t.ctypes.data_as(C.POINTER(C.c_int)), len(t), pos0))
+
+    def get_history(self, slot: int, n: int, pos0: int = 1) -> np.ndarray:
+        """the token record of `slot`, positions pos0 .. pos0+n-1 (llmk_rows_get_history)"""
+        out = np.zeros(n, np.int32)
+        _ck(lib().llmk_rows_get_history(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_int)), n, pos0))
+        return out
 
     def time(self, n: int, pos: int, iters: int) -> float:
         """average ms of one full pass of n rows at position pos (llmk_batch_time); overwrites slot state"""

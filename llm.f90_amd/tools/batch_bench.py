@@ -7,7 +7,12 @@ For n = 1, 2, 4, ... 128 rows and positions 25 and 1024: llmk_batch_time's milli
 greedy pick for every row) and the aggregate tokens per second n / pass; then llmk_decode_greedy's tokens per second on the same
 context (one sequence on the persistent kernel, or whatever path the shape gets).  Every figure is the median of --repeats
 measurements behind a warm-up, with the spread (max - min) / median beside it.  Weights are bench.py's synthetic ones (same seed).
-Prints a table on stdout and, with --json, one JSON line."""
+Prints a table on stdout and, with --json, one JSON line.
+
+    python -m llm_f90_amd.tools.batch_bench --shape tinyllama --type f32 --sampled
+
+measures whole decode calls instead (64 steps from position 25 at 8, 32 and 128 rows): greedy, one sampler per row, and -- through
+llmk_rows_decode, where the library has it -- a repeat penalty and log-prob records on top."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +56,51 @@ def build(shape_name: str, type_name: str, cls_q6k: bool):
     return llmk.Llmk(fw), shape
 
 
+SAMPLED_ROWS = (8, 32, 128)
+SAMPLED_POS, SAMPLED_STEPS = 25, 64
+
+
+def sampled(m, shape, repeats: int):
+    """--sampled: the wall clock of a whole decode call of SAMPLED_STEPS steps from SAMPLED_POS -- llmk_batch_decode greedy and with one
+    sampler per row, and, where the library exports the rows functions, llmk_rows_decode with a repeat penalty and with log-prob
+    records on top -- as the median of `repeats` calls behind a warm-up call.  Every call starts from the same rows: it rewrites the
+    K/V rows and the token records it wrote before."""
+    have_rows = hasattr(llmk.lib(), "llmk_rows_decode")
+    b = llmk.Batch(m, max(SAMPLED_ROWS), SAMPLED_POS + SAMPLED_STEPS - 1)
+    out = []
+    for n in SAMPLED_ROWS:
+        rows = (list(range(n)), [2 + i for i in range(n)], [SAMPLED_POS] * n)
+        sps = [llmk.sampler(0.9, 1000 + i, top_k=40) for i in range(n)]
+        cases = [("greedy", lambda: b.decode(*rows, SAMPLED_STEPS)),
+                 ("T0.9 top-k 40", lambda: b.decode(*rows, SAMPLED_STEPS, sps))]
+        if have_rows:
+            pens = [llmk.penalties(last_n=64, repeat=1.1) for _ in range(n)]
+            cases += [("+ repeat 1.1 / 64", lambda: b.decode_rows(*rows, SAMPLED_STEPS, sps, pens)),
+                      ("+ top_n 5", lambda: b.decode_rows(*rows, SAMPLED_STEPS, sps, pens, top_n=5, want_token_logprob=True))]
+        for name, call in cases:
+            call()                                              # warm-up
+            ms = []
+            for _ in range(repeats):
+                t0 = time.perf_counter()
+                call()
+                ms.append((time.perf_counter() - t0) * 1e3 / SAMPLED_STEPS)
+            med, spread = med_spread(ms)
+            out.append({"n": n, "sampler": name, "ms_per_step": med, "spread": spread, "tok_s": n / med * 1e3})
+    b.close()
+    return out
+
+
+def print_sampled(shape_name, type_name, rows, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# llmk_batch_decode / llmk_rows_decode, {shape_name} {type_name}, {SAMPLED_STEPS} steps from position {SAMPLED_POS}: wall clock of the call, "
+          f"median of {repeats} behind a warm-up (spread = (max - min) / median; + over greedy: ms/step above the greedy call of the same n)")
+    print(f"{'n':>5} {'sampler':>20} {'ms/step':>9} {'spread':>7} {'+- ms':>7} {'tok/s':>10} {'+ over greedy':>14}")
+    greedy = {r["n"]: r["ms_per_step"] for r in rows if r["sampler"] == "greedy"}
+    for r in rows:
+        print(f"{r['n']:5d} {r['sampler']:>20} {r['ms_per_step']:9.3f} {r['spread']:7.3f} {r['spread'] * r['ms_per_step']:7.3f} {r['tok_s']:10.1f} "
+              f"{r['ms_per_step'] - greedy[r['n']]:14.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shape", default="tinyllama", choices=sorted(gguf.SHAPES))
@@ -61,10 +111,20 @@ def main():
     ap.add_argument("--decode-steps", type=int, default=248, help="positions of one llmk_decode_greedy measurement (behind 8 warm-up positions)")
     ap.add_argument("--single-only", action="store_true",
                     help="only the llmk_decode_greedy figures: the baseline of another build of the library selected with LLMK_LIB")
+    ap.add_argument("--sampled", action="store_true",
+                    help="only the sampled-decode table: whole llmk_batch_decode / llmk_rows_decode calls at 8, 32 and 128 rows (also "
+                         "against another build selected with LLMK_LIB: the rows functions are measured where the library has them)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
     m, shape = build(a.shape, a.type, a.cls_q6k)
+    if a.sampled:
+        rows = sampled(m, shape, a.repeats)
+        m.close()
+        print_sampled(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "sampled": rows}))
+        return
     positions = [p for p in POSITIONS if p <= shape.seq_len]
     out = {"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "path": m.path_name(), "batch": [], "decode_greedy": {}}
 
