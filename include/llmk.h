@@ -461,6 +461,37 @@ int llmk_rows_sample_logits(llmk_batch *b, int n, const int *slots, const int *p
                             const llmk_sampler *samplers, const llmk_penalties *penalties, const llmk_logprobs *logprobs,
                             int *tokens_out, int *kept_out, float *tau_out, float *adjusted_out);
 
+/* A shared prefix: N completions of one prompt without N copies of its K/V rows.  A batch can hold ONE prefix,
+ * a single copy [n_layers][P][kv_dim] (f32) of the K/V rows of positions 1..P; slots are ATTACHED to it.  An attached slot is a
+ * sequence whose positions 1..P are the prefix and whose positions P+1.. live in the slot's own cache, still at cache row pos - 1.  In a
+ * pass the prefix rows are read once per group of 16 / (query heads per kv head) attached rows, not once per row.  ("prefix", not
+ * "batch": the llmk_batch_* list is closed.)
+ *
+ * set:     copies positions 1..n_pos of every layer from the CONTEXT's own cache into the batch's prefix.  A snapshot: later calls on
+ *          the context do not change it.  n_pos in [0, min(batch seq_len, context seq_len) - 1] (an attached row needs a position of
+ *          its own), else LLMK_E_ARG; 0 drops the prefix.  LLMK_E_STATE while any slot is attached.  The prefix, the column map, the
+ *          slots' `first` words and the part-state buffers of such passes are allocated by the first call that sets a prefix: a batch
+ *          that never does allocates and launches exactly what it did without these functions.
+ * attach:  LLMK_E_STATE without a prefix, LLMK_E_ARG for a slot out of range.  The slot becomes a new sequence behind the prefix: its
+ *          own cache rows are zeroed, and its token record if the batch has records, as llmk_batch_fork does (the caller records the
+ *          prompt with llmk_rows_set_history, as after a fork).  llmk_batch_fork on an attached slot detaches it: a forked slot is
+ *          self-contained.
+ * len:     P, 0 for no prefix, a negative LLMK_E_* on error (as llmk_path).
+ * A NULL batch is LLMK_E_ARG before anything touches a device, in all three.
+ * llmk_batch_forward, llmk_batch_decode, llmk_rows_decode, llmk_rows_sample_logits and llmk_batch_time take attached slots like any
+ * other, with one more check up front: a row of an attached slot must have pos > P, else LLMK_E_ARG before anything runs.  A pass may
+ * mix attached and unattached rows; penalties and records work unchanged (per slot, by absolute position).  The f16-range redo rewrites
+ * the rows' own K/V rows; the prefix is a copy of what the context's prefill left and is not redone.
+ * An attached row's logits are within the 1e-4 parity bar of llmk_forward's on that sequence alone and of the same slot filled by
+ * llmk_batch_fork -- not bit-identical to either: the attention folds the prefix's parts, then the row's own.  The same call on the same
+ * state returns the same bits (no float atomics, a fixed part order, no waiting across workgroups).  A pass WITHOUT an attached row
+ * returns the bits it returned before a prefix was set.
+ * Out of scope: more than one prefix per batch, a tree of prefixes, a shorter own cache for attached slots (the memory saving), f16
+ * K/V, any automatic choice between fork and attach. */
+int llmk_prefix_set(llmk_batch *b, int n_pos);
+int llmk_prefix_attach(llmk_batch *b, int slot);
+int llmk_prefix_len(llmk_batch *b);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

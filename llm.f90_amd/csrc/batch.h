@@ -7,6 +7,7 @@
 //   bd_attn        decode attention over many caches: one workgroup per (kv head, row, part of the row's timesteps)
 //   bd_attn_merge  the parts of a row folded in part order
 //   bd_advance     llmk_batch_decode: the picked id becomes the row's next token, its position moves on -- on the device
+//   bd_attn_prefix / bd_attn_own / bd_attn_fold   a pass with rows ATTACHED to the batch's shared prefix (llmk_prefix_*, below)
 // The caches are [L][n_slots][seq_len][KV] f32.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -228,6 +229,243 @@ __global__ __launch_bounds__(256) void bd_attn_merge_kernel(const float* __restr
             const float e = ml.x == -INFINITY ? 0.f : expf(ml.x - M);
             L += ml.y * e;
             val += po[((pbase + p) * BD_MAX_GROUP + q) * HS + d] * e;
+        }
+        out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+    }
+}
+
+// ---- a shared prefix (llmk_prefix_*)                                                                                  ------------
+// A batch can hold ONE copy of the K/V rows of positions 1..P, [L][P][KV]; an ATTACHED slot's sequence is those rows and then its own
+// cache rows P .. pos-1 (still indexed by absolute position).  A pass with at least one attached row runs three kernels per layer
+// instead of bd_attn_kernel (+ merge); a pass with none runs exactly what it ran before.
+//   bd_attn_prefix_kernel  the prefix rows against the query heads of up to RG attached rows at once: one read per column group
+//   bd_attn_own_kernel     bd_attn_kernel over a row's OWN rows first[slot] .. pos-1 (first = P attached, 0 not), never normalising
+//   bd_attn_fold_kernel    a (row, kv head)'s prefix parts in part order, then its own parts in part order
+// Part states in such a pass: np = prefix parts + own parts per (row, kv head), kv_mul query heads each (NOT padded to BD_MAX_GROUP:
+// the buffers hold LLMK_MAX_BATCH rows); state s of (b, kvh), head q: pml[((b * nkv + kvh) * np + s) * kv_mul + q], po that * HS.
+
+// rows per column group: the 16 MFMA columns hold (row, query head) pairs of one kv head
+__host__ __device__ inline int bd_prefix_rg(int kv_mul) { return BD_MAX_GROUP / kv_mul < 1 ? 1 : BD_MAX_GROUP / kv_mul; }
+__host__ __device__ inline int bd_prefix_groups(int n_att, int kv_mul) { return (n_att + bd_prefix_rg(kv_mul) - 1) / bd_prefix_rg(kv_mul); }
+// The prefix's split rule: bd_parts with the column groups of the attached rows in the place of the rows and P in the place of the
+// longest row.  Tiles per part: bd_tiles_per_part(P, parts).
+__host__ __device__ inline int bd_prefix_parts(int n_att, int n_kv_heads, int kv_mul, int P, int n_cu) {
+    return bd_parts(bd_prefix_groups(n_att, kv_mul), n_kv_heads, P, n_cu);
+}
+
+// bd_attn_kernel's tile loop for the kernels below: wave `wid` takes tiles t0 + wid, t0 + wid + 8, .. < t1 of the cache at kb / vb
+// (already at this lane's kv head and fragment); rows lo <= r < hi are visible, loads clamp the row index to hi - 1 (hi >= 1).
+template <int HS>
+__device__ __forceinline__ void bd_attn_tiles(const float (&qf)[HS / 4], const float* __restrict__ kb, const float* __restrict__ vb, int KV,
+                                              int lo, int hi, int t0, int t1, int wid, int li, int g, float& m_run, float& l_run,
+                                              pf_v4f (&O)[HS / 16]) {
+    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
+    const float scale = sqrtf((float)HS);
+    const int ntile = (hi + BD_TILE - 1) / BD_TILE;
+    float kn[DG], vn[4][NT];
+    auto load = [&](int r0) {
+        const float* kp = kb + (size_t)min(r0 + li, hi - 1) * KV;
+#pragma unroll
+        for (int m = 0; m < DG; m += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(kp + m);
+            kn[m] = v.x; kn[m + 1] = v.y; kn[m + 2] = v.z; kn[m + 3] = v.w;
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const float* vp = vb + (size_t)min(r0 + 4 * g + v, hi - 1) * KV;
+            if constexpr (NT % 4 == 0) {
+#pragma unroll
+                for (int t = 0; t < NT; t += 4) {
+                    const float4 x = *reinterpret_cast<const float4*>(vp + t);
+                    vn[v][t] = x.x; vn[v][t + 1] = x.y; vn[v][t + 2] = x.z; vn[v][t + 3] = x.w;
+                }
+            } else if constexpr (NT == 2) {
+                const float2 x = *reinterpret_cast<const float2*>(vp);
+                vn[v][0] = x.x; vn[v][1] = x.y;
+            } else {
+                vn[v][0] = vp[0];
+            }
+        }
+    };
+    load(min(t0 + wid, ntile - 1) * BD_TILE);
+    for (int kt = t0 + wid; kt < t1; kt += NW) {
+        const int r0 = kt * BD_TILE;
+        float kf[DG], vf[4][NT];
+#pragma unroll
+        for (int m = 0; m < DG; ++m) kf[m] = kn[m];
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
+        load(min(kt + NW, ntile - 1) * BD_TILE);
+        pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int m = 0; m < DG; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[m], qf[m], acc, 0, 0, 0);
+        float sc[4], mx = -INFINITY;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = r0 + 4 * g + v;
+            sc[v] = (r >= lo && r < hi) ? acc[v] / scale : -INFINITY;
+            mx = fmaxf(mx, sc[v]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const bool any = m_new != -INFINITY;
+        const float alpha = !any ? 1.f : (m_run == -INFINITY ? 0.f : expf(m_run - m_new));
+        float p[4], rs = 0.f;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            p[v] = (any && sc[v] != -INFINITY) ? expf(sc[v] - m_new) : 0.f;
+            rs += p[v];
+        }
+        rs += __shfl_xor(rs, 16, 64);
+        rs += __shfl_xor(rs, 32, 64);
+        l_run = l_run * alpha + rs;
+        m_run = m_new;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float ar = __shfl(alpha, 4 * g + r, 64);                     // O rows are columns 4g+r
+#pragma unroll
+            for (int t = 0; t < NT; ++t) O[t][r] *= ar;
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) O[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(p[v], vf[v][t], O[t], 0, 0, 0);
+    }
+}
+
+// The waves' running states through LDS into ONE part state per live column: column c's goes to state index state_of(c)
+// (bd_attn_kernel's merge, never normalised).  A part without a visible row leaves M = -inf, L = 0, O = 0.
+template <int HS, class StateOf>
+__device__ __forceinline__ void bd_attn_leave(float m_run, float l_run, const pf_v4f (&O)[HS / 16], int live, float* __restrict__ po,
+                                              float2* __restrict__ pml, StateOf state_of) {
+    constexpr int NT = HS / 16, NW = BD_WAVES;
+    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
+    float* so = reinterpret_cast<float*>(pf_smem);   // [NW][16][HS]
+    float* sm = so + NW * 16 * HS;                    // [NW][16]
+    float* sl = sm + NW * 16;                         // [NW][16]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    if (g == 0) {
+        sm[wid * 16 + li] = m_run;
+        sl[wid * 16 + li] = l_run;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) so[(size_t)(wid * 16 + 4 * g + r) * HS + NT * li + t] = O[t][r];
+    __syncthreads();
+    for (int idx = tid; idx < live * HS; idx += NW * WAVE) {
+        const int c = idx / HS, d = idx % HS;
+        float M = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[w * 16 + c]);
+        float L = 0.f, val = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float mw = sm[w * 16 + c];
+            const float e = mw == -INFINITY ? 0.f : expf(mw - M);
+            L += sl[w * 16 + c] * e;
+            val += so[(size_t)(w * 16 + c) * HS + d] * e;
+        }
+        const size_t s = state_of(c);
+        po[s * HS + d] = val;
+        if (d == 0) pml[s] = make_float2(M, L);
+    }
+}
+
+// One workgroup per (kv head, column group, prefix part).  colmap [groups][RG]: the pass's attached rows, in row order, -1 behind the
+// last.  Column c of a group is (row colmap[c / kv_mul], query head c % kv_mul of the kv head); columns from the last live one on
+// repeat it and are not written out.  Every attached row sees the whole prefix: the predicate is cache row < P alone.
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const float* __restrict__ Q, const float* __restrict__ pk,
+                                                                         const float* __restrict__ pv, float* __restrict__ po,
+                                                                         float2* __restrict__ pml, const int* __restrict__ colmap, int n,
+                                                                         int P, int KV, int kv_mul, int E, int tpp, int np) {
+    constexpr int DG = HS / 4, NT = HS / 16;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x, rg = bd_prefix_rg(kv_mul);
+    const int* cm = colmap + blockIdx.y * rg;
+    int nr = 0;
+    while (nr < rg && (unsigned)cm[nr] < (unsigned)n) ++nr;
+    if (nr == 0 || P < 1) return;                     // whole workgroup: no barrier is pending
+    const int live = nr * kv_mul, c = min(li, live - 1);
+    float qf[DG];
+    {
+        const float* qp = Q + (size_t)cm[c / kv_mul] * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG;
+#pragma unroll
+        for (int m = 0; m < DG; m += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(qp + m);
+            qf[m] = v.x; qf[m + 1] = v.y; qf[m + 2] = v.z; qf[m + 3] = v.w;
+        }
+    }
+    float m_run = -INFINITY, l_run = 0.f;
+    pf_v4f O[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
+    const int ntile = (P + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
+    bd_attn_tiles<HS>(qf, pk + (size_t)kvh * HS + g * DG, pv + (size_t)kvh * HS + NT * li, KV, 0, P, t0, t1, wid, li, g, m_run, l_run, O);
+    bd_attn_leave<HS>(m_run, l_run, O, live, po, pml, [&](int col) {
+        return (((size_t)cm[col / kv_mul] * nkv + kvh) * np + part) * kv_mul + col % kv_mul;
+    });
+}
+
+// bd_attn_kernel for a pass with attached rows: the row's own cache rows first[slot] .. pos-1, tiles counted from the one that holds
+// row `first` (that tile masks the rows below it); part `part` leaves state p0 + part.  One workgroup per (kv head, row, own part).
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const float* __restrict__ Q, const float* __restrict__ kc,
+                                                                      const float* __restrict__ vc, float* __restrict__ po,
+                                                                      float2* __restrict__ pml, BdCaches bc, const int* __restrict__ first,
+                                                                      int KV, int kv_mul, int E, int tpp, int np, int p0) {
+    constexpr int DG = HS / 4, NT = HS / 16;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, b = blockIdx.y, part = blockIdx.z, nkv = gridDim.x;
+    const BdRow row = bc.rows[b];
+    if (!bd_row_ok(bc, row)) return;                  // whole workgroup: no barrier is pending
+    const int lo = first[row.slot], nrows = row.pos;  // (the host refuses an attached row at pos <= P)
+    const int h = kvh * kv_mul + min(li, kv_mul - 1);
+    float qf[DG];
+    {
+        const float* qp = Q + (size_t)b * E + (size_t)h * HS + g * DG;
+#pragma unroll
+        for (int m = 0; m < DG; m += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(qp + m);
+            qf[m] = v.x; qf[m + 1] = v.y; qf[m + 2] = v.z; qf[m + 3] = v.w;
+        }
+    }
+    float m_run = -INFINITY, l_run = 0.f;
+    pf_v4f O[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
+    const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
+    const size_t base = (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS;
+    bd_attn_tiles<HS>(qf, kc + base + g * DG, vc + base + NT * li, KV, lo, nrows, t0, t1, wid, li, g, m_run, l_run, O);
+    bd_attn_leave<HS>(m_run, l_run, O, kv_mul, po, pml, [&](int q) { return (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q; });
+}
+
+// (row, kv head): the prefix parts 0 .. p0-1 in part order -- an unattached row of a mixed pass has none: nothing wrote them, they are
+// skipped, which is what folding M = -inf, L = 0 does -- then the own parts p0 .. np-1 in part order.  The row's last own row is
+// always visible, so L > 0.
+template <int HS>
+__global__ __launch_bounds__(256) void bd_attn_fold_kernel(const float* __restrict__ po, const float2* __restrict__ pml,
+                                                           float* __restrict__ out, BdCaches bc, const int* __restrict__ first,
+                                                           int kv_mul, int E, int np, int p0) {
+    const int kvh = blockIdx.x, b = blockIdx.y, nkv = gridDim.x;
+    const BdRow row = bc.rows[b];
+    if (!bd_row_ok(bc, row)) return;
+    const size_t sbase = ((size_t)b * nkv + kvh) * np;
+    const int pa = first[row.slot] > 0 ? 0 : p0;
+    for (int idx = threadIdx.x; idx < kv_mul * HS; idx += 256) {
+        const int q = idx / HS, d = idx % HS;
+        float M = -INFINITY;
+        for (int p = pa; p < np; ++p) M = fmaxf(M, pml[(sbase + p) * kv_mul + q].x);
+        float L = 0.f, val = 0.f;
+        for (int p = pa; p < np; ++p) {
+            const float2 ml = pml[(sbase + p) * kv_mul + q];
+            const float e = ml.x == -INFINITY ? 0.f : expf(ml.x - M);
+            L += ml.y * e;
+            val += po[((sbase + p) * kv_mul + q) * HS + d] * e;
         }
         out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
     }

@@ -259,6 +259,15 @@ struct llmk_batch {
     llmk_logprob_record *d_lp = nullptr, *h_lp = nullptr;      // [lp_cap] a call's records, [row][step]
     size_t lp_cap = 0;
     unsigned *d_lp_top = nullptr, *h_lp_top = nullptr;         // the call's top_n word
+    // a shared prefix (llmk_prefix_*, batch.h), allocated by the first llmk_prefix_set that sets one: a batch without one has none of it
+    int P = 0, n_attached = 0;                   // the prefix's positions; slots attached to it
+    size_t px_cap = 0;                           // positions d_pk / d_pv have room for
+    float *d_pk = nullptr, *d_pv = nullptr;      // [L][P][KV]: a snapshot of the context's rows of positions 1..P
+    int *d_first = nullptr, *h_first = nullptr;  // [n_slots] a slot's first own cache row: P attached, 0 not (h_first pinned)
+    int *d_colmap = nullptr, *h_colmap = nullptr;      // [LLMK_MAX_BATCH + BD_MAX_GROUP] bd_attn_prefix_kernel's column map (h_colmap pinned)
+    int pass_att = 0;                            // attached rows among the rows bd_upload_rows uploaded last
+    float* d_xpo = nullptr;                      // part states of a pass with attached rows:
+    float2* d_xpml = nullptr;                    //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_xpo that [hs]
 };
 
 namespace {
@@ -1454,7 +1463,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 405; }
+int llmk_version(void) { return 406; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2465,10 +2474,10 @@ constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 *
 
 static void batch_free(llmk_batch* b) {
     void* dev[] = {b->d_kc, b->d_vc, b->d_rows, b->d_tok, b->d_out, b->d_logits, b->d_po, b->d_pml, b->d_next, b->d_filt, b->d_out2, b->d_err, b->d_ids,
-                   b->d_hist, b->d_pen_cnt, b->d_pen, b->d_raw, b->d_lp, b->d_lp_top};
+                   b->d_hist, b->d_pen_cnt, b->d_pen, b->d_raw, b->d_lp, b->d_lp_top, b->d_pk, b->d_pv, b->d_first, b->d_colmap, b->d_xpo, b->d_xpml};
     for (void* p : dev)
         if (p) hipFree(p);
-    void* host[] = {b->h_rows, b->h_tok, b->h_filt, b->h_out, b->h_err, b->h_pen, b->h_lp, b->h_lp_top};
+    void* host[] = {b->h_rows, b->h_tok, b->h_filt, b->h_out, b->h_err, b->h_pen, b->h_lp, b->h_lp_top, b->h_first, b->h_colmap};
     for (void* p : host)
         if (p) hipHostFree(p);
     delete b;
@@ -2476,12 +2485,29 @@ static void batch_free(llmk_batch* b) {
 
 // One pass, ENQUEUED on the context's stream: the n rows in d_rows / d_tok through every layer, the classifier and the per-row first
 // maximum (into d_out + n); the logits of every row into d_logits when asked for.  max_pos: the longest row (the attention's split rule).
-static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp) {
+// With attached rows among them (pass_att > 0, llmk_prefix_*) the attention is the three kernels of batch.h's prefix section; `step`:
+// the rows stand `step` positions behind the uploaded ones (a decode's later passes).
+static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, int step = 0) {
     llmk_ctx* c = b->ctx;
     PfLane& w = c->pf[0];
     const int E = c->E, KV = c->KV, QKV = E + 2 * KV, T = n;
     const BdCaches bc{b->d_rows, (size_t)b->seq_len * KV, b->n_slots, b->seq_len};
-    const int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
+    int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
+    const bool shared = b->pass_att > 0;
+    int groups = 0, pparts = 0, ptpp = 0;
+    if (shared) {
+        // the own parts' split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`
+        int own = 0;
+        for (int i = 0; i < n; ++i) {
+            const int pos = b->h_rows[i].pos + step;
+            own = std::max(own, (pos + BD_TILE - 1) / BD_TILE - b->h_first[b->h_rows[i].slot] / BD_TILE);
+        }
+        parts = bd_parts(n, c->nkv, own * BD_TILE, c->n_cu);
+        tpp = bd_tiles_per_part(own * BD_TILE, parts);
+        groups = bd_prefix_groups(b->pass_att, c->kv_mul);
+        pparts = bd_prefix_parts(b->pass_att, c->nkv, c->kv_mul, b->P, c->n_cu);
+        ptpp = bd_tiles_per_part(b->P, pparts);
+    }
     PfEpiArgs e;
     // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
@@ -2492,6 +2518,19 @@ static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, c
         HIPRET(hipGetLastError());
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
+            if (shared) {
+                const int np = pparts + parts;
+                const size_t px = (size_t)l * b->P * KV;
+                hipLaunchKernelGGL((bd_attn_prefix_kernel<HS>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                                   w.Q, b->d_pk + px, b->d_pv + px, b->d_xpo, b->d_xpml, b->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
+                HIPRET(hipGetLastError());
+                hipLaunchKernelGGL((bd_attn_own_kernel<HS>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                                   w.Q, kc, vc, b->d_xpo, b->d_xpml, bc, b->d_first, KV, c->kv_mul, E, tpp, np, pparts);
+                HIPRET(hipGetLastError());
+                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_xpo, b->d_xpml, w.XB, bc, b->d_first,
+                                   c->kv_mul, E, np, pparts);
+                return hipGetLastError();
+            }
             hipLaunchKernelGGL((bd_attn_kernel<HS>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
                                w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
             HIPRET(hipGetLastError());
@@ -2528,6 +2567,7 @@ static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* 
         seen[slots[i]] = true;
         if (fed && (tokens[i] < 1 || tokens[i] > b->ctx->V)) return false;
         if (pos[i] < 1 || pos[i] > b->seq_len || span - 1 > b->seq_len - pos[i]) return false;
+        if (b->n_attached > 0 && pos[i] <= b->h_first[slots[i]]) return false;      // an attached slot's positions 1..P are the prefix
     }
     return true;
 }
@@ -2537,6 +2577,17 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
         b->h_tok[i] = tokens ? tokens[i] - 1 : 0;      // (null: rows that feed no token, bd_rows_ok)
     }
     hipStream_t st = b->ctx->stream;
+    b->pass_att = 0;
+    if (b->n_attached > 0) {
+        // the column map: the attached rows in row order, -1 up to the end of the last column group
+        for (int i = 0; i < n; ++i)
+            if (b->h_first[slots[i]] > 0) b->h_colmap[b->pass_att++] = i;
+        if (b->pass_att > 0) {
+            const int rg = bd_prefix_rg(b->ctx->kv_mul), cells = bd_prefix_groups(b->pass_att, b->ctx->kv_mul) * rg;
+            for (int k = b->pass_att; k < cells; ++k) b->h_colmap[k] = -1;
+            HIPRET(hipMemcpyAsync(b->d_colmap, b->h_colmap, (size_t)cells * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+    }
     HIPRET(hipMemcpyAsync(b->d_rows, b->h_rows, (size_t)n * sizeof(BdRow), hipMemcpyHostToDevice, st));
     return hipMemcpyAsync(b->d_tok, b->h_tok, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
 }
@@ -2603,6 +2654,13 @@ int llmk_batch_destroy(llmk_batch* b) {
     return LLMK_OK;
 }
 
+// a slot joins (first = P) or leaves (0) the prefix: its `first` word, here and on the device (ENQUEUED)
+static hipError_t prefix_first(llmk_batch* b, int slot, int first) {
+    b->n_attached += (first > 0) - (b->h_first[slot] > 0);
+    b->h_first[slot] = first;
+    return hipMemcpyAsync(b->d_first + slot, b->h_first + slot, sizeof(int), hipMemcpyHostToDevice, b->ctx->stream);
+}
+
 int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
     if (!b || slot < 0 || slot >= b->n_slots || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S)) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
@@ -2619,8 +2677,78 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
         }
     // a forked or emptied slot is a new sequence: no token fed yet (the caller records the prompt with llmk_rows_set_history)
     if (b->d_hist) HIPCHK(hipMemsetAsync(b->d_hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
+    if (b->h_first && b->h_first[slot] > 0) HIPCHK(prefix_first(b, slot, 0));      // a forked slot is self-contained: it leaves the prefix
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
+}
+
+// ---- a shared prefix (batch.h): one copy of the K/V rows of positions 1..P, the slots attached to it keep their own rows behind it ----
+int llmk_prefix_set(llmk_batch* b, int n_pos) {
+    if (!b || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S) - 1) return LLMK_E_ARG;
+    if (b->n_attached > 0) return LLMK_E_STATE;
+    llmk_ctx* c = b->ctx;
+    if (n_pos == 0) { b->P = 0; return LLMK_OK; }      // (the buffers stay for the next prefix)
+    int rc = check_ready(c);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t row = (size_t)c->KV, nb = LLMK_MAX_BATCH;
+    // what a pass with attached rows needs beyond the prefix rows (each once; a call that failed half way is picked up where it stopped)
+    const size_t states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul, words = (size_t)b->n_slots * sizeof(int);
+    if (!b->d_first) {
+        HIPCHK(dev_alloc(&b->d_first, words));
+        HIPCHK(hipMemsetAsync(b->d_first, 0, words, c->stream));
+    }
+    if (!b->h_first) {
+        HIPCHK(hipHostMalloc(&b->h_first, words, hipHostMallocDefault));
+        memset(b->h_first, 0, words);
+    }
+    if (!b->d_colmap) HIPCHK(dev_alloc(&b->d_colmap, (nb + BD_MAX_GROUP) * sizeof(int)));
+    if (!b->h_colmap) HIPCHK(hipHostMalloc(&b->h_colmap, (nb + BD_MAX_GROUP) * sizeof(int), hipHostMallocDefault));
+    if (!b->d_xpo) HIPCHK(dev_alloc(&b->d_xpo, states * c->hs * sizeof(float)));
+    if (!b->d_xpml) HIPCHK(dev_alloc(&b->d_xpml, states * sizeof(float2)));
+    HIPCHK(with_head_size(c->hs, [](auto hs) -> hipError_t {
+        constexpr int HS = decltype(hs)::value;
+        HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS)));
+        return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+    }));
+    if (b->px_cap < (size_t)n_pos) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (b->d_pk) { hipFree(b->d_pk); b->d_pk = nullptr; }
+        if (b->d_pv) { hipFree(b->d_pv); b->d_pv = nullptr; }
+        b->px_cap = 0; b->P = 0;
+        HIPCHK(dev_alloc(&b->d_pk, (size_t)c->L * n_pos * row * sizeof(float)));
+        HIPCHK(dev_alloc(&b->d_pv, (size_t)c->L * n_pos * row * sizeof(float)));
+        b->px_cap = (size_t)n_pos;
+    }
+    float* caches[2][2] = {{b->d_pk, c->d_kc}, {b->d_pv, c->d_vc}};
+    for (auto& p : caches)
+        for (int l = 0; l < c->L; ++l)
+            HIPCHK(hipMemcpyAsync(p[0] + (size_t)l * n_pos * row, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float),
+                                  hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b->P = n_pos;
+    return LLMK_OK;
+}
+
+int llmk_prefix_attach(llmk_batch* b, int slot) {
+    if (!b || slot < 0 || slot >= b->n_slots) return LLMK_E_ARG;
+    if (b->P < 1) return LLMK_E_STATE;
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // a new sequence behind the prefix: own rows and token record as llmk_batch_fork(b, slot, 0) leaves them
+    const size_t slot_rows = (size_t)b->seq_len * c->KV;
+    for (float* base : {b->d_kc, b->d_vc})
+        for (int l = 0; l < c->L; ++l)
+            HIPCHK(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(float), c->stream));
+    if (b->d_hist) HIPCHK(hipMemsetAsync(b->d_hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
+    HIPCHK(prefix_first(b, slot, b->P));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+
+int llmk_prefix_len(llmk_batch* b) {
+    if (!b) return -LLMK_E_ARG;
+    return b->P;
 }
 
 int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos, float* logits_out, int* argmax_out) {
@@ -2786,7 +2914,7 @@ static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, 
     HIPCHK(hipMemsetAsync(b->d_err, 0, sizeof(unsigned), c->stream));
     const int max_pos0 = *std::max_element(pos0, pos0 + n);
     for (int s = 0; s < steps; ++s) {
-        HIPCHK(bd_pass(b, n, max_pos0 + s, samplers != nullptr || lp != nullptr, sp));
+        HIPCHK(bd_pass(b, n, max_pos0 + s, samplers != nullptr || lp != nullptr, sp, s));
         // row i's draw: the kernels the verification hooks run, on the row's logits, position (the row words) and words.  The advance
         // runs behind them: the penalty kernel of the next step finds the fed token in d_tok and the new position in d_rows
         const int* picked = reinterpret_cast<const int*>(b->d_out + n);
@@ -2877,6 +3005,8 @@ int llmk_rows_get_history(llmk_batch* b, int slot, int* tokens_out, int n, int p
 
 int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     if (!b || !avg_ms || n < 1 || n > b->n_slots || pos < 1 || pos > b->seq_len || iters < 1) return LLMK_E_ARG;
+    for (int i = 0; i < n && b->n_attached > 0; ++i)
+        if (pos <= b->h_first[i]) return LLMK_E_ARG;      // (slots 0..n-1: an attached one's positions 1..P are the prefix)
     llmk_ctx* c = b->ctx;
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);

@@ -9,11 +9,13 @@
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
 !         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix]]
 !
 ! --parallel N (1 .. 128, one GPU): N completions of the prompt decoded TOGETHER (llmk_batch_*, DESIGN.md section 3i) -- the prompt is
 ! prefilled once and forked into N slots, every pass over the weights serves all N; seeds seed, seed+1, ... at -t > 0 (the filter
 ! flags apply), greedy at -t 0 (N equal texts).  The completions are printed after generation, each under a line [k], k = 0 .. N-1.
+! --share-prefix: the N slots are ATTACHED to one copy of the prompt's K/V rows (llmk_prefix_*) instead of holding a copy each: the
+! attention reads the prompt rows once per group of rows, not once per row.
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
 ! (one process per GPU, devices d..d+N-1), every rank loads the file and keeps its shard, the ranks meet through a
@@ -52,6 +54,7 @@ module arg_parse
      logical :: gguf_eps, gguf_rope_base   ! extension: honour the file's rms epsilon / RoPE base (the reference hard-codes
                                            ! 1e-5 and 10000, llama2.f90:454,545)
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
+     logical :: share_prefix      ! extension: --share-prefix: the --parallel slots share ONE copy of the prompt's K/V rows (llmk_prefix_*)
      integer :: parallel          ! extension: --parallel N (0 = off): N completions decoded together on one GPU (llmk_batch_*)
      integer :: logprobs          ! extension: --logprobs N (0 .. 20): the log-prob of every generated token and its N most likely
                                   ! alternatives, from the device (llmk_*_sample_lp); -1 = off
@@ -98,6 +101,7 @@ contains
     a%score = .false.
     a%logprobs = -1
     a%parallel = 0
+    a%share_prefix = .false.
 
     nargs = command_argument_count()
     i = 1
@@ -137,6 +141,7 @@ contains
        case ("--gguf-rope-base");    a%gguf_rope_base = .true.; i = i + 1
        case ("--encode");            a%encode_only = .true.;   i = i + 1
        case ("--score");             a%score = .true.;         i = i + 1
+       case ("--share-prefix");      a%share_prefix = .true.;  i = i + 1
        case ("--parallel")
           read (val, *) a%parallel
           if (a%parallel < 1 .or. a%parallel > 128) then
@@ -308,6 +313,10 @@ program llm
         print *, "--parallel: the penalties are not available for completions decoded together (llmk_batch_decode applies none)"
         stop 1
      end if
+  end if
+  if (opts%share_prefix .and. opts%parallel == 0) then
+     print *, "--share-prefix: nothing to share without --parallel N"
+     stop 1
   end if
   lead = opts%tp_rank == 0
   if (opts%ngpu > 1) call tp_launch_workers()
@@ -484,8 +493,14 @@ program llm
         if (opts%verbose) print *, "device sampler seed:", dseed
         par_sp = c_loc(par_samplers)
      end if
+     ! --share-prefix: one copy of the prompt's rows for all N slots (without a prompt there is nothing to share)
+     if (opts%share_prefix .and. k > 0) call llmk_check(llmk_prefix_set(pbatch, int(k, c_int)), "llmk_prefix_set")
      do j = 1, opts%parallel
-        call llmk_check(llmk_batch_fork(pbatch, int(j - 1, c_int), int(k, c_int)), "llmk_batch_fork")
+        if (opts%share_prefix .and. k > 0) then
+           call llmk_check(llmk_prefix_attach(pbatch, int(j - 1, c_int)), "llmk_prefix_attach")
+        else
+           call llmk_check(llmk_batch_fork(pbatch, int(j - 1, c_int), int(k, c_int)), "llmk_batch_fork")
+        end if
         par_slots(j) = int(j - 1, c_int)
         par_tokens(j) = int(token, c_int)
         par_pos(j) = int(k + 1, c_int)

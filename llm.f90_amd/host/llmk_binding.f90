@@ -311,6 +311,21 @@ module llmk_binding
        type(c_ptr), value :: samplers
        integer(c_int), intent(out) :: ids_out(*)
      end function
+     ! a shared prefix (include/llmk.h): `--parallel N --share-prefix`
+     integer(c_int) function llmk_prefix_set(batch, n_pos) bind(C, name="llmk_prefix_set")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n_pos
+     end function
+     integer(c_int) function llmk_prefix_attach(batch, slot) bind(C, name="llmk_prefix_attach")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot
+     end function
+     integer(c_int) function llmk_prefix_len(batch) bind(C, name="llmk_prefix_len")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+     end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
      ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too

@@ -29,7 +29,7 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
            "llmk_batch_decode", "llmk_batch_time", "llmk_rows_set_history", "llmk_rows_get_history", "llmk_rows_decode",
-           "llmk_rows_sample_logits", "llmk_reset", "llmk_timings",
+           "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -185,6 +185,10 @@ def lib():
             L.llmk_rows_get_history.argtypes = [vp, ci, pi, ci, ci]
             L.llmk_rows_decode.argtypes = [vp, ci, pi, pi, pi, ci, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(Logprobs), pi]
             L.llmk_rows_sample_logits.argtypes = [vp, ci, pi, pi, cf, C.POINTER(Sampler), C.POINTER(Penalties), C.POINTER(Logprobs), pi, pi, cf, cf]
+        if hasattr(L, "llmk_prefix_set"):
+            L.llmk_prefix_set.argtypes = [vp, ci]
+            L.llmk_prefix_attach.argtypes = [vp, ci]
+            L.llmk_prefix_len.argtypes = [vp]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -602,6 +606,23 @@ class Batch:
     def fork(self, slot: int, n_pos: int):
         """the context's K/V rows of positions 1..n_pos into `slot` (llmk_batch_fork); n_pos = 0 empties the slot"""
         _ck(lib().llmk_batch_fork(self._h, slot, n_pos))
+
+    def set_prefix(self, n_pos: int):
+        """the context's K/V rows of positions 1..n_pos become the batch's one shared prefix (llmk_prefix_set); 0 drops it"""
+        _ck(lib().llmk_prefix_set(self._h, n_pos))
+
+    def attach(self, slot: int):
+        """`slot` becomes a new sequence behind the prefix: its positions 1..P are the prefix's rows, read once for all attached rows
+        of a pass; its own rows start at position P + 1 (llmk_prefix_attach).  fork() detaches."""
+        _ck(lib().llmk_prefix_attach(self._h, slot))
+
+    @property
+    def prefix_len(self) -> int:
+        """positions of the shared prefix, 0 for none (llmk_prefix_len)"""
+        n = lib().llmk_prefix_len(self._h)
+        if n < 0:
+            _ck(-n)
+        return n
 
     def forward(self, slots, tokens, pos, want_logits: bool = True, want_argmax: bool = True):
         """one pass (llmk_batch_forward): (logits [n][V], argmax [n] 1-based), or the one that was asked for"""

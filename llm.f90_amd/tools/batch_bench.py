@@ -12,7 +12,13 @@ Prints a table on stdout and, with --json, one JSON line.
     python -m llm_f90_amd.tools.batch_bench --shape tinyllama --type f32 --sampled
 
 measures whole decode calls instead (64 steps from position 25 at 8, 32 and 128 rows): greedy, one sampler per row, and -- through
-llmk_rows_decode, where the library has it -- a repeat penalty and log-prob records on top."""
+llmk_rows_decode, where the library has it -- a repeat penalty and log-prob records on top.
+
+    python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k --shared-prefix 1000
+
+times the pass at 8, 32 and 128 rows and position --pos (1024) with the slots ATTACHED to one P-position prefix (llmk_prefix_*) and with
+the slots FORKED at P, in one process, alternating; against another build selected with LLMK_LIB that has no llmk_prefix_*, the forked
+figures alone (--forked-only: the same from this build, no prefix ever set)."""
 from __future__ import annotations
 
 import argparse
@@ -90,6 +96,58 @@ def sampled(m, shape, repeats: int):
     return out
 
 
+def shared_prefix(m, shape, P: int, pos: int, iters: int, repeats: int, forked_only: bool = False):
+    """--shared-prefix P: llmk_batch_time at SAMPLED_ROWS rows, all at `pos`, behind a P-position prompt prefilled on the context -- the
+    slots attached to one copy of its K/V rows, then the slots forked at P, `repeats` times in turn, each measurement behind a warm-up
+    of the same form."""
+    if not 1 <= P < pos <= shape.seq_len:
+        raise SystemExit(f"--shared-prefix P --pos Q: 1 <= P < Q <= {shape.seq_len}")
+    have = hasattr(llmk.lib(), "llmk_prefix_set") and not forked_only
+    m.reset()
+    m.prefill([2] + [3 + i % (shape.vocab_size - 3) for i in range(P - 1)], 1)
+    slots, b = max(SAMPLED_ROWS), None
+    while b is None:
+        try:
+            b = llmk.Batch(m, slots, pos)
+        except llmk.LlmkError as e:
+            if slots == 1:
+                raise
+            print(f"# pos {pos}: no room for {slots} slots ({e}); trying {slots // 2}", file=sys.stderr)
+            slots //= 2
+    out = []
+    for n in SAMPLED_ROWS:
+        if n > slots:
+            continue
+        ms = {"forked": [], "attached": []}
+        for _ in range(repeats):
+            for form in (("attached", "forked") if have else ("forked",)):
+                for j in range(n):
+                    b.fork(j, P)                                # (a fork detaches; the prefix is set with no slot attached)
+                if form == "attached":
+                    b.set_prefix(P)
+                    for j in range(n):
+                        b.attach(j)
+                b.time(n, pos, 3)                               # warm-up in this form
+                ms[form].append(b.time(n, pos, iters))
+        row = {"n": n, "pos": pos, "prefix": P}
+        for form, xs in ms.items():
+            if xs:
+                row[form + "_ms"], row[form + "_spread"] = med_spread(xs)
+        out.append(row)
+    b.close()
+    return out
+
+
+def print_shared(shape_name, type_name, rows, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# batched decode behind a shared prompt, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per form, "
+          f"the forms alternating (spread = (max - min) / median)")
+    print(f"{'n':>5} {'prefix':>7} {'pos':>6} {'forked ms':>10} {'spread':>7} {'attached ms':>12} {'spread':>7} {'forked / attached':>18}")
+    for r in rows:
+        att = f"{r['attached_ms']:12.3f} {r['attached_spread']:7.3f} {r['forked_ms'] / r['attached_ms']:18.2f}" if "attached_ms" in r else f"{'-':>12} {'-':>7} {'-':>18}"
+        print(f"{r['n']:5d} {r['prefix']:7d} {r['pos']:6d} {r['forked_ms']:10.3f} {r['forked_spread']:7.3f} {att}")
+
+
 def print_sampled(shape_name, type_name, rows, repeats):
     print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
     print(f"# llmk_batch_decode / llmk_rows_decode, {shape_name} {type_name}, {SAMPLED_STEPS} steps from position {SAMPLED_POS}: wall clock of the call, "
@@ -114,6 +172,13 @@ def main():
     ap.add_argument("--sampled", action="store_true",
                     help="only the sampled-decode table: whole llmk_batch_decode / llmk_rows_decode calls at 8, 32 and 128 rows (also "
                          "against another build selected with LLMK_LIB: the rows functions are measured where the library has them)")
+    ap.add_argument("--shared-prefix", type=int, default=0, metavar="P",
+                    help="only the shared-prefix table: the pass at 8, 32 and 128 rows at --pos with the slots attached to one P-position "
+                         "prefix and with the slots forked at P, alternating")
+    ap.add_argument("--pos", type=int, default=1024, help="the rows' position of --shared-prefix")
+    ap.add_argument("--forked-only", action="store_true",
+                    help="with --shared-prefix: only the forked figures, no prefix is ever set (what another build selected with LLMK_LIB "
+                         "that has no llmk_prefix_* measures: the like-for-like baseline of the unshared path)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
@@ -124,6 +189,13 @@ def main():
         print_sampled(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.repeats)
         if a.json:
             print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "sampled": rows}))
+        return
+    if a.shared_prefix:
+        rows = shared_prefix(m, shape, a.shared_prefix, a.pos, a.iters, a.repeats, a.forked_only)
+        m.close()
+        print_shared(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "shared_prefix": rows}))
         return
     positions = [p for p in POSITIONS if p <= shape.seq_len]
     out = {"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "path": m.path_name(), "batch": [], "decode_greedy": {}}
