@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE -- mirrors of the shared prefix's split and column arithmetic (llm.f90_amd/csrc/batch.h, the llmk_prefix_*
 section; bd_pass in csrc/llmk.hip for the own parts), as tests/batch_tiles.py mirrors bd_attn_kernel's.  Used by
 tests/test_batch_prefix_cpu.py (is every timestep visited once, every query head in one live column, every state inside its buffer?)
-and tests/test_batch_prefix_gpu.py (which prefix lengths split, where do the parts begin?)."""
+and tests/test_batch_prefix_gpu.py (which prefix lengths split, where do the parts begin?); the last section holds the case table of
+tests/test_batch_wide_gpu.py test 4, which tests/test_batch_wide_cpu.py checks on these mirrors."""
 from __future__ import annotations
 
 import batch_tiles as bt
@@ -114,3 +115,51 @@ def state_index(row: int, kvh: int, state: int, q: int, n_kv_heads: int, np_: in
 def state_capacity(n_kv_heads: int, kv_mul: int) -> int:
     """llmk_prefix_set: {M, L} entries of the part-state buffers"""
     return MAX_BATCH * n_kv_heads * 2 * bt.BD_MAX_PARTS * kv_mul
+
+
+# ---- wide passes (tests/test_batch_wide_cpu.py, tests/test_batch_wide_gpu.py test 4) --------------------------------------------------
+def prefix_tiles_per_wave(n_att: int, n_kv_heads: int, kv_mul: int, P: int, n_cu: int = bt.N_CU):
+    """[part][wave] -> the prefix tiles that wave of bd_attn_prefix_kernel multiplies in a pass with n_att attached rows"""
+    parts = prefix_parts(n_att, n_kv_heads, kv_mul, P, n_cu)
+    tpp = bt.bd_tiles_per_part(P, parts)
+    return [[bt.wave_tiles(*bt.part_tiles(P, p, tpp), w) for w in range(bt.BD_WAVES)] for p in range(parts)]
+
+
+def own_tiles_per_wave(rows, first: int, pos: int, n_kv_heads: int, n_cu: int = bt.N_CU):
+    """[part][wave] -> the tiles that wave of bd_attn_own_kernel multiplies for the row (first, pos) inside the pass `rows`"""
+    parts, tpp = own_parts(rows, n_kv_heads, n_cu)
+    ntile = (pos + bt.BD_TILE - 1) // bt.BD_TILE
+    out = []
+    for p in range(parts):
+        t0 = first // bt.BD_TILE + p * tpp
+        out.append([bt.wave_tiles(t0, min(t0 + tpp, ntile), w) for w in range(bt.BD_WAVES)])
+    return out
+
+
+def most(per_wave) -> int:
+    return max(len(ts) for part in per_wave for ts in part)
+
+
+# tiny-gqa's geometry (kv_mul 4: 4 rows per column group, 2 kv heads) with room for a long prefix
+WIDE_SEQ_LEN = 704
+WIDE_ATTACHED = 127       # slots 0 .. 126; slot 127 is forked, not attached
+WIDE_STAGGER = 8          # attached slot j joins at pass j % 8
+# case: (P, positions behind P that every row runs through, pass at which the unattached row joins -- None: there is none and slot
+# 127 is attached too).  P + run <= seq_len: behind P = 690 there are 14 positions
+WIDE_PREFIX_CASES = {"P560": (560, 40, WIDE_STAGGER), "P690": (690, 14, WIDE_STAGGER), "P19-own": (19, 150, None)}
+
+
+def wide_prefix_passes(case: str):
+    """test 4: [[(slot, first, pos) of every row, in row order]].  Attached slot j feeds positions P + 1 .. P + run in passes j % 8 ..;
+    the unattached slot (first = 0), forked at P, feeds the same positions from pass `join` on: the pass before it has 127 rows, that
+    pass 128.  Rows are listed by DESCENDING slot (the unattached row first: row index != column)."""
+    P, run, join = WIDE_PREFIX_CASES[case]
+    natt = WIDE_ATTACHED if join is not None else MAX_BATCH
+    start = {j: j % WIDE_STAGGER for j in range(natt)}
+    first = {j: P for j in range(natt)}
+    if join is not None:
+        start[WIDE_ATTACHED], first[WIDE_ATTACHED] = join, 0
+    passes = []
+    for t in range(max(start.values()) + run):
+        passes.append([(j, first[j], P + 1 + t - start[j]) for j in sorted(start, reverse=True) if start[j] <= t < start[j] + run])
+    return passes
