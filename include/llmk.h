@@ -180,6 +180,14 @@ int llmk_set_rope_freqs(llmk_ctx *ctx, const float *freqs, int n);
  * pos, llama2.f90:564-565).  logits_out: V floats, caller-owned host memory. */
 int llmk_forward(llmk_ctx *ctx, int token, int pos, float *logits_out);
 
+/* llmk_forward keeps the next greedy position in flight: once a caller has fed back the first maximum of
+ * the logits it received twice in a row, the launch for position pos + 1 is enqueued on the device's own greedy token before
+ * the call for pos returns, and a call that comes back with exactly that token and position finds its result under way; any other
+ * call drains the stream and runs as if nothing had been launched.  What a call returns does not change.  Whole-model f32 / f16
+ * contexts on the persistent kernel only; LLMK_FORWARD_AHEAD=0 in the environment at llmk_create switches it off.
+ * out = {speculative launches, hits, misses, 1 while a launch is in flight} since llmk_create. */
+int llmk_forward_ahead_stats(llmk_ctx *ctx, int out[4]);
+
 /* The prompt loop of llama2.f90:376-402 as ONE call: tokens[0..n) (1-based ids) sit at
  * positions pos0 .. pos0+n-1 (1-based); their KV-cache rows are written and logits_out[vocab_size] receives the
  * logits of the LAST position -- what n llmk_forward calls would leave behind, within the 1e-4 parity bar (only the

@@ -17,6 +17,7 @@
 #include "prefill.h"
 #include "batch.h"
 #include "tp_p2p.h"
+#include "forward_ahead.h"
 
 #include <rccl/rccl.h>
 
@@ -220,6 +221,17 @@ struct llmk_ctx {
     size_t sc_logits_cap = 0;
     bool sc_ready = false;
     int n_batches = 0;                     // live llmk_batch objects on this context (llmk_destroy refuses while there are any)
+    // llmk_forward with the next greedy position in flight (forward_ahead.h).  Position p's logits go to pinned
+    // buffer p & 1 -- [0] is h_logits, whose error word and ids() serve both -- so the host copies out of one while the next launch
+    // fills the other; fa_ev[p & 1] is recorded right behind position p's launch
+    bool fa_on = true;                     // LLMK_FORWARD_AHEAD=0: llmk_forward as it was
+    ForwardAhead fa;
+    bool fa_inflight = false;              // a speculative launch is on the stream (fa.armed says so too; this one survives fa.miss())
+    float* fa_buf[2] = {nullptr, nullptr};
+    float* fa_buf_dev[2] = {nullptr, nullptr};
+    const float* fa_logits = nullptr;      // where the last llmk_forward's logits still are (what fa.scan_due compares with)
+    int fa_tok0 = 0, fa_pos = 0;           // the last DELIVERED call's h_tokpos words (a settled speculation puts them back)
+    hipEvent_t fa_ev[2] = {nullptr, nullptr};
 };
 typedef llmk_ctx::PfLane PfLane;
 
@@ -482,7 +494,7 @@ hipError_t launch_embed(llmk_ctx* c) {
 // direct = true: token/pos/serial travel as kernel arguments and the logits (+ a sticky error word) are written
 // straight into the pinned host buffer, so a token is ONE launch and one stream sync (no copy nodes around it)
 // what a launch of the pipelined greedy decode adds to the arguments (all null otherwise)
-struct TkGreedy { int gflags = 0, id_index = 0; };
+struct TkGreedy { int gflags = 0, id_index = 0; float* logits = nullptr; };      // logits: llmk_forward's pinned buffer of this position (forward_ahead.h)
 template <class TK>
 hipError_t launch_token_kernel_t(llmk_ctx* c, bool direct, const TkGreedy& g) {
     TokenArgs a;
@@ -503,7 +515,7 @@ hipError_t launch_token_kernel_t(llmk_ctx* c, bool direct, const TkGreedy& g) {
     a.pos_imm = c->h_tokpos[1];
     a.serial_imm = c->h_tokpos[2];
     a.g_qkv = c->d_gran;         // qkv | xb | xa | hb | x (token_kernel.h tk_g_xb ...)
-    a.logits = direct ? c->h_logits_dev : c->d_logits;
+    a.logits = g.logits ? g.logits : direct ? c->h_logits_dev : c->d_logits;
     a.err = &c->dev_words()->err;
     a.herr = (direct || g.gflags) ? &c->host_words_dev()->err : nullptr;
     a.zeros = c->d_zeros;
@@ -822,12 +834,20 @@ int build_graph(llmk_ctx* c, TailMode tail, hipGraphExec_t* out) {
     return LLMK_OK;
 }
 
-int check_ready(llmk_ctx* c) {
-    if (!c) return LLMK_E_ARG;
+int tensors_ready(llmk_ctx* c) {
     for (int i = 0; i < LLMK_N_TENSORS; ++i)
         if (!c->t[i].uploaded) return LLMK_E_STATE;
     if (c->use_tk && tk_table[c->tk_shape - 1].q4 && c->q16_dirty) return q16_build(c);
     return LLMK_OK;
+}
+// Every entry point that works on a context's stream or buffers passes through here -- or, where it has no use for the tensors,
+// calls spec_settle itself -- before it touches them: a position llmk_forward left in flight (forward_ahead.h) is drained first.
+// llmk_forward alone goes by tensors_ready.
+int spec_settle(llmk_ctx* c);
+int check_ready(llmk_ctx* c) {
+    if (!c) return LLMK_E_ARG;
+    const int rc = spec_settle(c);
+    return rc ? rc : tensors_ready(c);
 }
 
 // The persistent kernel reported a timed-out exchange (its workgroups were not all running: the GPU was shared, or a
@@ -882,9 +902,34 @@ const char* tp_describe_err(const llmk_ctx* c, unsigned code, char* buf, size_t 
                   call, serial, call / 2u, (call & 1u) ? "w2" : "wo");
     return buf;
 }
+// A speculative launch of llmk_forward may be in flight: wait for it, look at the sticky word as run_token_pass does, and leave the
+// machine IDLE.  A launch nobody waits for is an ordinary token pass: it ends by itself, and all it leaves behind is KV row `next`
+// with the guessed token's K/V, which every path rewrites before reading it.
+//   0x2000: the launch found no finite logit among the candidates of the position before it (that position's logits, which the caller
+//           has or gets as they are, hold none): nothing of the kernel's is at fault, the word is cleared
+//   else:   a timed-out exchange: the kernel is retired as in run_token_pass, the next pass runs on the multi-kernel path
+// The device's word is read, not the host's copy: only workgroups that noticed the raised word store it there.
+int spec_settle(llmk_ctx* c) {
+    c->fa.interrupt();
+    if (!c->fa_inflight) return LLMK_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->fa_inflight = false;
+    c->h_tokpos[0] = c->fa_tok0;
+    c->h_tokpos[1] = c->fa_pos;
+    unsigned err = 0;
+    HIPCHK(hipMemcpy(&err, &c->dev_words()->err, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (err == 0) return LLMK_OK;
+    return (err & 0x2000u) ? tk_clear_err(c) : tk_retire(c, err, c->fa_pos + 1);
+}
+
+int token_pass(llmk_ctx* c, int token, int pos, TailMode tail);
 int run_token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
-    int rc = check_ready(c);
-    if (rc) return rc;
+    const int rc = check_ready(c);
+    return rc ? rc : token_pass(c, token, pos, tail);
+}
+int token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
+    int rc;
     if (token < 1 || token > c->V || pos < 1 || pos > c->S) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     c->h_tokpos[0] = token - 1;
@@ -1589,6 +1634,13 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(hipHostMalloc(&c->h_logits, (size_t)V * sizeof(float) + sizeof(TkHostWords) + (size_t)S * sizeof(int), hipHostMallocMapped));
     CK(hipHostGetDevicePointer((void**)&c->h_logits_dev, c->h_logits, 0));
     c->tk_direct = !(getenv("LLMK_TK_DIRECT") && getenv("LLMK_TK_DIRECT")[0] == '0');
+    // llmk_forward's second logits buffer (forward_ahead.h); LLMK_FORWARD_AHEAD=0: one launch and one stream sync per call, as before
+    c->fa_on = !(getenv("LLMK_FORWARD_AHEAD") && getenv("LLMK_FORWARD_AHEAD")[0] == '0');
+    c->fa_buf[0] = c->h_logits;
+    c->fa_buf_dev[0] = c->h_logits_dev;
+    CK(hipHostMalloc(&c->fa_buf[1], (size_t)V * sizeof(float), hipHostMallocMapped));
+    CK(hipHostGetDevicePointer((void**)&c->fa_buf_dev[1], c->fa_buf[1], 0));
+    for (int i = 0; i < 2; ++i) CK(hipEventCreateWithFlags(&c->fa_ev[i], hipEventDisableTiming));
     CK(hipHostMalloc(&c->h_next, sizeof(TkNext), hipHostMallocDefault));
     CK(hipHostMalloc(&c->h_samp, sizeof(llmk_sample_params), hipHostMallocDefault));
     CK(hipHostMalloc(&c->h_filt, sizeof(llmk_filter_params), hipHostMallocDefault));
@@ -1878,6 +1930,7 @@ int llmk_upload_rows(llmk_ctx* c, int tid, int layer, int row_offset, int rows, 
     if (ggml_type != t.type) return LLMK_E_TYPE;
     if (nbytes != (size_t)rows * row_bytes_for(ggml_type, g.K)) return LLMK_E_SIZE;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc = spec_settle(c); if (rc) return rc; }
     if (c->tp_size > 1) return upload_rows_sharded(c, tid, layer, row_offset, rows, (const uint8_t*)host, ggml_type);
     const size_t pitch = row_bytes_for(ggml_type, g.K);
     return upload_block(c, tid, layer, row_offset, rows, (const uint8_t*)host, pitch, 0, pitch);
@@ -1911,6 +1964,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
     const int kalign = ggml_type == LLMK_TYPE_Q6_K ? Q6K_WEIGHTS : ggml_type == LLMK_TYPE_Q4_0 ? 32 : ggml_type == LLMK_TYPE_F16 ? 8 : 4;
     if (d.K % kalign) return LLMK_E_SHAPE;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc = spec_settle(c); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(c->stream));
     if (t.data) HIPCHK(hipFree(t.data));
     if (c->pf_ready) pf_teardown(c);      // (the next setup prepares the new type's GEMM kernels: pf_prepare)
@@ -1944,6 +1998,7 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
 int llmk_set_rms_eps(llmk_ctx* c, float eps) {
     if (!c || !(eps > 0.f) || !(eps < 1.f)) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc = spec_settle(c); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->eps = eps;
     drop_graphs(c);   // kernel arguments are baked in
@@ -1953,15 +2008,136 @@ int llmk_set_rms_eps(llmk_ctx* c, float eps) {
 int llmk_set_rope_freqs(llmk_ctx* c, const float* freqs, int n) {
     if (!c || !freqs || n != c->hs / 2) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc = spec_settle(c); if (rc) return rc; }
     HIPCHK(hipMemcpy(c->d_rope, freqs, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    return LLMK_OK;
+}
+
+// ---- llmk_forward with the next greedy position in flight (forward_ahead.h has the policy, DESIGN.md section 3b the figures) ----
+// Only the direct-mode persistent kernel of a whole-model f32 / f16 context: a q4_0 shape's range-event redo, the timed and the
+// graph-less passes and the tensor-parallel ranks keep the one-launch-one-sync pass; so does the debug library's injected timeout.
+static bool fa_eligible(const llmk_ctx* c) {
+    if (!c->fa_on || !c->use_tk || !c->tk_direct || c->tp_size != 1 || c->comm || c->p2p) return false;
+    if ((c->cfg.flags & (LLMK_FLAG_TIMINGS | LLMK_FLAG_NO_GRAPH)) || tk_table[c->tk_shape - 1].q4) return false;
+    return !(TK_DEBUG && getenv("LLMK_TK_INJECT_TIMEOUT"));
+}
+// Position pos in the greedy instantiation, logits straight into pinned buffer pos & 1, candidates into cand[pos & 1].
+// spec: the token is the fold of position pos - 1's candidates (the launch before this one on the stream), and workgroup 0
+// publishes it, 1-based, in ids()[pos - 2] as it starts.  An event behind every launch: see fa_deliver.
+static int fa_launch(llmk_ctx* c, int token, int pos, bool spec) {
+    if (!spec) c->h_tokpos[0] = token - 1;
+    c->h_tokpos[1] = pos;
+    c->h_tokpos[2] += 1;
+    TkGreedy g;
+    g.gflags = TKG_GREEDY | (spec ? TKG_CAND_IN | TKG_ID : 0);
+    g.id_index = pos - 2;
+    g.logits = c->fa_buf_dev[pos & 1];
+    if (spec) {
+        c->host_words()->ids()[pos - 2] = 0;
+        c->fa_inflight = true;
+    }
+    c->tk_short_grid = false;
+    HIPCHK(launch_token_kernel(c, true, g));
+    HIPCHK(hipEventRecord(c->fa_ev[pos & 1], c->stream));
+    return LLMK_OK;
+}
+// The id the launch in flight published for the position before its own; 0: the stream drained without one (the sticky word was
+// raised).  The launch starts when the previous position ends, which the caller has already seen: the word is there, or about to be.
+static int fa_published_id(llmk_ctx* c, int slot, int* id) {
+    volatile int* ids = c->host_words()->ids();
+    while ((*id = ids[slot]) == 0) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) { *id = ids[slot]; break; }
+        if (q != hipErrorNotReady) return LLMK_E_HIP + (int)q;
+    }
+    return LLMK_OK;
+}
+// Wait for position pos, whose launch is on the stream, and hand its logits over.
+// Completion, with a launch for pos + 1 behind it (`more`): the event recorded between the two.  hipEventSynchronize on an event
+// without hipEventReleaseToDevice returns when the work in front of the event has completed AND its writes to host memory are
+// visible to this thread -- the same guarantee hipStreamSynchronize gives the direct-mode pass, for position pos alone.  (The other
+// candidate, polling the id the launch for pos + 1 publishes as it starts, costs no barrier packet but orders pos's plain stores to
+// pinned memory by nothing HIP documents: a relaxed system-scope store from another kernel.)  Without a launch behind: the stream.
+static int fa_deliver(llmk_ctx* c, int token, int pos, bool more, float* logits_out) {
+    HIPCHK(more ? hipEventSynchronize(c->fa_ev[pos & 1]) : hipStreamSynchronize(c->stream));
+    if (!more) c->fa_inflight = false;
+    const unsigned err = c->host_words()->err;
+    if (err != 0) {
+        // 0x2000 is the launch BEHIND this one finding no finite candidate (this position's logits hold none; they are delivered as
+        // they are); anything else is this launch's timed-out exchange: the position is redone on the multi-kernel path
+        c->fa_inflight = true;      // (whatever is on the stream: spec_settle drains it and reads the device's word)
+        const int rc = spec_settle(c);
+        if (rc) return rc;
+        if (!(err & 0x2000u)) {
+            const int rc2 = token_pass(c, token, pos, TAIL_LOGITS);
+            if (rc2) return rc2;
+            memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
+            return LLMK_OK;
+        }
+    }
+    c->tk_range_run = 0;
+    memcpy(logits_out, c->fa_buf[pos & 1], (size_t)c->V * sizeof(float));
+    if (err == 0) {
+        c->fa_logits = c->fa_buf[pos & 1];
+        c->fa.ran(pos);
+    }
+    c->fa_tok0 = token - 1;
+    c->fa_pos = pos;
     return LLMK_OK;
 }
 
 int llmk_forward(llmk_ctx* c, int token, int pos, float* logits_out) {
     if (!c || !logits_out) return LLMK_E_ARG;
-    int rc = run_token(c, token, pos, TAIL_LOGITS);
-    if (rc) return rc;
+    if (!fa_eligible(c)) {
+        int rc = run_token(c, token, pos, TAIL_LOGITS);
+        if (rc) return rc;
+        memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
+        return LLMK_OK;
+    }
+    int rc = tensors_ready(c);
+    if (rc == LLMK_OK && (token < 1 || token > c->V || pos < 1 || pos > c->S)) rc = LLMK_E_ARG;
+    if (rc == LLMK_OK && hipSetDevice(c->cfg.device) != hipSuccess) rc = LLMK_E_HIP;
+    if (rc) { spec_settle(c); return rc; }
+    ForwardAhead& fa = c->fa;
+    if (fa.armed) {
+        int id = 0;
+        if (fa.expects(pos) && (rc = fa_published_id(c, pos - 2, &id)) != LLMK_OK) { spec_settle(c); return rc; }
+        if (id == token) {      // (ids are 1-based: never 0)
+            const bool more = fa.hit(c->S);
+            if (more && (rc = fa_launch(c, 0, pos + 1, true)) != LLMK_OK) { spec_settle(c); return rc; }
+            if ((rc = fa_deliver(c, token, pos, more, logits_out)) != LLMK_OK) spec_settle(c);
+            return rc;
+        }
+        fa.miss();      // drain, then the call as it would have run with nothing in flight; it rewrites KV row pos
+        if ((rc = spec_settle(c)) != LLMK_OK) return rc;      // (the backoff that miss() started outlives the settling)
+    } else if (fa.scan_due(pos) && fa.scanned(fa_first_max(c->fa_logits, c->V) + 1 == token, pos, c->S)) {
+        // the arming call: the greedy instantiation scores its candidates with the device's sampling words, which must hold zeros
+        // (invT == 0) as in decode_run
+        TkDevWords* dw = c->dev_words();
+        hipError_t e = c->samp_dev.push(llmk_sample_params{}, [&] { return hipMemsetAsync(&dw->samp, 0, sizeof(llmk_sample_params), c->stream); });
+        if (e != hipSuccess) { spec_settle(c); return LLMK_E_HIP + (int)e; }
+        c->host_words()->err = 0;
+        if ((rc = fa_launch(c, token, pos, false)) == LLMK_OK) rc = fa_launch(c, 0, pos + 1, true);
+        if (rc == LLMK_OK) rc = fa_deliver(c, token, pos, true, logits_out);
+        if (rc) spec_settle(c);
+        return rc;
+    }
+    rc = token_pass(c, token, pos, TAIL_LOGITS);
+    if (rc) { fa.interrupt(); return rc; }
     memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
+    c->fa_logits = c->h_logits;
+    c->fa_tok0 = token - 1;
+    c->fa_pos = pos;
+    if (fa_eligible(c)) fa.ran(pos);      // (the pass may have retired the kernel)
+    return LLMK_OK;
+}
+
+int llmk_forward_ahead_stats(llmk_ctx* c, int out[4]) {
+    if (!c || !out) return LLMK_E_ARG;
+    out[0] = c->fa.launches;
+    out[1] = c->fa.hits;
+    out[2] = c->fa.misses;
+    out[3] = c->fa.armed ? 1 : 0;
     return LLMK_OK;
 }
 
@@ -2453,6 +2629,7 @@ int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
     if (!c || !tokens || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
     for (int i = 0; i < n; ++i)
         if (tokens[i] < 0 || tokens[i] > c->V) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const int rc = pen_setup(c);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->d_hist + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -2461,6 +2638,7 @@ int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
 }
 int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
     if (!c || !tokens_out || n < 1 || pos0 < 1 || pos0 + n - 1 > c->S) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const int rc = pen_setup(c);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(tokens_out, c->d_hist + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2648,6 +2826,7 @@ int llmk_batch_destroy(llmk_batch* b) {
     if (!b) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
     hipSetDevice(c->cfg.device);
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     hipStreamSynchronize(c->stream);
     --c->n_batches;
     batch_free(b);
@@ -2665,6 +2844,7 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
     if (!b || slot < 0 || slot >= b->n_slots || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S)) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const size_t row = (size_t)c->KV, slot_rows = (size_t)b->seq_len * row;
     float* caches[2][2] = {{b->d_kc, c->d_kc}, {b->d_vc, c->d_vc}};
     for (auto& p : caches)
@@ -2735,6 +2915,7 @@ int llmk_prefix_attach(llmk_batch* b, int slot) {
     if (b->P < 1) return LLMK_E_STATE;
     llmk_ctx* c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     // a new sequence behind the prefix: own rows and token record as llmk_batch_fork(b, slot, 0) leaves them
     const size_t slot_rows = (size_t)b->seq_len * c->KV;
     for (float* base : {b->d_kc, b->d_vc})
@@ -2986,6 +3167,7 @@ int llmk_rows_set_history(llmk_batch* b, int slot, const int* tokens, int n, int
     if (!b || !tokens || slot < 0 || slot >= b->n_slots || n < 1 || pos0 < 1 || pos0 + n - 1 > b->seq_len) return LLMK_E_ARG;
     for (int i = 0; i < n; ++i)
         if (tokens[i] < 0 || tokens[i] > b->ctx->V) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(b->ctx); if (rc_) return rc_; }
     const int rc = rows_pen_setup(b);
     if (rc) return rc;
     hipStream_t st = b->ctx->stream;
@@ -2995,6 +3177,7 @@ int llmk_rows_set_history(llmk_batch* b, int slot, const int* tokens, int n, int
 }
 int llmk_rows_get_history(llmk_batch* b, int slot, int* tokens_out, int n, int pos0) {
     if (!b || !tokens_out || slot < 0 || slot >= b->n_slots || n < 1 || pos0 < 1 || pos0 + n - 1 > b->seq_len) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(b->ctx); if (rc_) return rc_; }
     const int rc = rows_pen_setup(b);
     if (rc) return rc;
     hipStream_t st = b->ctx->stream;
@@ -3037,6 +3220,7 @@ int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
 int llmk_reset(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc = spec_settle(c); if (rc) return rc; }
     const size_t kvn = (size_t)c->L * c->S * c->KVl * sizeof(float);
     HIPCHK(hipMemsetAsync(c->d_kc, 0, kvn, c->stream));
     HIPCHK(hipMemsetAsync(c->d_vc, 0, kvn, c->stream));
@@ -3212,6 +3396,7 @@ int llmk_cls_form(llmk_ctx* c, int rows) {
 int llmk_peek(llmk_ctx* c, int which, int layer, int pos, float* out, int n) {
     if (!c || !out || n <= 0) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc = spec_settle(c); if (rc) return rc; }
     const float* src = nullptr;
     int len = 0;
     switch (which) {
@@ -3260,6 +3445,7 @@ int llmk_tp_init_comm(llmk_ctx* c, const char id_in[128]) {
     if (!c || !id_in || c->comm) return LLMK_E_ARG;
     if (c->p2p) return LLMK_E_STATE;      // llmk_tp_p2p_disable first: a ctx runs ONE kind of collective
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     ncclUniqueId id;
     memcpy(&id, id_in, sizeof(id));
     if (ncclCommInitRank(&c->comm, c->tp_size, id, c->tp_rank) != ncclSuccess) { c->comm = nullptr; return LLMK_E_COMM; }
@@ -3288,6 +3474,7 @@ static int tp_inbox_alloc(llmk_ctx* c) {
 
 int llmk_tp_p2p_handle(llmk_ctx* c, char handle_out[64]) {
     if (!c || !handle_out) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     int rc = tp_inbox_alloc(c);
     if (rc) return rc;
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is 64 bytes");
@@ -3299,6 +3486,7 @@ int llmk_tp_p2p_handle(llmk_ctx* c, char handle_out[64]) {
 
 int llmk_tp_p2p_connect(llmk_ctx* c, const char* handles) {
     if (!c || !handles || c->p2p) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     int rc = tp_inbox_alloc(c);
     if (rc) return rc;
     for (int r = 0; r < c->tp_size; ++r) {
@@ -3316,6 +3504,7 @@ int llmk_tp_p2p_connect(llmk_ctx* c, const char* handles) {
 
 int llmk_tp_p2p_connect_local(llmk_ctx* c, llmk_ctx* const* ranks) {
     if (!c || !ranks || c->p2p) return LLMK_E_ARG;
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     int rc = tp_inbox_alloc(c);
     if (rc) return rc;
     for (int r = 0; r < c->tp_size; ++r) {
@@ -3427,6 +3616,7 @@ int llmk_tp_p2p_stress(llmk_ctx* c, int iters, unsigned seed) { return tp_selfte
 int llmk_tp_p2p_disable(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->p2p = false;
     drop_graphs(c);
@@ -3472,18 +3662,21 @@ int llmk_tp_segment(llmk_ctx* c, int seg, int layer) {
 int llmk_tp_read_partial(llmk_ctx* c, float* out) {
     if (!c || !out) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipMemcpy(out, c->d_part, (size_t)c->E * sizeof(float), hipMemcpyDeviceToHost));
     return LLMK_OK;
 }
 int llmk_tp_write_partial(llmk_ctx* c, const float* in) {
     if (!c || !in) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipMemcpy(c->d_part, in, (size_t)c->E * sizeof(float), hipMemcpyHostToDevice));
     return LLMK_OK;
 }
 int llmk_tp_read_logits(llmk_ctx* c, float* out_slice) {
     if (!c || !out_slice) return LLMK_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipMemcpy(out_slice, c->d_logits + (size_t)c->tp_rank * c->Vl, (size_t)c->Vl * sizeof(float), hipMemcpyDeviceToHost));
     return LLMK_OK;
 }
@@ -3503,6 +3696,7 @@ int llmk_tensor_checksum(llmk_ctx* c, int tid, unsigned long long* out) {
     const DevTensor& t = c->t[tid];
     if (!t.data) return LLMK_E_STATE;
     HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const size_t nwords = (size_t)d.rows * (d.layered ? c->L : 1) * t.row_bytes / 4;
     unsigned long long* d_out = nullptr;
     HIPCHK(dev_alloc(&d_out, sizeof(*d_out)));
@@ -3561,6 +3755,7 @@ int llmk_destroy(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
     if (c->n_batches > 0) return LLMK_E_STATE;      // its batches go first (llmk_batch_destroy): they run on this context's weights and stream
     hipSetDevice(c->cfg.device);
+    if (c->stream) spec_settle(c);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->comm) ncclCommDestroy(c->comm);
     for (int r = 0; r < TP_MAX_RANKS; ++r)
@@ -3587,6 +3782,9 @@ int llmk_destroy(llmk_ctx* c) {
         if (c->q16[i]) hipFree(c->q16[i]);
     if (c->h_tokpos) hipHostFree(c->h_tokpos);
     if (c->h_logits) hipHostFree(c->h_logits);
+    if (c->fa_buf[1]) hipHostFree(c->fa_buf[1]);
+    for (hipEvent_t e : c->fa_ev)
+        if (e) hipEventDestroy(e);
     if (c->h_next) hipHostFree(c->h_next);
     if (c->h_samp) hipHostFree(c->h_samp);
     if (c->h_filt) hipHostFree(c->h_filt);

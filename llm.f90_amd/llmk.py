@@ -24,7 +24,7 @@ FLAG_NO_GRAPH, FLAG_TIMINGS, FLAG_MULTI_KERNEL = 1, 2, 4
 SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_comm", "llmk_tp_p2p_handle", "llmk_tp_p2p_connect",
            "llmk_tp_p2p_connect_local", "llmk_tp_p2p_selftest", "llmk_tp_p2p_stress", "llmk_tp_p2p_disable", "llmk_tp_begin", "llmk_tp_segment",
            "llmk_tp_read_partial", "llmk_tp_write_partial", "llmk_tp_read_logits", "llmk_upload", "llmk_upload_rows",
-           "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
+           "llmk_set_rope_freqs", "llmk_set_tensor_type", "llmk_set_rms_eps", "llmk_forward", "llmk_forward_ahead_stats", "llmk_prefill", "llmk_forward_greedy", "llmk_decode_greedy",
            "llmk_forward_sample", "llmk_decode_sample", "llmk_forward_sample_ex", "llmk_decode_sample_ex", "llmk_sample_logits", "llmk_set_history", "llmk_get_history",
            "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
@@ -150,6 +150,8 @@ def lib():
         L.llmk_set_tensor_type.argtypes = [vp, ci, ci]
         L.llmk_set_rms_eps.argtypes = [vp, C.c_float]
         L.llmk_forward.argtypes = [vp, ci, ci, cf]
+        if hasattr(L, "llmk_forward_ahead_stats"):      # (absent from an older build selected with LLMK_LIB for an A/B)
+            L.llmk_forward_ahead_stats.argtypes = [vp, C.POINTER(ci)]
         L.llmk_prefill.argtypes = [vp, C.POINTER(ci), ci, ci, cf]
         L.llmk_forward_greedy.argtypes = [vp, ci, ci, C.POINTER(ci)]
         L.llmk_decode_greedy.argtypes = [vp, ci, ci, ci, C.POINTER(ci), vp, vp]
@@ -295,6 +297,12 @@ class Llmk:
     def forward_raw(self, token: int, pos: int) -> int:
         """Hot loop for bench.py: no copy of the result, returns the status code."""
         return lib().llmk_forward(self._h, token, pos, self._logits.ctypes.data_as(C.POINTER(C.c_float)))
+
+    def forward_ahead_stats(self) -> dict:
+        """llmk_forward's next-position launches since create: {"launches", "hits", "misses", "armed"} (llmk_forward_ahead_stats)"""
+        out = (C.c_int * 4)()
+        _ck(lib().llmk_forward_ahead_stats(self._h, out))
+        return {"launches": out[0], "hits": out[1], "misses": out[2], "armed": bool(out[3])}
 
     def prefill(self, tokens, pos0: int = 1) -> np.ndarray:
         """tokens (1-based ids) at positions pos0.. in one call; logits of the last position (llama2.f90:376-402)."""
