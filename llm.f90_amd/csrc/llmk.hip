@@ -18,10 +18,13 @@
 #include "batch.h"
 #include "tp_p2p.h"
 #include "forward_ahead.h"
+#include "owned.h"
 
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <memory>
+#include <utility>
 #include <vector>
 
 #include <float.h>
@@ -44,27 +47,6 @@ static int q16_build(llmk_ctx* c);        // (defined behind the upload helpers 
 
 namespace {
 
-// Every device allocation of the shim goes through here.  LLMK_POISON=1 (a test aid: tests/test_tp70_gpu.py and
-// tests/host_tools/gpu_job.sh poison) fills the fresh allocation with 0xFF bytes -- NaN as f32 or f16, -1 as an integer --
-// BEFORE the shim's own initialisation: a kernel that reads memory the shim never wrote then yields NaN every time,
-// whatever the allocator happened to hand out (a fresh process usually sees zero pages, a long-lived one does not).
-template <class T>
-hipError_t dev_alloc(T** p, size_t bytes) {
-    static const bool poison = getenv("LLMK_POISON") && getenv("LLMK_POISON")[0] == '1';
-    hipError_t e = hipMalloc((void**)p, bytes);
-    // (the fill must be COMPLETE when this returns: the shim's own initialisation often goes to the ctx's non-blocking stream, which the
-    // null stream does not order -- round 6's first poison run: the self-test's mismatch counter read 0xFFFFFFFF on three ranks.  And it
-    // must not wait for the DEVICE: with two ranks in one process a rank's kernel may be spinning for its peer, whose host thread is
-    // in here -- the second poison run.  So: a stream of its own for the calling thread, and a wait for that stream alone)
-    if (e == hipSuccess && poison) {
-        static thread_local hipStream_t ps = nullptr;
-        if (!ps) e = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0xFF, bytes, ps);
-        if (e == hipSuccess) e = hipStreamSynchronize(ps);
-    }
-    return e;
-}
-
 struct TensorDesc {
     bool layered;   // has a leading layer dimension
     int rows;       // rows per layer (1 for vectors)
@@ -73,12 +55,33 @@ struct TensorDesc {
 };
 
 struct DevTensor {
+    DevBuf<char> own;        // the allocation behind `data`; empty: a view into another tensor's (the rmsnorm gains share one)
     void* data = nullptr;    // f32/f16 rows; q4_0: rows of K/2 nibble bytes followed by the row's K/32 f16 scales
     size_t row_bytes = 0;    // bytes per row in `data` (q4_0: 9K/16 rounded up to 16)
     int type = LLMK_TYPE_F32;
     bool uploaded = false;
     size_t rows_uploaded = 0;
-    bool alias = false;      // `data` points into another tensor's allocation (the rmsnorm gains share one): never freed itself
+};
+
+// The sampler's lazily created records, one definition for a context (one sequence, one row) and a batch (n_slots sequences,
+// LLMK_MAX_BATCH rows).  Each is empty until the first call that needs it (pen_setup, lp_setup), which builds it aside and moves it in
+// whole: an empty one reads as null pointers everywhere.
+// Penalties and logit bias (sample_penalty.h): the token records (hist[seq][q - 1] = the 1-based token fed at position q, 0 = none), the
+// counts of the penalty kernels ([seq][V], all zero between launches), a row's parameters on the device and the pinned words they
+// are copied from
+struct PenaltyState {
+    DevBuf<int> hist, cnt;
+    DevBuf<llmk_penalty_params> d_pen;
+    PinnedBuf<llmk_penalty_params> h_pen;
+};
+// Log-prob records (logprob.h): on the device and pinned, the top_n word (pinned; a batch's kernels read a device copy, a context's
+// read TkDevWords::lp_top_n) and the raw logits that are set aside in front of the penalty kernel
+struct LogprobState {
+    DevBuf<llmk_logprob_record> d;
+    PinnedBuf<llmk_logprob_record> h;      // (allocated last: its size says that both are there)
+    DevBuf<unsigned> d_top;
+    PinnedBuf<unsigned> h_top;
+    DevBuf<float> raw;
 };
 
 // What a token pass hands back: the logits (llmk_forward), the device argmax (llmk_forward_greedy) or the device sample
@@ -108,58 +111,51 @@ struct DevShadow {
 struct llmk_ctx {
     llmk_config cfg;
     int E, H, L, nh, nkv, V, S, hs, KV, kv_mul;
+    // (declared before every buffer and event: members are destroyed in reverse order, so the stream outlives what ran on it)
+    Stream stream;
     // tensor-parallel shard of this ctx (tp_size == 1: the whole model). Local dims: q columns, kv dim,
     // hidden rows, vocab rows and heads owned by this rank (Megatron split).
     int tp_rank = 0, tp_size = 1;
     int Eq, KVl, Hl, Vl, nhl;
     ncclComm_t comm = nullptr;
     // one-shot peer-memory collectives (tp_p2p.h): this rank's inbox (fine-grained HBM) and the peers' as mapped here
-    unsigned long long* d_inbox = nullptr;
-    unsigned* d_tp_bad = nullptr;         // the self-test's mismatch counter (allocated with the inbox: see tp_selftest_run)
+    DevBuf<unsigned long long> d_inbox;
+    DevBuf<unsigned> d_tp_bad;            // the self-test's mismatch counter (allocated with the inbox: see tp_selftest_run)
     TpPeers peers = {};
     void* ipc_mapped[TP_MAX_RANKS] = {};
     bool p2p = false;
-    float* d_part = nullptr;       // [E] partial sums of the row-parallel GEMVs (wo, w2) before the all-reduce
+    DevBuf<float> d_part;          // [E] partial sums of the row-parallel GEMVs (wo, w2) before the all-reduce
     TensorDesc gdesc[LLMK_N_TENSORS];  // the full (unsharded) tensors, what llmk_upload is handed
     TensorDesc desc[LLMK_N_TENSORS];
     DevTensor t[LLMK_N_TENSORS];
-    float *d_kc = nullptr, *d_vc = nullptr;  // [L][S][KV]  (RunState, weight_module.f90:33-40)
-    float *d_x = nullptr, *d_q = nullptr, *d_xb = nullptr, *d_hb = nullptr, *d_logits = nullptr, *d_rope = nullptr;
-    int *d_tokpos = nullptr, *d_next = nullptr;
-    int* h_tokpos = nullptr;  // pinned {token0, pos1}
-    float* h_logits = nullptr;  // pinned [V], then host_words()
-    float* h_logits_dev = nullptr;   // the same buffer as the device sees it (token kernel direct mode)
+    DevBuf<float> d_kc, d_vc;      // [L][S][KV]  (RunState, weight_module.f90:33-40)
+    DevBuf<float> d_x, d_q, d_xb, d_hb, d_rope;
+    DevBuf<float> d_logits;        // [V], then dev_words()
+    DevBuf<int> d_tokpos, d_next;
+    PinnedBuf<int> h_tokpos;    // pinned {token0, pos1}
+    PinnedBuf<float> h_logits;       // mapped: [V], then host_words(); dev(): as the device sees it (token kernel direct mode)
     bool tk_direct = true;
-    TkNext* h_next = nullptr;   // pinned
+    PinnedBuf<TkNext> h_next;
     // the scratch words behind the logits vectors (scratch_layout.h): the device's, the host's, the host's as the device sees them
     TkDevWords* dev_words() const { return tk_words_behind<TkDevWords>(d_logits, V); }
     TkHostWords* host_words() const { return tk_words_behind<TkHostWords>(h_logits, V); }
-    TkHostWords* host_words_dev() const { return tk_words_behind<TkHostWords>(h_logits_dev, V); }
-    hipStream_t stream = nullptr;
+    TkHostWords* host_words_dev() const { return tk_words_behind<TkHostWords>(h_logits.dev(), V); }
     hipGraphExec_t graph[TAIL_COUNT][2] = {};   // the token pass with each tail, without / with the log-prob record, captured at first use (drop_graphs)
-    llmk_sample_params* h_samp = nullptr;   // pinned: invT and seed of the current sampling call
+    PinnedBuf<llmk_sample_params> h_samp;   // invT and seed of the current sampling call
     // the device's copy of them (TkDevWords::samp): zeros from llmk_create on.  A pipelined decode writes them only when they differ,
     // so a greedy one on a ctx that never sampled enqueues nothing new
     DevShadow<llmk_sample_params> samp_dev = {{}, true};
     // the same pair for the truncated sampler (a filter, a penalty or a bias on): its parameters sit behind the sampling words
     // (TkDevWords::filt)
-    llmk_filter_params* h_filt = nullptr;
+    PinnedBuf<llmk_filter_params> h_filt;
     DevShadow<llmk_filter_params> filt_dev;
-    // penalties and logit bias (llmk_*_sample_pen, sample_penalty.h), allocated by the first call that needs them (pen_setup): the
-    // token record (S ints: hist[q - 1] = the 1-based token fed at position q, 0 = none), the V counts of sample_penalty_kernel (all
-    // zero between launches), the parameters on the device and the pinned words they are copied from
-    int* d_hist = nullptr;
-    int* d_pen_cnt = nullptr;
-    llmk_penalty_params* d_pen = nullptr;
-    llmk_penalty_params* h_pen = nullptr;
-    // decode log-probs (llmk_*_sample_lp, logprob.h), allocated by the first call that asks for them (lp_setup): S + 1 records on the
-    // device and in pinned memory -- [q - 1]: position q of a pipelined decode; [S]: what the tail of a token pass, or the hook, leaves
-    // -- the pinned top_n word, and the V raw logits that are set aside in front of sample_penalty_kernel
-    llmk_logprob_record *d_lp = nullptr, *h_lp = nullptr;
-    unsigned* h_lp_top = nullptr;
-    float* d_lp_raw = nullptr;
+    // penalties and logit bias (llmk_*_sample_pen): one sequence of S positions, one row
+    PenaltyState pen;
+    // decode log-probs (llmk_*_sample_lp): S + 1 records -- [q - 1]: position q of a pipelined decode; [S]: what the tail of a token
+    // pass, or the hook, leaves -- and [V] raw logits
+    LogprobState lp;
     int lp_top_n = -1;      // the running call's request (logprob_request .. LpScope), -1: none -- every site enqueues what it always did
-    hipEvent_t ev[8] = {};
+    Event ev[8];
     float times[5] = {0, 0, 0, 0, 0};
     int n_cu = 256;
     float eps = 1e-5f;     // rmsnorm epsilon: the reference's constant (llama2.f90:454) unless llmk_set_rms_eps
@@ -172,54 +168,59 @@ struct llmk_ctx {
     // its rate for good); TK_RANGE_LIMIT of them in a row retire it after all (a model it cannot hold), and its unit copies are freed
     int tk_range_events = 0, tk_range_run = 0;
     int tk_shape = 0;      // 1-based index into tk_table (the instantiated shapes: LLMK_TK_SHAPES), 0 = none
-    unsigned long long* d_gran = nullptr;  // exchange granules: qkv | xb | xa | hb | x | attention parts
-    float4* d_zeros = nullptr;
-    unsigned long long* d_trace = nullptr;  // debug stamps (LLMK_TK_TRACE=1)
+    DevBuf<unsigned long long> d_gran;     // exchange granules: qkv | xb | xa | hb | x | attention parts
+    DevBuf<float4> d_zeros;
+    DevBuf<unsigned long long> d_trace;    // debug stamps (LLMK_TK_TRACE=1)
     size_t tk_lds = 0;
     size_t tk_ngran = 0;   // granules in d_gran (the last TK_QSC_GRANULES: the q4_0 kernels' per-layer scale records, tk_qsc_records)
     // pipelined greedy decode (llmk_decode_greedy): per-CU classifier maxima of the last two launches, and the ids as they
     // are resolved (host-mapped; 0 = not there yet)
     // (the candidates sit behind the device error word, the ids behind the host error word: scratch_layout.h)
-    // batched prefill (prefill.h), allocated by the first llmk_prefill.  Two LANES = workspace set + stream: consecutive
-    // 128-position batches of a prompt alternate between them, so one batch's small kernels (epilogues, attention) and
-    // launch gaps run under the other's GEMMs.  The only cross-batch dependency is the KV cache: batch k+1's attention in
-    // layer l waits for batch k's K/V rows of layer l (event kv[l]).
+    // batched prefill (prefill.h), built by the first llmk_prefill (pf_setup) and dropped as a whole (pf.reset()).  Two LANES =
+    // workspace set + stream: consecutive 128-position batches of a prompt alternate between them, so one batch's small kernels
+    // (epilogues, attention) and launch gaps run under the other's GEMMs.  The only cross-batch dependency is the KV cache: batch
+    // k+1's attention in layer l waits for batch k's K/V rows of layer l (event kv[l]).
     struct PfLane {
-        float *X = nullptr, *Xs = nullptr, *Q = nullptr, *XB = nullptr, *HB = nullptr, *P = nullptr, *xn = nullptr;
-        unsigned* lowcnt = nullptr;        // [2][PF_TMAX]: the GEMM workgroups' votes on positions that are small as a whole (prefill.h pf_low_check)
-        hipStream_t stream = nullptr;      // lane 0: the ctx stream
-        std::vector<hipEvent_t> kv;        // per layer: this lane's batch has written its K/V rows
-        hipEvent_t done = nullptr;         // this lane's batch has left the last layer
-    } pf[2];
-    int* pf_tok = nullptr;
-    std::vector<int> pf_tok0;              // what pf_tok is uploaded from: alive until the call has synchronised
-    hipEvent_t pf_start = nullptr;         // tokens are on the device (and everything before the prefill call is done)
-    bool pf_ready = false;                 // pf_setup ran to its end
-    // uploads are staged through the shim's OWN pinned memory (upload_block): two buffers, an event each
-    void* up_stage[2] = {nullptr, nullptr};
-    void* up_stage_dev[2] = {nullptr, nullptr};      // the same buffers as the device addresses them
-    void* up_tmp[2] = {nullptr, nullptr};            // device scratch of the q4_0 re-packing (written and read by kernels only)
-    hipEvent_t up_done[2] = {nullptr, nullptr};
-    unsigned long long* up_acc = nullptr;            // device word of the upload verification's 16-bit word sums
-    bool up_ready = false;                           // all of the above exist (set only after every allocation succeeded)
+        Stream own;                        // lane 1's stream (declared first: destroyed after the lane's buffers and events)
+        hipStream_t stream = nullptr;      // the lane's stream: lane 0 the ctx stream, lane 1 `own` (a view either way)
+        DevBuf<float> X, Xs, Q, XB, HB, P, xn;
+        DevBuf<unsigned> lowcnt;           // [2][PF_TMAX]: the GEMM workgroups' votes on positions that are small as a whole (prefill.h pf_low_check)
+        std::vector<Event> kv;             // per layer: this lane's batch has written its K/V rows
+        Event done;                        // this lane's batch has left the last layer
+    };
+    struct Prefill {
+        PfLane lane[2];
+        DevBuf<int> tok;                   // a call's tokens, 0-based
+        Event start;                       // tokens are on the device (and everything before the prefill call is done)
+        DevBuf<unsigned> flag;             // device word: an activation did not fit f16 (the call is redone on the f32 instruction)
+    };
+    std::unique_ptr<Prefill> pf;
+    std::vector<int> pf_tok0;              // what pf->tok is uploaded from: alive until the call has synchronised
+    // uploads are staged through the shim's OWN pinned memory (upload_block), built by the first upload: two buffers, an event each
+    struct Upload {
+        PinnedBuf<char> stage[2];          // mapped: the kernels read stage[b].dev()
+        DevBuf<char> tmp[2];               // device scratch of the q4_0 re-packing (written and read by kernels only)
+        Event done[2];
+        DevBuf<unsigned long long> acc;    // device word of the upload verification's 16-bit word sums
+    };
+    std::unique_ptr<Upload> up;
     // q4_0 matrices in the persistent kernel's UNIT layout (q4_units.h: 16 rows x 32 blocks as matrix-core operands), built from
     // the row layout -- which the multi-kernel path, the prefill and the fallback keep reading -- at the first token after an upload
-    void* q16[LLMK_N_TENSORS] = {};
+    DevBuf<char> q16[LLMK_N_TENSORS];
     bool q16_dirty = true;
     bool pf_hm = false;                    // GEMMs on v_mfma_f32_16x16x32_f16, activations (and f32 / q4_0 weights) as two f16 pieces (prefill.h)
-    unsigned* pf_flag = nullptr;           // device word: an activation did not fit f16 (the call is redone on the f32 instruction)
     size_t pf_pcap = 0;                    // floats in each lane's partial-tile workspace P
-    // llmk_score (prefill.h pf_score_kernel), allocated by the first scoring call: per lane the positions' partial results and target
-    // logits (and, for a q6_K classifier, a batch of logits rows); the call's targets and results; the logits of a call that asks for them
-    float4* sc_part[2] = {nullptr, nullptr};
-    float* sc_tgt[2] = {nullptr, nullptr};
-    float* sc_z[2] = {nullptr, nullptr};
-    int* sc_targets = nullptr;             // [S] 0-based, < 0: none
-    float* sc_out = nullptr;               // [2S]: a call's n log-probs, then its n argmax ids
-    float* h_sc = nullptr;                 // pinned image of sc_out
-    float* sc_logits = nullptr;            // [sc_logits_cap][V]
-    size_t sc_logits_cap = 0;
-    bool sc_ready = false;
+    // llmk_score (prefill.h pf_score_kernel), built by the first scoring call (sc_setup): per lane the positions' partial results and
+    // target logits (and, for a q6_K classifier, a batch of logits rows); the call's targets and results; the logits of a call that asks for them
+    struct Score {
+        DevBuf<float4> part[2];
+        DevBuf<float> tgt[2], z[2];
+        DevBuf<int> targets;               // [S] 0-based, < 0: none
+        DevBuf<float> out;                 // [2S]: a call's n log-probs, then its n argmax ids
+        PinnedBuf<float> h_out;            // pinned image of `out`
+        DevBuf<float> logits;              // [positions][V], grown by the call that asks for more (reserve)
+    };
+    std::unique_ptr<Score> sc;
     int n_batches = 0;                     // live llmk_batch objects on this context (llmk_destroy refuses while there are any)
     // llmk_forward with the next greedy position in flight (forward_ahead.h).  Position p's logits go to pinned
     // buffer p & 1 -- [0] is h_logits, whose error word and ids() serve both -- so the host copies out of one while the next launch
@@ -227,11 +228,12 @@ struct llmk_ctx {
     bool fa_on = true;                     // LLMK_FORWARD_AHEAD=0: llmk_forward as it was
     ForwardAhead fa;
     bool fa_inflight = false;              // a speculative launch is on the stream (fa.armed says so too; this one survives fa.miss())
-    float* fa_buf[2] = {nullptr, nullptr};
-    float* fa_buf_dev[2] = {nullptr, nullptr};
+    PinnedBuf<float> fa_second;            // [V], mapped: buffer 1
+    float* fa_buf[2] = {nullptr, nullptr};       // views: [0] h_logits, [1] fa_second ...
+    float* fa_buf_dev[2] = {nullptr, nullptr};   // ... and as the device sees them
     const float* fa_logits = nullptr;      // where the last llmk_forward's logits still are (what fa.scan_due compares with)
     int fa_tok0 = 0, fa_pos = 0;           // the last DELIVERED call's h_tokpos words (a settled speculation puts them back)
-    hipEvent_t fa_ev[2] = {nullptr, nullptr};
+    Event fa_ev[2];
 };
 typedef llmk_ctx::PfLane PfLane;
 
@@ -241,45 +243,42 @@ typedef llmk_ctx::PfLane PfLane;
 struct llmk_batch {
     llmk_ctx* ctx = nullptr;
     int n_slots = 0, seq_len = 0;
-    float *d_kc = nullptr, *d_vc = nullptr;      // [L][n_slots][seq_len][KV]
-    BdRow* d_rows = nullptr;                     // [LLMK_MAX_BATCH] row words
-    int* d_tok = nullptr;                        // [LLMK_MAX_BATCH] 0-based fed ids
-    float* d_out = nullptr;                      // [2 * LLMK_MAX_BATCH]: (unused log-probs), then the rows' first maxima (1-based ints)
-    float* d_logits = nullptr;                   // [n_slots][V]
-    float* d_po = nullptr;                       // attention parts: [n_cu][BD_MAX_GROUP][hs] unnormalised outputs ...
-    float2* d_pml = nullptr;                     // ... and [n_cu][BD_MAX_GROUP] {M, L}
-    int* d_next = nullptr;                       // [LLMK_MAX_BATCH] the samplers' picks
-    llmk_filter_params* d_filt = nullptr;        // [LLMK_MAX_BATCH] row i's sampler
-    unsigned* d_out2 = nullptr;                  // [LLMK_MAX_BATCH][2] sample_filter_kernel's {kept, tau}
-    unsigned* d_err = nullptr;                   // a decode step had no finite logit in some row
-    int* d_ids = nullptr;                        // [ids_cap] a decode's ids, row-major
-    size_t ids_cap = 0;
+    DevBuf<float> d_kc, d_vc;                    // [L][n_slots][seq_len][KV]
+    DevBuf<BdRow> d_rows;                        // [LLMK_MAX_BATCH] row words
+    DevBuf<int> d_tok;                           // [LLMK_MAX_BATCH] 0-based fed ids
+    DevBuf<float> d_out;                         // [2 * LLMK_MAX_BATCH]: (unused log-probs), then the rows' first maxima (1-based ints)
+    DevBuf<float> d_logits;                      // [n_slots][V]
+    DevBuf<float> d_po;                          // attention parts: [n_cu][BD_MAX_GROUP][hs] unnormalised outputs ...
+    DevBuf<float2> d_pml;                        // ... and [n_cu][BD_MAX_GROUP] {M, L}
+    DevBuf<int> d_next;                          // [LLMK_MAX_BATCH] the samplers' picks
+    DevBuf<llmk_filter_params> d_filt;           // [LLMK_MAX_BATCH] row i's sampler
+    DevBuf<unsigned> d_out2;                     // [LLMK_MAX_BATCH][2] sample_filter_kernel's {kept, tau}
+    DevBuf<unsigned> d_err;                      // a decode step had no finite logit in some row
+    DevBuf<int> d_ids;                           // a decode's ids, row-major; grown by the call that needs more (reserve)
     // pinned: what a call uploads (rows, tokens, samplers) and reads back (first maxima, error word)
-    BdRow* h_rows = nullptr;
-    int* h_tok = nullptr;
-    llmk_filter_params* h_filt = nullptr;
-    float* h_out = nullptr;
-    unsigned* h_err = nullptr;
-    // penalties, logit bias and log-prob records of the rows functions (llmk_rows_*), allocated by the first call that needs them
-    // (rows_pen_setup, rows_lp_setup) as a context's are.  Logits, parameters, picks and records are per ROW of a call; the token
-    // records and the counts are per SLOT: a sequence keeps its record whichever row of a call it is
-    int* d_hist = nullptr;                       // [n_slots][seq_len] hist[slot][q - 1] = the 1-based token fed at position q, 0 = none
-    int* d_pen_cnt = nullptr;                    // [n_slots][V] sample_penalty_rows_kernel's counts, all zero between launches
-    llmk_penalty_params* d_pen = nullptr;        // [LLMK_MAX_BATCH] row i's penalties and bias ...
-    llmk_penalty_params* h_pen = nullptr;        // ... and the pinned words they are copied from
-    float* d_raw = nullptr;                      // [n_slots][V] the raw logits, set aside in front of the penalty kernel for the records
-    llmk_logprob_record *d_lp = nullptr, *h_lp = nullptr;      // [lp_cap] a call's records, [row][step]
-    size_t lp_cap = 0;
-    unsigned *d_lp_top = nullptr, *h_lp_top = nullptr;         // the call's top_n word
-    // a shared prefix (llmk_prefix_*, batch.h), allocated by the first llmk_prefix_set that sets one: a batch without one has none of it
+    PinnedBuf<BdRow> h_rows;
+    PinnedBuf<int> h_tok;
+    PinnedBuf<llmk_filter_params> h_filt;
+    PinnedBuf<float> h_out;
+    PinnedBuf<unsigned> h_err;
+    // penalties, logit bias and log-prob records of the rows functions (llmk_rows_*), as a context's.  Logits, parameters, picks and
+    // records are per ROW of a call -- the records [row][step], grown by the call that needs more -- the token records and the counts
+    // are per SLOT: a sequence keeps its record whichever row of a call it is
+    PenaltyState pen;
+    LogprobState lp;
+    // a shared prefix (llmk_prefix_*, batch.h), built by the first llmk_prefix_set that sets one: a batch without one has none of it
     int P = 0, n_attached = 0;                   // the prefix's positions; slots attached to it
-    size_t px_cap = 0;                           // positions d_pk / d_pv have room for
-    float *d_pk = nullptr, *d_pv = nullptr;      // [L][P][KV]: a snapshot of the context's rows of positions 1..P
-    int *d_first = nullptr, *h_first = nullptr;  // [n_slots] a slot's first own cache row: P attached, 0 not (h_first pinned)
-    int *d_colmap = nullptr, *h_colmap = nullptr;      // [LLMK_MAX_BATCH + BD_MAX_GROUP] bd_attn_prefix_kernel's column map (h_colmap pinned)
+    struct Prefix {
+        DevBuf<int> d_first;                     // [n_slots] a slot's first own cache row: P attached, 0 not ...
+        PinnedBuf<int> h_first;                  // ... and the pinned words it is copied from
+        DevBuf<int> d_colmap;                    // [LLMK_MAX_BATCH + BD_MAX_GROUP] bd_attn_prefix_kernel's column map
+        PinnedBuf<int> h_colmap;
+        DevBuf<float> d_xpo;                     // part states of a pass with attached rows:
+        DevBuf<float2> d_xpml;                   //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_xpo that [hs]
+        DevBuf<float> d_pk, d_pv;                // [L][P][KV]: a snapshot of the context's rows of positions 1..P, grown by reserve
+    };
+    std::unique_ptr<Prefix> px;
     int pass_att = 0;                            // attached rows among the rows bd_upload_rows uploaded last
-    float* d_xpo = nullptr;                      // part states of a pass with attached rows:
-    float2* d_xpml = nullptr;                    //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_xpo that [hs]
 };
 
 namespace {
@@ -515,7 +514,7 @@ hipError_t launch_token_kernel_t(llmk_ctx* c, bool direct, const TkGreedy& g) {
     a.pos_imm = c->h_tokpos[1];
     a.serial_imm = c->h_tokpos[2];
     a.g_qkv = c->d_gran;         // qkv | xb | xa | hb | x (token_kernel.h tk_g_xb ...)
-    a.logits = g.logits ? g.logits : direct ? c->h_logits_dev : c->d_logits;
+    a.logits = g.logits ? g.logits : direct ? c->h_logits.dev() : c->d_logits;
     a.err = &c->dev_words()->err;
     a.herr = (direct || g.gflags) ? &c->host_words_dev()->err : nullptr;
     a.zeros = c->d_zeros;
@@ -605,9 +604,9 @@ int tk_setup(llmk_ctx* c, int id) {
                   "tk_qsc_front: the attention parts are TkAttPlan's");
     const size_t ngran = tk_qsc_front<TK>() + TK_QSC_GRANULES;
     c->tk_ngran = ngran;
-    if (!c->d_gran) HIPCHK(dev_alloc(&c->d_gran, ngran * sizeof(unsigned long long)));      // (kept over a re-type of the classifier: same shape)
-    if (!c->d_zeros) HIPCHK(dev_alloc(&c->d_zeros, (size_t)TK_NCU * TK_WAVES * 1024));
-    if (TK_DEBUG && getenv("LLMK_TK_TRACE")) HIPCHK(dev_alloc(&c->d_trace, (size_t)TK_NCU * TK_TRACE_N * 8));   // libllmk_debug.so only
+    if (!c->d_gran) HIPCHK(c->d_gran.alloc(ngran));      // (kept over a re-type of the classifier: same shape)
+    if (!c->d_zeros) HIPCHK(c->d_zeros.alloc((size_t)TK_NCU * TK_WAVES * 1024 / sizeof(float4)));
+    if (TK_DEBUG && getenv("LLMK_TK_TRACE")) HIPCHK(c->d_trace.alloc((size_t)TK_NCU * TK_TRACE_N));   // libllmk_debug.so only (a re-setup frees the last one)
     HIPCHK(hipMemset(c->d_gran, 0, ngran * sizeof(unsigned long long)));
     HIPCHK(hipMemset(c->d_zeros, 0, (size_t)TK_NCU * TK_WAVES * 1024));
     c->use_tk = true;
@@ -665,30 +664,30 @@ hipError_t enqueue_logprob(llmk_ctx* c, const float* logits, const int* id_ptr, 
     return hipGetLastError();
 }
 hipError_t copy_logprob_top(llmk_ctx* c) {      // (top_n travels like token and position: a copy out of pinned memory)
-    return hipMemcpyAsync(&c->dev_words()->lp_top_n, c->h_lp_top, sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
+    return hipMemcpyAsync(&c->dev_words()->lp_top_n, c->lp.h_top, sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
 }
 hipError_t enqueue_sampler(llmk_ctx* c, bool penalty, const SamplerSite& s) {
     TkDevWords* dw = c->dev_words();
     if (penalty) {
-        if (s.lp) HIPRET(hipMemcpyAsync(c->d_lp_raw, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        if (s.copy_pen) HIPRET(hipMemcpyAsync(c->d_pen, c->h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
+        if (s.lp) HIPRET(hipMemcpyAsync(c->lp.raw, c->d_logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        if (s.copy_pen) HIPRET(hipMemcpyAsync(c->pen.d_pen, c->pen.h_pen, sizeof(llmk_penalty_params), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(sample_penalty_kernel, dim3(1), dim3(SP_THREADS), 0, c->stream, c->d_logits, c->V, s.tokpos, s.pos, s.token, s.prev,
-                           c->d_pen, c->d_hist, s.record, c->d_pen_cnt);
+                           c->pen.d_pen, c->pen.hist, s.record, c->pen.cnt);
         HIPRET(hipGetLastError());
     }
     if (s.copy_filt) HIPRET(hipMemcpyAsync(&dw->filt, c->h_filt, sizeof(llmk_filter_params), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(sample_filter_kernel, dim3(1), dim3(SF_THREADS), 0, c->stream, c->d_logits, c->V, s.tokpos, s.pos, &dw->filt, c->d_next,
                        s.cand, s.ncand, dw->filter_out);
     HIPRET(hipGetLastError());
-    return s.lp ? enqueue_logprob(c, penalty ? c->d_lp_raw : c->d_logits, c->d_next, nullptr, 0, 0, s.lp) : hipSuccess;
+    return s.lp ? enqueue_logprob(c, penalty ? c->lp.raw : c->d_logits, c->d_next, nullptr, 0, 0, s.lp) : hipSuccess;
 }
 
 hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
     if (tail != TAIL_LOGITS) {
-        llmk_logprob_record* lp = c->lp_top_n >= 0 ? c->d_lp + c->S : nullptr;
+        llmk_logprob_record* lp = c->lp_top_n >= 0 ? c->lp.d + c->S : nullptr;
         if (lp) HIPRET(copy_logprob_top(c));
         if (tail == TAIL_FILTER || tail == TAIL_PENALTY) {
-            HIPRET(enqueue_sampler(c, tail == TAIL_PENALTY, {c->d_tokpos, 0, 0, nullptr, c->d_hist, nullptr, 0, true, true, lp}));
+            HIPRET(enqueue_sampler(c, tail == TAIL_PENALTY, {c->d_tokpos, 0, 0, nullptr, c->pen.hist, nullptr, 0, true, true, lp}));
             lp = nullptr;      // (enqueued)
         } else if (tail == TAIL_SAMPLE) {
             // invT and the seed travel like token and position: a copy out of pinned memory, read when the graph replays it
@@ -699,7 +698,7 @@ hipError_t enqueue_tail(llmk_ctx* c, TailMode tail) {
         }
         HIPRET(hipGetLastError());
         if (lp) HIPRET(enqueue_logprob(c, c->d_logits, c->d_next, nullptr, 0, 0, lp));
-        if (c->lp_top_n >= 0) HIPRET(hipMemcpyAsync(c->h_lp + c->S, c->d_lp + c->S, sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+        if (c->lp_top_n >= 0) HIPRET(hipMemcpyAsync(c->lp.h + c->S, c->lp.d + c->S, sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
         HIPRET(hipMemcpyAsync(&c->h_next->id, c->d_next, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPRET(hipMemcpyAsync(&c->h_next->err, &c->dev_words()->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     } else {      // the logits and, behind them, the error word: TkDevWords::err lands in TkHostWords::err
@@ -876,8 +875,7 @@ int tk_retire(llmk_ctx* c, unsigned code, int pos) {
     c->use_tk = false;
     c->tk_retired = true;
     drop_graphs(c);
-    for (int i = 0; i < LLMK_N_TENSORS; ++i)       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
-        if (c->q16[i]) { hipFree(c->q16[i]); c->q16[i] = nullptr; }
+    for (DevBuf<char>& units : c->q16) units.reset();       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
     c->q16_dirty = true;
     // what the sticky word says (token_kernel.h): 0x2000 no finite candidate among the classifier maxima (pipelined greedy decode),
     // 0x4000 an activation beyond the f16 range of the q4_0 kernels' x image, anything else a bounded spin that ran out
@@ -1060,29 +1058,19 @@ PfPlan pf_plan(const llmk_ctx* c, int rows, int K, int T = PF_TMAX, int wt = -1)
 }
 int pf_max_slots(const PfPlan& p) { return (p.nk - 1) / p.U + 2; }
 hipError_t pf_prepare(const llmk_ctx* c);
-void pf_teardown(llmk_ctx* c) {
-    for (PfLane& w : c->pf) {
-        float** bufs[] = {&w.X, &w.Xs, &w.Q, &w.XB, &w.HB, &w.P, &w.xn};
-        for (float** b : bufs) { if (*b) hipFree(*b); *b = nullptr; }
-        if (w.lowcnt) { hipFree(w.lowcnt); w.lowcnt = nullptr; }
-        for (hipEvent_t e : w.kv) if (e) hipEventDestroy(e);
-        w.kv.clear();
-        if (w.done) { hipEventDestroy(w.done); w.done = nullptr; }
-    }
-    if (c->pf[1].stream) { hipStreamDestroy(c->pf[1].stream); c->pf[1].stream = nullptr; }
-    c->pf[0].stream = nullptr;
-    if (c->pf_start) { hipEventDestroy(c->pf_start); c->pf_start = nullptr; }
-    if (c->pf_tok) { hipFree(c->pf_tok); c->pf_tok = nullptr; }
-    if (c->pf_flag) { hipFree(c->pf_flag); c->pf_flag = nullptr; }
-    c->pf_ready = false;
-}
-// Workspaces, the second lane's stream, the KV events and the kernels' dynamic-LDS limits.  pf_ready is set only after
-// the LAST step succeeded; a failure part-way frees everything again, so a later llmk_prefill retries the setup instead
-// of launching on null buffers.
-int pf_setup_inner(llmk_ctx* c) {
+// Workspaces, the second lane's stream, the KV events and the kernels' dynamic-LDS limits, built aside: the context gets them only
+// after the LAST step succeeded; a failure part-way releases everything again, so a later llmk_prefill starts the setup over
+// instead of launching on null buffers.
+// choose: a setup from scratch also picks the matrix instruction (the f16 one unless LLMK_PF_F32_MFMA=1) -- llmk_prefill and the
+// timing hook both say so, so that a hook called first (or after a redo that dropped the workspaces) cannot leave the context on
+// the slow instruction (advisor, round 5); the redo in llmk_prefill sets pf_hm = false itself and does not
+int pf_setup(llmk_ctx* c, bool choose = false) {
+    if (c->pf) return LLMK_OK;
+    if (choose) c->pf_hm = !(getenv("LLMK_PF_F32_MFMA") && getenv("LLMK_PF_F32_MFMA")[0] == '1');
+    auto pf = std::make_unique<llmk_ctx::Prefill>();
     const size_t T = PF_TMAX;
-    HIPCHK(dev_alloc(&c->pf_flag, sizeof(unsigned)));
-    HIPCHK(hipMemset(c->pf_flag, 0, sizeof(unsigned)));
+    HIPCHK(pf->flag.alloc(1));
+    HIPCHK(hipMemset(pf->flag, 0, sizeof(unsigned)));
     const int rows[4] = {c->E + 2 * c->KV, c->E, 2 * c->H, c->E};
     size_t pcap = 0;
     const int Ks[4] = {c->E, c->E, c->E, c->H};
@@ -1091,35 +1079,22 @@ int pf_setup_inner(llmk_ctx* c) {
     c->pf_pcap = pcap;
     HIPCHK(pf_prepare(c));
     for (int i = 0; i < 2; ++i) {
-        PfLane& w = c->pf[i];
-        HIPCHK(dev_alloc(&w.X, T * c->E * sizeof(float)));
-        HIPCHK(dev_alloc(&w.Xs, T * c->E * sizeof(float)));
-        HIPCHK(dev_alloc(&w.Q, T * c->E * sizeof(float)));
-        HIPCHK(dev_alloc(&w.XB, T * c->E * sizeof(float)));
-        HIPCHK(dev_alloc(&w.HB, T * c->H * sizeof(float)));
-        HIPCHK(dev_alloc(&w.P, pcap * sizeof(float)));
-        HIPCHK(dev_alloc(&w.xn, T * sizeof(float)));
-        HIPCHK(dev_alloc(&w.lowcnt, 2 * T * sizeof(unsigned)));
+        PfLane& w = pf->lane[i];
+        for (DevBuf<float>* x : {&w.X, &w.Xs, &w.Q, &w.XB}) HIPCHK(x->alloc(T * c->E));
+        HIPCHK(w.HB.alloc(T * c->H));
+        HIPCHK(w.P.alloc(pcap));
+        HIPCHK(w.xn.alloc(T));
+        HIPCHK(w.lowcnt.alloc(2 * T));
         HIPCHK(hipMemset(w.lowcnt, 0, 2 * T * sizeof(unsigned)));
-        if (i == 0) w.stream = c->stream;
-        else HIPCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-        w.kv.assign(c->L, nullptr);
-        for (int l = 0; l < c->L; ++l) HIPCHK(hipEventCreateWithFlags(&w.kv[l], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+        if (i == 1) HIPCHK(w.own.create(hipStreamNonBlocking));
+        w.stream = i == 0 ? (hipStream_t)c->stream : (hipStream_t)w.own;
+        w.kv.resize(c->L);
+        for (Event& e : w.kv) HIPCHK(e.create(hipEventDisableTiming));
+        HIPCHK(w.done.create(hipEventDisableTiming));
     }
-    HIPCHK(hipEventCreateWithFlags(&c->pf_start, hipEventDisableTiming));
-    HIPCHK(dev_alloc(&c->pf_tok, (size_t)c->S * sizeof(int)));
-    return LLMK_OK;
-}
-// choose: a setup from scratch also picks the matrix instruction (the f16 one unless LLMK_PF_F32_MFMA=1) -- llmk_prefill and the
-// timing hook both say so, so that a hook called first (or after a redo that tore the workspaces down) cannot leave the context on
-// the slow instruction (advisor, round 5); the redo in llmk_prefill sets pf_hm = false itself and does not
-int pf_setup(llmk_ctx* c, bool choose = false) {
-    if (c->pf_ready) return LLMK_OK;
-    if (choose) c->pf_hm = !(getenv("LLMK_PF_F32_MFMA") && getenv("LLMK_PF_F32_MFMA")[0] == '1');
-    const int rc = pf_setup_inner(c);
-    if (rc) { pf_teardown(c); return rc; }
-    c->pf_ready = true;
+    HIPCHK(pf->start.create(hipEventDisableTiming));
+    HIPCHK(pf->tok.alloc((size_t)c->S));
+    c->pf = std::move(pf);
     return LLMK_OK;
 }
 // dynamic-LDS request of pf_gemm_kernel<NG, *, NR> (> half of the CU's 160 KB: pins one workgroup per CU, so every CU
@@ -1192,14 +1167,14 @@ hipError_t pf_gemm_launch(llmk_ctx* c, const PfLane& w, const PfGemmArgs& a, con
             // arithmetic under the other's matrix instructions (round 5, profiles/r05_prefill_eight_waves.txt: w1|w3 GEMM 33.0 -> 30.9 us on
             // TinyLlama q4_0, 96.2 -> 88.8 at 7B; f16 and f32 weights, which have no such arithmetic, lose 4-6 % to the doubled LDS reads)
             if (wt == LLMK_TYPE_Q4_0) {
-                hipLaunchKernelGGL((pf_gemm_h_kernel<8, 1, WT_Q4_0, 8>), grid, dim3(8 * WAVE), smem_h, w.stream, a, c->pf_flag, w.lowcnt);
+                hipLaunchKernelGGL((pf_gemm_h_kernel<8, 1, WT_Q4_0, 8>), grid, dim3(8 * WAVE), smem_h, w.stream, a, c->pf->flag, w.lowcnt);
                 return hipGetLastError();
             }
         }
-        if (wt == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q4_0>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
-        else if (wt == LLMK_TYPE_Q6_K) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q6_K>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
-        else if (wt == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F16>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
-        else hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F32>), grid, block, smem_h, w.stream, a, c->pf_flag, w.lowcnt);
+        if (wt == LLMK_TYPE_Q4_0) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q4_0>), grid, block, smem_h, w.stream, a, c->pf->flag, w.lowcnt);
+        else if (wt == LLMK_TYPE_Q6_K) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_Q6_K>), grid, block, smem_h, w.stream, a, c->pf->flag, w.lowcnt);
+        else if (wt == LLMK_TYPE_F16) hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F16>), grid, block, smem_h, w.stream, a, c->pf->flag, w.lowcnt);
+        else hipLaunchKernelGGL((pf_gemm_h_kernel<NG, NR, WT_F32>), grid, block, smem_h, w.stream, a, c->pf->flag, w.lowcnt);
         return hipGetLastError();
     }
     if (wt == LLMK_TYPE_Q6_K) return hipErrorInvalidValue;      // (sc_plan keeps q6_K rows off the f32 instruction)
@@ -1215,10 +1190,10 @@ hipError_t pf_gemm(llmk_ctx* c, const PfLane& w, const void* W, int row_stride, 
     a.W = W; a.X = X; a.P = w.P; a.rows = rows; a.K = K; a.T = T; a.RS = row_stride;
     a.nk = p.nk; a.U = p.U; a.total = p.total;
 #ifdef LLMK_PF_TRACE
-    a.trace = (unsigned long long*)(X == w.HB ? w.Q : w.HB);   // debug build: stamps land in the SwiGLU buffer (llmk_peek 7); the w2 GEMM reads that one: its stamps go to the (dead) q buffer
+    a.trace = (unsigned long long*)(X == w.HB ? w.Q : w.HB).get();   // debug build: stamps land in the SwiGLU buffer (llmk_peek 7); the w2 GEMM reads that one: its stamps go to the (dead) q buffer
 #endif
     e->U = p.U; e->nk = p.nk; e->sh = p.nr == 2 ? 7 : 6;
-    e->lowcnt = c->pf_hm ? w.lowcnt : nullptr; e->flag = c->pf_flag; e->gemm_blocks = p.grid;
+    e->lowcnt = c->pf_hm ? w.lowcnt : nullptr; e->flag = c->pf->flag; e->gemm_blocks = p.grid;
 #define PF_CASE(NG_)                                                                         \
     case NG_: return p.nr == 2 ? pf_gemm_launch<NG_, 2>(c, w, a, p, wt) : pf_gemm_launch<NG_, 1>(c, w, a, p, wt)
     switch ((T + 15) / 16) {
@@ -1272,44 +1247,28 @@ ScPlan sc_plan(const llmk_ctx* c, int rows = PF_TMAX) {
     }
     return sp;
 }
-void sc_teardown(llmk_ctx* c) {
-    for (int i = 0; i < 2; ++i) {
-        if (c->sc_part[i]) { hipFree(c->sc_part[i]); c->sc_part[i] = nullptr; }
-        if (c->sc_tgt[i]) { hipFree(c->sc_tgt[i]); c->sc_tgt[i] = nullptr; }
-        if (c->sc_z[i]) { hipFree(c->sc_z[i]); c->sc_z[i] = nullptr; }
-    }
-    if (c->sc_targets) { hipFree(c->sc_targets); c->sc_targets = nullptr; }
-    if (c->sc_out) { hipFree(c->sc_out); c->sc_out = nullptr; }
-    if (c->h_sc) { hipHostFree(c->h_sc); c->h_sc = nullptr; }
-    if (c->sc_logits) { hipFree(c->sc_logits); c->sc_logits = nullptr; }
-    c->sc_logits_cap = 0;
-    c->sc_ready = false;
-}
-int sc_setup_inner(llmk_ctx* c) {
+// built aside, as pf_setup builds the prefill's
+int sc_setup(llmk_ctx* c) {
+    if (c->sc) return LLMK_OK;
+    auto sc = std::make_unique<llmk_ctx::Score>();
     // partial slots per position: at most one more than V / PF_SC_ROWS per chunk, and a chunk has at least 128 rows
     const size_t slots = (size_t)(c->V + PF_SC_ROWS - 1) / PF_SC_ROWS + (size_t)c->V / 128 + 2;
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(dev_alloc(&c->sc_part[i], (size_t)PF_TMAX * slots * sizeof(float4)));
-        HIPCHK(dev_alloc(&c->sc_tgt[i], (size_t)PF_TMAX * sizeof(float)));
+        HIPCHK(sc->part[i].alloc((size_t)PF_TMAX * slots));
+        HIPCHK(sc->tgt[i].alloc((size_t)PF_TMAX));
     }
-    HIPCHK(dev_alloc(&c->sc_targets, (size_t)c->S * sizeof(int)));
-    HIPCHK(dev_alloc(&c->sc_out, (size_t)2 * c->S * sizeof(float)));
-    HIPCHK(hipHostMalloc(&c->h_sc, (size_t)2 * c->S * sizeof(float), hipHostMallocDefault));
+    HIPCHK(sc->targets.alloc((size_t)c->S));
+    HIPCHK(sc->out.alloc((size_t)2 * c->S));
+    HIPCHK(sc->h_out.alloc((size_t)2 * c->S));
     if (c->t[LLMK_WCLS].type == LLMK_TYPE_Q6_K)
-        for (int i = 0; i < 2; ++i) HIPCHK(dev_alloc(&c->sc_z[i], (size_t)PF_TMAX * c->V * sizeof(float)));
-    return LLMK_OK;
-}
-int sc_setup(llmk_ctx* c) {
-    if (c->sc_ready) return LLMK_OK;
-    const int rc = sc_setup_inner(c);
-    if (rc) { sc_teardown(c); return rc; }
-    c->sc_ready = true;
+        for (int i = 0; i < 2; ++i) HIPCHK(sc->z[i].alloc((size_t)PF_TMAX * c->V));
+    c->sc = std::move(sc);
     return LLMK_OK;
 }
 // the merge of a batch's partials: log-probs and ids of positions i0 .. i0+T-1 of the call
 hipError_t sc_merge(llmk_ctx* c, int lane, hipStream_t st, const ScoreJob& sj, int nparts, int T, int i0) {
-    hipLaunchKernelGGL(pf_score_merge_kernel, dim3(T), dim3(64), 0, st, c->sc_part[lane], nparts, sj.want_lp ? c->sc_targets + i0 : nullptr,
-                       c->sc_tgt[lane], (sj.out ? sj.out : c->sc_out) + i0, reinterpret_cast<int*>((sj.out ? sj.out : c->sc_out) + sj.n) + i0);
+    hipLaunchKernelGGL(pf_score_merge_kernel, dim3(T), dim3(64), 0, st, c->sc->part[lane], nparts, sj.want_lp ? c->sc->targets + i0 : nullptr,
+                       c->sc->tgt[lane], (sj.out ? sj.out : c->sc->out) + i0, reinterpret_cast<int*>((sj.out ? sj.out : c->sc->out) + sj.n) + i0);
     return hipGetLastError();
 }
 // after the last layer of a batch (w.Xs = x * final gains, w.xn: pf_epi_resid_norm_kernel): positions i0 .. i0+T-1 of the call
@@ -1318,14 +1277,14 @@ hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const 
     const int V = c->V, E = c->E;
     // (a q6_K classifier: the call's plan is that of a whole batch; a batch below the crossover -- the last one of a call -- has its own)
     const ScPlan sp = ct.type == LLMK_TYPE_Q6_K && sj.sp.R > 0 && T < SC_Q6K_GEMM_MIN_ROWS ? sc_plan(c, T) : sj.sp;
-    float* const logits = sj.logits ? sj.logits : c->sc_logits;
+    float* const logits = sj.logits ? sj.logits : c->sc->logits;
     PfScoreArgs s;
     memset(&s, 0, sizeof(s));
-    s.zp = (size_t)V; s.V = V; s.nparts = sp.nparts; s.part = c->sc_part[lane];
-    s.targets = sj.want_lp ? c->sc_targets + i0 : nullptr; s.tgt = c->sc_tgt[lane];
+    s.zp = (size_t)V; s.V = V; s.nparts = sp.nparts; s.part = c->sc->part[lane];
+    s.targets = sj.want_lp ? c->sc->targets + i0 : nullptr; s.tgt = c->sc->tgt[lane];
     if (ct.type == LLMK_TYPE_Q6_K && sp.R == 0) {
         // q6_K rows without the GEMM (sc_plan): the decode classifier (final rmsnorm inside, q6k.h) on each of the batch's rows
-        float* Z = sj.want_logits ? logits + (size_t)i0 * V : c->sc_z[lane];
+        float* Z = sj.want_logits ? logits + (size_t)i0 * V : c->sc->z[lane];
         const size_t smem = 16 + (size_t)E * sizeof(float);
         const int blocks = (V + GEMV_WAVES * Q6K_RPW - 1) / (GEMV_WAVES * Q6K_RPW);
         for (int t = 0; t < T; ++t) {
@@ -1430,7 +1389,7 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
             return hipGetLastError();
         });
     }));
-    if (sj) HIPRET(sc_batch(c, w, &w == &c->pf[1] ? 1 : 0, e, *sj, T, i0));
+    if (sj) HIPRET(sc_batch(c, w, &w == &c->pf->lane[1] ? 1 : 0, e, *sj, T, i0));
     if (last) HIPRET(hipMemcpyAsync(c->d_x, w.X + (size_t)(T - 1) * E, (size_t)E * sizeof(float), hipMemcpyDeviceToDevice, w.stream));
     return hipEventRecord(w.done, w.stream);
 }
@@ -1445,6 +1404,12 @@ bool pf_shape_ok(const llmk_ctx* c) {
 bool pf_eligible(const llmk_ctx* c) {
     return pf_shape_ok(c) && !(getenv("LLMK_PREFILL") && getenv("LLMK_PREFILL")[0] == '0');
 }
+// the f16-range flag of the passes enqueued so far, on its way to TkHostWords::pf_flag (ENQUEUED on the ctx stream)
+hipError_t pf_fetch_flag(llmk_ctx* c) {
+    unsigned* h_flag = &c->host_words()->pf_flag;
+    *h_flag = 0;
+    return c->pf_hm ? hipMemcpyAsync(h_flag, c->pf->flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
 // The batched pass of llmk_prefill and (sj: with the classifier and log-softmax of every position) llmk_score, ENQUEUED: tokens[0..n)
 // (1-based ids) at positions pos0 .. pos0+n-1 in batches of PF_TMAX that alternate between the two lanes, then the f16-range flag on
 // its way to TkHostWords::pf_flag.  The caller adds its own tail to the ctx stream and synchronises that stream once: everything
@@ -1452,28 +1417,26 @@ bool pf_eligible(const llmk_ctx* c) {
 int pf_run(llmk_ctx* c, const int* tokens, int n, int pos0, const ScoreJob* sj) {
     c->pf_tok0.assign(tokens, tokens + n);
     for (int& t : c->pf_tok0) --t;
-    HIPCHK(hipMemcpyAsync(c->pf_tok, c->pf_tok0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->pf->tok, c->pf_tok0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     // these positions are being rewritten by other kernels: whatever an earlier sequence's decode left in the q4_0 persistent kernel's
     // scale records (token_kernel.h tk_qsc; tagged by position only) must not pass for "the position before" of the decode that follows
     HIPCHK(tk_qsc_clear(c, c->stream));
-    HIPCHK(hipEventRecord(c->pf_start, c->stream));
-    HIPCHK(hipStreamWaitEvent(c->pf[1].stream, c->pf_start, 0));
+    HIPCHK(hipEventRecord(c->pf->start, c->stream));
+    HIPCHK(hipStreamWaitEvent(c->pf->lane[1].stream, c->pf->start, 0));
     int k = 0;
     for (int i = 0; i < n; i += PF_TMAX, ++k) {
         // batch k runs on lane k % 2; its lane's previous batch (k - 2) is ordered by the stream, batch k - 1 by the KV events
         const bool last = i + PF_TMAX >= n;
-        const hipError_t pe = pf_batch(c, c->pf[k & 1], k > 0 ? &c->pf[(k - 1) & 1] : nullptr, c->pf_tok + i, std::min(PF_TMAX, n - i), pos0 + i, last, sj, i);
+        const hipError_t pe = pf_batch(c, c->pf->lane[k & 1], k > 0 ? &c->pf->lane[(k - 1) & 1] : nullptr, c->pf->tok + i, std::min(PF_TMAX, n - i), pos0 + i, last, sj, i);
         if (pe != hipSuccess) {   // nothing of this call may still be running (on either lane) when it returns
-            hipStreamSynchronize(c->pf[1].stream);
+            hipStreamSynchronize(c->pf->lane[1].stream);
             hipStreamSynchronize(c->stream);
             return LLMK_E_HIP + (int)pe;
         }
     }
     // what follows runs on the ctx stream (= lane 0's): after everything lane 1 was given, too
-    if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->pf[1].done, 0));
-    unsigned* h_flag = &c->host_words()->pf_flag;
-    *h_flag = 0;
-    if (c->pf_hm) HIPCHK(hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->pf->lane[1].done, 0));
+    HIPCHK(pf_fetch_flag(c));
     return LLMK_OK;
 }
 // did the synchronised call's batched pass raise the f16-range flag?
@@ -1493,14 +1456,14 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
         fprintf(stderr, "llmk: %s met %s; %s\n", who, for_good ? "an activation beyond the f16 range" : "a position whose activations are all below 2^-7",
                 for_good ? "this context's prompt GEMMs run on the f32 matrix instruction from now on" : "this call is redone on the f32 matrix instruction");
     }
-    HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));
+    HIPCHK(hipMemsetAsync(c->pf->flag, 0, sizeof(unsigned), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    pf_teardown(c);
+    c->pf.reset();
     c->pf_hm = false;
     int rc = pf_setup(c);
     if (rc) return rc;
     rc = again();
-    if (!for_good) pf_teardown(c);          // (pf_ready = false: the next call sets the f16 instruction up again)
+    if (!for_good) c->pf.reset();          // (the next call sets the f16 instruction up again)
     return rc;
 }
 
@@ -1603,49 +1566,50 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
         t.row_bytes = dev_row_bytes(t.type, d.K);
         // the three rmsnorm gain tensors share ONE allocation, att [L][E] | ffn [L][E] | final [E]: the persistent kernel
         // addresses them from one pointer (token_kernel.h TokenArgs::rms)
-        if (i == LLMK_RMS_FFN_WEIGHT || i == LLMK_RMS_FINAL_WEIGHT) {
-            t.alias = true;
+        if (i == LLMK_RMS_FFN_WEIGHT || i == LLMK_RMS_FINAL_WEIGHT) {      // (views: `own` stays empty)
             t.data = (char*)c->t[LLMK_RMS_ATT_WEIGHT].data + (size_t)(i == LLMK_RMS_FFN_WEIGHT ? L : 2 * L) * E * sizeof(float);
             continue;
         }
         const size_t extra = i == LLMK_RMS_ATT_WEIGHT ? ((size_t)L + 1) * E * sizeof(float) : 0;
-        CK(dev_alloc(&t.data, rows * t.row_bytes + extra + TENSOR_SLACK));
+        CK(t.own.alloc(rows * t.row_bytes + extra + TENSOR_SLACK));
+        t.data = t.own;
         if (rc == LLMK_OK) {
             if (t.type == LLMK_TYPE_Q4_0) CK(hipMemset(t.data, 0, rows * t.row_bytes + TENSOR_SLACK));
             else CK(hipMemset((char*)t.data + rows * t.row_bytes + extra, 0, TENSOR_SLACK));
         }
     }
     const size_t kvn = (size_t)L * S * c->KVl;
-    CK(dev_alloc(&c->d_kc, kvn * sizeof(float)));
-    CK(dev_alloc(&c->d_vc, kvn * sizeof(float)));
-    CK(dev_alloc(&c->d_x, (size_t)E * sizeof(float)));
-    CK(dev_alloc(&c->d_q, (size_t)E * sizeof(float)));
-    CK(dev_alloc(&c->d_xb, (size_t)E * sizeof(float)));
-    CK(dev_alloc(&c->d_hb, (size_t)H * sizeof(float)));
-    CK(dev_alloc(&c->d_part, (size_t)E * sizeof(float)));
+    CK(c->d_kc.alloc(kvn));
+    CK(c->d_vc.alloc(kvn));
+    CK(c->d_x.alloc((size_t)E));
+    CK(c->d_q.alloc((size_t)E));
+    CK(c->d_xb.alloc((size_t)E));
+    CK(c->d_hb.alloc((size_t)H));
+    CK(c->d_part.alloc((size_t)E));
     // the logits, then the device's scratch words (scratch_layout.h TkDevWords: the sticky error word first)
+    static_assert(sizeof(TkDevWords) % sizeof(float) == 0 && sizeof(TkHostWords) % sizeof(float) == 0, "the scratch words are whole floats' worth");
     const size_t logits_bytes = (size_t)V * sizeof(float) + sizeof(TkDevWords);
-    CK(dev_alloc(&c->d_logits, logits_bytes));
-    CK(dev_alloc(&c->d_rope, (size_t)(hs / 2) * sizeof(float)));
-    CK(dev_alloc(&c->d_tokpos, 4 * sizeof(int)));
-    CK(dev_alloc(&c->d_next, 2 * sizeof(int)));
-    CK(hipHostMalloc(&c->h_tokpos, 4 * sizeof(int), hipHostMallocDefault));
+    CK(c->d_logits.alloc(logits_bytes / sizeof(float)));
+    CK(c->d_rope.alloc((size_t)(hs / 2)));
+    CK(c->d_tokpos.alloc(4));
+    CK(c->d_next.alloc(2));
+    CK(c->h_tokpos.alloc(4));
     // the logits, then the host's scratch words (TkHostWords) and the S ids of the pipelined decode
-    CK(hipHostMalloc(&c->h_logits, (size_t)V * sizeof(float) + sizeof(TkHostWords) + (size_t)S * sizeof(int), hipHostMallocMapped));
-    CK(hipHostGetDevicePointer((void**)&c->h_logits_dev, c->h_logits, 0));
+    CK(c->h_logits.alloc_mapped((size_t)V + sizeof(TkHostWords) / sizeof(float) + (size_t)S));
     c->tk_direct = !(getenv("LLMK_TK_DIRECT") && getenv("LLMK_TK_DIRECT")[0] == '0');
     // llmk_forward's second logits buffer (forward_ahead.h); LLMK_FORWARD_AHEAD=0: one launch and one stream sync per call, as before
     c->fa_on = !(getenv("LLMK_FORWARD_AHEAD") && getenv("LLMK_FORWARD_AHEAD")[0] == '0');
+    CK(c->fa_second.alloc_mapped((size_t)V));
     c->fa_buf[0] = c->h_logits;
-    c->fa_buf_dev[0] = c->h_logits_dev;
-    CK(hipHostMalloc(&c->fa_buf[1], (size_t)V * sizeof(float), hipHostMallocMapped));
-    CK(hipHostGetDevicePointer((void**)&c->fa_buf_dev[1], c->fa_buf[1], 0));
-    for (int i = 0; i < 2; ++i) CK(hipEventCreateWithFlags(&c->fa_ev[i], hipEventDisableTiming));
-    CK(hipHostMalloc(&c->h_next, sizeof(TkNext), hipHostMallocDefault));
-    CK(hipHostMalloc(&c->h_samp, sizeof(llmk_sample_params), hipHostMallocDefault));
-    CK(hipHostMalloc(&c->h_filt, sizeof(llmk_filter_params), hipHostMallocDefault));
-    CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (int i = 0; i < 8; ++i) CK(hipEventCreate(&c->ev[i]));
+    c->fa_buf_dev[0] = c->h_logits.dev();
+    c->fa_buf[1] = c->fa_second;
+    c->fa_buf_dev[1] = c->fa_second.dev();
+    for (Event& e : c->fa_ev) CK(e.create(hipEventDisableTiming));
+    CK(c->h_next.alloc(1));
+    CK(c->h_samp.alloc(1));
+    CK(c->h_filt.alloc(1));
+    CK(c->stream.create(hipStreamNonBlocking));
+    for (Event& e : c->ev) CK(e.create());
     // The whole-token persistent kernel serves the shapes it is instantiated for, on a full 256-CU part
     if (rc == LLMK_OK) rc = tk_setup_all(c);
     if (rc == LLMK_OK) {   // raise the dynamic-LDS limits the token pass needs, or reject the shape here (see g_prepare)
@@ -1754,17 +1718,17 @@ static int q16_build(llmk_ctx* c) {
         if (t.type != LLMK_TYPE_Q4_0 || d.rows % Q16_ROWS) return LLMK_E_SHAPE;
         const size_t rows = (size_t)d.rows * (d.layered ? c->L : 1), bytes = q16_bytes(rows, d.K);
         if (!c->q16[tid]) {
-            HIPCHK(dev_alloc(&c->q16[tid], bytes + TENSOR_SLACK));
-            HIPCHK(hipMemset((char*)c->q16[tid] + bytes, 0, TENSOR_SLACK));
+            HIPCHK(c->q16[tid].alloc(bytes + TENSOR_SLACK));
+            HIPCHK(hipMemset(c->q16[tid] + bytes, 0, TENSOR_SLACK));
         }
         hipLaunchKernelGGL(q16_units_kernel, dim3((unsigned)(bytes / Q16_UNIT_BYTES)), dim3(64), 0, c->stream, (const char*)t.data, t.row_bytes, d.K,
-                           q16_ncs(d.K), (char*)c->q16[tid]);
+                           q16_ncs(d.K), c->q16[tid].get());
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     if (verify_uploads()) {
-        unsigned long long* d_acc = nullptr;
-        HIPCHK(dev_alloc(&d_acc, sizeof(*d_acc)));
+        DevBuf<unsigned long long> d_acc;
+        HIPCHK(d_acc.alloc(1));
         int rc = LLMK_OK;
         for (int i = 0; i < 5 && rc == LLMK_OK; ++i) {
             const int tid = mats[i];
@@ -1780,7 +1744,6 @@ static int q16_build(llmk_ctx* c) {
                 rc = LLMK_E_VERIFY;
             }
         }
-        hipFree(d_acc);
         if (rc) return rc;
     }
     c->q16_dirty = false;
@@ -1797,19 +1760,19 @@ static int upload_block(llmk_ctx* c, int tid, int layer, int dst_row0, int nrows
     const size_t first_row = (size_t)layer * d.rows + dst_row0;
     const bool verify = verify_uploads();
     int rc = LLMK_OK;
-    if (!c->up_ready) {
-        // the staging objects live as long as the ctx (llmk_destroy frees whatever exists); `up_ready` only after ALL of them do, so a
-        // failure half-way is retried from where it stopped instead of dereferencing what is missing (advisor, round 4)
+    if (!c->up) {
+        // the staging objects live as long as the ctx; built aside, so the ctx has all of them or none (advisor, round 4: a failure
+        // half-way must not leave something missing to be dereferenced)
+        auto up = std::make_unique<llmk_ctx::Upload>();
         for (int b = 0; b < 2; ++b) {
-            if (!c->up_stage[b]) HIPCHK(hipHostMalloc(&c->up_stage[b], UP_STAGE_BYTES, hipHostMallocMapped));
-            if (!c->up_stage_dev[b]) HIPCHK(hipHostGetDevicePointer(&c->up_stage_dev[b], c->up_stage[b], 0));
-            if (!c->up_done[b]) HIPCHK(hipEventCreateWithFlags(&c->up_done[b], hipEventDisableTiming));
-            if (!c->up_tmp[b]) HIPCHK(dev_alloc(&c->up_tmp[b], UP_STAGE_BYTES));
+            HIPCHK(up->stage[b].alloc_mapped(UP_STAGE_BYTES));
+            HIPCHK(up->done[b].create(hipEventDisableTiming));
+            HIPCHK(up->tmp[b].alloc(UP_STAGE_BYTES));
         }
-        if (!c->up_acc) HIPCHK(dev_alloc(&c->up_acc, sizeof(*c->up_acc)));
-        c->up_ready = true;
+        HIPCHK(up->acc.alloc(1));
+        c->up = std::move(up);
     }
-    unsigned long long* const d_acc = c->up_acc;
+    unsigned long long* const d_acc = c->up->acc;
     const bool q6 = t.type == LLMK_TYPE_Q6_K;
     const bool q4 = t.type == LLMK_TYPE_Q4_0 || q6;      // re-packed on the way (q6_K: its own kernel, q6k.h)
     // whole 16-bit words on the host side; the non-q4_0 path moves 32-bit words into rows row_bytes apart (advisor, round 4)
@@ -1824,24 +1787,24 @@ static int upload_block(llmk_ctx* c, int tid, int layer, int dst_row0, int nrows
         int b = 0;
         for (size_t r = 0; r < (size_t)nrows && rc == LLMK_OK; r += rows_per_chunk, b ^= 1) {
             const size_t n = (size_t)nrows - r < rows_per_chunk ? (size_t)nrows - r : rows_per_chunk;
-            hipError_t e = hipEventSynchronize(c->up_done[b]);             // the kernel that read this buffer's previous chunk has finished
+            hipError_t e = hipEventSynchronize(c->up->done[b]);             // the kernel that read this buffer's previous chunk has finished
             if (e != hipSuccess) { rc = LLMK_E_HIP + (int)e; break; }
-            want += stage_rows((uint8_t*)c->up_stage[b], src + r * spitch + col_off, spitch, col_bytes, n);
+            want += stage_rows((uint8_t*)c->up->stage[b].get(), src + r * spitch + col_off, spitch, col_bytes, n);
             // a KERNEL moves the chunk from the (device-mapped) staging buffer into the tensor -- re-packing q4_0 blocks on the
             // way -- so nothing a copy engine wrote is ever read by a kernel
             if (q4) {   // (wide loads over PCIe into a device scratch first: the re-packing reads 2 bytes at a time)
-                hipLaunchKernelGGL(stage_copy_kernel, dim3(1024), dim3(256), 0, 0, (const unsigned*)c->up_stage_dev[b], (unsigned*)c->up_tmp[b],
+                hipLaunchKernelGGL(stage_copy_kernel, dim3(1024), dim3(256), 0, 0, (const unsigned*)c->up->stage[b].dev(), (unsigned*)c->up->tmp[b].get(),
                                    (n * col_bytes + 3) / 4);
-                if (q6) hipLaunchKernelGGL(q6k_repack_kernel, dim3(1024), dim3(256), 0, 0, (const uint8_t*)c->up_tmp[b], dst0 + r * t.row_bytes,
+                if (q6) hipLaunchKernelGGL(q6k_repack_kernel, dim3(1024), dim3(256), 0, 0, (const uint8_t*)c->up->tmp[b].get(), dst0 + r * t.row_bytes,
                                            n * (size_t)(d.K / Q6K_WEIGHTS), d.K / Q6K_WEIGHTS, t.row_bytes);
                 else
-                hipLaunchKernelGGL(q4_repack_kernel, dim3(1024), dim3(256), 0, 0, (const uint8_t*)c->up_tmp[b], dst0 + r * t.row_bytes,
+                hipLaunchKernelGGL(q4_repack_kernel, dim3(1024), dim3(256), 0, 0, (const uint8_t*)c->up->tmp[b].get(), dst0 + r * t.row_bytes,
                                    n * blocks_per_row, (int)blocks_per_row, t.row_bytes);
             }
-            else hipLaunchKernelGGL(stage_copy_kernel, dim3(1024), dim3(256), 0, 0, (const unsigned*)c->up_stage_dev[b], (unsigned*)(dst0 + r * t.row_bytes),
+            else hipLaunchKernelGGL(stage_copy_kernel, dim3(1024), dim3(256), 0, 0, (const unsigned*)c->up->stage[b].dev(), (unsigned*)(dst0 + r * t.row_bytes),
                                     n * col_bytes / 4);
             e = hipGetLastError();
-            if (e == hipSuccess) e = hipEventRecord(c->up_done[b], 0);
+            if (e == hipSuccess) e = hipEventRecord(c->up->done[b], 0);
             if (e != hipSuccess) rc = LLMK_E_HIP + (int)e;
         }
         if (rc != LLMK_OK || !verify) break;
@@ -1966,17 +1929,20 @@ int llmk_set_tensor_type(llmk_ctx* c, int tid, int ggml_type) {
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc = spec_settle(c); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (t.data) HIPCHK(hipFree(t.data));
-    if (c->pf_ready) pf_teardown(c);      // (the next setup prepares the new type's GEMM kernels: pf_prepare)
-    t.data = nullptr;
+    // the new rows, allocated and zeroed BEFORE the old ones go: a call that fails here leaves the tensor as it was, and no state has
+    // a typed, un-uploaded classifier without memory behind it
+    const size_t bytes = (size_t)d.rows * (d.layered ? c->L : 1) * dev_row_bytes(ggml_type, d.K) + TENSOR_SLACK;
+    DevBuf<char> fresh;
+    HIPCHK(fresh.alloc(bytes));
+    HIPCHK(hipMemset(fresh, 0, bytes));
+    c->pf.reset();      // (the next setup prepares the new type's GEMM kernels: pf_prepare)
+    t.own = std::move(fresh);
+    t.data = t.own;
     t.type = ggml_type;
     t.uploaded = false;
     t.rows_uploaded = 0;
-    const size_t rows = (size_t)d.rows * (d.layered ? c->L : 1);
     t.row_bytes = dev_row_bytes(ggml_type, d.K);
-    HIPCHK(dev_alloc(&t.data, rows * t.row_bytes + TENSOR_SLACK));
-    HIPCHK(hipMemset(t.data, 0, rows * t.row_bytes + TENSOR_SLACK));
-    if (c->q16[tid]) { HIPCHK(hipFree(c->q16[tid])); c->q16[tid] = nullptr; }      // the classifier's unit copy, if one was built
+    c->q16[tid].reset();      // the classifier's unit copy, if one was built
     c->q16_dirty = true;
     if (c->use_tk) {
         c->use_tk = false;
@@ -2207,16 +2173,12 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
             }
         }
     }
-    if (batched && sj.want_logits && c->sc_logits_cap < (size_t)n) {
-        if (c->sc_logits) { hipFree(c->sc_logits); c->sc_logits = nullptr; c->sc_logits_cap = 0; }
-        HIPCHK(dev_alloc(&c->sc_logits, (size_t)n * V * sizeof(float)));
-        c->sc_logits_cap = (size_t)n;
-    }
+    if (batched && sj.want_logits) HIPCHK(c->sc->logits.reserve((size_t)n * V, c->stream));
     std::vector<int> tg0;
     if (sj.want_lp) {
         tg0.assign(targets, targets + n);
         for (int& t : tg0) --t;                                  // 0-based; -1 = no target here
-        HIPCHK(hipMemcpyAsync(c->sc_targets, tg0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->sc->targets, tg0.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
     if (!batched) {
         // tensor-parallel ranks, shapes off the 64-column step, LLMK_PREFILL=0: token by token; the pass leaves the position's logits in
@@ -2230,8 +2192,8 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
             if (logits_out) memcpy(logits_out + (size_t)i * V, c->h_logits, (size_t)V * sizeof(float));
             PfScoreArgs s;
             memset(&s, 0, sizeof(s));
-            s.Z = c->h_logits_dev; s.zp = (size_t)V; s.V = V; s.nparts = np; s.part = c->sc_part[0];
-            s.targets = sj.want_lp ? c->sc_targets + i : nullptr; s.tgt = c->sc_tgt[0];
+            s.Z = c->h_logits.dev(); s.zp = (size_t)V; s.V = V; s.nparts = np; s.part = c->sc->part[0];
+            s.targets = sj.want_lp ? c->sc->targets + i : nullptr; s.tgt = c->sc->tgt[0];
             hipLaunchKernelGGL((pf_score_kernel<false>), dim3(np, 1), dim3(256), 0, c->stream, e, s);
             HIPCHK(hipGetLastError());
             HIPCHK(sc_merge(c, 0, c->stream, sj, np, 1, i));
@@ -2242,18 +2204,18 @@ int llmk_score(llmk_ctx* c, const int* tokens, int n, int pos0, const int* targe
         if (rc) return rc;
     }
     // the results: one copy, n floats and n ints
-    HIPCHK(hipMemcpyAsync(c->h_sc, c->sc_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->sc->h_out, c->sc->out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (batched && pf_flagged(c)) {
         static bool told = false;
         return pf_redo(c, "llmk_score", &told, [&] { return llmk_score(c, tokens, n, pos0, targets, logprob_out, argmax_out, logits_out); });
     }
-    const int* ids = reinterpret_cast<const int*>(c->h_sc + n);
+    const int* ids = reinterpret_cast<const int*>(c->sc->h_out + n);
     for (int i = 0; i < n; ++i)
         if (ids[i] < 1 || ids[i] > V) return LLMK_E_NONFINITE;      // no logit of the position is finite (pf_score_merge_kernel answers id 0)
-    if (logprob_out) memcpy(logprob_out, c->h_sc, (size_t)n * sizeof(float));
+    if (logprob_out) memcpy(logprob_out, c->sc->h_out, (size_t)n * sizeof(float));
     if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
-    if (batched && logits_out) HIPCHK(hipMemcpy(logits_out, c->sc_logits, (size_t)n * V * sizeof(float), hipMemcpyDeviceToHost));
+    if (batched && logits_out) HIPCHK(hipMemcpy(logits_out, c->sc->logits, (size_t)n * V * sizeof(float), hipMemcpyDeviceToHost));
     return LLMK_OK;
 }
 
@@ -2270,29 +2232,25 @@ int token_out(llmk_ctx* c, int token, int pos, TailMode tail, int* next_token) {
 
 // ---- the device sampler (sample.h, sample_filter.h, sample_penalty.h): one request, three bodies ------------------------------------
 static_assert(LLMK_PENALTY_MAX_BIAS == LLMK_MAX_LOGIT_BIAS, "sample_penalty.h and llmk.h agree on the length of the bias list");
-// the record, the counts and the parameter words: allocated (and zeroed) by the first call that needs them
-static int pen_setup(llmk_ctx* c) {
-    if (c->d_hist && c->d_pen_cnt && c->d_pen && c->h_pen) return LLMK_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (!c->d_hist) {
-        HIPCHK(dev_alloc(&c->d_hist, (size_t)c->S * sizeof(int)));
-        HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)c->S * sizeof(int), c->stream));
-    }
-    if (!c->d_pen_cnt) {
-        HIPCHK(dev_alloc(&c->d_pen_cnt, (size_t)c->V * sizeof(int)));
-        HIPCHK(hipMemsetAsync(c->d_pen_cnt, 0, (size_t)c->V * sizeof(int), c->stream));
-    }
-    if (!c->d_pen) {
-        HIPCHK(dev_alloc(&c->d_pen, sizeof(llmk_penalty_params)));
-        HIPCHK(hipMemsetAsync(c->d_pen, 0, sizeof(llmk_penalty_params), c->stream));
-    }
-    if (!c->h_pen) {
-        HIPCHK(hipHostMalloc(&c->h_pen, sizeof(llmk_penalty_params), hipHostMallocDefault));
-        memset(c->h_pen, 0, sizeof(llmk_penalty_params));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
+// the token records of `seqs` sequences of `positions` each, their counts over V ids and the parameter words of `rows` rows: built
+// aside (and zeroed) by the first call that needs them
+static int pen_setup(PenaltyState& pen, int device, hipStream_t st, size_t seqs, size_t positions, size_t V, size_t rows) {
+    if (pen.h_pen) return LLMK_OK;
+    HIPCHK(hipSetDevice(device));
+    PenaltyState p;
+    HIPCHK(p.hist.alloc(seqs * positions));
+    HIPCHK(p.hist.zero(st));
+    HIPCHK(p.cnt.alloc(seqs * V));
+    HIPCHK(p.cnt.zero(st));
+    HIPCHK(p.d_pen.alloc(rows));
+    HIPCHK(p.d_pen.zero(st));
+    HIPCHK(p.h_pen.alloc(rows));
+    memset(p.h_pen, 0, rows * sizeof(llmk_penalty_params));
+    HIPCHK(hipStreamSynchronize(st));
+    pen = std::move(p);
     return LLMK_OK;
 }
+static int pen_setup(llmk_ctx* c) { return pen_setup(c->pen, c->cfg.device, c->stream, 1, (size_t)c->S, (size_t)c->V, 1); }
 // ---- decode log-probs (logprob.h) ----
 static_assert(LLMK_LOGPROB_MAX_TOP == LLMK_MAX_TOP_LOGPROBS, "logprob.h and llmk.h agree on the length of the list");
 // the checks of a log-prob request: nothing runs and nothing is allocated here
@@ -2302,31 +2260,32 @@ static bool logprob_args_ok(const llmk_ctx* c, const llmk_logprobs* lp) {
     if (lp->top_n > 0 && (!lp->top_tokens || !lp->top_logprobs)) return false;
     return c->tp_size == 1 && !c->comm && !c->p2p;
 }
-// the records, the pinned top_n word and, under penalties, the raw logits: allocated by the first call that needs them
-static int lp_setup(llmk_ctx* c, bool raw) {
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t bytes = ((size_t)c->S + 1) * sizeof(llmk_logprob_record);
-    if (!c->d_lp) {
-        HIPCHK(dev_alloc(&c->d_lp, bytes));
-        HIPCHK(hipMemsetAsync(c->d_lp, 0, bytes, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+// Room for nrec records on the device and in pinned memory (zeroed; a request for more than there is drains `st` and replaces both),
+// the pinned top_n word -- dev_top: and a device copy of it -- and, under penalties, nraw raw logits (0: none): each allocated by the
+// first call that needs it
+static int lp_setup(LogprobState& lp, int device, hipStream_t st, size_t nrec, size_t nraw, bool dev_top) {
+    HIPCHK(hipSetDevice(device));
+    if (lp.h.size() < nrec) {
+        HIPCHK(lp.d.reserve(nrec, st));
+        HIPCHK(lp.d.zero(st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(lp.h.alloc(nrec));
+        memset(lp.h, 0, nrec * sizeof(llmk_logprob_record));
     }
-    if (!c->h_lp) {
-        HIPCHK(hipHostMalloc(&c->h_lp, bytes, hipHostMallocDefault));
-        memset(c->h_lp, 0, bytes);
+    if (!lp.h_top) {
+        HIPCHK(lp.h_top.alloc(1));
+        *lp.h_top = 0u;
     }
-    if (!c->h_lp_top) {
-        HIPCHK(hipHostMalloc(&c->h_lp_top, sizeof(unsigned), hipHostMallocDefault));
-        *c->h_lp_top = 0u;
-    }
-    if (raw && !c->d_lp_raw) HIPCHK(dev_alloc(&c->d_lp_raw, (size_t)c->V * sizeof(float)));
+    if (dev_top && !lp.d_top) HIPCHK(lp.d_top.alloc(1));
+    if (nraw && !lp.raw) HIPCHK(lp.raw.alloc(nraw));
     return LLMK_OK;
 }
+static int lp_setup(llmk_ctx* c, bool raw) { return lp_setup(c->lp, c->cfg.device, c->stream, (size_t)c->S + 1, raw ? (size_t)c->V : 0, false); }
 // a checked request becomes the running call's (every site reads c->lp_top_n); LpScope ends it
 static int logprob_request(llmk_ctx* c, const llmk_logprobs* lp, bool raw) {
     const int rc = lp_setup(c, raw);
     if (rc) return rc;
-    *c->h_lp_top = (unsigned)lp->top_n;
+    *c->lp.h_top = (unsigned)lp->top_n;
     c->lp_top_n = lp->top_n;
     return LLMK_OK;
 }
@@ -2334,13 +2293,15 @@ struct LpScope {
     llmk_ctx* c;
     ~LpScope() { c->lp_top_n = -1; }
 };
-// record `from` of the pinned block into entry i of the caller's arrays
-static void logprob_deliver(const llmk_ctx* c, const llmk_logprobs* lp, int i, int from) {
-    const llmk_logprob_record& r = c->h_lp[from];
-    if (lp->token_logprob) lp->token_logprob[i] = r.token_logprob;
-    for (int j = 0; j < lp->top_n; ++j) {
-        lp->top_tokens[(size_t)i * lp->top_n + j] = r.top_tokens[j];
-        lp->top_logprobs[(size_t)i * lp->top_n + j] = r.top_logprobs[j];
+// n pinned records into entries 0 .. n-1 of the caller's arrays
+static void logprob_deliver(const llmk_logprob_record* rec, size_t n, const llmk_logprobs* lp) {
+    for (size_t k = 0; k < n; ++k) {
+        const llmk_logprob_record& r = rec[k];
+        if (lp->token_logprob) lp->token_logprob[k] = r.token_logprob;
+        for (int j = 0; j < lp->top_n; ++j) {
+            lp->top_tokens[k * lp->top_n + j] = r.top_tokens[j];
+            lp->top_logprobs[k * lp->top_n + j] = r.top_logprobs[j];
+        }
     }
 }
 
@@ -2395,7 +2356,7 @@ static int sampler_request(llmk_ctx* c, const llmk_sampler* sp, const llmk_penal
     int rc = pen_setup(c);
     if (rc) return rc;
     if (lp && (rc = logprob_request(c, lp, true)) != LLMK_OK) return rc;
-    *c->h_pen = pen;
+    *c->pen.h_pen = pen;
     *tail = TAIL_PENALTY;
     return LLMK_OK;
 }
@@ -2451,14 +2412,14 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
             HIPCHK(launch_token_kernel(c, false, g));
             // the fed token: the host's at the first position, afterwards the id the filter kernel of the position before left in d_next
             if (filter_tail)
-                HIPCHK(enqueue_sampler(c, tail == TAIL_PENALTY, {nullptr, pos0 + i, token, i ? c->d_next : nullptr, c->d_hist,
+                HIPCHK(enqueue_sampler(c, tail == TAIL_PENALTY, {nullptr, pos0 + i, token, i ? c->d_next : nullptr, c->pen.hist,
                                                                  dw->cand[(pos0 + i) & 1], TK_NCU, i == 0, false,
-                                                                 lp ? c->d_lp + (pos0 + i - 1) : nullptr}));
+                                                                 lp ? c->lp.d + (pos0 + i - 1) : nullptr}));
             else if (lp)      // the id: the fold of this launch's candidates, as the next launch (or cand_resolve_kernel) takes it
-                HIPCHK(enqueue_logprob(c, c->d_logits, nullptr, dw->cand[(pos0 + i) & 1], TK_NCU, 0, c->d_lp + (pos0 + i - 1)));
+                HIPCHK(enqueue_logprob(c, c->d_logits, nullptr, dw->cand[(pos0 + i) & 1], TK_NCU, 0, c->lp.d + (pos0 + i - 1)));
         }
         if (lp)      // the records of the whole call, in one copy
-            HIPCHK(hipMemcpyAsync(c->h_lp + (pos0 - 1), c->d_lp + (pos0 - 1), (size_t)n * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(c->lp.h + (pos0 - 1), c->lp.d + (pos0 - 1), (size_t)n * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
         hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, dw->cand[(pos0 + n - 1) & 1], h_ids_dev + (n - 1), c->d_next, &dw->err, c->V);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&c->h_next->err, &dw->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -2482,7 +2443,7 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         }
         const unsigned err = c->h_next->err;
         if (err == 0 && done == n) {
-            for (int i = 0; lp && i < n; ++i) logprob_deliver(c, lp, i, pos0 + i - 1);
+            if (lp) logprob_deliver(c->lp.h + (pos0 - 1), (size_t)n, lp);
             return LLMK_OK;
         }
         // a timed-out exchange: every later launch drained on the sticky word.  Retire the token kernel and redo the rest,
@@ -2499,10 +2460,10 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         if (rc) return rc;
         if (c->h_next->id < 1 || c->h_next->id > c->V) return LLMK_E_NONFINITE;      // (before the callback sees it)
         token = ids_out[i] = c->h_next->id;
-        if (lp) c->h_lp[pos0 + i - 1] = c->h_lp[c->S];      // (a redone position rewrites its record)
+        if (lp) c->lp.h[pos0 + i - 1] = c->lp.h[c->S];      // (a redone position rewrites its record)
         if (on_token) on_token(i, token, user);
     }
-    for (int i = 0; lp && i < n; ++i) logprob_deliver(c, lp, i, pos0 + i - 1);
+    if (lp) logprob_deliver(c->lp.h + (pos0 - 1), (size_t)n, lp);
     return LLMK_OK;
 }
 
@@ -2596,7 +2557,7 @@ int llmk_forward_sample_lp(llmk_ctx* c, int token, int pos, const llmk_sampler* 
     TailMode tail = TAIL_GREEDY;
     rc = sp ? sampler_request(c, sp, pn, &tail, lp) : logprob_request(c, lp, false);
     if (rc == LLMK_OK) rc = token_out(c, token, pos, tail, next_token);
-    if (rc == LLMK_OK) logprob_deliver(c, lp, 0, c->S);
+    if (rc == LLMK_OK) logprob_deliver(c->lp.h + c->S, 1, lp);
     return rc;
 }
 int llmk_decode_sample_lp(llmk_ctx* c, int token, int pos0, int n, const llmk_sampler* sp, const llmk_penalties* pn, const llmk_logprobs* lp,
@@ -2616,13 +2577,13 @@ int llmk_logprob_logits(llmk_ctx* c, const float* logits, int token, int top_n, 
     int rc = check_ready(c);
     if (rc) return rc;
     if ((rc = lp_setup(c, false)) != LLMK_OK) return rc;      // (no site reads a running request here: the kernel is enqueued below)
-    *c->h_lp_top = (unsigned)top_n;
+    *c->lp.h_top = (unsigned)top_n;
     HIPCHK(hipMemcpyAsync(c->d_logits, logits, (size_t)c->V * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(copy_logprob_top(c));
-    HIPCHK(enqueue_logprob(c, c->d_logits, nullptr, nullptr, 0, token, c->d_lp + c->S));
-    HIPCHK(hipMemcpyAsync(c->h_lp + c->S, c->d_lp + c->S, sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(enqueue_logprob(c, c->d_logits, nullptr, nullptr, 0, token, c->lp.d + c->S));
+    HIPCHK(hipMemcpyAsync(c->lp.h + c->S, c->lp.d + c->S, sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    logprob_deliver(c, &lp, 0, c->S);
+    logprob_deliver(c->lp.h + c->S, 1, &lp);
     return LLMK_OK;
 }
 int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
@@ -2632,7 +2593,7 @@ int llmk_set_history(llmk_ctx* c, const int* tokens, int n, int pos0) {
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const int rc = pen_setup(c);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_hist + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->pen.hist + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
 }
@@ -2641,7 +2602,7 @@ int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const int rc = pen_setup(c);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(tokens_out, c->d_hist + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tokens_out, c->pen.hist + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
 }
@@ -2650,24 +2611,13 @@ int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
 static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
 constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 * BD_WAVES * 16) * sizeof(float); }
 
-static void batch_free(llmk_batch* b) {
-    void* dev[] = {b->d_kc, b->d_vc, b->d_rows, b->d_tok, b->d_out, b->d_logits, b->d_po, b->d_pml, b->d_next, b->d_filt, b->d_out2, b->d_err, b->d_ids,
-                   b->d_hist, b->d_pen_cnt, b->d_pen, b->d_raw, b->d_lp, b->d_lp_top, b->d_pk, b->d_pv, b->d_first, b->d_colmap, b->d_xpo, b->d_xpml};
-    for (void* p : dev)
-        if (p) hipFree(p);
-    void* host[] = {b->h_rows, b->h_tok, b->h_filt, b->h_out, b->h_err, b->h_pen, b->h_lp, b->h_lp_top, b->h_first, b->h_colmap};
-    for (void* p : host)
-        if (p) hipHostFree(p);
-    delete b;
-}
-
 // One pass, ENQUEUED on the context's stream: the n rows in d_rows / d_tok through every layer, the classifier and the per-row first
 // maximum (into d_out + n); the logits of every row into d_logits when asked for.  max_pos: the longest row (the attention's split rule).
 // With attached rows among them (pass_att > 0, llmk_prefix_*) the attention is the three kernels of batch.h's prefix section; `step`:
 // the rows stand `step` positions behind the uploaded ones (a decode's later passes).
 static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, int step = 0) {
     llmk_ctx* c = b->ctx;
-    PfLane& w = c->pf[0];
+    PfLane& w = c->pf->lane[0];
     const int E = c->E, KV = c->KV, QKV = E + 2 * KV, T = n;
     const BdCaches bc{b->d_rows, (size_t)b->seq_len * KV, b->n_slots, b->seq_len};
     int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
@@ -2678,7 +2628,7 @@ static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, c
         int own = 0;
         for (int i = 0; i < n; ++i) {
             const int pos = b->h_rows[i].pos + step;
-            own = std::max(own, (pos + BD_TILE - 1) / BD_TILE - b->h_first[b->h_rows[i].slot] / BD_TILE);
+            own = std::max(own, (pos + BD_TILE - 1) / BD_TILE - b->px->h_first[b->h_rows[i].slot] / BD_TILE);
         }
         parts = bd_parts(n, c->nkv, own * BD_TILE, c->n_cu);
         tpp = bd_tiles_per_part(own * BD_TILE, parts);
@@ -2700,12 +2650,12 @@ static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, c
                 const int np = pparts + parts;
                 const size_t px = (size_t)l * b->P * KV;
                 hipLaunchKernelGGL((bd_attn_prefix_kernel<HS>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
-                                   w.Q, b->d_pk + px, b->d_pv + px, b->d_xpo, b->d_xpml, b->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
+                                   w.Q, b->px->d_pk + px, b->px->d_pv + px, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
                 HIPRET(hipGetLastError());
                 hipLaunchKernelGGL((bd_attn_own_kernel<HS>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
-                                   w.Q, kc, vc, b->d_xpo, b->d_xpml, bc, b->d_first, KV, c->kv_mul, E, tpp, np, pparts);
+                                   w.Q, kc, vc, b->px->d_xpo, b->px->d_xpml, bc, b->px->d_first, KV, c->kv_mul, E, tpp, np, pparts);
                 HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_xpo, b->d_xpml, w.XB, bc, b->d_first,
+                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->px->d_xpo, b->px->d_xpml, w.XB, bc, b->px->d_first,
                                    c->kv_mul, E, np, pparts);
                 return hipGetLastError();
             }
@@ -2745,7 +2695,7 @@ static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* 
         seen[slots[i]] = true;
         if (fed && (tokens[i] < 1 || tokens[i] > b->ctx->V)) return false;
         if (pos[i] < 1 || pos[i] > b->seq_len || span - 1 > b->seq_len - pos[i]) return false;
-        if (b->n_attached > 0 && pos[i] <= b->h_first[slots[i]]) return false;      // an attached slot's positions 1..P are the prefix
+        if (b->n_attached > 0 && pos[i] <= b->px->h_first[slots[i]]) return false;      // an attached slot's positions 1..P are the prefix
     }
     return true;
 }
@@ -2759,21 +2709,15 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
     if (b->n_attached > 0) {
         // the column map: the attached rows in row order, -1 up to the end of the last column group
         for (int i = 0; i < n; ++i)
-            if (b->h_first[slots[i]] > 0) b->h_colmap[b->pass_att++] = i;
+            if (b->px->h_first[slots[i]] > 0) b->px->h_colmap[b->pass_att++] = i;
         if (b->pass_att > 0) {
             const int rg = bd_prefix_rg(b->ctx->kv_mul), cells = bd_prefix_groups(b->pass_att, b->ctx->kv_mul) * rg;
-            for (int k = b->pass_att; k < cells; ++k) b->h_colmap[k] = -1;
-            HIPRET(hipMemcpyAsync(b->d_colmap, b->h_colmap, (size_t)cells * sizeof(int), hipMemcpyHostToDevice, st));
+            for (int k = b->pass_att; k < cells; ++k) b->px->h_colmap[k] = -1;
+            HIPRET(hipMemcpyAsync(b->px->d_colmap, b->px->h_colmap, (size_t)cells * sizeof(int), hipMemcpyHostToDevice, st));
         }
     }
     HIPRET(hipMemcpyAsync(b->d_rows, b->h_rows, (size_t)n * sizeof(BdRow), hipMemcpyHostToDevice, st));
     return hipMemcpyAsync(b->d_tok, b->h_tok, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
-}
-// the f16-range flag on its way to the host (as pf_run leaves it)
-static hipError_t bd_fetch_flag(llmk_ctx* c) {
-    unsigned* h_flag = &c->host_words()->pf_flag;
-    *h_flag = 0;
-    return c->pf_hm ? hipMemcpyAsync(h_flag, c->pf_flag, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
 }
 
 int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) {
@@ -2783,42 +2727,39 @@ int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) {
     if (rc) return rc;
     if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;
     HIPCHK(hipSetDevice(c->cfg.device));
-    llmk_batch* b = new llmk_batch;
+    // built aside: the caller gets the batch only after every step succeeded (a failure releases what was made)
+    auto b = std::make_unique<llmk_batch>();
     b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len;
     ScPlan sp;
-    if ((rc = bd_ready(b, &sp, n_slots)) != LLMK_OK) { delete b; return rc; }
-    const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV * sizeof(float), nb = LLMK_MAX_BATCH;
-    auto alloc = [&]() -> int {
-        HIPCHK(dev_alloc(&b->d_kc, cache));
-        HIPCHK(dev_alloc(&b->d_vc, cache));
-        HIPCHK(hipMemsetAsync(b->d_kc, 0, cache, c->stream));
-        HIPCHK(hipMemsetAsync(b->d_vc, 0, cache, c->stream));
-        HIPCHK(dev_alloc(&b->d_rows, nb * sizeof(BdRow)));
-        HIPCHK(dev_alloc(&b->d_tok, nb * sizeof(int)));
-        HIPCHK(dev_alloc(&b->d_out, 2 * nb * sizeof(float)));
-        HIPCHK(dev_alloc(&b->d_logits, (size_t)n_slots * c->V * sizeof(float)));
-        // parts > 1 only while rows x kv heads x parts <= n_cu (bd_parts)
-        HIPCHK(dev_alloc(&b->d_po, (size_t)c->n_cu * BD_MAX_GROUP * c->hs * sizeof(float)));
-        HIPCHK(dev_alloc(&b->d_pml, (size_t)c->n_cu * BD_MAX_GROUP * sizeof(float2)));
-        HIPCHK(dev_alloc(&b->d_next, nb * sizeof(int)));
-        HIPCHK(dev_alloc(&b->d_filt, nb * sizeof(llmk_filter_params)));
-        HIPCHK(dev_alloc(&b->d_out2, 2 * nb * sizeof(unsigned)));
-        HIPCHK(dev_alloc(&b->d_err, sizeof(unsigned)));
-        HIPCHK(hipHostMalloc(&b->h_rows, nb * sizeof(BdRow), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&b->h_tok, nb * sizeof(int), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&b->h_filt, nb * sizeof(llmk_filter_params), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&b->h_out, 2 * nb * sizeof(float), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&b->h_err, sizeof(unsigned), hipHostMallocDefault));
-        HIPCHK(with_head_size(c->hs, [](auto hs) {
-            constexpr int HS = decltype(hs)::value;
-            return hipFuncSetAttribute((const void*)bd_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
-        }));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return LLMK_OK;
-    };
-    if ((rc = alloc()) != LLMK_OK) { batch_free(b); return rc; }
+    if ((rc = bd_ready(b.get(), &sp, n_slots)) != LLMK_OK) return rc;
+    const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV, nb = LLMK_MAX_BATCH;
+    HIPCHK(b->d_kc.alloc(cache));
+    HIPCHK(b->d_vc.alloc(cache));
+    HIPCHK(b->d_kc.zero(c->stream));
+    HIPCHK(b->d_vc.zero(c->stream));
+    HIPCHK(b->d_rows.alloc(nb));
+    HIPCHK(b->d_tok.alloc(nb));
+    HIPCHK(b->d_out.alloc(2 * nb));
+    HIPCHK(b->d_logits.alloc((size_t)n_slots * c->V));
+    // parts > 1 only while rows x kv heads x parts <= n_cu (bd_parts)
+    HIPCHK(b->d_po.alloc((size_t)c->n_cu * BD_MAX_GROUP * c->hs));
+    HIPCHK(b->d_pml.alloc((size_t)c->n_cu * BD_MAX_GROUP));
+    HIPCHK(b->d_next.alloc(nb));
+    HIPCHK(b->d_filt.alloc(nb));
+    HIPCHK(b->d_out2.alloc(2 * nb));
+    HIPCHK(b->d_err.alloc(1));
+    HIPCHK(b->h_rows.alloc(nb));
+    HIPCHK(b->h_tok.alloc(nb));
+    HIPCHK(b->h_filt.alloc(nb));
+    HIPCHK(b->h_out.alloc(2 * nb));
+    HIPCHK(b->h_err.alloc(1));
+    HIPCHK(with_head_size(c->hs, [](auto hs) {
+        constexpr int HS = decltype(hs)::value;
+        return hipFuncSetAttribute((const void*)bd_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+    }));
+    HIPCHK(hipStreamSynchronize(c->stream));
     ++c->n_batches;
-    *out = b;
+    *out = b.release();
     return LLMK_OK;
 }
 
@@ -2829,15 +2770,15 @@ int llmk_batch_destroy(llmk_batch* b) {
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     hipStreamSynchronize(c->stream);
     --c->n_batches;
-    batch_free(b);
+    delete b;
     return LLMK_OK;
 }
 
 // a slot joins (first = P) or leaves (0) the prefix: its `first` word, here and on the device (ENQUEUED)
 static hipError_t prefix_first(llmk_batch* b, int slot, int first) {
-    b->n_attached += (first > 0) - (b->h_first[slot] > 0);
-    b->h_first[slot] = first;
-    return hipMemcpyAsync(b->d_first + slot, b->h_first + slot, sizeof(int), hipMemcpyHostToDevice, b->ctx->stream);
+    b->n_attached += (first > 0) - (b->px->h_first[slot] > 0);
+    b->px->h_first[slot] = first;
+    return hipMemcpyAsync(b->px->d_first + slot, b->px->h_first + slot, sizeof(int), hipMemcpyHostToDevice, b->ctx->stream);
 }
 
 int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
@@ -2856,8 +2797,8 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
                 HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         }
     // a forked or emptied slot is a new sequence: no token fed yet (the caller records the prompt with llmk_rows_set_history)
-    if (b->d_hist) HIPCHK(hipMemsetAsync(b->d_hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
-    if (b->h_first && b->h_first[slot] > 0) HIPCHK(prefix_first(b, slot, 0));      // a forked slot is self-contained: it leaves the prefix
+    if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
+    if (b->px && b->px->h_first[slot] > 0) HIPCHK(prefix_first(b, slot, 0));      // a forked slot is self-contained: it leaves the prefix
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
 }
@@ -2872,35 +2813,31 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->cfg.device));
     const size_t row = (size_t)c->KV, nb = LLMK_MAX_BATCH;
-    // what a pass with attached rows needs beyond the prefix rows (each once; a call that failed half way is picked up where it stopped)
-    const size_t states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul, words = (size_t)b->n_slots * sizeof(int);
-    if (!b->d_first) {
-        HIPCHK(dev_alloc(&b->d_first, words));
-        HIPCHK(hipMemsetAsync(b->d_first, 0, words, c->stream));
+    if (!b->px) {
+        // what a pass with attached rows needs beyond the prefix rows, built aside by the first call that sets a prefix
+        auto px = std::make_unique<llmk_batch::Prefix>();
+        const size_t states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul, words = (size_t)b->n_slots;
+        HIPCHK(px->d_first.alloc(words));
+        HIPCHK(px->d_first.zero(c->stream));
+        HIPCHK(px->h_first.alloc(words));
+        memset(px->h_first, 0, words * sizeof(int));
+        HIPCHK(px->d_colmap.alloc(nb + BD_MAX_GROUP));
+        HIPCHK(px->h_colmap.alloc(nb + BD_MAX_GROUP));
+        HIPCHK(px->d_xpo.alloc(states * c->hs));
+        HIPCHK(px->d_xpml.alloc(states));
+        HIPCHK(with_head_size(c->hs, [](auto hs) -> hipError_t {
+            constexpr int HS = decltype(hs)::value;
+            HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS)));
+            return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+        }));
+        b->px = std::move(px);
     }
-    if (!b->h_first) {
-        HIPCHK(hipHostMalloc(&b->h_first, words, hipHostMallocDefault));
-        memset(b->h_first, 0, words);
-    }
-    if (!b->d_colmap) HIPCHK(dev_alloc(&b->d_colmap, (nb + BD_MAX_GROUP) * sizeof(int)));
-    if (!b->h_colmap) HIPCHK(hipHostMalloc(&b->h_colmap, (nb + BD_MAX_GROUP) * sizeof(int), hipHostMallocDefault));
-    if (!b->d_xpo) HIPCHK(dev_alloc(&b->d_xpo, states * c->hs * sizeof(float)));
-    if (!b->d_xpml) HIPCHK(dev_alloc(&b->d_xpml, states * sizeof(float2)));
-    HIPCHK(with_head_size(c->hs, [](auto hs) -> hipError_t {
-        constexpr int HS = decltype(hs)::value;
-        HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS)));
-        return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
-    }));
-    if (b->px_cap < (size_t)n_pos) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (b->d_pk) { hipFree(b->d_pk); b->d_pk = nullptr; }
-        if (b->d_pv) { hipFree(b->d_pv); b->d_pv = nullptr; }
-        b->px_cap = 0; b->P = 0;
-        HIPCHK(dev_alloc(&b->d_pk, (size_t)c->L * n_pos * row * sizeof(float)));
-        HIPCHK(dev_alloc(&b->d_pv, (size_t)c->L * n_pos * row * sizeof(float)));
-        b->px_cap = (size_t)n_pos;
-    }
-    float* caches[2][2] = {{b->d_pk, c->d_kc}, {b->d_pv, c->d_vc}};
+    // the prefix rows: room for n_pos positions (a longer prefix than any before drains the stream and replaces both blocks)
+    const size_t px_rows = (size_t)c->L * n_pos * row;
+    if (b->px->d_pv.size() < px_rows) b->P = 0;
+    HIPCHK(b->px->d_pk.reserve(px_rows, c->stream));
+    HIPCHK(b->px->d_pv.reserve(px_rows, c->stream));
+    float* caches[2][2] = {{b->px->d_pk, c->d_kc}, {b->px->d_pv, c->d_vc}};
     for (auto& p : caches)
         for (int l = 0; l < c->L; ++l)
             HIPCHK(hipMemcpyAsync(p[0] + (size_t)l * n_pos * row, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float),
@@ -2918,10 +2855,10 @@ int llmk_prefix_attach(llmk_batch* b, int slot) {
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     // a new sequence behind the prefix: own rows and token record as llmk_batch_fork(b, slot, 0) leaves them
     const size_t slot_rows = (size_t)b->seq_len * c->KV;
-    for (float* base : {b->d_kc, b->d_vc})
+    for (float* base : {b->d_kc.get(), b->d_vc.get()})
         for (int l = 0; l < c->L; ++l)
             HIPCHK(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(float), c->stream));
-    if (b->d_hist) HIPCHK(hipMemsetAsync(b->d_hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
+    if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     HIPCHK(prefix_first(b, slot, b->P));
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
@@ -2941,7 +2878,7 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos));
     HIPCHK(bd_pass(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp));
     HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(bd_fetch_flag(c));
+    HIPCHK(pf_fetch_flag(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (pf_flagged(c)) {
         static bool told = false;
@@ -2956,49 +2893,10 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
 }
 
 // ---- the rows functions: a batch's samplers, penalties, bias and log-prob records, one workgroup per row of the pass ----
-// the slots' token records, their counts and the rows' penalty words: allocated (and zeroed) by the first call that needs them
+// the slots' token records, their counts and the rows' penalty words (pen_setup)
 static int rows_pen_setup(llmk_batch* b) {
-    if (b->d_hist && b->d_pen_cnt && b->d_pen && b->h_pen) return LLMK_OK;
     llmk_ctx* c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t hist = (size_t)b->n_slots * b->seq_len * sizeof(int), cnt = (size_t)b->n_slots * c->V * sizeof(int);
-    const size_t pen = (size_t)LLMK_MAX_BATCH * sizeof(llmk_penalty_params);
-    if (!b->d_hist) {
-        HIPCHK(dev_alloc(&b->d_hist, hist));
-        HIPCHK(hipMemsetAsync(b->d_hist, 0, hist, c->stream));
-    }
-    if (!b->d_pen_cnt) {
-        HIPCHK(dev_alloc(&b->d_pen_cnt, cnt));
-        HIPCHK(hipMemsetAsync(b->d_pen_cnt, 0, cnt, c->stream));
-    }
-    if (!b->d_pen) {
-        HIPCHK(dev_alloc(&b->d_pen, pen));
-        HIPCHK(hipMemsetAsync(b->d_pen, 0, pen, c->stream));
-    }
-    if (!b->h_pen) {
-        HIPCHK(hipHostMalloc(&b->h_pen, pen, hipHostMallocDefault));
-        memset(b->h_pen, 0, pen);
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return LLMK_OK;
-}
-// room for a call's nrec records on the device and in pinned memory (grown like d_ids), the top_n word and, under penalties, the raw logits
-static int rows_lp_setup(llmk_batch* b, size_t nrec, bool raw) {
-    llmk_ctx* c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (b->lp_cap < nrec) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (b->d_lp) { hipFree(b->d_lp); b->d_lp = nullptr; }
-        if (b->h_lp) { hipHostFree(b->h_lp); b->h_lp = nullptr; }
-        b->lp_cap = 0;
-        HIPCHK(dev_alloc(&b->d_lp, nrec * sizeof(llmk_logprob_record)));
-        HIPCHK(hipHostMalloc(&b->h_lp, nrec * sizeof(llmk_logprob_record), hipHostMallocDefault));
-        b->lp_cap = nrec;
-    }
-    if (!b->d_lp_top) HIPCHK(dev_alloc(&b->d_lp_top, sizeof(unsigned)));
-    if (!b->h_lp_top) HIPCHK(hipHostMalloc(&b->h_lp_top, sizeof(unsigned), hipHostMallocDefault));
-    if (raw && !b->d_raw) HIPCHK(dev_alloc(&b->d_raw, (size_t)b->n_slots * c->V * sizeof(float)));
-    return LLMK_OK;
+    return pen_setup(b->pen, c->cfg.device, c->stream, (size_t)b->n_slots, (size_t)b->seq_len, (size_t)c->V, LLMK_MAX_BATCH);
 }
 // What the rows of a call ask for: every entry checked (sampler_words, penalty_words; the window against the BATCH's seq_len), nothing
 // allocated before every check has passed and nothing at all by a call that needs no record.  The samplers' words go to h_filt; with a
@@ -3020,11 +2918,11 @@ static int rows_request(llmk_batch* b, int n, const llmk_sampler* samplers, cons
     int rc;
     if (*pen_on) {
         if ((rc = rows_pen_setup(b)) != LLMK_OK) return rc;
-        memcpy(b->h_pen, pen.data(), (size_t)n * sizeof(llmk_penalty_params));
+        memcpy(b->pen.h_pen, pen.data(), (size_t)n * sizeof(llmk_penalty_params));
     }
     if (lp) {
-        if ((rc = rows_lp_setup(b, nrec, *pen_on)) != LLMK_OK) return rc;
-        *b->h_lp_top = (unsigned)lp->top_n;
+        if ((rc = lp_setup(b->lp, c->cfg.device, c->stream, nrec, *pen_on ? (size_t)b->n_slots * c->V : 0, true)) != LLMK_OK) return rc;
+        *b->lp.h_top = (unsigned)lp->top_n;
     }
     return LLMK_OK;
 }
@@ -3035,12 +2933,12 @@ static int rows_request(llmk_batch* b, int n, const llmk_sampler* samplers, cons
 // d_lp + i * stride + step.  Returns where the picks are.
 static hipError_t rows_enqueue(llmk_batch* b, int n, bool sampled, bool pen, bool record, bool lp, int stride, int step, const int** picked) {
     llmk_ctx* c = b->ctx;
-    const int* rows = reinterpret_cast<const int*>(b->d_rows);
+    const int* rows = reinterpret_cast<const int*>(b->d_rows.get());
     if (sampled) {
         if (pen) {
-            if (lp) HIPRET(hipMemcpyAsync(b->d_raw, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            if (lp) HIPRET(hipMemcpyAsync(b->lp.raw, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             hipLaunchKernelGGL(sample_penalty_rows_kernel, dim3(n), dim3(SP_THREADS), 0, c->stream, b->d_logits, c->V, rows, record ? b->d_tok : nullptr,
-                               b->d_pen, b->d_hist, record ? b->d_hist : nullptr, b->d_pen_cnt, b->n_slots, b->seq_len);
+                               b->pen.d_pen, b->pen.hist, record ? b->pen.hist : nullptr, b->pen.cnt, b->n_slots, b->seq_len);
             HIPRET(hipGetLastError());
         }
         hipLaunchKernelGGL(sample_filter_rows_kernel, dim3(n), dim3(SF_THREADS), 0, c->stream, b->d_logits, c->V, rows, b->d_filt, b->d_next, b->d_out2);
@@ -3048,8 +2946,8 @@ static hipError_t rows_enqueue(llmk_batch* b, int n, bool sampled, bool pen, boo
         *picked = b->d_next;
     }
     if (lp) {
-        hipLaunchKernelGGL(sample_logprob_rows_kernel, dim3(n), dim3(SF_THREADS), 0, c->stream, (sampled && pen) ? b->d_raw : b->d_logits, c->V, *picked,
-                           b->d_lp_top, b->d_lp, stride, step);
+        hipLaunchKernelGGL(sample_logprob_rows_kernel, dim3(n), dim3(SF_THREADS), 0, c->stream, (sampled && pen) ? b->lp.raw : b->d_logits, c->V, *picked,
+                           b->lp.d_top, b->lp.d, stride, step);
         HIPRET(hipGetLastError());
     }
     return hipSuccess;
@@ -3058,22 +2956,10 @@ static hipError_t rows_enqueue(llmk_batch* b, int n, bool sampled, bool pen, boo
 static hipError_t rows_upload_words(llmk_batch* b, int n, bool sampled, bool pen, bool lp) {
     hipStream_t st = b->ctx->stream;
     if (sampled) HIPRET(hipMemcpyAsync(b->d_filt, b->h_filt, (size_t)n * sizeof(llmk_filter_params), hipMemcpyHostToDevice, st));
-    if (pen) HIPRET(hipMemcpyAsync(b->d_pen, b->h_pen, (size_t)n * sizeof(llmk_penalty_params), hipMemcpyHostToDevice, st));
-    if (lp) HIPRET(hipMemcpyAsync(b->d_lp_top, b->h_lp_top, sizeof(unsigned), hipMemcpyHostToDevice, st));
+    if (pen) HIPRET(hipMemcpyAsync(b->pen.d_pen, b->pen.h_pen, (size_t)n * sizeof(llmk_penalty_params), hipMemcpyHostToDevice, st));
+    if (lp) HIPRET(hipMemcpyAsync(b->lp.d_top, b->lp.h_top, sizeof(unsigned), hipMemcpyHostToDevice, st));
     return hipSuccess;
 }
-// the pinned records [row][step] into the caller's arrays
-static void rows_deliver(const llmk_batch* b, const llmk_logprobs* lp, size_t nrec) {
-    for (size_t k = 0; k < nrec; ++k) {
-        const llmk_logprob_record& r = b->h_lp[k];
-        if (lp->token_logprob) lp->token_logprob[k] = r.token_logprob;
-        for (int j = 0; j < lp->top_n; ++j) {
-            lp->top_tokens[k * lp->top_n + j] = r.top_tokens[j];
-            lp->top_logprobs[k * lp->top_n + j] = r.top_logprobs[j];
-        }
-    }
-}
-
 // llmk_batch_decode and llmk_rows_decode (`who`): the former is the latter without penalties and records
 static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, const int* tokens, const int* pos0, int steps,
                        const llmk_sampler* samplers, const llmk_penalties* penalties, const llmk_logprobs* lp, int* ids_out) {
@@ -3085,11 +2971,7 @@ static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, 
     if (rc) return rc;
     ScPlan sp;
     if ((rc = bd_ready(b, &sp, n)) != LLMK_OK) return rc;
-    if (b->ids_cap < nids) {
-        if (b->d_ids) { hipFree(b->d_ids); b->d_ids = nullptr; b->ids_cap = 0; }
-        HIPCHK(dev_alloc(&b->d_ids, nids * sizeof(int)));
-        b->ids_cap = nids;
-    }
+    HIPCHK(b->d_ids.reserve(nids, c->stream));
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos0));
     HIPCHK(rows_upload_words(b, n, samplers != nullptr, pen, lp != nullptr));
     HIPCHK(hipMemsetAsync(b->d_err, 0, sizeof(unsigned), c->stream));
@@ -3103,9 +2985,9 @@ static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, 
         hipLaunchKernelGGL(bd_advance_kernel, dim3(1), dim3(LLMK_MAX_BATCH), 0, c->stream, picked, n, c->V, s, steps, b->d_ids, b->d_tok, b->d_rows, b->d_err);
         HIPCHK(hipGetLastError());
     }
-    if (lp) HIPCHK(hipMemcpyAsync(b->h_lp, b->d_lp, nids * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+    if (lp) HIPCHK(hipMemcpyAsync(b->lp.h, b->lp.d, nids * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(b->h_err, b->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(bd_fetch_flag(c));
+    HIPCHK(pf_fetch_flag(c));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (pf_flagged(c)) {
         // The redone call starts from the caller's rows again and finds the state a first call finds: the token records are indexed by
@@ -3116,7 +2998,7 @@ static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, 
     }
     HIPCHK(hipMemcpy(ids_out, b->d_ids, nids * sizeof(int), hipMemcpyDeviceToHost));
     if (*b->h_err) return LLMK_E_NONFINITE;
-    if (lp) rows_deliver(b, lp, nids);
+    if (lp) logprob_deliver(b->lp.h, nids, lp);      // [row][step]
     return LLMK_OK;
 }
 
@@ -3150,7 +3032,7 @@ int llmk_rows_sample_logits(llmk_batch* b, int n, const int* slots, const int* p
     HIPCHK(hipMemcpyAsync(tokens_out, picked, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(out2.data(), b->d_out2, out2.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     if (adjusted_out) HIPCHK(hipMemcpyAsync(adjusted_out, b->d_logits, nv, hipMemcpyDeviceToHost, c->stream));
-    if (logprobs) HIPCHK(hipMemcpyAsync(b->h_lp, b->d_lp, (size_t)n * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
+    if (logprobs) HIPCHK(hipMemcpyAsync(b->lp.h, b->lp.d, (size_t)n * sizeof(llmk_logprob_record), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; ++i) {
         if (kept_out) kept_out[i] = (int)out2[2 * i];
@@ -3158,7 +3040,7 @@ int llmk_rows_sample_logits(llmk_batch* b, int n, const int* slots, const int* p
     }
     for (int i = 0; i < n; ++i)
         if (tokens_out[i] < 1 || tokens_out[i] > c->V) return LLMK_E_NONFINITE;
-    if (logprobs) rows_deliver(b, logprobs, (size_t)n);
+    if (logprobs) logprob_deliver(b->lp.h, (size_t)n, logprobs);
     return LLMK_OK;
 }
 
@@ -3171,7 +3053,7 @@ int llmk_rows_set_history(llmk_batch* b, int slot, const int* tokens, int n, int
     const int rc = rows_pen_setup(b);
     if (rc) return rc;
     hipStream_t st = b->ctx->stream;
-    HIPCHK(hipMemcpyAsync(b->d_hist + (size_t)slot * b->seq_len + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->pen.hist + (size_t)slot * b->seq_len + (pos0 - 1), tokens, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     return LLMK_OK;
 }
@@ -3181,7 +3063,7 @@ int llmk_rows_get_history(llmk_batch* b, int slot, int* tokens_out, int n, int p
     const int rc = rows_pen_setup(b);
     if (rc) return rc;
     hipStream_t st = b->ctx->stream;
-    HIPCHK(hipMemcpyAsync(tokens_out, b->d_hist + (size_t)slot * b->seq_len + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(tokens_out, b->pen.hist + (size_t)slot * b->seq_len + (pos0 - 1), (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return LLMK_OK;
 }
@@ -3189,7 +3071,7 @@ int llmk_rows_get_history(llmk_batch* b, int slot, int* tokens_out, int n, int p
 int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     if (!b || !avg_ms || n < 1 || n > b->n_slots || pos < 1 || pos > b->seq_len || iters < 1) return LLMK_E_ARG;
     for (int i = 0; i < n && b->n_attached > 0; ++i)
-        if (pos <= b->h_first[i]) return LLMK_E_ARG;      // (slots 0..n-1: an attached one's positions 1..P are the prefix)
+        if (pos <= b->px->h_first[i]) return LLMK_E_ARG;      // (slots 0..n-1: an attached one's positions 1..P are the prefix)
     llmk_ctx* c = b->ctx;
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);
@@ -3199,18 +3081,16 @@ int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     HIPCHK(bd_upload_rows(b, n, slots, tokens, posv));
     HIPCHK(bd_pass(b, n, pos, false, sp));      // warm-up
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    hipError_t pe = hipEventCreate(&e1);
+    Event e0, e1;
+    HIPCHK(e0.create());
+    hipError_t pe = e1.create();
     if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
     for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, pos, false, sp);
     if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
     if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
     float ms = 0.f;
     if (pe == hipSuccess) pe = hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    HIPCHK(hipMemsetAsync(c->pf_flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
+    HIPCHK(hipMemsetAsync(c->pf->flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
     HIPCHK(hipStreamSynchronize(c->stream));
     if (pe != hipSuccess) return LLMK_E_HIP + (int)pe;
     *avg_ms = ms / (float)iters;
@@ -3226,9 +3106,9 @@ int llmk_reset(llmk_ctx* c) {
     HIPCHK(hipMemsetAsync(c->d_vc, 0, kvn, c->stream));
     HIPCHK(hipMemsetAsync(&c->dev_words()->err, 0, sizeof(unsigned), c->stream));   // the token kernel's sticky error word
     HIPCHK(tk_qsc_clear(c, c->stream));      // a new sequence: no position before it (the q4_0 kernels' scale records, token_kernel.h tk_qsc)
-    if (c->d_hist) {                         // ... and no token fed yet (the record of the penalties; their counts are zero between launches anyway)
-        HIPCHK(hipMemsetAsync(c->d_hist, 0, (size_t)c->S * sizeof(int), c->stream));
-        HIPCHK(hipMemsetAsync(c->d_pen_cnt, 0, (size_t)c->V * sizeof(int), c->stream));
+    if (c->pen.hist) {                         // ... and no token fed yet (the record of the penalties; their counts are zero between launches anyway)
+        HIPCHK(hipMemsetAsync(c->pen.hist, 0, (size_t)c->S * sizeof(int), c->stream));
+        HIPCHK(hipMemsetAsync(c->pen.cnt, 0, (size_t)c->V * sizeof(int), c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->host_words()->err = 0;
@@ -3301,8 +3181,8 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
         }
         // activations of ordinary size (every float 0x3c3c3c3c = 0.0115): an all-zero workspace would make every workgroup of the f16-instruction
         // GEMM cast its low-end votes (prefill.h pf_low_check: 32k atomics per launch, +16 us) -- a path real activations do not take
-        HIPCHK(hipMemsetAsync(c->pf[0].Xs, 0x3c, (size_t)PF_TMAX * c->E * sizeof(float), c->stream));
-        HIPCHK(hipMemsetAsync(c->pf[0].HB, 0x3c, (size_t)PF_TMAX * c->H * sizeof(float), c->stream));
+        HIPCHK(hipMemsetAsync(c->pf->lane[0].Xs, 0x3c, (size_t)PF_TMAX * c->E * sizeof(float), c->stream));
+        HIPCHK(hipMemsetAsync(c->pf->lane[0].HB, 0x3c, (size_t)PF_TMAX * c->H * sizeof(float), c->stream));
     }
     // Successive launches walk the layers so the weight stream never re-hits the 256 MiB Infinity
     // Cache (the classifier has one matrix: its figure is cache-assisted beyond the first launch).
@@ -3323,7 +3203,7 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
             const DevTensor& ct = c->t[LLMK_WCLS];
             for (int k = 0; k < sp.nchunks; ++k) {
                 const int r0 = k * sp.R;
-                HIPRET(pf_gemm(c, c->pf[0], (const char*)ct.data + (size_t)r0 * ct.row_bytes, (int)ct.row_bytes, c->pf[0].Xs, std::min(sp.R, c->V - r0), c->E,
+                HIPRET(pf_gemm(c, c->pf->lane[0], (const char*)ct.data + (size_t)r0 * ct.row_bytes, (int)ct.row_bytes, c->pf->lane[0].Xs, std::min(sp.R, c->V - r0), c->E,
                                PF_TMAX, &e, ct.type));
             }
             return hipSuccess;
@@ -3333,9 +3213,9 @@ int llmk_time_kernel(llmk_ctx* c, int kernel, int iters, float* avg_ms, double* 
             const int tid = kernel == 7 ? LLMK_W13 : kernel == 8 ? LLMK_WQKV : kernel == 9 ? LLMK_WO : LLMK_W2;
             const int rows = kernel == 7 ? 2 * c->H : kernel == 8 ? c->E + 2 * c->KV : c->E;
             const char* w = (const char*)c->t[tid].data + (size_t)l * rows * c->t[tid].row_bytes;
-            const float* X = kernel == 10 ? c->pf[0].HB : c->pf[0].Xs;
+            const float* X = kernel == 10 ? c->pf->lane[0].HB : c->pf->lane[0].Xs;
             const int K = kernel == 10 ? c->H : c->E;
-            return pf_gemm(c, c->pf[0], w, (int)c->t[tid].row_bytes, X, rows, K, PF_TMAX, &e);
+            return pf_gemm(c, c->pf->lane[0], w, (int)c->t[tid].row_bytes, X, rows, K, PF_TMAX, &e);
         }
         switch (kernel) {
             case 0: return launch_qkv(c, l);
@@ -3411,7 +3291,10 @@ int llmk_peek(llmk_ctx* c, int which, int layer, int pos, float* out, int n) {
             len = c->KVl;
             break;
 #ifdef LLMK_PF_TRACE
-        case 7: src = c->pf[0].HB; len = PF_TMAX * c->H; break;
+        case 7:
+            if (!c->pf) return LLMK_E_ARG;
+            src = c->pf->lane[0].HB; len = PF_TMAX * c->H;
+            break;
 #endif
         case 8: {  // the q4_0 persistent kernels' per-layer scale records (token_kernel.h tk_qsc): [2 buffers][TK_QSC_LMAX] x {|xb|, |hb|, pos, pos}
             size_t ng;
@@ -3422,7 +3305,7 @@ int llmk_peek(llmk_ctx* c, int which, int layer, int pos, float* out, int n) {
         }
         case 6:  // debug: raw trace stamps reinterpret as floats (2 per stamp)
             if (!c->d_trace) return LLMK_E_ARG;
-            src = (const float*)c->d_trace; len = TK_NCU * TK_TRACE_N * 2;
+            src = (const float*)c->d_trace.get(); len = TK_NCU * TK_TRACE_N * 2;
             break;
         default: return LLMK_E_ARG;
     }
@@ -3459,9 +3342,9 @@ static int tp_inbox_alloc(llmk_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     const size_t bytes = tp_inbox_granules(c->tp_size, c->E, c->V) * sizeof(unsigned long long);
     // fine-grained: peers' stores over xGMI and this device's system-scope polls meet in memory, not in a stale L2 line
-    HIPCHK(hipExtMallocWithFlags((void**)&c->d_inbox, bytes, hipDeviceMallocFinegrained));
+    HIPCHK(c->d_inbox.alloc_finegrained(bytes / sizeof(unsigned long long)));
     HIPCHK(hipMemset(c->d_inbox, 0, bytes));      // tag 0 is never a valid epoch
-    HIPCHK(dev_alloc(&c->d_tp_bad, sizeof(unsigned)));
+    HIPCHK(c->d_tp_bad.alloc(1));
     HIPCHK(hipDeviceSynchronize());
     c->peers.inbox[c->tp_rank] = c->d_inbox;
     // bound of every spin of the exchange kernels in WALL-CLOCK ticks (tp_p2p.h): 20 s unless LLMK_TP_TIMEOUT_MS says otherwise
@@ -3698,16 +3581,15 @@ int llmk_tensor_checksum(llmk_ctx* c, int tid, unsigned long long* out) {
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const size_t nwords = (size_t)d.rows * (d.layered ? c->L : 1) * t.row_bytes / 4;
-    unsigned long long* d_out = nullptr;
-    HIPCHK(dev_alloc(&d_out, sizeof(*d_out)));
-    hipError_t e = hipMemsetAsync(d_out, 0, sizeof(*d_out), c->stream);
+    DevBuf<unsigned long long> d_out;
+    HIPCHK(d_out.alloc(1));
+    hipError_t e = d_out.zero(c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(checksum_kernel, dim3(1024), dim3(256), 0, c->stream, (const unsigned*)t.data, nwords, d_out);
+        hipLaunchKernelGGL(checksum_kernel, dim3(1024), dim3(256), 0, c->stream, (const unsigned*)t.data, nwords, d_out.get());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(*d_out), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(*out), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_out);
     return e == hipSuccess ? LLMK_OK : LLMK_E_HIP + (int)e;
 }
 
@@ -3760,40 +3642,8 @@ int llmk_destroy(llmk_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     for (int r = 0; r < TP_MAX_RANKS; ++r)
         if (c->ipc_mapped[r]) hipIpcCloseMemHandle(c->ipc_mapped[r]);
-    if (c->d_inbox) hipFree(c->d_inbox);
-    if (c->d_tp_bad) hipFree(c->d_tp_bad);
     drop_graphs(c);
-    for (int i = 0; i < LLMK_N_TENSORS; ++i) {
-        if (c->t[i].data && !c->t[i].alias) hipFree(c->t[i].data);
-    }
-    pf_teardown(c);
-    sc_teardown(c);
-    void* dev[] = {c->d_kc, c->d_vc, c->d_x, c->d_q, c->d_xb, c->d_hb, c->d_logits, c->d_rope, c->d_tokpos, c->d_next,
-                   c->d_gran, c->d_zeros, c->d_trace, c->d_part, c->d_hist, c->d_pen_cnt, c->d_pen, c->d_lp, c->d_lp_raw};
-    for (void* p : dev)
-        if (p) hipFree(p);
-    for (int b = 0; b < 2; ++b) {
-        if (c->up_stage[b]) hipHostFree(c->up_stage[b]);
-        if (c->up_tmp[b]) hipFree(c->up_tmp[b]);
-        if (c->up_done[b]) hipEventDestroy(c->up_done[b]);
-    }
-    if (c->up_acc) hipFree(c->up_acc);
-    for (int i = 0; i < LLMK_N_TENSORS; ++i)
-        if (c->q16[i]) hipFree(c->q16[i]);
-    if (c->h_tokpos) hipHostFree(c->h_tokpos);
-    if (c->h_logits) hipHostFree(c->h_logits);
-    if (c->fa_buf[1]) hipHostFree(c->fa_buf[1]);
-    for (hipEvent_t e : c->fa_ev)
-        if (e) hipEventDestroy(e);
-    if (c->h_next) hipHostFree(c->h_next);
-    if (c->h_samp) hipHostFree(c->h_samp);
-    if (c->h_filt) hipHostFree(c->h_filt);
-    if (c->h_pen) hipHostFree(c->h_pen);
-    if (c->h_lp) hipHostFree(c->h_lp);
-    if (c->h_lp_top) hipHostFree(c->h_lp_top);
-    for (int i = 0; i < 8; ++i)
-        if (c->ev[i]) hipEventDestroy(c->ev[i]);
-    if (c->stream) hipStreamDestroy(c->stream);
+    // everything else the context holds is owned (owned.h): the buffers and events go before the stream, which is declared first
     delete c;
     return LLMK_OK;
 }

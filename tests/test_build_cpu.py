@@ -83,3 +83,22 @@ def test_scratch_words_are_addressed_through_their_structs():
             if raw.search(code):
                 hits.append(f"{name}:{n}: {line.strip()}")
     assert not hits, "\n".join(hits)
+
+
+def test_the_shim_allocates_and_releases_through_its_owners_only():
+    """What the shim allocates or creates is held by the move-only owners of csrc/owned.h, whose destructors release it: no hand-kept
+    teardown list can fall behind a new field again.  Outside comments, llmk.hip spells none of the runtime's allocate / create /
+    free / destroy calls (as a substring: the ...WithFlags and ...Async forms are meant too); owned.h does, and llmk.hip reaches it."""
+    calls = ("hipMalloc", "hipHostMalloc", "hipFree", "hipHostFree", "hipEventCreate", "hipEventDestroy", "hipStreamCreate", "hipStreamDestroy")
+    csrc = os.path.join(ROOT, "llm.f90_amd", "csrc")
+
+    def code(name):
+        return [(n, line.split("//", 1)[0]) for n, line in enumerate(open(os.path.join(csrc, name)), 1)]
+    hits = [f"llmk.hip:{n}: {c.strip()}" for n, c in code("llmk.hip") for w in calls if w in c]
+    assert not hits, "\n".join(hits)
+    owned = "\n".join(c for _, c in code("owned.h"))
+    missing = [w for w in calls if not re.search(r"\b%s(WithFlags)?\b" % w, owned)]
+    assert not missing, f"owned.h never names {missing}"
+    seen = set()
+    _quoted_includes(os.path.join(csrc, "llmk.hip"), seen)
+    assert os.path.normpath(os.path.join(csrc, "owned.h")) in seen
