@@ -494,11 +494,42 @@ int llmk_rows_sample_logits(llmk_batch *b, int n, const int *slots, const int *p
  * llmk_batch_fork -- not bit-identical to either: the attention folds the prefix's parts, then the row's own.  The same call on the same
  * state returns the same bits (no float atomics, a fixed part order, no waiting across workgroups).  A pass WITHOUT an attached row
  * returns the bits it returned before a prefix was set.
- * Out of scope: more than one prefix per batch, a tree of prefixes, a shorter own cache for attached slots (the memory saving), f16
- * K/V, any automatic choice between fork and attach. */
+ * Out of scope: more than one prefix per batch, a tree of prefixes, a shorter own cache for attached slots (the memory saving),
+ * any automatic choice between fork and attach.  (f16 K/V: llmk_cache_create, below.) */
 int llmk_prefix_set(llmk_batch *b, int n_pos);
 int llmk_prefix_attach(llmk_batch *b, int slot);
 int llmk_prefix_len(llmk_batch *b);
+
+/* A batch whose K/V caches are IEEE half precision: half the bytes the attention reads per pass and half the
+ * device memory per slot.  ("cache", not "batch": the llmk_batch_* list is closed.)  The type is the caller's choice at creation and
+ * covers the slots' own caches AND the shared prefix -- no mixed types within a batch, no automatic choice.  The context's own cache,
+ * llmk_prefill and the persistent kernel stay f32.
+ *
+ * create:  kv_type LLMK_TYPE_F32 or LLMK_TYPE_F16, anything else LLMK_E_TYPE; every other check is llmk_batch_create's, with the same
+ *          codes.  With LLMK_TYPE_F32 it IS llmk_batch_create: same code path, same allocations, same launches, same bits.  The handle
+ *          is an llmk_batch: llmk_batch_*, llmk_rows_* and llmk_prefix_* take it with their contracts unchanged (the parity wording
+ *          aside, below).  Caches the device has no room for: LLMK_E_NOMEM, nothing is left allocated.
+ * type:    LLMK_TYPE_F32 | LLMK_TYPE_F16, a negative LLMK_E_* on error (as llmk_path).
+ * bytes:   device bytes of the K/V caches plus the prefix rows, if the batch has any (as allocated: a prefix's blocks only grow).
+ * peek:    verification hook, like llmk_peek: n cache rows of kv_dim floats each -- K (which 0) or V (1) of positions pos0 .. pos0+n-1
+ *          (1-based) of `slot` in `layer`, converted to f32 (exact for f16); slot -1 reads the prefix, positions 1..P.  Out-of-range
+ *          arguments: LLMK_E_ARG.  Both cache types.
+ * A NULL batch is LLMK_E_ARG (llmk_cache_type: -LLMK_E_ARG) before anything touches a device, in all of them.
+ *
+ * STORED VALUES of an f16 batch: h = (x != x) ? NaN : RNE_f16(clamp(x, -65504, 65504)) -- round to nearest even, f16 subnormals
+ * kept, where x is the f32 value the f32 path stores at that place: at a pass's K/V write what the f32 batch's kernel computes (the
+ * same function up to the store), at llmk_batch_fork and llmk_prefix_set the context's f32 row.  Values SATURATE at +-65504 instead of
+ * becoming infinite: one outlier must not turn a row's softmax into NaN.  The attention converts the loaded halves back to f32 in
+ * registers (exact) and from there runs the arithmetic of the f32 kernels unchanged, so an f16 batch's pass is DEFINED as the f32 pass
+ * over a cache that holds the rounded values; the determinism rules carry over (no float atomics, fixed part order, no waiting across
+ * workgroups: the same call on the same state gives the same bits).  The f16-range redo rewrites the rows' K/V rows in the batch's type.
+ * Parity: rounding K/V to f16 moves a row's logits by a few 1e-4 of max |logit| against llmk_forward's on that sequence (measured on
+ * the test models), so an f16 batch is NOT within the 1e-4 bar of the f32 paths; it is within it of the float64 forward pass fed the
+ * rows the batch stored (tests/kv16_ref.py). */
+int llmk_cache_create(llmk_ctx *ctx, int n_slots, int seq_len, int kv_type, llmk_batch **out);
+int llmk_cache_type(llmk_batch *b);    /* LLMK_TYPE_F32 | LLMK_TYPE_F16, negative LLMK_E_* on error */
+int llmk_cache_bytes(llmk_batch *b, unsigned long long *out);   /* device bytes of the K/V caches + the prefix, if any */
+int llmk_cache_peek(llmk_batch *b, int which, int layer, int slot, int pos0, int n, float *out);
 
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);

@@ -8,7 +8,7 @@
 //   bd_attn_merge  the parts of a row folded in part order
 //   bd_advance     llmk_batch_decode: the picked id becomes the row's next token, its position moves on -- on the device
 //   bd_attn_prefix / bd_attn_own / bd_attn_fold   a pass with rows ATTACHED to the batch's shared prefix (llmk_prefix_*, below)
-// The caches are [L][n_slots][seq_len][KV] f32.
+// The caches are [L][n_slots][seq_len][KV], f32 or -- a batch of llmk_cache_create(.., LLMK_TYPE_F16) -- IEEE half.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -66,6 +66,88 @@ __global__ void bd_epi_qkv_kernel(PfEpiArgs a, BdCaches bc) {
     pf_epi_qkv_pair(a, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
     pf_epi_qkv_pair(a, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
 }
+// The same for a batch with f16 caches (llmk_cache_create): the layer's caches are kc / vc (a.kc, a.vc are not read), Q still goes out
+// in f32, and a K / V element is stored as pf_kv_half of the value the kernel above stores (pf_epi_qkv_pair_h: the same expressions up
+// to the store).
+__global__ void bd_epi_qkv_h_kernel(PfEpiArgs a, BdCaches bc, _Float16* __restrict__ kc, _Float16* __restrict__ vc) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    if (p4 >= a.rows / 4) return;
+    const BdRow r = bc.rows[t];
+    if (!bd_row_ok(bc, r)) return;
+    const float4 s4 = pf_sum4(a, t, 4 * p4);
+    a.pos0 = r.pos - t;
+    kc += (size_t)r.slot * bc.slot_stride;
+    vc += (size_t)r.slot * bc.slot_stride;
+    pf_epi_qkv_pair_h(a, kc, vc, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
+    pf_epi_qkv_pair_h(a, kc, vc, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
+}
+
+// f32 rows of the context's cache into an f16 batch (llmk_batch_fork, llmk_prefix_set): n elements (a multiple of 4) of every layer
+// and of K (blockIdx.z 0) and V (1), element i of layer l from src[l * src_layer + i] to dst[l * dst_layer + i], as pf_kv_half.
+__global__ void bd_to_half_kernel(const float* __restrict__ sk, const float* __restrict__ sv, _Float16* __restrict__ dk,
+                                  _Float16* __restrict__ dv, size_t n, size_t src_layer, size_t dst_layer) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const float* src = (blockIdx.z ? sv : sk) + blockIdx.y * src_layer;
+    _Float16* dst = (blockIdx.z ? dv : dk) + blockIdx.y * dst_layer;
+    for (size_t i = 4 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x); i < n; i += 4 * (size_t)gridDim.x * blockDim.x) {
+        const float4 x = *reinterpret_cast<const float4*>(src + i);
+        *reinterpret_cast<h4*>(dst + i) = (h4){pf_kv_half(x.x), pf_kv_half(x.y), pf_kv_half(x.z), pf_kv_half(x.w)};
+    }
+}
+
+// ---- a tile's K / V fragments, requested one tile ahead                                                               ------------
+// Lane (li, g) of a wave holds, of the tile at cache row r0: K row r0 + li, elements g * DG .. + DG (kb points at the lane's first);
+// V rows r0 + 4g + v, v = 0..3, elements NT * li .. + NT (vb likewise).  Unconditional loads of a row index clamped to `last`.
+// The look-ahead registers' types are BdAhead<HS, T>::K / V.  f32 caches: float[DG] and float[4][NT], loaded by the statements the
+// kernels always had (they stand in the kernels, so that the f32 instantiations compile to the instructions they compiled to before
+// the caches had a type).  f16 caches: BdHalfAhead keeps the halves PACKED in the look-ahead registers (half the VGPRs) and converts at
+// use, exactly; its loads are as wide as the fragment: K 16 bytes (8 halves) a piece at head sizes 32 .. 128 and one 8-byte load at
+// 16, V 2 | 4 | 8 | 16 bytes.  kv_dim % 16 == 0 keeps every row 32-byte aligned in either type.
+template <int N>
+struct BdHalves { typedef _Float16 type __attribute__((ext_vector_type(N))); };
+template <>
+struct BdHalves<1> { typedef _Float16 type; };
+template <int HS>
+struct BdHalfAhead {
+    static constexpr int DG = HS / 4, NT = HS / 16, KW = DG < 8 ? DG : 8;      // KW: halves per K load
+    typedef typename BdHalves<KW>::type K[DG / KW];
+    typedef typename BdHalves<NT>::type V[4];
+    static __device__ __forceinline__ void load(K& kn, V& vn, const _Float16* kb, const _Float16* vb, int KV, int r0, int li, int g, int last) {
+        const _Float16* kp = kb + (size_t)min(r0 + li, last) * KV;
+#pragma unroll
+        for (int m = 0; m < DG / KW; ++m) kn[m] = *reinterpret_cast<const typename BdHalves<KW>::type*>(kp + m * KW);
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            vn[v] = *reinterpret_cast<const typename BdHalves<NT>::type*>(vb + (size_t)min(r0 + 4 * g + v, last) * KV);
+    }
+    static __device__ __forceinline__ void take(const K& kn, const V& vn, float (&kf)[DG], float (&vf)[4][NT]) {
+#pragma unroll
+        for (int m = 0; m < DG; ++m) kf[m] = (float)kn[m / KW][m % KW];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            if constexpr (NT == 1) {
+                vf[v][0] = (float)vn[v];
+            } else {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) vf[v][t] = (float)vn[v][t];
+            }
+        }
+    }
+};
+
+template <int HS, class T>
+struct BdAhead;
+template <int HS>
+struct BdAhead<HS, float> {
+    typedef float K[HS / 4];
+    typedef float V[4][HS / 16];
+};
+template <int HS>
+struct BdAhead<HS, _Float16> {
+    typedef typename BdHalfAhead<HS>::K K;
+    typedef typename BdHalfAhead<HS>::V V;
+};
 
 // ---- decode attention over many caches                                                      llama2.f90:572-598 ------------
 // pf_attn_kernel's layout with the 16 MFMA query columns holding the kv_mul QUERY HEADS OF ONE KV GROUP (padded by repeating the
@@ -74,9 +156,10 @@ __global__ void bd_epi_qkv_kernel(PfEpiArgs a, BdCaches bc) {
 // parts == 1: the normalised output goes to `out`.  Otherwise the part leaves its state -- the maximum M, the sum L and the
 // unnormalised output relative to M, per query head -- in po / pml, and bd_attn_merge_kernel folds a row's parts in part order.
 // An empty part (a short row next to a long one) leaves M = -inf, L = 0.
-template <int HS>
-__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* __restrict__ Q, const float* __restrict__ kc,
-                                                                  const float* __restrict__ vc, float* __restrict__ out,
+// T: the caches' element type, float or _Float16 (BdAhead: only the loads and the conversion differ).
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                  const T* __restrict__ vc, float* __restrict__ out,
                                                                   float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
                                                                   int KV, int kv_mul, int E, int tpp) {
     constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
@@ -104,44 +187,54 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* _
     pf_v4f O[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
-    const float* kb = kc + (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS + g * DG;
-    const float* vb = vc + (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS + NT * li;
+    const T* kb = kc + (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS + g * DG;
+    const T* vb = vc + (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS + NT * li;
     const int ntile = (nrows + BD_TILE - 1) / BD_TILE;
     const int t0 = part * tpp, t1 = min(t0 + tpp, ntile);
     // K / V fragments of a tile are requested one tile ahead (unconditional loads of a clamped row index)
-    float kn[DG], vn[4][NT];
-#define BD_ATT_LOAD(R0_)                                                                                  \
-    do {                                                                                                  \
-        const float* kp_ = kb + (size_t)min((R0_) + li, nrows - 1) * KV;                                  \
-        _Pragma("unroll") for (int m = 0; m < DG; m += 4) {                                               \
-            const float4 v_ = *reinterpret_cast<const float4*>(kp_ + m);                                  \
-            kn[m] = v_.x; kn[m + 1] = v_.y; kn[m + 2] = v_.z; kn[m + 3] = v_.w;                           \
-        }                                                                                                 \
-        _Pragma("unroll") for (int v = 0; v < 4; ++v) {                                                   \
-            const float* vp_ = vb + (size_t)min((R0_) + 4 * g + v, nrows - 1) * KV;                       \
-            if constexpr (NT % 4 == 0) {                                                                  \
-                _Pragma("unroll") for (int t = 0; t < NT; t += 4) {                                       \
-                    const float4 x_ = *reinterpret_cast<const float4*>(vp_ + t);                          \
-                    vn[v][t] = x_.x; vn[v][t + 1] = x_.y; vn[v][t + 2] = x_.z; vn[v][t + 3] = x_.w;       \
-                }                                                                                         \
-            } else if constexpr (NT == 2) {                                                               \
-                const float2 x_ = *reinterpret_cast<const float2*>(vp_);                                  \
-                vn[v][0] = x_.x; vn[v][1] = x_.y;                                                         \
-            } else {                                                                                      \
-                vn[v][0] = vp_[0];                                                                        \
-            }                                                                                             \
-        }                                                                                                 \
+    // (f32: float kn[DG], vn[4][NT] and the statements the kernel always had; f16: BdHalfAhead)
+    typename BdAhead<HS, T>::K kn;
+    typename BdAhead<HS, T>::V vn;
+#define BD_ATT_LOAD(R0_)                                                                                      \
+    do {                                                                                                      \
+        if constexpr (std::is_same_v<T, float>) {                                                             \
+            const float* kp_ = kb + (size_t)min((R0_) + li, nrows - 1) * KV;                                  \
+            _Pragma("unroll") for (int m = 0; m < DG; m += 4) {                                               \
+                const float4 v_ = *reinterpret_cast<const float4*>(kp_ + m);                                  \
+                kn[m] = v_.x; kn[m + 1] = v_.y; kn[m + 2] = v_.z; kn[m + 3] = v_.w;                           \
+            }                                                                                                 \
+            _Pragma("unroll") for (int v = 0; v < 4; ++v) {                                                   \
+                const float* vp_ = vb + (size_t)min((R0_) + 4 * g + v, nrows - 1) * KV;                       \
+                if constexpr (NT % 4 == 0) {                                                                  \
+                    _Pragma("unroll") for (int t = 0; t < NT; t += 4) {                                       \
+                        const float4 x_ = *reinterpret_cast<const float4*>(vp_ + t);                          \
+                        vn[v][t] = x_.x; vn[v][t + 1] = x_.y; vn[v][t + 2] = x_.z; vn[v][t + 3] = x_.w;       \
+                    }                                                                                         \
+                } else if constexpr (NT == 2) {                                                               \
+                    const float2 x_ = *reinterpret_cast<const float2*>(vp_);                                  \
+                    vn[v][0] = x_.x; vn[v][1] = x_.y;                                                         \
+                } else {                                                                                      \
+                    vn[v][0] = vp_[0];                                                                        \
+                }                                                                                             \
+            }                                                                                                 \
+        } else {                                                                                              \
+            BdHalfAhead<HS>::load(kn, vn, kb, vb, KV, (R0_), li, g, nrows - 1);                               \
+        }                                                                                                     \
     } while (0)
     BD_ATT_LOAD(min(t0 + wid, ntile - 1) * BD_TILE);
     for (int kt = t0 + wid; kt < t1; kt += NW) {
         const int r0 = kt * BD_TILE;
         float kf[DG], vf[4][NT];
+        if constexpr (std::is_same_v<T, float>) {
 #pragma unroll
-        for (int m = 0; m < DG; ++m) kf[m] = kn[m];
+            for (int m = 0; m < DG; ++m) kf[m] = kn[m];
 #pragma unroll
-        for (int v = 0; v < 4; ++v)
+            for (int v = 0; v < 4; ++v)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
+                for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
+        } else {
+            BdHalfAhead<HS>::take(kn, vn, kf, vf);
+        }
         BD_ATT_LOAD(min(kt + NW, ntile - 1) * BD_TILE);
         pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -255,48 +348,57 @@ __host__ __device__ inline int bd_prefix_parts(int n_att, int n_kv_heads, int kv
 
 // bd_attn_kernel's tile loop for the kernels below: wave `wid` takes tiles t0 + wid, t0 + wid + 8, .. < t1 of the cache at kb / vb
 // (already at this lane's kv head and fragment); rows lo <= r < hi are visible, loads clamp the row index to hi - 1 (hi >= 1).
-template <int HS>
-__device__ __forceinline__ void bd_attn_tiles(const float (&qf)[HS / 4], const float* __restrict__ kb, const float* __restrict__ vb, int KV,
+template <int HS, class T>
+__device__ __forceinline__ void bd_attn_tiles(const float (&qf)[HS / 4], const T* __restrict__ kb, const T* __restrict__ vb, int KV,
                                               int lo, int hi, int t0, int t1, int wid, int li, int g, float& m_run, float& l_run,
                                               pf_v4f (&O)[HS / 16]) {
     constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
     const float scale = sqrtf((float)HS);
     const int ntile = (hi + BD_TILE - 1) / BD_TILE;
-    float kn[DG], vn[4][NT];
+    typename BdAhead<HS, T>::K kn;      // (as in bd_attn_kernel: the f32 statements are the ones this function always had)
+    typename BdAhead<HS, T>::V vn;
     auto load = [&](int r0) {
-        const float* kp = kb + (size_t)min(r0 + li, hi - 1) * KV;
+        if constexpr (std::is_same_v<T, float>) {
+            const float* kp = kb + (size_t)min(r0 + li, hi - 1) * KV;
 #pragma unroll
-        for (int m = 0; m < DG; m += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(kp + m);
-            kn[m] = v.x; kn[m + 1] = v.y; kn[m + 2] = v.z; kn[m + 3] = v.w;
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float* vp = vb + (size_t)min(r0 + 4 * g + v, hi - 1) * KV;
-            if constexpr (NT % 4 == 0) {
-#pragma unroll
-                for (int t = 0; t < NT; t += 4) {
-                    const float4 x = *reinterpret_cast<const float4*>(vp + t);
-                    vn[v][t] = x.x; vn[v][t + 1] = x.y; vn[v][t + 2] = x.z; vn[v][t + 3] = x.w;
-                }
-            } else if constexpr (NT == 2) {
-                const float2 x = *reinterpret_cast<const float2*>(vp);
-                vn[v][0] = x.x; vn[v][1] = x.y;
-            } else {
-                vn[v][0] = vp[0];
+            for (int m = 0; m < DG; m += 4) {
+                const float4 v = *reinterpret_cast<const float4*>(kp + m);
+                kn[m] = v.x; kn[m + 1] = v.y; kn[m + 2] = v.z; kn[m + 3] = v.w;
             }
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const float* vp = vb + (size_t)min(r0 + 4 * g + v, hi - 1) * KV;
+                if constexpr (NT % 4 == 0) {
+#pragma unroll
+                    for (int t = 0; t < NT; t += 4) {
+                        const float4 x = *reinterpret_cast<const float4*>(vp + t);
+                        vn[v][t] = x.x; vn[v][t + 1] = x.y; vn[v][t + 2] = x.z; vn[v][t + 3] = x.w;
+                    }
+                } else if constexpr (NT == 2) {
+                    const float2 x = *reinterpret_cast<const float2*>(vp);
+                    vn[v][0] = x.x; vn[v][1] = x.y;
+                } else {
+                    vn[v][0] = vp[0];
+                }
+            }
+        } else {
+            BdHalfAhead<HS>::load(kn, vn, kb, vb, KV, r0, li, g, hi - 1);
         }
     };
     load(min(t0 + wid, ntile - 1) * BD_TILE);
     for (int kt = t0 + wid; kt < t1; kt += NW) {
         const int r0 = kt * BD_TILE;
         float kf[DG], vf[4][NT];
+        if constexpr (std::is_same_v<T, float>) {
 #pragma unroll
-        for (int m = 0; m < DG; ++m) kf[m] = kn[m];
+            for (int m = 0; m < DG; ++m) kf[m] = kn[m];
 #pragma unroll
-        for (int v = 0; v < 4; ++v)
+            for (int v = 0; v < 4; ++v)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
+                for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
+        } else {
+            BdHalfAhead<HS>::take(kn, vn, kf, vf);
+        }
         load(min(kt + NW, ntile - 1) * BD_TILE);
         pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -378,9 +480,9 @@ __device__ __forceinline__ void bd_attn_leave(float m_run, float l_run, const pf
 // One workgroup per (kv head, column group, prefix part).  colmap [groups][RG]: the pass's attached rows, in row order, -1 behind the
 // last.  Column c of a group is (row colmap[c / kv_mul], query head c % kv_mul of the kv head); columns from the last live one on
 // repeat it and are not written out.  Every attached row sees the whole prefix: the predicate is cache row < P alone.
-template <int HS>
-__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const float* __restrict__ Q, const float* __restrict__ pk,
-                                                                         const float* __restrict__ pv, float* __restrict__ po,
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const float* __restrict__ Q, const T* __restrict__ pk,
+                                                                         const T* __restrict__ pv, float* __restrict__ po,
                                                                          float2* __restrict__ pml, const int* __restrict__ colmap, int n,
                                                                          int P, int KV, int kv_mul, int E, int tpp, int np) {
     constexpr int DG = HS / 4, NT = HS / 16;
@@ -405,7 +507,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const f
 #pragma unroll
     for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
     const int ntile = (P + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
-    bd_attn_tiles<HS>(qf, pk + (size_t)kvh * HS + g * DG, pv + (size_t)kvh * HS + NT * li, KV, 0, P, t0, t1, wid, li, g, m_run, l_run, O);
+    bd_attn_tiles<HS, T>(qf, pk + (size_t)kvh * HS + g * DG, pv + (size_t)kvh * HS + NT * li, KV, 0, P, t0, t1, wid, li, g, m_run, l_run, O);
     bd_attn_leave<HS>(m_run, l_run, O, live, po, pml, [&](int col) {
         return (((size_t)cm[col / kv_mul] * nkv + kvh) * np + part) * kv_mul + col % kv_mul;
     });
@@ -413,9 +515,9 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const f
 
 // bd_attn_kernel for a pass with attached rows: the row's own cache rows first[slot] .. pos-1, tiles counted from the one that holds
 // row `first` (that tile masks the rows below it); part `part` leaves state p0 + part.  One workgroup per (kv head, row, own part).
-template <int HS>
-__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const float* __restrict__ Q, const float* __restrict__ kc,
-                                                                      const float* __restrict__ vc, float* __restrict__ po,
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                      const T* __restrict__ vc, float* __restrict__ po,
                                                                       float2* __restrict__ pml, BdCaches bc, const int* __restrict__ first,
                                                                       int KV, int kv_mul, int E, int tpp, int np, int p0) {
     constexpr int DG = HS / 4, NT = HS / 16;
@@ -440,7 +542,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const floa
     for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
     const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
     const size_t base = (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS;
-    bd_attn_tiles<HS>(qf, kc + base + g * DG, vc + base + NT * li, KV, lo, nrows, t0, t1, wid, li, g, m_run, l_run, O);
+    bd_attn_tiles<HS, T>(qf, kc + base + g * DG, vc + base + NT * li, KV, lo, nrows, t0, t1, wid, li, g, m_run, l_run, O);
     bd_attn_leave<HS>(m_run, l_run, O, kv_mul, po, pml, [&](int q) { return (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q; });
 }
 

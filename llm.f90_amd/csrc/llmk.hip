@@ -243,7 +243,9 @@ typedef llmk_ctx::PfLane PfLane;
 struct llmk_batch {
     llmk_ctx* ctx = nullptr;
     int n_slots = 0, seq_len = 0;
-    DevBuf<float> d_kc, d_vc;                    // [L][n_slots][seq_len][KV]
+    int kv_type = LLMK_TYPE_F32;                 // the caches' and the prefix's element type (llmk_cache_create): ONE pair of each is allocated
+    DevBuf<float> d_kc, d_vc;                    // [L][n_slots][seq_len][KV], an f32 batch's ...
+    DevBuf<_Float16> d_kc16, d_vc16;             // ... and an f16 batch's (BdKv<T> below picks the pair by element type)
     DevBuf<BdRow> d_rows;                        // [LLMK_MAX_BATCH] row words
     DevBuf<int> d_tok;                           // [LLMK_MAX_BATCH] 0-based fed ids
     DevBuf<float> d_out;                         // [2 * LLMK_MAX_BATCH]: (unused log-probs), then the rows' first maxima (1-based ints)
@@ -276,6 +278,7 @@ struct llmk_batch {
         DevBuf<float> d_xpo;                     // part states of a pass with attached rows:
         DevBuf<float2> d_xpml;                   //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_xpo that [hs]
         DevBuf<float> d_pk, d_pv;                // [L][P][KV]: a snapshot of the context's rows of positions 1..P, grown by reserve
+        DevBuf<_Float16> d_pk16, d_pv16;         // the same in an f16 batch: the prefix has the batch's type
     };
     std::unique_ptr<Prefix> px;
     int pass_att = 0;                            // attached rows among the rows bd_upload_rows uploaded last
@@ -1439,6 +1442,113 @@ int pf_run(llmk_ctx* c, const int* tokens, int n, int pos0, const ScoreJob* sj) 
     HIPCHK(pf_fetch_flag(c));
     return LLMK_OK;
 }
+// ---- batched decode (batch.h, DESIGN.md section 3i) -----------------------------------------------------------------------------------
+static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
+constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 * BD_WAVES * 16) * sizeof(float); }
+
+// A batch's caches and prefix rows by element type (llmk_cache_create: float or _Float16, one type per batch), and f(T()) for the
+// type a batch has.  What differs between the types on the host: the buffers, the kernels' instantiation, and a converting kernel in
+// the place of the device-to-device copy from the context's f32 rows.
+template <class T> struct BdKv;
+template <> struct BdKv<float> {
+    static DevBuf<float>& kc(llmk_batch* b) { return b->d_kc; }
+    static DevBuf<float>& vc(llmk_batch* b) { return b->d_vc; }
+    static DevBuf<float>& pk(llmk_batch::Prefix& p) { return p.d_pk; }
+    static DevBuf<float>& pv(llmk_batch::Prefix& p) { return p.d_pv; }
+};
+template <> struct BdKv<_Float16> {
+    static DevBuf<_Float16>& kc(llmk_batch* b) { return b->d_kc16; }
+    static DevBuf<_Float16>& vc(llmk_batch* b) { return b->d_vc16; }
+    static DevBuf<_Float16>& pk(llmk_batch::Prefix& p) { return p.d_pk16; }
+    static DevBuf<_Float16>& pv(llmk_batch::Prefix& p) { return p.d_pv16; }
+};
+template <class F>
+static auto with_kv_type(const llmk_batch* b, F f) { return b->kv_type == LLMK_TYPE_F16 ? f(_Float16()) : f(float()); }
+// rows [n][KV] of every layer of the context's f32 caches into a batch's K and V buffers (dk, dv; layers dst_layer elements apart),
+// ENQUEUED: the copy an f32 batch always made, the converting kernel for an f16 one (batch.h bd_to_half_kernel)
+static hipError_t bd_copy_ctx_rows(llmk_ctx* c, float* dk, float* dv, size_t n, size_t dst_layer) {
+    float* caches[2][2] = {{dk, c->d_kc}, {dv, c->d_vc}};
+    for (auto& p : caches)
+        for (int l = 0; l < c->L; ++l)
+            HIPRET(hipMemcpyAsync(p[0] + (size_t)l * dst_layer, p[1] + (size_t)l * c->S * c->KV, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    return hipSuccess;
+}
+static hipError_t bd_copy_ctx_rows(llmk_ctx* c, _Float16* dk, _Float16* dv, size_t n, size_t dst_layer) {
+    const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
+    hipLaunchKernelGGL(bd_to_half_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
+    return hipGetLastError();
+}
+
+// One pass, ENQUEUED on the context's stream: the n rows in d_rows / d_tok through every layer, the classifier and the per-row first
+// maximum (into d_out + n); the logits of every row into d_logits when asked for.  max_pos: the longest row (the attention's split rule).
+// With attached rows among them (pass_att > 0, llmk_prefix_*) the attention is the three kernels of batch.h's prefix section; `step`:
+// the rows stand `step` positions behind the uploaded ones (a decode's later passes).
+template <class TC>      // TC: the caches' element type
+static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, int step) {
+    llmk_ctx* c = b->ctx;
+    PfLane& w = c->pf->lane[0];
+    const int E = c->E, KV = c->KV, QKV = E + 2 * KV, T = n;
+    const BdCaches bc{b->d_rows, (size_t)b->seq_len * KV, b->n_slots, b->seq_len};
+    int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
+    const bool shared = b->pass_att > 0;
+    int groups = 0, pparts = 0, ptpp = 0;
+    if (shared) {
+        // the own parts' split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`
+        int own = 0;
+        for (int i = 0; i < n; ++i) {
+            const int pos = b->h_rows[i].pos + step;
+            own = std::max(own, (pos + BD_TILE - 1) / BD_TILE - b->px->h_first[b->h_rows[i].slot] / BD_TILE);
+        }
+        parts = bd_parts(n, c->nkv, own * BD_TILE, c->n_cu);
+        tpp = bd_tiles_per_part(own * BD_TILE, parts);
+        groups = bd_prefix_groups(b->pass_att, c->kv_mul);
+        pparts = bd_prefix_parts(b->pass_att, c->nkv, c->kv_mul, b->P, c->n_cu);
+        ptpp = bd_tiles_per_part(b->P, pparts);
+    }
+    PfEpiArgs e;
+    // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
+    HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
+        TC* kc = BdKv<TC>::kc(b) + (size_t)l * b->n_slots * bc.slot_stride;
+        TC* vc = BdKv<TC>::vc(b) + (size_t)l * b->n_slots * bc.slot_stride;
+        if constexpr (std::is_same_v<TC, float>) {
+            a.kc = kc; a.vc = vc;
+            hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc);
+        } else {
+            a.kc = a.vc = nullptr;      // (the context's caches are not this pass's)
+            hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc, kc, vc);
+        }
+        HIPRET(hipGetLastError());
+        return with_head_size(c->hs, [&](auto hs) {
+            constexpr int HS = decltype(hs)::value;
+            if (shared) {
+                const int np = pparts + parts;
+                const size_t px = (size_t)l * b->P * KV;
+                hipLaunchKernelGGL((bd_attn_prefix_kernel<HS, TC>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                                   w.Q, BdKv<TC>::pk(*b->px) + px, BdKv<TC>::pv(*b->px) + px, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
+                HIPRET(hipGetLastError());
+                hipLaunchKernelGGL((bd_attn_own_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                                   w.Q, kc, vc, b->px->d_xpo, b->px->d_xpml, bc, b->px->d_first, KV, c->kv_mul, E, tpp, np, pparts);
+                HIPRET(hipGetLastError());
+                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->px->d_xpo, b->px->d_xpml, w.XB, bc, b->px->d_first,
+                                   c->kv_mul, E, np, pparts);
+                return hipGetLastError();
+            }
+            hipLaunchKernelGGL((bd_attn_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                               w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
+            HIPRET(hipGetLastError());
+            if (parts > 1) hipLaunchKernelGGL((bd_attn_merge_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, c->kv_mul, E, parts);
+            return hipGetLastError();
+        });
+    }));
+    ScoreJob sj{false, want_logits, n, sp};
+    sj.out = b->d_out;
+    sj.logits = b->d_logits;
+    return sc_batch(c, w, 0, e, sj, T, 0);
+}
+static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, int step = 0) {
+    return with_kv_type(b, [&](auto t) { return bd_pass_of<decltype(t)>(b, n, max_pos, want_logits, sp, step); });
+}
+
 // did the synchronised call's batched pass raise the f16-range flag?
 bool pf_flagged(const llmk_ctx* c) { return c->pf_hm && c->host_words()->pf_flag != 0; }
 
@@ -1471,7 +1581,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 406; }
+int llmk_version(void) { return 407; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2607,71 +2717,7 @@ int llmk_get_history(llmk_ctx* c, int* tokens_out, int n, int pos0) {
     return LLMK_OK;
 }
 
-// ---- batched decode (batch.h, DESIGN.md section 3i) -----------------------------------------------------------------------------------
-static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
-constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 * BD_WAVES * 16) * sizeof(float); }
-
-// One pass, ENQUEUED on the context's stream: the n rows in d_rows / d_tok through every layer, the classifier and the per-row first
-// maximum (into d_out + n); the logits of every row into d_logits when asked for.  max_pos: the longest row (the attention's split rule).
-// With attached rows among them (pass_att > 0, llmk_prefix_*) the attention is the three kernels of batch.h's prefix section; `step`:
-// the rows stand `step` positions behind the uploaded ones (a decode's later passes).
-static hipError_t bd_pass(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, int step = 0) {
-    llmk_ctx* c = b->ctx;
-    PfLane& w = c->pf->lane[0];
-    const int E = c->E, KV = c->KV, QKV = E + 2 * KV, T = n;
-    const BdCaches bc{b->d_rows, (size_t)b->seq_len * KV, b->n_slots, b->seq_len};
-    int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
-    const bool shared = b->pass_att > 0;
-    int groups = 0, pparts = 0, ptpp = 0;
-    if (shared) {
-        // the own parts' split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`
-        int own = 0;
-        for (int i = 0; i < n; ++i) {
-            const int pos = b->h_rows[i].pos + step;
-            own = std::max(own, (pos + BD_TILE - 1) / BD_TILE - b->px->h_first[b->h_rows[i].slot] / BD_TILE);
-        }
-        parts = bd_parts(n, c->nkv, own * BD_TILE, c->n_cu);
-        tpp = bd_tiles_per_part(own * BD_TILE, parts);
-        groups = bd_prefix_groups(b->pass_att, c->kv_mul);
-        pparts = bd_prefix_parts(b->pass_att, c->nkv, c->kv_mul, b->P, c->n_cu);
-        ptpp = bd_tiles_per_part(b->P, pparts);
-    }
-    PfEpiArgs e;
-    // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
-    HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
-        float* kc = b->d_kc + (size_t)l * b->n_slots * bc.slot_stride;
-        float* vc = b->d_vc + (size_t)l * b->n_slots * bc.slot_stride;
-        a.kc = kc; a.vc = vc;
-        hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc);
-        HIPRET(hipGetLastError());
-        return with_head_size(c->hs, [&](auto hs) {
-            constexpr int HS = decltype(hs)::value;
-            if (shared) {
-                const int np = pparts + parts;
-                const size_t px = (size_t)l * b->P * KV;
-                hipLaunchKernelGGL((bd_attn_prefix_kernel<HS>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
-                                   w.Q, b->px->d_pk + px, b->px->d_pv + px, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
-                HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((bd_attn_own_kernel<HS>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
-                                   w.Q, kc, vc, b->px->d_xpo, b->px->d_xpml, bc, b->px->d_first, KV, c->kv_mul, E, tpp, np, pparts);
-                HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->px->d_xpo, b->px->d_xpml, w.XB, bc, b->px->d_first,
-                                   c->kv_mul, E, np, pparts);
-                return hipGetLastError();
-            }
-            hipLaunchKernelGGL((bd_attn_kernel<HS>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
-                               w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
-            HIPRET(hipGetLastError());
-            if (parts > 1) hipLaunchKernelGGL((bd_attn_merge_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, c->kv_mul, E, parts);
-            return hipGetLastError();
-        });
-    }));
-    ScoreJob sj{false, want_logits, n, sp};
-    sj.out = b->d_out;
-    sj.logits = b->d_logits;
-    return sc_batch(c, w, 0, e, sj, T, 0);
-}
-
+// ---- batched decode (batch.h): the entry points; the pass itself (bd_pass) is above, in front of pf_redo --------
 // the context's side of a pass: workspaces, the classifier's kernels and its row chunks (they follow the matrix instruction in use)
 static int bd_ready(llmk_batch* b, ScPlan* sp, int rows) {
     llmk_ctx* c = b->ctx;
@@ -2720,23 +2766,59 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
     return hipMemcpyAsync(b->d_tok, b->h_tok, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
 }
 
-int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) {
+// an IEEE half's bits as the f32 of the same value (host side of llmk_cache_peek; subnormals, infinities and NaN included)
+static float bd_half_bits_to_float(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
+    uint32_t u;
+    if (ex == 0x1Fu) {
+        u = sign | 0x7F800000u | (man << 13);
+    } else if (ex != 0) {
+        u = sign | ((ex + 112u) << 23) | (man << 13);
+    } else {
+        // man * 2^-24, exact in f32
+        float f = (float)man * 5.9604644775390625e-8f;
+        memcpy(&u, &f, sizeof u);
+        u |= sign;
+    }
+    float f;
+    memcpy(&f, &u, sizeof f);
+    return f;
+}
+
+// an allocation the device has no room for is the caller's to handle (llmk_cache_create sizes caches by n_slots x seq_len), not a HIP fault
+static int bd_alloc_rc(hipError_t e) {
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();      // (the runtime keeps the error for the next hipGetLastError: a launch check must not find it)
+        return LLMK_E_NOMEM;
+    }
+    return e == hipSuccess ? LLMK_OK : LLMK_E_HIP + (int)e;
+}
+
+// llmk_batch_create IS this with LLMK_TYPE_F32: the caches of an f32 batch are allocated, zeroed and used as they always were
+static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) {
     if (!c || !out || n_slots < 1 || n_slots > LLMK_MAX_BATCH || seq_len < 1 || seq_len > c->S) return LLMK_E_ARG;
     *out = nullptr;
+    if (kv_type != LLMK_TYPE_F32 && kv_type != LLMK_TYPE_F16) return LLMK_E_TYPE;
     int rc = check_ready(c);      // (an incomplete context is LLMK_E_STATE whatever its shape)
     if (rc) return rc;
     if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;
     HIPCHK(hipSetDevice(c->cfg.device));
     // built aside: the caller gets the batch only after every step succeeded (a failure releases what was made)
     auto b = std::make_unique<llmk_batch>();
-    b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len;
+    b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len; b->kv_type = kv_type;
     ScPlan sp;
     if ((rc = bd_ready(b.get(), &sp, n_slots)) != LLMK_OK) return rc;
     const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV, nb = LLMK_MAX_BATCH;
-    HIPCHK(b->d_kc.alloc(cache));
-    HIPCHK(b->d_vc.alloc(cache));
-    HIPCHK(b->d_kc.zero(c->stream));
-    HIPCHK(b->d_vc.zero(c->stream));
+    rc = with_kv_type(b.get(), [&](auto t) -> int {
+        using TC = decltype(t);
+        int rc_;
+        if ((rc_ = bd_alloc_rc(BdKv<TC>::kc(b.get()).alloc(cache))) != LLMK_OK) return rc_;
+        if ((rc_ = bd_alloc_rc(BdKv<TC>::vc(b.get()).alloc(cache))) != LLMK_OK) return rc_;
+        HIPCHK(BdKv<TC>::kc(b.get()).zero(c->stream));
+        HIPCHK(BdKv<TC>::vc(b.get()).zero(c->stream));
+        return LLMK_OK;
+    });
+    if (rc) return rc;
     HIPCHK(b->d_rows.alloc(nb));
     HIPCHK(b->d_tok.alloc(nb));
     HIPCHK(b->d_out.alloc(2 * nb));
@@ -2753,14 +2835,61 @@ int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) {
     HIPCHK(b->h_filt.alloc(nb));
     HIPCHK(b->h_out.alloc(2 * nb));
     HIPCHK(b->h_err.alloc(1));
-    HIPCHK(with_head_size(c->hs, [](auto hs) {
+    HIPCHK(with_head_size(c->hs, [&](auto hs) {
         constexpr int HS = decltype(hs)::value;
-        return hipFuncSetAttribute((const void*)bd_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+        return with_kv_type(b.get(), [](auto t) {
+            return hipFuncSetAttribute((const void*)bd_attn_kernel<HS, decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+        });
     }));
     HIPCHK(hipStreamSynchronize(c->stream));
     ++c->n_batches;
     *out = b.release();
     return LLMK_OK;
+}
+
+int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) { return bd_create(c, n_slots, seq_len, LLMK_TYPE_F32, out); }
+int llmk_cache_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) { return bd_create(c, n_slots, seq_len, kv_type, out); }
+
+int llmk_cache_type(llmk_batch* b) {
+    if (!b) return -LLMK_E_ARG;
+    return b->kv_type;
+}
+
+// device bytes of the K/V caches and of the prefix rows (the blocks as they are allocated: a prefix's only grow)
+int llmk_cache_bytes(llmk_batch* b, unsigned long long* out) {
+    if (!b || !out) return LLMK_E_ARG;
+    *out = with_kv_type(b, [&](auto t) -> unsigned long long {
+        using TC = decltype(t);
+        size_t n = BdKv<TC>::kc(b).size() + BdKv<TC>::vc(b).size();
+        if (b->px) n += BdKv<TC>::pk(*b->px).size() + BdKv<TC>::pv(*b->px).size();
+        return (unsigned long long)n * sizeof(TC);
+    });
+    return LLMK_OK;
+}
+
+// The verification hook of the caches: n rows [kv_dim] of K (which 0) or V (1), positions pos0 .. pos0+n-1 of `slot` in `layer`, or of
+// the prefix (slot -1, positions 1..P), as f32 -- exact for either type.
+int llmk_cache_peek(llmk_batch* b, int which, int layer, int slot, int pos0, int n, float* out) {
+    if (!b || !out || (which != 0 && which != 1) || layer < 0 || layer >= b->ctx->L || n < 1 || pos0 < 1) return LLMK_E_ARG;
+    if (slot < -1 || slot >= b->n_slots || n > (slot < 0 ? b->P : b->seq_len) - (pos0 - 1)) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t row = (size_t)c->KV, cnt = (size_t)n * row;
+    return with_kv_type(b, [&](auto t) -> int {
+        using TC = decltype(t);
+        const TC* src = slot < 0 ? (which ? BdKv<TC>::pv(*b->px) : BdKv<TC>::pk(*b->px)) + ((size_t)layer * b->P + (pos0 - 1)) * row
+                                 : (which ? BdKv<TC>::vc(b) : BdKv<TC>::kc(b)) + (((size_t)layer * b->n_slots + slot) * b->seq_len + (pos0 - 1)) * row;
+        if constexpr (std::is_same_v<TC, float>) {
+            HIPCHK(hipMemcpy(out, src, cnt * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            std::vector<uint16_t> h(cnt);
+            HIPCHK(hipMemcpy(h.data(), src, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < cnt; ++i) out[i] = bd_half_bits_to_float(h[i]);
+        }
+        return LLMK_OK;
+    });
 }
 
 int llmk_batch_destroy(llmk_batch* b) {
@@ -2787,15 +2916,25 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     const size_t row = (size_t)c->KV, slot_rows = (size_t)b->seq_len * row;
-    float* caches[2][2] = {{b->d_kc, c->d_kc}, {b->d_vc, c->d_vc}};
-    for (auto& p : caches)
-        for (int l = 0; l < c->L; ++l) {
-            float* dst = p[0] + ((size_t)l * b->n_slots + slot) * slot_rows;
-            if ((size_t)n_pos < (size_t)b->seq_len)      // rows beyond n_pos: as in a fresh slot
-                HIPCHK(hipMemsetAsync(dst + (size_t)n_pos * row, 0, (slot_rows - (size_t)n_pos * row) * sizeof(float), c->stream));
-            if (n_pos > 0)
-                HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        }
+    if (b->kv_type == LLMK_TYPE_F32) {
+        float* caches[2][2] = {{b->d_kc, c->d_kc}, {b->d_vc, c->d_vc}};
+        for (auto& p : caches)
+            for (int l = 0; l < c->L; ++l) {
+                float* dst = p[0] + ((size_t)l * b->n_slots + slot) * slot_rows;
+                if ((size_t)n_pos < (size_t)b->seq_len)      // rows beyond n_pos: as in a fresh slot
+                    HIPCHK(hipMemsetAsync(dst + (size_t)n_pos * row, 0, (slot_rows - (size_t)n_pos * row) * sizeof(float), c->stream));
+                if (n_pos > 0)
+                    HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            }
+    } else {
+        // the same on the f16 caches: zero halves behind n_pos, the context's f32 rows converted (pf_kv_half) in the place of the copy
+        for (_Float16* base : {b->d_kc16.get(), b->d_vc16.get()})
+            for (int l = 0; l < c->L && (size_t)n_pos < (size_t)b->seq_len; ++l)
+                HIPCHK(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows + (size_t)n_pos * row, 0,
+                                      (slot_rows - (size_t)n_pos * row) * sizeof(_Float16), c->stream));
+        if (n_pos > 0)
+            HIPCHK(bd_copy_ctx_rows(c, b->d_kc16 + (size_t)slot * slot_rows, b->d_vc16 + (size_t)slot * slot_rows, (size_t)n_pos * row, (size_t)b->n_slots * slot_rows));
+    }
     // a forked or emptied slot is a new sequence: no token fed yet (the caller records the prompt with llmk_rows_set_history)
     if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     if (b->px && b->px->h_first[slot] > 0) HIPCHK(prefix_first(b, slot, 0));      // a forked slot is self-contained: it leaves the prefix
@@ -2825,23 +2964,29 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
         HIPCHK(px->h_colmap.alloc(nb + BD_MAX_GROUP));
         HIPCHK(px->d_xpo.alloc(states * c->hs));
         HIPCHK(px->d_xpml.alloc(states));
-        HIPCHK(with_head_size(c->hs, [](auto hs) -> hipError_t {
+        HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
             constexpr int HS = decltype(hs)::value;
-            HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS)));
-            return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+            return with_kv_type(b, [](auto t) -> hipError_t {
+                using TC = decltype(t);
+                HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS)));
+                return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+            });
         }));
         b->px = std::move(px);
     }
     // the prefix rows: room for n_pos positions (a longer prefix than any before drains the stream and replaces both blocks)
     const size_t px_rows = (size_t)c->L * n_pos * row;
-    if (b->px->d_pv.size() < px_rows) b->P = 0;
-    HIPCHK(b->px->d_pk.reserve(px_rows, c->stream));
-    HIPCHK(b->px->d_pv.reserve(px_rows, c->stream));
-    float* caches[2][2] = {{b->px->d_pk, c->d_kc}, {b->px->d_pv, c->d_vc}};
-    for (auto& p : caches)
-        for (int l = 0; l < c->L; ++l)
-            HIPCHK(hipMemcpyAsync(p[0] + (size_t)l * n_pos * row, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float),
-                                  hipMemcpyDeviceToDevice, c->stream));
+    rc = with_kv_type(b, [&](auto t) -> int {
+        using TC = decltype(t);
+        auto &pk = BdKv<TC>::pk(*b->px), &pv = BdKv<TC>::pv(*b->px);
+        if (pv.size() < px_rows) b->P = 0;
+        int rc_;
+        if ((rc_ = bd_alloc_rc(pk.reserve(px_rows, c->stream))) != LLMK_OK) return rc_;
+        if ((rc_ = bd_alloc_rc(pv.reserve(px_rows, c->stream))) != LLMK_OK) return rc_;
+        HIPCHK(bd_copy_ctx_rows(c, pk.get(), pv.get(), (size_t)n_pos * row, (size_t)n_pos * row));
+        return LLMK_OK;
+    });
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     b->P = n_pos;
     return LLMK_OK;
@@ -2855,9 +3000,13 @@ int llmk_prefix_attach(llmk_batch* b, int slot) {
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     // a new sequence behind the prefix: own rows and token record as llmk_batch_fork(b, slot, 0) leaves them
     const size_t slot_rows = (size_t)b->seq_len * c->KV;
-    for (float* base : {b->d_kc.get(), b->d_vc.get()})
-        for (int l = 0; l < c->L; ++l)
-            HIPCHK(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(float), c->stream));
+    HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
+        using TC = decltype(t);
+        for (TC* base : {BdKv<TC>::kc(b).get(), BdKv<TC>::vc(b).get()})
+            for (int l = 0; l < c->L; ++l)
+                HIPRET(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(TC), c->stream));
+        return hipSuccess;
+    }));
     if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     HIPCHK(prefix_first(b, slot, b->P));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -969,6 +969,40 @@ __device__ __forceinline__ void pf_epi_qkv_pair(const PfEpiArgs& a, int t, int r
         dst[1] = a1;
     }
 }
+// A K/V cache element of a batch with f16 caches (llmk_cache_*, batch.h): round to nearest even, f16 subnormals kept, SATURATING at
+// +-65504 -- one outlier must not turn a row's softmax into NaN through an infinite score -- and NaN stays NaN (fminf / fmaxf would
+// drop it, hence the branch).  A plain cast: v_cvt_f16_f32 under the default rounding mode, not cvt_pkrtz (that rounds toward zero).
+__device__ __forceinline__ _Float16 pf_kv_half(float x) { return x != x ? (_Float16)x : (_Float16)fminf(fmaxf(x, -65504.f), 65504.f); }
+typedef _Float16 pf_h2 __attribute__((ext_vector_type(2)));
+// pf_epi_qkv_pair for such a batch: the same expressions up to the store (keep the two in step); Q goes out in f32, a K / V pair as
+// two halves in one 4-byte store (r0 is even).  kc / vc: this layer's caches [S][KV] of halves; a.kc / a.vc are not read.
+__device__ __forceinline__ void pf_epi_qkv_pair_h(const PfEpiArgs& a, _Float16* kc, _Float16* vc, int t, int r0, float a0, float a1) {
+    const int pos = a.pos0 + t;
+    if (r0 < a.E + a.KV) {
+        const int i0 = (r0 < a.E) ? r0 : r0 - a.E;
+        const float rval = (float)pos * a.rope[(i0 % a.hs) >> 1];
+        const float fcr = cosf(rval), fci = sinf(rval);
+        // (products and sums rounded one by one: that is what pf_epi_qkv_pair compiles to -- its two products are one packed multiply,
+        // which nothing is contracted into -- and here the compiler would otherwise fuse them; tests/test_batch_kv16_gpu.py test 1
+        // compares the stored rows of the two forms bit for bit)
+        float o0, o1;
+        {
+#pragma clang fp contract(off)
+            const float p00 = a0 * fcr, p11 = a1 * fci, p01 = a0 * fci, p10 = a1 * fcr;
+            o0 = p00 - p11;
+            o1 = p01 + p10;
+        }
+        if (r0 < a.E) {
+            float* dst = a.out + (size_t)t * a.E + i0;
+            dst[0] = o0;
+            dst[1] = o1;
+        } else {
+            *reinterpret_cast<pf_h2*>(kc + (size_t)(pos - 1) * a.KV + i0) = (pf_h2){pf_kv_half(o0), pf_kv_half(o1)};
+        }
+    } else {
+        *reinterpret_cast<pf_h2*>(vc + (size_t)(pos - 1) * a.KV + (r0 - a.E - a.KV)) = (pf_h2){pf_kv_half(a0), pf_kv_half(a1)};
+    }
+}
 __global__ void pf_epi_qkv_kernel(PfEpiArgs a) {
     // a thread takes four rows = two pairs (16-byte loads of the partial tiles); E, KV and the head size are multiples of 4,
     // so both pairs lie in the same part (q, k or v)

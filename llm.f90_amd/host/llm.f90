@@ -9,13 +9,15 @@
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
 !         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix]]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix] [--kv-f16]]
 !
 ! --parallel N (1 .. 128, one GPU): N completions of the prompt decoded TOGETHER (llmk_batch_*, DESIGN.md section 3i) -- the prompt is
 ! prefilled once and forked into N slots, every pass over the weights serves all N; seeds seed, seed+1, ... at -t > 0 (the filter
 ! flags apply), greedy at -t 0 (N equal texts).  The completions are printed after generation, each under a line [k], k = 0 .. N-1.
 ! --share-prefix: the N slots are ATTACHED to one copy of the prompt's K/V rows (llmk_prefix_*) instead of holding a copy each: the
 ! attention reads the prompt rows once per group of rows, not once per row.
+! --kv-f16: the N slots' K/V caches -- and the shared prefix -- hold IEEE halves (llmk_cache_create): half the bytes per pass and per
+! slot, the stored values rounded to nearest even and saturated at +-65504.  Refused without --parallel: the context's own cache is f32.
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
 ! (one process per GPU, devices d..d+N-1), every rank loads the file and keeps its shard, the ranks meet through a
@@ -55,6 +57,7 @@ module arg_parse
                                            ! 1e-5 and 10000, llama2.f90:454,545)
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
      logical :: share_prefix      ! extension: --share-prefix: the --parallel slots share ONE copy of the prompt's K/V rows (llmk_prefix_*)
+     logical :: kv_f16            ! extension: --kv-f16: the --parallel slots' K/V caches and the shared prefix are f16 (llmk_cache_create)
      integer :: parallel          ! extension: --parallel N (0 = off): N completions decoded together on one GPU (llmk_batch_*)
      integer :: logprobs          ! extension: --logprobs N (0 .. 20): the log-prob of every generated token and its N most likely
                                   ! alternatives, from the device (llmk_*_sample_lp); -1 = off
@@ -102,6 +105,7 @@ contains
     a%logprobs = -1
     a%parallel = 0
     a%share_prefix = .false.
+    a%kv_f16 = .false.
 
     nargs = command_argument_count()
     i = 1
@@ -142,6 +146,7 @@ contains
        case ("--encode");            a%encode_only = .true.;   i = i + 1
        case ("--score");             a%score = .true.;         i = i + 1
        case ("--share-prefix");      a%share_prefix = .true.;  i = i + 1
+       case ("--kv-f16");            a%kv_f16 = .true.;        i = i + 1
        case ("--parallel")
           read (val, *) a%parallel
           if (a%parallel < 1 .or. a%parallel > 128) then
@@ -283,6 +288,7 @@ program llm
   real(c_float), allocatable, target :: lp_token(:), lp_top(:)
   integer(c_int32_t), allocatable, target :: lp_top_ids(:)
   integer :: lp_n, lp_w
+  integer(c_long_long) :: kv_bytes                   ! --vx with --parallel: the device bytes of the batch's K/V caches
   type(c_ptr) :: pbatch                             ! --parallel N: the batch, its rows and samplers, the ids [row][step]
   integer(c_int), allocatable :: par_slots(:), par_tokens(:), par_pos(:), par_ids(:)
   type(llmk_sampler), allocatable, target :: par_samplers(:)
@@ -316,6 +322,10 @@ program llm
   end if
   if (opts%share_prefix .and. opts%parallel == 0) then
      print *, "--share-prefix: nothing to share without --parallel N"
+     stop 1
+  end if
+  if (opts%kv_f16 .and. opts%parallel == 0) then
+     print *, "--kv-f16: only the K/V caches of --parallel N can be f16 (the context's own cache stays f32)"
      stop 1
   end if
   lead = opts%tp_rank == 0
@@ -463,13 +473,22 @@ program llm
         print *, "--parallel: the prompt (", k, "tokens ) leaves no position to generate within -n", seq_len
         stop 1
      end if
-     rc = llmk_batch_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), pbatch)
+     if (opts%kv_f16) then
+        rc = llmk_cache_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), 1_c_int, pbatch)      ! LLMK_TYPE_F16
+     else
+        rc = llmk_batch_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), pbatch)
+     end if
      if (rc == 2) then                               ! LLMK_E_SHAPE
         print *, "--parallel: this model's shape has no batched pass (emb_dim and hidden_dim must be multiples of 64, kv_dim of 16, " // &
              "at most 16 query heads per kv head)"
         stop 1
      end if
      call llmk_check(rc, "llmk_batch_create")
+     if (opts%verbose_ext) then
+        call llmk_check(llmk_cache_bytes(pbatch, kv_bytes), "llmk_cache_bytes")
+        print '(A,A,A,I0,A,I0,A)', " batch K/V caches: ", merge("f16", "f32", llmk_cache_type(pbatch) == 1), ", ", opts%parallel, &
+             " slots, ", kv_bytes, " bytes"
+     end if
      t_start = clock_ticks()
      token = 2
      if (k > 0) then

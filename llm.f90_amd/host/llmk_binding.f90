@@ -326,6 +326,28 @@ module llmk_binding
        import :: c_int, c_ptr
        type(c_ptr), value :: batch
      end function
+     ! a batch whose K/V caches (and shared prefix) have the element type kv_type: 0 = f32 (llmk_batch_create itself), 1 = f16
+     integer(c_int) function llmk_cache_create(ctx, n_slots, seq_len, kv_type, batch) bind(C, name="llmk_cache_create")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: n_slots, seq_len, kv_type
+       type(c_ptr), intent(out) :: batch
+     end function
+     integer(c_int) function llmk_cache_type(batch) bind(C, name="llmk_cache_type")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+     end function
+     integer(c_int) function llmk_cache_bytes(batch, nbytes) bind(C, name="llmk_cache_bytes")
+       import :: c_int, c_ptr, c_long_long
+       type(c_ptr), value :: batch
+       integer(c_long_long), intent(out) :: nbytes
+     end function
+     integer(c_int) function llmk_cache_peek(batch, which, layer, slot, pos0, n, out) bind(C, name="llmk_cache_peek")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: batch
+       integer(c_int), value :: which, layer, slot, pos0, n
+       real(c_float), intent(out) :: out(*)
+     end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
      ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too

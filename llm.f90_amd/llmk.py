@@ -29,7 +29,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_forward_sample_pen", "llmk_decode_sample_pen", "llmk_sample_logits_pen", "llmk_forward_sample_lp", "llmk_decode_sample_lp",
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
            "llmk_batch_decode", "llmk_batch_time", "llmk_rows_set_history", "llmk_rows_get_history", "llmk_rows_decode",
-           "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len", "llmk_reset", "llmk_timings",
+           "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len",
+           "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -61,6 +62,7 @@ def sampler(temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, m
 
 MAX_LOGIT_BIAS = 256
 MAX_BATCH = 128
+KV_TYPES = {"f32": 0, "f16": 1}             # a batch's K/V cache types (llmk_cache_create): LLMK_TYPE_F32 / LLMK_TYPE_F16
 CLS_NONE, CLS_GEMM, CLS_ROWS = 0, 1, 2      # llmk_cls_form: LLMK_CLS_*
 
 
@@ -191,6 +193,11 @@ def lib():
             L.llmk_prefix_set.argtypes = [vp, ci]
             L.llmk_prefix_attach.argtypes = [vp, ci]
             L.llmk_prefix_len.argtypes = [vp]
+        if hasattr(L, "llmk_cache_create"):
+            L.llmk_cache_create.argtypes = [vp, ci, ci, ci, C.POINTER(vp)]
+            L.llmk_cache_type.argtypes = [vp]
+            L.llmk_cache_bytes.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+            L.llmk_cache_peek.argtypes = [vp, ci, ci, ci, ci, ci, cf]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -597,12 +604,41 @@ class Llmk:
 class Batch:
     """Batched decode (llmk_batch_*): n_slots sequences with K/V caches of their own on the weights of the
     Llmk context `model`; every pass takes one position of up to n_slots of them.  Slots count from 0; tokens and positions are
-    1-based.  Calls on a batch and on its context must not overlap.  Close the batch before its context."""
+    1-based.  Calls on a batch and on its context must not overlap.  Close the batch before its context.
+    kv_type "f16": the slots' caches and the shared prefix hold IEEE halves (llmk_cache_create) -- half the bytes, the stored values
+    rounded to nearest even and saturated at +-65504 (include/llmk.h); "f32" is llmk_batch_create, as before.  An int is passed
+    through as the LLMK_TYPE_* id it is."""
 
-    def __init__(self, model: Llmk, n_slots: int, seq_len: int | None = None):
+    def __init__(self, model: Llmk, n_slots: int, seq_len: int | None = None, kv_type="f32"):
         self.model, self.n_slots, self.V = model, n_slots, model.V
         self._h = C.c_void_p()
-        _ck(lib().llmk_batch_create(model._h, n_slots, seq_len or model.shape.seq_len, C.byref(self._h)))
+        if kv_type == "f32":
+            _ck(lib().llmk_batch_create(model._h, n_slots, seq_len or model.shape.seq_len, C.byref(self._h)))
+        else:
+            if isinstance(kv_type, str) and kv_type not in KV_TYPES:
+                raise ValueError(f"kv_type {kv_type!r}: one of {sorted(KV_TYPES)}")
+            _ck(lib().llmk_cache_create(model._h, n_slots, seq_len or model.shape.seq_len, KV_TYPES.get(kv_type, kv_type), C.byref(self._h)))
+
+    @property
+    def kv_type(self) -> str:
+        """"f32" or "f16": the element type of the batch's K/V caches and prefix (llmk_cache_type)"""
+        t = lib().llmk_cache_type(self._h)
+        if t < 0:
+            _ck(-t)
+        return {v: k for k, v in KV_TYPES.items()}[t]
+
+    def cache_bytes(self) -> int:
+        """device bytes of the K/V caches plus the prefix rows, if any (llmk_cache_bytes)"""
+        n = C.c_ulonglong()
+        _ck(lib().llmk_cache_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def peek_kv(self, which: int, layer: int, slot: int, pos0: int, n: int) -> np.ndarray:
+        """verification hook (llmk_cache_peek): cache rows [n][kv_dim] as f32 -- K (which 0) or V (1) of positions pos0 .. pos0+n-1
+        (1-based) of `slot` in `layer`; slot -1 reads the shared prefix"""
+        out = np.empty((max(n, 0), self.model.shape.kv_dim), np.float32)
+        _ck(lib().llmk_cache_peek(self._h, which, layer, slot, pos0, n, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     @staticmethod
     def _rows(slots, tokens, pos):

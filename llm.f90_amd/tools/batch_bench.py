@@ -18,7 +18,13 @@ llmk_rows_decode, where the library has it -- a repeat penalty and log-prob reco
 
 times the pass at 8, 32 and 128 rows and position --pos (1024) with the slots ATTACHED to one P-position prefix (llmk_prefix_*) and with
 the slots FORKED at P, in one process, alternating; against another build selected with LLMK_LIB that has no llmk_prefix_*, the forked
-figures alone (--forked-only: the same from this build, no prefix ever set)."""
+figures alone (--forked-only: the same from this build, no prefix ever set).
+
+    python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k --kv both --shared-prefix 1000
+
+times the pass at 8, 32 and 128 rows, at positions 25 and --pos, with f32 and with f16 K/V caches (llmk_cache_create): two batches in
+ONE process, the types alternating measurement by measurement; forked slots, and -- with --shared-prefix P, at --pos -- slots attached
+behind P positions.  --kv f32 | f16 measures one type alone."""
 from __future__ import annotations
 
 import argparse
@@ -138,6 +144,68 @@ def shared_prefix(m, shape, P: int, pos: int, iters: int, repeats: int, forked_o
     return out
 
 
+def kv_types(m, shape, kinds, P: int, pos: int, iters: int, repeats: int):
+    """--kv: llmk_batch_time at SAMPLED_ROWS rows at positions 25 and `pos` on one batch per K/V type in `kinds`, all alive together,
+    the types alternating `repeats` times, each measurement behind a warm-up of the same type and form.  Forms: the slots forked
+    behind the prompt (position - 1 prompt positions, or P), and with P > 0 at `pos` the slots attached to a P-position prefix."""
+    positions = [q for q in (SAMPLED_POS, pos) if q <= shape.seq_len]
+    if P and not 1 <= P < pos <= shape.seq_len:
+        raise SystemExit(f"--shared-prefix P --pos Q: 1 <= P < Q <= {shape.seq_len}")
+    m.reset()
+    m.prefill([2] + [3 + i % (shape.vocab_size - 3) for i in range(max(P, SAMPLED_POS) - 1)], 1)
+    out = []
+    for q in positions:
+        slots, bs = max(SAMPLED_ROWS), None
+        while bs is None:
+            made = {}
+            try:
+                for kind in kinds:
+                    made[kind] = llmk.Batch(m, slots, q, kv_type=kind)
+                bs = made
+            except llmk.LlmkError as e:
+                for b in made.values():
+                    b.close()
+                if slots == 1:
+                    raise
+                print(f"# pos {q}: no room for {slots} slots of {' + '.join(kinds)} ({e}); trying {slots // 2}", file=sys.stderr)
+                slots //= 2
+        behind = min(P, q - 1) if P else min(SAMPLED_POS, q) - 1
+        for form in (("forked", "attached") if P and q > P else ("forked",)):
+            for n in SAMPLED_ROWS:
+                if n > slots:
+                    continue
+                ms = {kind: [] for kind in kinds}
+                for b in bs.values():
+                    for j in range(n):
+                        b.fork(j, behind)                        # (a fork detaches; the prefix is set with no slot attached)
+                    if form == "attached":
+                        b.set_prefix(P)
+                        for j in range(n):
+                            b.attach(j)
+                for _ in range(repeats):
+                    for kind, b in bs.items():
+                        b.time(n, q, 3)                          # warm-up of this type
+                        ms[kind].append(b.time(n, q, iters))
+                row = {"n": n, "pos": q, "form": form, "behind": behind, "bytes": {kind: b.cache_bytes() for kind, b in bs.items() if hasattr(llmk.lib(), "llmk_cache_bytes")}}
+                for kind, xs in ms.items():
+                    row[kind + "_ms"], row[kind + "_spread"] = med_spread(xs)
+                out.append(row)
+        for b in bs.values():
+            b.close()
+    return out
+
+
+def print_kv(shape_name, type_name, kinds, rows, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# batched decode by K/V cache type, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per type, "
+          f"the types alternating in one process (spread = (max - min) / median)")
+    print(f"{'n':>5} {'pos':>6} {'form':>9} {'behind':>7} " + " ".join(f"{k + ' ms':>10} {'spread':>7}" for k in kinds) + (f" {'f32 / f16':>10}" if len(kinds) == 2 else ""))
+    for r in rows:
+        cells = " ".join(f"{r[k + '_ms']:10.3f} {r[k + '_spread']:7.3f}" for k in kinds)
+        ratio = f" {r['f32_ms'] / r['f16_ms']:10.2f}" if len(kinds) == 2 else ""
+        print(f"{r['n']:5d} {r['pos']:6d} {r['form']:>9} {r['behind']:7d} {cells}{ratio}")
+
+
 def print_shared(shape_name, type_name, rows, iters, repeats):
     print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
     print(f"# batched decode behind a shared prompt, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per form, "
@@ -179,6 +247,9 @@ def main():
     ap.add_argument("--forked-only", action="store_true",
                     help="with --shared-prefix: only the forked figures, no prefix is ever set (what another build selected with LLMK_LIB "
                          "that has no llmk_prefix_* measures: the like-for-like baseline of the unshared path)")
+    ap.add_argument("--kv", choices=["f32", "f16", "both"], default=None,
+                    help="only the K/V-type table: the pass at 8, 32 and 128 rows at positions 25 and --pos on batches with f32 and / or f16 "
+                         "K/V caches, alternating in one process; with --shared-prefix P also attached behind P positions at --pos")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
@@ -189,6 +260,14 @@ def main():
         print_sampled(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.repeats)
         if a.json:
             print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "sampled": rows}))
+        return
+    if a.kv:
+        kinds = ("f32", "f16") if a.kv == "both" else (a.kv,)
+        rows = kv_types(m, shape, kinds, a.shared_prefix, a.pos, a.iters, a.repeats)
+        m.close()
+        print_kv(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), kinds, rows, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "kv": rows}))
         return
     if a.shared_prefix:
         rows = shared_prefix(m, shape, a.shared_prefix, a.pos, a.iters, a.repeats, a.forked_only)
