@@ -173,6 +173,7 @@ struct llmk_ctx {
     DevBuf<unsigned long long> d_trace;    // debug stamps (LLMK_TK_TRACE=1)
     size_t tk_lds = 0;
     size_t tk_ngran = 0;   // granules in d_gran (the last TK_QSC_GRANULES: the q4_0 kernels' per-layer scale records, tk_qsc_records)
+    int tk_qsc_pos = 0;    // the position of the last launch that may have left records, 0: none since they were cleared (tk_qsc_before_launch)
     // pipelined greedy decode (llmk_decode_greedy): per-CU classifier maxima of the last two launches, and the ids as they
     // are resolved (host-mapped; 0 = not there yet)
     // (the candidates sit behind the device error word, the ids behind the host error word: scratch_layout.h)
@@ -637,7 +638,42 @@ unsigned long long* tk_qsc_records(const llmk_ctx* c, size_t* n) {
 hipError_t tk_qsc_clear(llmk_ctx* c, hipStream_t st) {
     size_t n;
     unsigned long long* rec = tk_qsc_records(c, &n);
+    c->tk_qsc_pos = 0;
     return rec ? hipMemsetAsync(rec, 0, n * sizeof(unsigned long long), st) : hipSuccess;
+}
+// The records are tagged by position only, and a launch with a range event writes none behind the event: the HOST keeps them those of
+// the sequence being fed (invariant R).  Every field of both buffers whose tag is not `keep` goes back to zero.
+// Off the hot path (a rewind, the end of a pipelined call on a range event) and on an idle stream: 4 KB to the host and back
+hipError_t tk_qsc_keep(llmk_ctx* c, int keep) {
+    size_t n;
+    unsigned long long* rec = tk_qsc_records(c, &n);
+    c->tk_qsc_pos = keep;
+    if (!rec) return hipSuccess;
+    float4 h[2 * TK_QSC_LMAX];
+    static_assert(sizeof(h) == TK_QSC_GRANULES * sizeof(unsigned long long), "two buffers of TK_QSC_LMAX records");
+    HIPRET(hipMemcpyAsync(h, rec, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPRET(hipStreamSynchronize(c->stream));
+    bool dropped = false;
+    for (float4& r : h) {
+        int tz, tw;
+        memcpy(&tz, &r.z, sizeof(int));
+        memcpy(&tw, &r.w, sizeof(int));
+        if (tz != keep && (tz != 0 || r.x != 0.f)) { r.x = r.z = 0.f; dropped = true; }
+        if (tw != keep && (tw != 0 || r.y != 0.f)) { r.y = r.w = 0.f; dropped = true; }
+    }
+    if (!dropped) return hipSuccess;
+    HIPRET(hipMemcpyAsync(rec, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    return hipStreamSynchronize(c->stream);      // (h is this frame's)
+}
+// In front of a token-kernel launch at `pos`.  A launch that continues the one before it finds its own
+// buffer tagged pos - 2 or older, which nobody takes for history.  Any other launch -- the same position again with another token, a
+// rewind, a jump -- may find tags >= pos there that an earlier sequence left, and if it meets an event the layers behind it keep them
+// for position pos + 1 to read: such a launch first drops everything but position pos - 1's fields, which its own sequence shares.
+hipError_t tk_qsc_before_launch(llmk_ctx* c, int pos) {
+    if (!c->use_tk || !tk_table[c->tk_shape - 1].q4) return hipSuccess;
+    const hipError_t e = pos == c->tk_qsc_pos + 1 ? hipSuccess : tk_qsc_keep(c, pos - 1);
+    c->tk_qsc_pos = pos;
+    return e;
 }
 
 // The two sampler kernels on the logits in d_logits, as EVERY site enqueues them -- the tail of a token pass (enqueue_tail), behind
@@ -935,6 +971,7 @@ int token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
     HIPCHK(hipSetDevice(c->cfg.device));
     c->h_tokpos[0] = token - 1;
     c->h_tokpos[1] = pos;
+    HIPCHK(tk_qsc_before_launch(c, pos));
     const bool timed = (c->cfg.flags & LLMK_FLAG_TIMINGS) != 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         c->h_tokpos[2] += 1;  // token serial: makes every exchange epoch of this pass unique
@@ -2499,6 +2536,7 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         TkDevWords* dw = c->dev_words();
         memset(h_ids, 0, (size_t)n * sizeof(int));
         c->host_words()->err = 0;
+        HIPCHK(tk_qsc_before_launch(c, pos0));
         // the GR launches score their classifier rows with the sampling words (token_kernel.h tk_sample_params): the request's, or
         // zeros -- invT = 0 is greedy, which is also what the sampler kernels run behind (enqueue_sampler).  Those words and the
         // filter's are written only where the device holds others
@@ -2554,6 +2592,8 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         const unsigned err = c->h_next->err;
         if (err == 0 && done == n) {
             if (lp) logprob_deliver(c->lp.h + (pos0 - 1), (size_t)n, lp);
+            c->tk_range_run = 0;      // (clean positions: a range event of the next call is not "in a row" with one of the last call)
+            c->tk_qsc_pos = pos0 + n - 1;
             return LLMK_OK;
         }
         // a timed-out exchange: every later launch drained on the sticky word.  Retire the token kernel and redo the rest,
@@ -2562,6 +2602,12 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         // position through run_token, which redoes just the positions that need it and keeps the kernel: see there)
         rc = tk_range_only(err) ? tk_clear_err(c) : tk_retire(c, err, pos0 + done);
         if (rc) return rc;
+        // The launches queued behind the event have run on its debris, and may have left records of it under their own positions (the
+        // sticky word stops the exchanges, not the record of a vector that happened to arrive): only the record of the last position
+        // whose id arrived is worth keeping -- what the launch in between overwrote of it is dropped with the rest.  The positions in
+        // front of the event ran clean: the event is not "in a row" with an earlier call's.
+        if (tk_range_only(err)) HIPCHK(tk_qsc_keep(c, pos0 + done - 1));
+        if (done > 0) c->tk_range_run = 0;
         if (done > 0) token = ids_out[done - 1];
         c->tk_short_grid = false;
     }
