@@ -18,6 +18,7 @@
 #include "batch.h"
 #include "tp_p2p.h"
 #include "forward_ahead.h"
+#include "tk_recover.h"
 #include "owned.h"
 
 #include <rccl/rccl.h>
@@ -162,18 +163,13 @@ struct llmk_ctx {
     // persistent whole-token kernel (token_kernel.h)
     bool use_tk = false;
     bool tk_short_grid = false;   // libllmk_debug.so only (LLMK_TK_INJECT_TIMEOUT)
-    bool tk_retired = false;   // the token kernel timed out once on this ctx: it stays on the multi-kernel path
-    // q4_0 persistent kernels: positions whose activations did not fit the f16 image of x (sticky word 0x4000) are redone ONE AT A TIME
-    // on the multi-kernel path and the kernel stays in use (advisor, round 5: one such position used to cost the context a third of
-    // its rate for good); TK_RANGE_LIMIT of them in a row retire it after all (a model it cannot hold), and its unit copies are freed
-    int tk_range_events = 0, tk_range_run = 0;
+    TkRecovery tk;                // what the kernel's sticky error word means for this ctx (tk_recover.h; carried out by tk_perform)
     int tk_shape = 0;      // 1-based index into tk_table (the instantiated shapes: LLMK_TK_SHAPES), 0 = none
     DevBuf<unsigned long long> d_gran;     // exchange granules: qkv | xb | xa | hb | x | attention parts
     DevBuf<float4> d_zeros;
     DevBuf<unsigned long long> d_trace;    // debug stamps (LLMK_TK_TRACE=1)
     size_t tk_lds = 0;
     size_t tk_ngran = 0;   // granules in d_gran (the last TK_QSC_GRANULES: the q4_0 kernels' per-layer scale records, tk_qsc_records)
-    int tk_qsc_pos = 0;    // the position of the last launch that may have left records, 0: none since they were cleared (tk_qsc_before_launch)
     // pipelined greedy decode (llmk_decode_greedy): per-CU classifier maxima of the last two launches, and the ids as they
     // are resolved (host-mapped; 0 = not there yet)
     // (the candidates sit behind the device error word, the ids behind the host error word: scratch_layout.h)
@@ -564,8 +560,8 @@ hipError_t launch_token_kernel(llmk_ctx* c, bool direct = false, const TkGreedy&
 }
 // the last position of a pipelined greedy run has no next launch to fold its candidates: this does (1 wave)
 // (no id while the sticky error word is set, and none from candidates without a finite maximum: see tk_token).  Like tk_token it
-// adds 0x2000 only to a clear word: behind a range event (0x4000) the drained launches leave candidates that need not be finite,
-// and 0x2000 on top would make the host retire the kernel instead of redoing the one position (tk_range_only)
+// adds TK_ERR_NO_FINITE only to a clear word: behind a range event the drained launches leave candidates that need not be finite,
+// and the mark on top would make the host retire the kernel instead of redoing the one position (tk_range_only)
 __global__ __launch_bounds__(64) void cand_resolve_kernel(const float2* __restrict__ cand, int* id_out, int* next, unsigned* err, int V) {
     float bv;
     int bi;
@@ -573,7 +569,7 @@ __global__ __launch_bounds__(64) void cand_resolve_kernel(const float2* __restri
     if (threadIdx.x == 0) {
         const bool none = (unsigned)bi >= (unsigned)V;
         const unsigned e = *err;
-        if (none && e == 0) atomicOr(err, 0x2000u);
+        if (none && e == 0) atomicOr(err, TK_ERR_NO_FINITE);
         if (!none && e == 0) {
             next[0] = bi + 1;
             __hip_atomic_store(id_out, bi + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -615,13 +611,14 @@ int tk_setup(llmk_ctx* c, int id) {
     HIPCHK(hipMemset(c->d_zeros, 0, (size_t)TK_NCU * TK_WAVES * 1024));
     c->use_tk = true;
     c->tk_shape = id;
+    c->tk.cleared();
     return LLMK_OK;
 }
 
 // The whole-token persistent kernel serves the shapes it is instantiated for, on a full 256-CU part.  Called at create and again
 // when the classifier gets a type of its own (llmk_set_tensor_type: the q6_K instantiations).
 int tk_setup_all(llmk_ctx* c) {
-    if ((c->cfg.flags & (LLMK_FLAG_MULTI_KERNEL | LLMK_FLAG_TIMINGS)) || c->n_cu != TK_NCU || c->tp_size != 1 || c->tk_retired) return LLMK_OK;
+    if ((c->cfg.flags & (LLMK_FLAG_MULTI_KERNEL | LLMK_FLAG_TIMINGS)) || c->n_cu != TK_NCU || c->tp_size != 1 || c->tk.retired) return LLMK_OK;
     int rc = LLMK_OK;
     for (int i = 0; i < TK_NSHAPES && rc == LLMK_OK; ++i) rc = tk_table[i].setup(c, i + 1);      // (the first match takes the ctx)
     return rc;
@@ -638,42 +635,28 @@ unsigned long long* tk_qsc_records(const llmk_ctx* c, size_t* n) {
 hipError_t tk_qsc_clear(llmk_ctx* c, hipStream_t st) {
     size_t n;
     unsigned long long* rec = tk_qsc_records(c, &n);
-    c->tk_qsc_pos = 0;
+    c->tk.cleared();
     return rec ? hipMemsetAsync(rec, 0, n * sizeof(unsigned long long), st) : hipSuccess;
 }
 // The records are tagged by position only, and a launch with a range event writes none behind the event: the HOST keeps them those of
-// the sequence being fed (invariant R).  Every field of both buffers whose tag is not `keep` goes back to zero.
-// Off the hot path (a rewind, the end of a pipelined call on a range event) and on an idle stream: 4 KB to the host and back
+// the sequence being fed (invariant R), by tk_recover.h's rules; this is their device side.  Every field of both
+// buffers whose tag is not `keep` goes back to zero (tk_qsc_filter).  Off the hot path (a rewind, the end of a pipelined call on a
+// range event) and on an idle stream: 4 KB to the host and back
 hipError_t tk_qsc_keep(llmk_ctx* c, int keep) {
     size_t n;
     unsigned long long* rec = tk_qsc_records(c, &n);
-    c->tk_qsc_pos = keep;
-    if (!rec) return hipSuccess;
-    float4 h[2 * TK_QSC_LMAX];
+    if (!rec || keep == TK_KEEP_ALL) return hipSuccess;
+    TkQscRecord h[2 * TK_QSC_LMAX];
     static_assert(sizeof(h) == TK_QSC_GRANULES * sizeof(unsigned long long), "two buffers of TK_QSC_LMAX records");
     HIPRET(hipMemcpyAsync(h, rec, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPRET(hipStreamSynchronize(c->stream));
-    bool dropped = false;
-    for (float4& r : h) {
-        int tz, tw;
-        memcpy(&tz, &r.z, sizeof(int));
-        memcpy(&tw, &r.w, sizeof(int));
-        if (tz != keep && (tz != 0 || r.x != 0.f)) { r.x = r.z = 0.f; dropped = true; }
-        if (tw != keep && (tw != 0 || r.y != 0.f)) { r.y = r.w = 0.f; dropped = true; }
-    }
-    if (!dropped) return hipSuccess;
+    if (!tk_qsc_filter(h, 2 * TK_QSC_LMAX, keep)) return hipSuccess;
     HIPRET(hipMemcpyAsync(rec, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     return hipStreamSynchronize(c->stream);      // (h is this frame's)
 }
-// In front of a token-kernel launch at `pos`.  A launch that continues the one before it finds its own
-// buffer tagged pos - 2 or older, which nobody takes for history.  Any other launch -- the same position again with another token, a
-// rewind, a jump -- may find tags >= pos there that an earlier sequence left, and if it meets an event the layers behind it keep them
-// for position pos + 1 to read: such a launch first drops everything but position pos - 1's fields, which its own sequence shares.
+// in front of a token-kernel launch at `pos`: TkRecovery::before_launch has the rule
 hipError_t tk_qsc_before_launch(llmk_ctx* c, int pos) {
-    if (!c->use_tk || !tk_table[c->tk_shape - 1].q4) return hipSuccess;
-    const hipError_t e = pos == c->tk_qsc_pos + 1 ? hipSuccess : tk_qsc_keep(c, pos - 1);
-    c->tk_qsc_pos = pos;
-    return e;
+    return tk_qsc_keep(c, c->tk.before_launch(pos, c->use_tk && tk_table[c->tk_shape - 1].q4));
 }
 
 // The two sampler kernels on the logits in d_logits, as EVERY site enqueues them -- the tail of a token pass (enqueue_tail), behind
@@ -800,7 +783,9 @@ hipError_t launch_tp_allgather(llmk_ctx* c, unsigned jseed = 0) {   // every ran
     return hipGetLastError();
 }
 
-hipError_t enqueue_token(llmk_ctx* c, TailMode tail, bool timed) {
+// One token pass on the stream.  tk: the persistent kernel (the path of a ctx with use_tk), else the multi-kernel launches -- which such
+// a ctx also takes, eagerly, for a position its kernel could not hold (token_pass).  Tensor-parallel ranks have one path
+hipError_t enqueue_token(llmk_ctx* c, TailMode tail, bool timed, bool tk) {
     HIPRET(hipMemcpyAsync(c->d_tokpos, c->h_tokpos, 4 * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (c->p2p) {   // tensor-parallel over peer memory: the whole token is stream work (replayable from a hipGraph)
         HIPRET(launch_embed(c));
@@ -817,7 +802,7 @@ hipError_t enqueue_token(llmk_ctx* c, TailMode tail, bool timed) {
         HIPRET(launch_tp_allgather(c));
         return enqueue_tail(c, tail);
     }
-    if (c->use_tk) {
+    if (tk) {
         HIPRET(launch_token_kernel(c));
         return enqueue_tail(c, tail);
     }
@@ -862,7 +847,7 @@ void drop_graphs(llmk_ctx* c) {
 int build_graph(llmk_ctx* c, TailMode tail, hipGraphExec_t* out) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    hipError_t e = enqueue_token(c, tail, false);
+    hipError_t e = enqueue_token(c, tail, false, c->use_tk);
     hipError_t e2 = hipStreamEndCapture(c->stream, &g);
     if (e != hipSuccess) { if (g) hipGraphDestroy(g); return LLMK_E_HIP + (int)e; }
     HIPCHK(e2);
@@ -888,17 +873,14 @@ int check_ready(llmk_ctx* c) {
     return rc ? rc : tensors_ready(c);
 }
 
-// The persistent kernel reported a timed-out exchange (its workgroups were not all running: the GPU was shared, or a
-// wedged peer).  Its error word is sticky by design (every CU drains instead of spinning on), so: clear it, retire the
-// token kernel for this context and tell the user once.  The caller re-runs the SAME position on the multi-kernel path,
-// which rewrites that position's KV rows and recomputes x from the embedding: nothing of the failed launch survives.
-constexpr int TK_RANGE_LIMIT = 4;
 // debug library only (LLMK_TK_INJECT_TIMEOUT=pos): the token kernel is launched one workgroup short at this position, so its peers
 // really time out
 bool tk_inject_timeout(int pos) {
     const char* at = TK_DEBUG ? getenv("LLMK_TK_INJECT_TIMEOUT") : nullptr;
     return at && atoi(at) == pos;
 }
+// the sticky word a completed pass left on the host: behind the logits, or with the tail's id
+unsigned tk_pass_err(const llmk_ctx* c, TailMode tail) { return tail != TAIL_LOGITS ? c->h_next->err : c->host_words()->err; }
 int tk_clear_err(llmk_ctx* c) {
     HIPCHK(hipMemsetAsync(&c->dev_words()->err, 0, sizeof(unsigned), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -906,22 +888,22 @@ int tk_clear_err(llmk_ctx* c) {
     c->h_next->err = 0;
     return LLMK_OK;
 }
-// 0x4000 and nothing else: this position's activations did not fit the q4_0 kernels' f16 image; the kernel itself is sound
-bool tk_range_only(unsigned code) { return (code & 0x4000u) != 0 && (code & 0x2f00u) == 0; }
-int tk_retire(llmk_ctx* c, unsigned code, int pos) {
-    int rc = tk_clear_err(c);
-    if (rc) return rc;
+// What TkRecovery (tk_recover.h) answered to the word `code` of the launch at `pos`, carried out.  The word is sticky by design (every
+// CU drains instead of spinning on), so all but CLEAN clear it.  RETIRE: the kernel reported a timed-out exchange (its workgroups were
+// not all running: the GPU was shared, or a wedged peer) or a model it cannot hold -- the ctx leaves the token kernel for good and the
+// user is told once.  After REDO and RETIRE the caller runs the SAME position on the multi-kernel path, which rewrites that
+// position's KV rows and recomputes x from the embedding: nothing of the failed launch survives.
+int tk_perform(llmk_ctx* c, TkVerdict what, unsigned code, int pos) {
+    if (what == TkVerdict::CLEAN) return LLMK_OK;
+    const int rc = tk_clear_err(c);
+    if (rc || what != TkVerdict::RETIRE) return rc;
     c->use_tk = false;
-    c->tk_retired = true;
+    c->tk.retired = true;
     drop_graphs(c);
     for (DevBuf<char>& units : c->q16) units.reset();       // the q4_0 kernels' second copy of the matrices (3.8 GB at 7B): nobody reads it again
     c->q16_dirty = true;
-    // what the sticky word says (token_kernel.h): 0x2000 no finite candidate among the classifier maxima (pipelined greedy decode),
-    // 0x4000 an activation beyond the f16 range of the q4_0 kernels' x image, anything else a bounded spin that ran out
-    const char* what = (code & 0x2000u) ? "found no finite logit among its candidates"
-                     : (code & 0x4000u) ? "met an activation beyond the f16 range of its matrix-core operands"
-                                        : "timed out waiting for its peer workgroups";
-    fprintf(stderr, "llmk: the persistent token kernel %s (code 0x%x, position %d); this context continues on the multi-kernel path\n", what, code, pos);
+    fprintf(stderr, "llmk: the persistent token kernel %s (code 0x%x, position %d); this context continues on the multi-kernel path\n",
+            tk_err_words(code), code, pos);
     return LLMK_OK;
 }
 
@@ -941,10 +923,8 @@ const char* tp_describe_err(const llmk_ctx* c, unsigned code, char* buf, size_t 
 }
 // A speculative launch of llmk_forward may be in flight: wait for it, look at the sticky word as run_token_pass does, and leave the
 // machine IDLE.  A launch nobody waits for is an ordinary token pass: it ends by itself, and all it leaves behind is KV row `next`
-// with the guessed token's K/V, which every path rewrites before reading it.
-//   0x2000: the launch found no finite logit among the candidates of the position before it (that position's logits, which the caller
-//           has or gets as they are, hold none): nothing of the kernel's is at fault, the word is cleared
-//   else:   a timed-out exchange: the kernel is retired as in run_token_pass, the next pass runs on the multi-kernel path
+// with the guessed token's K/V, which every path rewrites before reading it.  TkRecovery::settled says what its word means: no finite
+// candidate clears it, anything else retires the kernel and the next pass runs on the multi-kernel path.
 // The device's word is read, not the host's copy: only workgroups that noticed the raised word store it there.
 int spec_settle(llmk_ctx* c) {
     c->fa.interrupt();
@@ -956,8 +936,7 @@ int spec_settle(llmk_ctx* c) {
     c->h_tokpos[1] = c->fa_pos;
     unsigned err = 0;
     HIPCHK(hipMemcpy(&err, &c->dev_words()->err, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (err == 0) return LLMK_OK;
-    return (err & 0x2000u) ? tk_clear_err(c) : tk_retire(c, err, c->fa_pos + 1);
+    return tk_perform(c, TkRecovery::settled(err), err, c->fa_pos + 1);
 }
 
 int token_pass(llmk_ctx* c, int token, int pos, TailMode tail);
@@ -981,7 +960,7 @@ int token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
             if (rc) return rc;
             HIPCHK(enqueue_tail(c, tail));
         } else if (timed || (c->cfg.flags & LLMK_FLAG_NO_GRAPH)) {
-            HIPCHK(enqueue_token(c, tail, timed));
+            HIPCHK(enqueue_token(c, tail, timed, c->use_tk));
         } else if (c->use_tk && tail == TAIL_LOGITS && c->tk_direct) {
             c->host_words()->err = 0;
             HIPCHK(launch_token_kernel(c, true));
@@ -995,33 +974,28 @@ int token_pass(llmk_ctx* c, int token, int pos, TailMode tail) {
         }
         HIPCHK(hipStreamSynchronize(c->stream));
         if (c->p2p) {   // a peer never delivered its granules: the sticky word says so (cleared by llmk_reset)
-            const unsigned perr = tail != TAIL_LOGITS ? c->h_next->err : c->host_words()->err;
+            const unsigned perr = tk_pass_err(c, tail);
             char what[160];
             if (perr) fprintf(stderr, "llmk: rank %d of %d: a peer's granules never arrived (%s; position %d, serial %d)\n",
                               c->tp_rank, c->tp_size, tp_describe_err(c, perr, what, sizeof(what)), pos, c->h_tokpos[2]);
             return perr ? LLMK_E_TIMEOUT : LLMK_OK;
         }
         if (!c->use_tk) return LLMK_OK;
-        const unsigned err = tail != TAIL_LOGITS ? c->h_next->err : c->host_words()->err;
-        if (err == 0) { c->tk_range_run = 0; return LLMK_OK; }
-        if (tk_range_only(err) && c->tk_range_run + 1 < TK_RANGE_LIMIT) {
+        const unsigned err = tk_pass_err(c, tail);
+        const TkRecovery::Single v = c->tk.single(err);
+        if (v.first_event)
+            fprintf(stderr, "llmk: position %d holds an activation beyond the f16 range of the persistent q4_0 kernel's operands (code 0x%x): that "
+                            "position is redone on the multi-kernel path, the kernel stays in use\n", pos, err);
+        rc = tk_perform(c, v.what, err, pos);
+        if (rc || v.what == TkVerdict::CLEAN) return rc;
+        if (v.what == TkVerdict::REDO) {
             // THIS position on the multi-kernel path (f32 activations throughout; eager launches: the ctx's graphs hold the token
             // kernel), the persistent kernel again from the next one
-            ++c->tk_range_run;
-            if (c->tk_range_events++ == 0)
-                fprintf(stderr, "llmk: position %d holds an activation beyond the f16 range of the persistent q4_0 kernel's operands (code 0x%x): that "
-                                "position is redone on the multi-kernel path, the kernel stays in use\n", pos, err);
-            rc = tk_clear_err(c);
-            if (rc) return rc;
-            c->use_tk = false;
-            const hipError_t e = enqueue_token(c, tail, false);
-            c->use_tk = true;
-            HIPCHK(e);
+            HIPCHK(enqueue_token(c, tail, false, false));
             HIPCHK(hipStreamSynchronize(c->stream));
             return LLMK_OK;
         }
-        rc = tk_retire(c, err, pos);   // then once more, on the multi-kernel path
-        if (rc) return rc;
+        // (retired: once more, on the multi-kernel path)
     }
     return LLMK_E_TIMEOUT;
 }
@@ -2154,9 +2128,9 @@ static int fa_launch(llmk_ctx* c, int token, int pos, bool spec) {
     HIPCHK(hipEventRecord(c->fa_ev[pos & 1], c->stream));
     return LLMK_OK;
 }
-// The id the launch in flight published for the position before its own; 0: the stream drained without one (the sticky word was
-// raised).  The launch starts when the previous position ends, which the caller has already seen: the word is there, or about to be.
-static int fa_published_id(llmk_ctx* c, int slot, int* id) {
+// The id (1-based) that a launch on the stream publishes in ids()[slot] as it starts: the one it took for the position before its own.
+// 0: the stream drained without one (the sticky word was raised)
+static int tk_published_id(llmk_ctx* c, int slot, int* id) {
     volatile int* ids = c->host_words()->ids();
     while ((*id = ids[slot]) == 0) {
         const hipError_t q = hipStreamQuery(c->stream);
@@ -2174,23 +2148,23 @@ static int fa_published_id(llmk_ctx* c, int slot, int* id) {
 static int fa_deliver(llmk_ctx* c, int token, int pos, bool more, float* logits_out) {
     HIPCHK(more ? hipEventSynchronize(c->fa_ev[pos & 1]) : hipStreamSynchronize(c->stream));
     if (!more) c->fa_inflight = false;
-    const unsigned err = c->host_words()->err;
-    if (err != 0) {
-        // 0x2000 is the launch BEHIND this one finding no finite candidate (this position's logits hold none; they are delivered as
+    const TkVerdict v = TkRecovery::settled(c->host_words()->err);
+    if (v != TkVerdict::CLEAN) {
+        // NO_FINITE is the launch BEHIND this one finding no finite candidate (this position's logits hold none; they are delivered as
         // they are); anything else is this launch's timed-out exchange: the position is redone on the multi-kernel path
         c->fa_inflight = true;      // (whatever is on the stream: spec_settle drains it and reads the device's word)
         const int rc = spec_settle(c);
         if (rc) return rc;
-        if (!(err & 0x2000u)) {
+        if (v != TkVerdict::NO_FINITE) {
             const int rc2 = token_pass(c, token, pos, TAIL_LOGITS);
             if (rc2) return rc2;
             memcpy(logits_out, c->h_logits, (size_t)c->V * sizeof(float));
             return LLMK_OK;
         }
     }
-    c->tk_range_run = 0;
+    c->tk.clean();
     memcpy(logits_out, c->fa_buf[pos & 1], (size_t)c->V * sizeof(float));
-    if (err == 0) {
+    if (v == TkVerdict::CLEAN) {
         c->fa_logits = c->fa_buf[pos & 1];
         c->fa.ran(pos);
     }
@@ -2214,7 +2188,7 @@ int llmk_forward(llmk_ctx* c, int token, int pos, float* logits_out) {
     ForwardAhead& fa = c->fa;
     if (fa.armed) {
         int id = 0;
-        if (fa.expects(pos) && (rc = fa_published_id(c, pos - 2, &id)) != LLMK_OK) { spec_settle(c); return rc; }
+        if (fa.expects(pos) && (rc = tk_published_id(c, pos - 2, &id)) != LLMK_OK) { spec_settle(c); return rc; }
         if (id == token) {      // (ids are 1-based: never 0)
             const bool more = fa.hit(c->S);
             if (more && (rc = fa_launch(c, 0, pos + 1, true)) != LLMK_OK) { spec_settle(c); return rc; }
@@ -2571,43 +2545,32 @@ int decode_run(llmk_ctx* c, int token, int pos0, int n, TailMode tail, int* ids_
         hipLaunchKernelGGL(cand_resolve_kernel, dim3(1), dim3(64), 0, c->stream, dw->cand[(pos0 + n - 1) & 1], h_ids_dev + (n - 1), c->d_next, &dw->err, c->V);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&c->h_next->err, &dw->err, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        // drain: ids are 1-based, 0 = not resolved yet
-        volatile int* ids = h_ids;
-        while (done < n) {
-            if (ids[done] != 0) {
-                ids_out[done] = ids[done];
-                if (on_token) on_token(done, ids_out[done], user);
-                ++done;
-                continue;
-            }
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q == hipSuccess) { if (ids[done] == 0) break; continue; }   // stream drained without the id: an error below
-            if (q != hipErrorNotReady) return LLMK_E_HIP + (int)q;
+        // drain: ids are 1-based, 0 = the stream drained without this one: an error below
+        for (int id; done < n; ++done) {
+            if ((rc = tk_published_id(c, done, &id)) != LLMK_OK) return rc;
+            if (id == 0) break;
+            ids_out[done] = id;
+            if (on_token) on_token(done, id, user);
         }
         HIPCHK(hipStreamSynchronize(c->stream));
+        volatile int* ids = h_ids;
         for (; done < n && ids[done] != 0; ++done) {
             ids_out[done] = ids[done];
             if (on_token) on_token(done, ids_out[done], user);
         }
         const unsigned err = c->h_next->err;
-        if (err == 0 && done == n) {
+        const TkRecovery::Pipelined end = c->tk.pipelined_end(pos0, n, done, err);
+        if (end.what == TkVerdict::CLEAN) {
             if (lp) logprob_deliver(c->lp.h + (pos0 - 1), (size_t)n, lp);
-            c->tk_range_run = 0;      // (clean positions: a range event of the next call is not "in a row" with one of the last call)
-            c->tk_qsc_pos = pos0 + n - 1;
             return LLMK_OK;
         }
-        // a timed-out exchange: every later launch drained on the sticky word.  Retire the token kernel and redo the rest,
-        // from the first position whose id never arrived, on the multi-kernel path (it rewrites those KV rows).
-        // (0x4000 alone -- an activation beyond the q4_0 kernel's f16 image at ONE position: the rest of the call goes position by
-        // position through run_token, which redoes just the positions that need it and keeps the kernel: see there)
-        rc = tk_range_only(err) ? tk_clear_err(c) : tk_retire(c, err, pos0 + done);
+        // every launch behind the trouble drained on the sticky word: the rest of the call, from the first position whose id never
+        // arrived, goes position by position through run_token -- on the multi-kernel path after a retirement (it rewrites those KV
+        // rows), else on the kernel, which redoes just the positions that need it (token_pass) -- once the records that the launches
+        // behind a range event left of its debris are dropped
+        rc = tk_perform(c, end.what, err, end.resume);
         if (rc) return rc;
-        // The launches queued behind the event have run on its debris, and may have left records of it under their own positions (the
-        // sticky word stops the exchanges, not the record of a vector that happened to arrive): only the record of the last position
-        // whose id arrived is worth keeping -- what the launch in between overwrote of it is dropped with the rest.  The positions in
-        // front of the event ran clean: the event is not "in a row" with an earlier call's.
-        if (tk_range_only(err)) HIPCHK(tk_qsc_keep(c, pos0 + done - 1));
-        if (done > 0) c->tk_range_run = 0;
+        HIPCHK(tk_qsc_keep(c, end.keep));
         if (done > 0) token = ids_out[done - 1];
         c->tk_short_grid = false;
     }

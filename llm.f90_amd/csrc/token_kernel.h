@@ -36,6 +36,7 @@
 #include "kernels.h"
 #include "q4_units.h"
 #include "q6k.h"
+#include "tk_recover.h"           // (the sticky error word's vocabulary: TK_ERR_*)
 
 // ---- measurement knobs (defaults = the product; -D... builds a variant library for an A/B) ---------------------------
 // loads per lane the service wave keeps in flight in one pass of the hb gather (no gains are held across it).  H = 5632 is
@@ -479,7 +480,7 @@ __device__ __forceinline__ bool tk_gather_part(__amdgpu_buffer_rsrc_t rs, int fi
         if ((spin & 63) == 63) {
             if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
             if (spin > TK_SPIN_LIMIT) {
-                if (lane == 0) __hip_atomic_store(err, 0x100u + (epoch & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) __hip_atomic_store(err, TK_ERR_SPIN_GATHER + (epoch & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 return false;
             }
         }
@@ -590,10 +591,10 @@ __device__ __forceinline__ float tk_predict(float now, float hist) { return hist
 // is read behind: the device word is stored by other waves without an order against this load, and later gathers over the debris overwrite it)
 __device__ __forceinline__ bool tk_rec_ok(const float* red8, unsigned epoch) {
     const unsigned e = reinterpret_cast<const unsigned*>(red8)[TK_EVT];
-    return e == 0 || e == (0x4000u | (epoch & 0xffu));
+    return e == 0 || e == (TK_ERR_RANGE | (epoch & 0xffu));
 }
 __device__ __forceinline__ void tk_evt_note(unsigned* evt, unsigned epoch, int lane) {
-    if (evt && lane == 0 && *evt == 0) *evt = 0x4000u | (epoch & 0xffu);
+    if (evt && lane == 0 && *evt == 0) *evt = TK_ERR_RANGE | (epoch & 0xffu);
 }
 // the largest |element| layer l's vector KIND (0 xb, 1 hb) had at the position before (0 when that position left no record)
 __device__ __forceinline__ float tk_hist_amax(const float4* qsc_lds, int l, int L, int kind, int pos) {
@@ -661,7 +662,7 @@ __device__ __forceinline__ bool tk_coop_part(__amdgpu_buffer_rsrc_t rs, int firs
                     // the kernel for this context and redoes the position on the multi-kernel path (f32 throughout)
                     if (amx) { const float wm = wave_max(amax); if (lane == 0) *amx = wm; }
                     if (!nowait && __any(!(amax < 60000.f))) {
-                        if (lane == 0) __hip_atomic_store(err, 0x4000u + (epoch & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lane == 0) __hip_atomic_store(err, TK_ERR_RANGE + (epoch & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         tk_evt_note(evt, epoch, lane);
                         return false;
                     }
@@ -672,7 +673,7 @@ __device__ __forceinline__ bool tk_coop_part(__amdgpu_buffer_rsrc_t rs, int firs
                 // (a range event another workgroup met in this very vector -- all of them read the same one; anything else ends the launch)
                 if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { tk_evt_note(evt, epoch, lane); return false; }
                 if (spin > TK_SPIN_LIMIT) {
-                    if (lane == 0) __hip_atomic_store(err, 0x400u + (epoch & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (lane == 0) __hip_atomic_store(err, TK_ERR_SPIN_COOP + (epoch & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     tk_evt_note(evt, epoch, lane);
                     return false;
                 }
@@ -1312,7 +1313,7 @@ __device__ __forceinline__ int tk_token(const TokenArgs& a, int c, int lane) {
             // is added only to a clear word, so a range event of the previous position stays a range event (the kernel stays in use).
             if (c == 0 && lane == 0) {
                 const unsigned e = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (none && e == 0) atomicOr(a.err, 0x2000u);
+                if (none && e == 0) atomicOr(a.err, TK_ERR_NO_FINITE);
                 if ((a.gflags & TKG_ID) && e == 0 && !none)
                     __hip_atomic_store(reinterpret_cast<int*>(a.herr + 4) + a.tok_imm, bi + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
@@ -1458,7 +1459,7 @@ __device__ __forceinline__ void tk_service(const TokenArgs& a, char* lds, int c,
                 bool fits;
                 xn_att = tk_stage_q16<SH>(a.emb + (size_t)tok * SH::E, tk_rms_att(a, 0, SH::E), xraw, xs, lane, a.eps, sc_att, fits);   // :520, :527
                 if (!fits && !nosync) {      // an embedding row times its gains that no f16 holds: the same sticky word as a gather's (tk_coop_part)
-                    if (lane == 0) __hip_atomic_store(a.err, 0x4000u + (e_q & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (lane == 0) __hip_atomic_store(a.err, TK_ERR_RANGE + (e_q & 0xff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     tk_evt_note(reinterpret_cast<unsigned*>(red8) + TK_EVT, e_q, lane);
                     ok = false;
                 }
@@ -1539,7 +1540,7 @@ __device__ __forceinline__ void tk_service(const TokenArgs& a, char* lds, int c,
                 if ((spin & 63) == 63) {
                     if (__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { ok = false; break; }
                     if (spin > TK_SPIN_LIMIT) {
-                        if (lane == 0) __hip_atomic_store(a.err, 0x200u + (unsigned)l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lane == 0) __hip_atomic_store(a.err, TK_ERR_SPIN_QKV + (unsigned)l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         ok = false; break;
                     }
                 }
@@ -1608,7 +1609,7 @@ __device__ __forceinline__ void tk_service(const TokenArgs& a, char* lds, int c,
                         if ((spin & 63) == 63) {
                             if (__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { ok = false; break; }
                             if (spin > TK_SPIN_LIMIT) {
-                                if (lane == 0) __hip_atomic_store(a.err, 0x300u + (unsigned)l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                if (lane == 0) __hip_atomic_store(a.err, TK_ERR_SPIN_PARTS + (unsigned)l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                 ok = false; break;
                             }
                         }
@@ -1792,8 +1793,8 @@ __device__ __forceinline__ void tk_service(const TokenArgs& a, char* lds, int c,
     // copy of the word (direct mode): NaN logits returned as an answer.  All of this CU's gathers lie behind the barrier above.
     if constexpr (SH::Q4) { if (ok && lane == 0 && !nosync) ok = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0; }
     if (!ok && lane == 0) {
-        const unsigned cause = atomicOr(a.err, 0x1000u);      // (what the first failing wave left there: a timed-out spin's code, 0x4000 ...)
-        if (a.herr) __hip_atomic_store(a.herr, cause | 0x1000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const unsigned cause = atomicOr(a.err, TK_ERR_DRAINED);      // (what the first failing wave left there: a timed-out spin's code, 0x4000 ...)
+        if (a.herr) __hip_atomic_store(a.herr, cause | TK_ERR_DRAINED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 

@@ -102,3 +102,35 @@ def test_the_shim_allocates_and_releases_through_its_owners_only():
     seen = set()
     _quoted_includes(os.path.join(csrc, "llmk.hip"), seen)
     assert os.path.normpath(os.path.join(csrc, "owned.h")) in seen
+
+
+def test_the_sticky_error_word_has_one_vocabulary_and_one_policy():
+    """The persistent kernel's sticky error word is spelled in csrc/tk_recover.h alone, and the host's reaction to it is that
+    header's TkRecovery, carried out by llmk.hip's tk_perform.  Outside comments, neither llmk.hip nor token_kernel.h spells the
+    word's marks as literals again; llmk.hip declares none of the four loose fields the policy replaced; and it takes a context
+    off the kernel in two places only -- tk_perform and llmk_set_tensor_type (no `use_tk = false; ... use_tk = true;` around a
+    launch: enqueue_token takes the path as an argument)."""
+    csrc = os.path.join(ROOT, "llm.f90_amd", "csrc")
+
+    def code(name):
+        return [(n, line.split("//", 1)[0]) for n, line in enumerate(open(os.path.join(csrc, name)), 1)]
+    literal = re.compile(r"\b0x0*(2000|4000|2f00|1000)u?\b", re.I)
+    hits = [f"{name}:{n}: {c.strip()}" for name in ("llmk.hip", "token_kernel.h") for n, c in code(name) if literal.search(c)]
+    assert not hits, "\n".join(hits)
+    shim = code("llmk.hip")
+    fields = re.compile(r"\b(tk_range_run|tk_range_events|tk_retired|tk_qsc_pos)\b")
+    hits = [f"llmk.hip:{n}: {c.strip()}" for n, c in shim if fields.search(c)]
+    assert not hits, "\n".join(hits)
+    # the two assignments, each inside the function that may make it (the last function header above the line)
+    header = re.compile(r"^(?:static )?(?:int|hipError_t|bool|void|unsigned) (\w+)\(")
+    owner, owners = None, []
+    for n, c in shim:
+        m = header.match(c)
+        owner = m.group(1) if m else owner
+        if re.search(r"\buse_tk\s*=\s*false\b", c) and not re.match(r"\s*bool use_tk = false;", c):
+            owners.append(owner)
+    assert sorted(owners) == ["llmk_set_tensor_type", "tk_perform"], owners
+    for name in ("llmk.hip", "token_kernel.h"):
+        seen = set()
+        _quoted_includes(os.path.join(csrc, name), seen)
+        assert os.path.normpath(os.path.join(csrc, "tk_recover.h")) in seen, name
