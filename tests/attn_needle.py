@@ -1,4 +1,5 @@
-"""TEST INFRASTRUCTURE -- "needle" models for the attention kernels, and a float64 reference of the whole forward pass.
+"""TEST INFRASTRUCTURE -- "needle" models for the attention kernels; the float64 reference of the forward pass is tests/ref_pass.py,
+to which forward_all adds layer 0's softmax rows, the two mutations of the sensitivity checks and the suffix re-run.
 
 synth_fused's weights give attention scores of about N(0, 1): the softmax is nearly flat, and one timestep that a kernel drops,
 duplicates or reads from the wrong row moves the output by about 1/pos of one V row -- least exactly where the boundary code of
@@ -10,13 +11,13 @@ Used by tests/test_attn_needle_cpu.py (is the construction sound?) and tests/tes
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 import functools
 
 import numpy as np
 
 from llm_f90_amd.tools import gguf
+from ref_pass import Causal, RefPass
 
 # ------------------------------------------------------------------------------------------------
 # mirrors of the kernels' tile arithmetic
@@ -134,86 +135,25 @@ def encode_fused(fw32, ggml_type: int):
 # ------------------------------------------------------------------------------------------------
 # float64 reference: all positions of a sequence at once
 # ------------------------------------------------------------------------------------------------
-def _rope_freqs(hs: int) -> np.ndarray:
-    """the reference's f32 frequencies, 1 / powf(10000, (2j+1)/hs) (oracle/llm_oracle.c:99-100), through libm like the oracle"""
-    libm = ctypes.CDLL("libm.so.6")
-    libm.powf.restype, libm.powf.argtypes = ctypes.c_float, [ctypes.c_float, ctypes.c_float]
-    return np.array([np.float32(1.0) / np.float32(libm.powf(10000.0, float(np.float32(2 * j + 1) / np.float32(hs))))
-                     for j in range(hs // 2)], np.float32)
-
-
 def forward_all(fw, tokens, dtype=np.float64, drop=None, kv_head_shift: int = 0, cache=None):
-    """Batched causal forward pass of f32 FusedWeights over `tokens` (1-based ids at positions 1 .. n) in `dtype`, with the
-    reference's conventions as oracle/llm_oracle.c states them: interleaved RoPE pairs with exponent (2j+1)/hs and 1-based pos,
-    rmsnorm eps 1e-5 inside the root, GQA head h -> kv head h / kv_mul, SwiGLU as g / (1 + exp(-g)) * up.
+    """ref_pass.RefPass (the model and its conventions are stated there) over `tokens` (1-based ids at positions 1 .. n) in `dtype`.
     Returns (logits [n][V], att0 [nh][n][n]): att0 = layer 0's softmax rows, for inspection (None on a suffix run, see cache).
 
-    Mutations, for the sensitivity checks of the CPU test only:
+    Mutations, for the sensitivity checks of the CPU test only (ref_pass.Causal):
       drop=(layer, t)   timestep t is masked in that layer for all LATER queries (t' > t);
       kv_head_shift=k   query head h reads kv head (h / kv_mul + k) % nkv in every layer.
-    cache: a dict.  An intact run fills it (per-layer K / V, logits); a drop run that is given the filled cache recomputes only
-    the rows behind t -- the others cannot change -- and copies the rest."""
-    dt = np.dtype(dtype).type
-    s = fw.shape
-    E, H, L, nh, nkv, hs, KV = s.emb_dim, s.hidden_dim, s.n_layers, s.n_heads, s.n_kv_heads, s.head_size, s.kv_dim
-    kv_mul = nh // nkv
+    cache: a dict.  An intact run fills it (the pass, its per-layer K / V, logits); a drop run that is given the filled cache
+    recomputes only the rows behind t -- the others cannot change -- on a fork of that pass and copies the rest."""
     tokens = np.asarray(tokens)
-    n = len(tokens)
-    suffix = drop is not None and cache is not None and "logits" in cache and kv_head_shift == 0
-    r0 = drop[1] + 1 if suffix else 0
-    fill = cache is not None and not suffix and drop is None and kv_head_shift == 0
-    rows = np.arange(r0, n)
-    x = fw.token_embedding_table[tokens[r0:] - 1].astype(dt)
-    ang = (rows + 1).astype(dt)[:, None] * _rope_freqs(hs).astype(dt)[None, :]
-    c, sn = np.cos(ang), np.sin(ang)
-
-    def rope(a, heads):
-        a = a.reshape(len(rows), heads, hs // 2, 2)
-        o = np.empty_like(a)
-        o[..., 0] = a[..., 0] * c[:, None, :] - a[..., 1] * sn[:, None, :]
-        o[..., 1] = a[..., 0] * sn[:, None, :] + a[..., 1] * c[:, None, :]
-        return o.reshape(len(rows), heads, hs)
-
-    def rms(v, w):
-        return v * w.astype(dt) / np.sqrt((v * v).mean(axis=1, keepdims=True) + dt(1e-5))
-
-    att0 = None if suffix else np.zeros((nh, n, n), dt)
-    for l in range(L):
-        qkv = rms(x, fw.rms_att_weight[l]) @ fw.wqkv[l].astype(dt).T
-        q = rope(qkv[:, :E], nh)
-        k = rope(qkv[:, E:E + KV], nkv)
-        v = qkv[:, E + KV:].reshape(len(rows), nkv, hs)
-        if suffix:
-            k = np.concatenate([cache["k"][l][:r0], k])
-            v = np.concatenate([cache["v"][l][:r0], v])
-        elif fill:
-            cache.setdefault("k", []).append(k)
-            cache.setdefault("v", []).append(v)
-        out = np.empty((len(rows), nh, hs), dt)
-        for b0 in range(0, len(rows), 256):             # row blocks: a block only meets the columns its last query sees
-            rb = slice(b0, min(b0 + 256, len(rows)))
-            nc = int(rows[rb][-1]) + 1
-            vis = np.arange(nc)[None, :] <= rows[rb, None]
-            if drop is not None and drop[0] == l and drop[1] < nc:
-                vis[rows[rb] > drop[1], drop[1]] = False
-            for h in range(nh):
-                g = (h // kv_mul + kv_head_shift) % nkv
-                sc = np.where(vis, (q[rb, h] @ k[:nc, g].T) / np.sqrt(dt(hs)), -np.inf)
-                p = np.exp(sc - sc.max(axis=1, keepdims=True))
-                p /= p.sum(axis=1, keepdims=True)
-                if l == 0 and att0 is not None:
-                    att0[h, rb, :nc] = p
-                out[rb, h] = p @ v[:nc, g]
-        x = x + out.reshape(len(rows), E) @ fw.wo[l].astype(dt).T
-        h13 = rms(x, fw.rms_ffn_weight[l]) @ fw.w13[l].astype(dt).T
-        gate, up = h13[:, :H], h13[:, H:]
-        x = x + (gate / (1 + np.exp(-gate)) * up) @ fw.w2[l].astype(dt).T
-    logits = rms(x, fw.rms_final_weight) @ fw.wcls.astype(dt).T
-    if suffix:
-        logits = np.concatenate([cache["logits"][:r0], logits])
-    elif fill:
-        cache["logits"] = logits
-    return logits, att0
+    if drop is not None and kv_head_shift == 0 and cache is not None and "logits" in cache:
+        r0 = drop[1] + 1
+        logits = cache["pass"].fork(r0).feed(tokens[r0:], attend=Causal(drop))
+        return np.concatenate([cache["logits"][:r0], logits]), None
+    p, att = RefPass(fw, dtype), Causal(drop, kv_head_shift, keep_att0=True)
+    logits = p.feed(tokens, attend=att)
+    if cache is not None and drop is None and kv_head_shift == 0:
+        cache.update({"pass": p, "k": p.k, "v": p.v, "logits": logits})
+    return logits, att.att0
 
 
 # ------------------------------------------------------------------------------------------------

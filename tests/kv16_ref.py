@@ -2,8 +2,8 @@
 
 Rounding K and V to f16 where the cache is written moves the logits of the test models by 3e-4 .. 5e-4 of max |logit|: the oracle at
 REL_TOL = 1e-4 cannot judge such a batch.  A reference that rounds its OWN K/V cannot either: arithmetic noise of 1e-6 flips single
-f16 roundings from layer 1 on, and two such references (float64, float32) differ by up to 1e-4.  So forward_fed() restates
-attn_needle.forward_all with each layer's attention reading GIVEN cache rows -- the rows the device stored, read back with
+f16 roundings from layer 1 on, and two such references (float64, float32) differ by up to 1e-4.  So forward_fed() is the pass
+of tests/ref_pass.py with one thing added: each layer's attention reads GIVEN cache rows -- the rows the device stored, read back with
 llmk_cache_peek, the current position's row included.  All that then remains between the device and the reference is f32 arithmetic,
 and the bar is REL_TOL again.  tests/test_batch_kv16_cpu.py proves the yardstick without a device.
 
@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from attn_needle import _rope_freqs
+from ref_pass import Given, RefPass
 
 F16_MAX = 65504.0
 
@@ -51,47 +51,11 @@ def half_mirror(x) -> np.ndarray:
 
 
 def forward_fed(fw, tokens, K, V, pos=None):
-    """The float64 forward pass of attn_needle.forward_all over f32 FusedWeights with the reference's conventions (interleaved RoPE
-    pairs, exponent (2j+1)/hs, 1-based positions, rmsnorm eps 1e-5 inside the root, GQA head h -> kv head h / kv_mul, SwiGLU as
-    g / (1 + exp(-g)) * up), except that layer l's attention reads the GIVEN cache rows K[l], V[l] ([rows][kv_dim], cache row r =
-    position r + 1) and never its own keys and values: row i feeds tokens[i] (1-based id) at position pos[i] (1-based; None: 1 .. n)
-    and attends over cache rows 0 .. pos[i] - 1, its own position's row included.  Returns logits [n][V]."""
-    dt = np.float64
-    s = fw.shape
-    E, H, L, nh, nkv, hs = s.emb_dim, s.hidden_dim, s.n_layers, s.n_heads, s.n_kv_heads, s.head_size
-    kv_mul = nh // nkv
-    tokens = np.asarray(tokens)
-    n = len(tokens)
-    pos = np.arange(1, n + 1) if pos is None else np.asarray(pos)
-    assert pos.shape == (n,) and pos.min() >= 1
-    x = fw.token_embedding_table[tokens - 1].astype(dt)
-    ang = pos.astype(dt)[:, None] * _rope_freqs(hs).astype(dt)[None, :]
-    c, sn = np.cos(ang), np.sin(ang)
-
-    def rms(v, w):
-        return v * w.astype(dt) / np.sqrt((v * v).mean(axis=1, keepdims=True) + dt(1e-5))
-
-    head_of = np.arange(nh) // kv_mul
-    for l in range(L):
-        a = (rms(x, fw.rms_att_weight[l]) @ fw.wqkv[l][:E].astype(dt).T).reshape(n, nh, hs // 2, 2)
-        q = np.empty_like(a)
-        q[..., 0] = a[..., 0] * c[:, None, :] - a[..., 1] * sn[:, None, :]
-        q[..., 1] = a[..., 0] * sn[:, None, :] + a[..., 1] * c[:, None, :]
-        q = q.reshape(n, nh, hs)
-        Kl, Vl = (np.asarray(z[l], dt).reshape(-1, nkv, hs) for z in (K, V))
-        assert len(Kl) >= pos.max() and len(Vl) >= pos.max(), (l, len(Kl), int(pos.max()))
-        out = np.empty((n, nh, hs), dt)
-        for i in range(n):
-            nc = int(pos[i])
-            sc = np.einsum("hd,thd->ht", q[i], Kl[:nc, head_of]) / np.sqrt(dt(hs))
-            p = np.exp(sc - sc.max(axis=1, keepdims=True))
-            p /= p.sum(axis=1, keepdims=True)
-            out[i] = np.einsum("ht,thd->hd", p, Vl[:nc, head_of])
-        x = x + out.reshape(n, E) @ fw.wo[l].astype(dt).T
-        h13 = rms(x, fw.rms_ffn_weight[l]) @ fw.w13[l].astype(dt).T
-        gate, up = h13[:, :H], h13[:, H:]
-        x = x + (gate / (1 + np.exp(-gate)) * up) @ fw.w2[l].astype(dt).T
-    return rms(x, fw.rms_final_weight) @ fw.wcls.astype(dt).T
+    """The float64 pass of ref_pass.RefPass over f32 FusedWeights, except that layer l's attention reads the GIVEN cache rows K[l],
+    V[l] ([rows][kv_dim], cache row r = position r + 1) and never its own keys and values (ref_pass.Given): row i feeds tokens[i]
+    (1-based id) at position pos[i] (1-based; None: 1 .. n) and attends over cache rows 0 .. pos[i] - 1, its own position's row
+    included.  Returns logits [n][V]."""
+    return RefPass(fw).feed(tokens, pos, Given(K, V))
 
 
 def peek_all(b, n_layers: int, slot: int, n: int):

@@ -3,7 +3,7 @@
 Each launch of the q4_0 token kernel leaves, per layer, the largest |element| of its xb (attention output) and hb (SwiGLU output)
 vectors, tagged with its position, in the buffer of its position's parity; the next position scales its f16 hi | lo images from
 them.  This module holds
-  * Pass / forward_maxima: a float64 forward pass (the conventions of attn_needle.forward_all) that also returns those maxima;
+  * Pass / forward_maxima: the float64 forward pass of tests/ref_pass.py, to which they add those maxima, collected through its tap;
   * a mirror in plain Python of the kernel's scale rule (tk_pow2_inv .. tk_hist_amax, the fit test of tk_coop_part) and of the host's
     part of the protocol (who clears the records, what a redo leaves): Mirror says where a fed sequence raises a range event and
     which records each launch leaves;
@@ -17,90 +17,27 @@ import functools
 
 import numpy as np
 
-from attn_needle import _rope_freqs
 from llm_f90_amd.tools import gguf
+from ref_pass import RefPass
 
 REL_TOL = 1e-4          # conftest.REL_TOL (a test asserts that they are the same number)
 
 # ------------------------------------------------------------------------------------------------
 # float64 reference with the maxima
 # ------------------------------------------------------------------------------------------------
-class Pass:
-    """A causal forward pass over f32 FusedWeights in `dtype` that keeps its keys and values, so that a greedy loop feeds one token
-    at a time.  The reference's conventions as oracle/llm_oracle.c states them: interleaved RoPE pairs with exponent (2j+1)/hs and
-    1-based positions, rmsnorm eps 1e-5 inside the root, GQA head h -> kv head h / kv_mul, SwiGLU as g / (1 + exp(-g)) * up.
-    The embedding table is read where a token is fed, not copied: a row edited later counts from then on."""
-
-    def __init__(self, fw, dtype=np.float64, _share=None, _n=0):
-        assert fw.ggml_type == gguf.GGML_F32
-        self.fw, self.dt, self.s = fw, np.dtype(dtype).type, fw.shape
-        if _share is None:
-            c = lambda a: np.ascontiguousarray(a, self.dt)
-            self.w = dict(att=c(fw.rms_att_weight), ffn=c(fw.rms_ffn_weight), fin=c(fw.rms_final_weight),
-                          qkv=[c(w.T) for w in fw.wqkv], wo=[c(w.T) for w in fw.wo], w13=[c(w.T) for w in fw.w13],
-                          w2=[c(w.T) for w in fw.w2], cls=c(fw.wcls.T), freqs=_rope_freqs(self.s.head_size).astype(self.dt))
-            self.k = [np.zeros((0, self.s.n_kv_heads, self.s.head_size), self.dt) for _ in range(self.s.n_layers)]
-            self.v = [k.copy() for k in self.k]
-        else:
-            self.w = _share.w
-            self.k = [k[:_n] for k in _share.k]
-            self.v = [v[:_n] for v in _share.v]
-
-    @property
-    def n(self) -> int:
-        return len(self.k[0])
-
-    def fork(self, n: int) -> "Pass":
-        """a pass that has fed this one's first n positions (the weights are shared, the rows copied on the next feed)"""
-        assert 0 <= n <= self.n
-        return Pass(self.fw, self.dt, _share=self, _n=n)
+class Pass(RefPass):
+    """ref_pass.RefPass whose feed also returns the maxima the kernel records"""
 
     def feed(self, tokens):
         """tokens (1-based ids) at the next len(tokens) positions.  Returns (logits [m][V], xb [m][L], hb [m][L]): per position and
         layer the largest |element| of the attention output (all heads, in front of wo) and of silu(gate) * up."""
-        dt, s = self.dt, self.s
-        E, H, L, nh, nkv, hs, KV = s.emb_dim, s.hidden_dim, s.n_layers, s.n_heads, s.n_kv_heads, s.head_size, s.kv_dim
-        kv_mul = nh // nkv
-        tokens = np.asarray(tokens).reshape(-1)
-        m, n0 = len(tokens), self.n
-        rows = np.arange(n0, n0 + m)
-        x = self.fw.token_embedding_table[tokens - 1].astype(dt)
-        ang = (rows + 1).astype(dt)[:, None] * self.w["freqs"][None, :]
-        c, sn = np.cos(ang), np.sin(ang)
+        m = np.size(tokens)
+        amax = {"xb": np.empty((m, self.s.n_layers)), "hb": np.empty((m, self.s.n_layers))}
 
-        def rope(a, heads):
-            a = a.reshape(m, heads, hs // 2, 2)
-            o = np.empty_like(a)
-            o[..., 0] = a[..., 0] * c[:, None, :] - a[..., 1] * sn[:, None, :]
-            o[..., 1] = a[..., 0] * sn[:, None, :] + a[..., 1] * c[:, None, :]
-            return o.reshape(m, heads, hs)
-
-        def rms(v, w):
-            return v * w / np.sqrt((v * v).mean(axis=1, keepdims=True) + dt(1e-5))
-
-        vis = np.arange(n0 + m)[None, :] <= rows[:, None]
-        xb, hb = np.empty((m, L)), np.empty((m, L))
-        for l in range(L):
-            qkv = rms(x, self.w["att"][l]) @ self.w["qkv"][l]
-            q = rope(qkv[:, :E], nh)
-            self.k[l] = k = np.concatenate([self.k[l], rope(qkv[:, E:E + KV], nkv)])
-            self.v[l] = v = np.concatenate([self.v[l], qkv[:, E + KV:].reshape(m, nkv, hs)])
-            out = np.empty((m, nh, hs), dt)
-            for h in range(nh):
-                g = h // kv_mul
-                sc = np.where(vis, (q[:, h] @ k[:, g].T) / np.sqrt(dt(hs)), -np.inf)
-                p = np.exp(sc - sc.max(axis=1, keepdims=True))
-                p /= p.sum(axis=1, keepdims=True)
-                out[:, h] = p @ v[:, g]
-            out = out.reshape(m, E)
-            xb[:, l] = np.abs(out).max(axis=1)
-            x = x + out @ self.w["wo"][l]
-            h13 = rms(x, self.w["ffn"][l]) @ self.w["w13"][l]
-            gate, up = h13[:, :H], h13[:, H:]
-            act = gate / (1 + np.exp(-gate)) * up
-            hb[:, l] = np.abs(act).max(axis=1)
-            x = x + act @ self.w["w2"][l]
-        return rms(x, self.w["fin"]) @ self.w["cls"], xb, hb
+        def tap(l, name, a):
+            if name in amax:
+                amax[name][:, l] = np.abs(a).max(axis=1)
+        return super().feed(tokens, tap=tap), amax["xb"], amax["hb"]
 
 
 def forward_maxima(fw_f32, tokens, dtype=np.float64):

@@ -22,13 +22,15 @@ elsewhere their slots hold the format's plain class.
 LIMIT: this is a DECODING suite.  |w| <= 8 everywhere, no infinite or NaN d, |d| <= 1: it injects no faults and does not redo
 the activation-range tests (test_parity_gpu.py: activations beyond f16, small xb / hb).
 
-The reference is forward64: the model of oracle/llm_oracle.c in float64 numpy on the decoded weights.
+The reference is forward64: the float64 pass of tests/ref_pass.py on the decoded weights, to which it adds the read-out of the
+K / V rows of every layer and of the last layer's q, xb, hb and x.
 """
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 from conftest import REL_TOL, rel_err
+from ref_pass import RefPass
 
 Q6K_BYTES, Q4_BYTES = 210, 18
 H_2M24, H_SUBMAX, H_MINNORM = 0x0001, 0x03FF, 0x0400      # f16 bits: 2^-24, 2^-14 - 2^-24, 2^-14
@@ -382,61 +384,19 @@ def row_classes(shape, classes):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the reference: oracle/llm_oracle.c step by step, in float64
+# the reference: ref_pass.RefPass in float64, with the vectors the tests read out
 # ----------------------------------------------------------------------------------------------------------------------
-def _mm(W, X, chunk=4096):
-    """X [n][K] times W [rows][K] (any float type) transposed, in float64, a slice of rows at a time"""
-    out = np.empty((X.shape[0], W.shape[0]), np.float64)
-    for r0 in range(0, W.shape[0], chunk):
-        out[:, r0:r0 + chunk] = X @ np.asarray(W[r0:r0 + chunk], np.float64).T
-    return out
-
-
-def _rmsnorm(X, w, eps):
-    return X * np.asarray(w, np.float64) / np.sqrt(np.mean(X * X, axis=1, keepdims=True) + eps)
-
-
 def forward64(fw, tokens, eps=1e-5):
-    """The model of oracle/llm_oracle.c (llama2.f90:480-640) in float64 on DECODED weights (fw.as_f32()), tokens (1-based) at
+    """ref_pass.RefPass (the model of oracle/llm_oracle.c) in float64 on DECODED weights (fw.as_f32()), tokens (1-based) at
     positions 1..n.  Returns logits [n][V], the K (rotated) and V cache rows k, v [L][n][KV], and of the LAST layer q (rotated),
     xb (attention output), hb (SwiGLU output) and x (residual stream behind the layer), each [n][.]."""
-    assert fw.ggml_type == 0
-    s = fw.shape
-    E, H, L, KV, hs, nh = s.emb_dim, s.hidden_dim, s.n_layers, s.kv_dim, s.head_size, s.n_heads
-    kv_mul = nh // s.n_kv_heads
-    n = len(tokens)
-    X = np.asarray(fw.token_embedding_table, np.float64)[np.asarray(tokens) - 1]
-    i1 = np.arange(1, E, 2)                                        # the reference's 1-based odd i: the pair (i - 1, i) 0-based
-    freq = 1.0 / np.power(10000.0, (i1 % hs) / hs)                 # exponent (2 j + 1) / hs
-    ang = np.arange(1, n + 1)[:, None] * freq[None, :]             # pos * freq, pos 1-based
-    fcr, fci = np.cos(ang), np.sin(ang)
+    p, n, out = RefPass(fw, eps=eps), len(tokens), {}
 
-    def rope(a, npairs):
-        a0, a1 = a[:, 0:2 * npairs:2].copy(), a[:, 1:2 * npairs:2].copy()
-        a[:, 0:2 * npairs:2] = a0 * fcr[:, :npairs] - a1 * fci[:, :npairs]
-        a[:, 1:2 * npairs:2] = a0 * fci[:, :npairs] + a1 * fcr[:, :npairs]
-    out = {"k": np.empty((L, n, KV)), "v": np.empty((L, n, KV))}
-    for l in range(L):
-        xb = _rmsnorm(X, fw.rms_att_weight[l], eps)
-        qkv = _mm(fw.wqkv[l], xb)
-        q, k, v = qkv[:, :E].copy(), qkv[:, E:E + KV].copy(), qkv[:, E + KV:].copy()
-        rope(q, E // 2)
-        rope(k, KV // 2)                                           # "while i < kv_dim": every pair of k
-        out["k"][l], out["v"][l] = k, v
-        att = np.zeros((n, E))
-        for p in range(n):
-            for h in range(nh):
-                g = h // kv_mul
-                sc = k[:p + 1, g * hs:(g + 1) * hs] @ q[p, h * hs:(h + 1) * hs] / np.sqrt(float(hs))
-                e = np.exp(sc - sc.max())
-                att[p, h * hs:(h + 1) * hs] = (e / e.sum()) @ v[:p + 1, g * hs:(g + 1) * hs]
-        X = X + _mm(fw.wo[l], att)
-        h13 = _mm(fw.w13[l], _rmsnorm(X, fw.rms_ffn_weight[l], eps))
-        gate = h13[:, :H]
-        hb = gate * (1.0 / (1.0 + np.exp(-gate))) * h13[:, H:]
-        X = X + _mm(fw.w2[l], hb)
-        out.update(q=q, xb=att, hb=hb, x=X.copy())
-    out["logits"] = _mm(fw.wcls, _rmsnorm(X, fw.rms_final_weight, eps))
+    def tap(l, name, a):
+        if l == fw.shape.n_layers - 1 and name in ("q", "xb", "hb", "x"):
+            out[name] = a.reshape(n, -1)
+    out["logits"] = p.feed(tokens, tap=tap)
+    out["k"], out["v"] = (np.stack([a.reshape(n, -1) for a in z]) for z in (p.k, p.v))
     return out
 
 
