@@ -5,9 +5,11 @@
 //   row words      {slot, pos} per row (pos 1-based): which of the batch's K/V caches the row lives in, and where
 //   bd_epi_qkv     pf_epi_qkv_pair's arithmetic with the position and the cache base taken from the row words
 //   bd_attn        decode attention over many caches: one workgroup per (kv head, row, part of the row's timesteps)
-//   bd_attn_merge  the parts of a row folded in part order
+//   bd_attn_fold   the parts of a row folded in part order
 //   bd_advance     llmk_batch_decode: the picked id becomes the row's next token, its position moves on -- on the device
-//   bd_attn_prefix / bd_attn_own / bd_attn_fold   a pass with rows ATTACHED to the batch's shared prefix (llmk_prefix_*, below)
+//   bd_attn_prefix / bd_attn_own   a pass with rows ATTACHED to the batch's shared prefix (llmk_prefix_*, below)
+// bd_attn_prefix / bd_attn_own are setup around attn_tiles.h's tile loop, wave merge and look-ahead loads (shared with pf_attn_kernel);
+// bd_attn keeps the same statements written out (the reason stands at the kernel).
 // The caches are [L][n_slots][seq_len][KV], f32 or -- a batch of llmk_cache_create(.., LLMK_TYPE_F16) -- IEEE half.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -96,67 +98,21 @@ __global__ void bd_to_half_kernel(const float* __restrict__ sk, const float* __r
     }
 }
 
-// ---- a tile's K / V fragments, requested one tile ahead                                                               ------------
-// Lane (li, g) of a wave holds, of the tile at cache row r0: K row r0 + li, elements g * DG .. + DG (kb points at the lane's first);
-// V rows r0 + 4g + v, v = 0..3, elements NT * li .. + NT (vb likewise).  Unconditional loads of a row index clamped to `last`.
-// The look-ahead registers' types are BdAhead<HS, T>::K / V.  f32 caches: float[DG] and float[4][NT], loaded by the statements the
-// kernels always had (they stand in the kernels, so that the f32 instantiations compile to the instructions they compiled to before
-// the caches had a type).  f16 caches: BdHalfAhead keeps the halves PACKED in the look-ahead registers (half the VGPRs) and converts at
-// use, exactly; its loads are as wide as the fragment: K 16 bytes (8 halves) a piece at head sizes 32 .. 128 and one 8-byte load at
-// 16, V 2 | 4 | 8 | 16 bytes.  kv_dim % 16 == 0 keeps every row 32-byte aligned in either type.
-template <int N>
-struct BdHalves { typedef _Float16 type __attribute__((ext_vector_type(N))); };
-template <>
-struct BdHalves<1> { typedef _Float16 type; };
-template <int HS>
-struct BdHalfAhead {
-    static constexpr int DG = HS / 4, NT = HS / 16, KW = DG < 8 ? DG : 8;      // KW: halves per K load
-    typedef typename BdHalves<KW>::type K[DG / KW];
-    typedef typename BdHalves<NT>::type V[4];
-    static __device__ __forceinline__ void load(K& kn, V& vn, const _Float16* kb, const _Float16* vb, int KV, int r0, int li, int g, int last) {
-        const _Float16* kp = kb + (size_t)min(r0 + li, last) * KV;
-#pragma unroll
-        for (int m = 0; m < DG / KW; ++m) kn[m] = *reinterpret_cast<const typename BdHalves<KW>::type*>(kp + m * KW);
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-            vn[v] = *reinterpret_cast<const typename BdHalves<NT>::type*>(vb + (size_t)min(r0 + 4 * g + v, last) * KV);
-    }
-    static __device__ __forceinline__ void take(const K& kn, const V& vn, float (&kf)[DG], float (&vf)[4][NT]) {
-#pragma unroll
-        for (int m = 0; m < DG; ++m) kf[m] = (float)kn[m / KW][m % KW];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            if constexpr (NT == 1) {
-                vf[v][0] = (float)vn[v];
-            } else {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) vf[v][t] = (float)vn[v][t];
-            }
-        }
-    }
-};
-
-template <int HS, class T>
-struct BdAhead;
-template <int HS>
-struct BdAhead<HS, float> {
-    typedef float K[HS / 4];
-    typedef float V[4][HS / 16];
-};
-template <int HS>
-struct BdAhead<HS, _Float16> {
-    typedef typename BdHalfAhead<HS>::K K;
-    typedef typename BdHalfAhead<HS>::V V;
-};
-
 // ---- decode attention over many caches                                                      llama2.f90:572-598 ------------
 // pf_attn_kernel's layout with the 16 MFMA query columns holding the kv_mul QUERY HEADS OF ONE KV GROUP (padded by repeating the
 // last) instead of 16 prompt positions: row b's K/V rows 0 .. pos_b-1 of slot_b cross L2 once for the whole group.  One workgroup
 // per (kv head, row, part); its 8 waves take the part's 16-row tiles round robin, each with a running softmax, and merge through LDS.
 // parts == 1: the normalised output goes to `out`.  Otherwise the part leaves its state -- the maximum M, the sum L and the
-// unnormalised output relative to M, per query head -- in po / pml, and bd_attn_merge_kernel folds a row's parts in part order.
+// unnormalised output relative to M, per query head -- in po / pml, and bd_attn_fold_kernel folds a row's parts in part order.
 // An empty part (a short row next to a long one) leaves M = -inf, L = 0.
-// T: the caches' element type, float or _Float16 (BdAhead: only the loads and the conversion differ).
+// T: the caches' element type, float or _Float16.
+// THE ONE KERNEL THAT DOES NOT CALL attn_tiles.h's attn_tiles / attn_merge_waves: the statements below are those functions', written
+// out (only the look-ahead types are shared).  On the shared text the f32 instantiation at head size 64 had the same registers and
+// one instruction fewer, but another order of the look-ahead loads among the MFMAs, and the unshared pass measured 0.9 % slower at
+// position 1,024 (profiles/attn_tiles_ab.txt); every smaller step towards the shared text -- the Q loader, the f32 load, the take,
+// the merge, each alone -- moved the schedule of some instantiation too.  As it stands all eight instantiations compile to the
+// instructions they had before attn_tiles.h.  A change to the attention arithmetic is made there AND here; tests/test_build_cpu.py
+// holds this to the one exception.
 template <int HS, class T = float>
 __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
                                                                   const T* __restrict__ vc, float* __restrict__ out,
@@ -192,9 +148,8 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* _
     const int ntile = (nrows + BD_TILE - 1) / BD_TILE;
     const int t0 = part * tpp, t1 = min(t0 + tpp, ntile);
     // K / V fragments of a tile are requested one tile ahead (unconditional loads of a clamped row index)
-    // (f32: float kn[DG], vn[4][NT] and the statements the kernel always had; f16: BdHalfAhead)
-    typename BdAhead<HS, T>::K kn;
-    typename BdAhead<HS, T>::V vn;
+    typename AttnAhead<HS, T>::K kn;
+    typename AttnAhead<HS, T>::V vn;
 #define BD_ATT_LOAD(R0_)                                                                                      \
     do {                                                                                                      \
         if constexpr (std::is_same_v<T, float>) {                                                             \
@@ -218,7 +173,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* _
                 }                                                                                             \
             }                                                                                                 \
         } else {                                                                                              \
-            BdHalfAhead<HS>::load(kn, vn, kb, vb, KV, (R0_), li, g, nrows - 1);                               \
+            AttnAhead<HS, _Float16>::load(kn, vn, kb, vb, KV, (R0_), li, g, nrows - 1);                               \
         }                                                                                                     \
     } while (0)
     BD_ATT_LOAD(min(t0 + wid, ntile - 1) * BD_TILE);
@@ -233,7 +188,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* _
 #pragma unroll
                 for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
         } else {
-            BdHalfAhead<HS>::take(kn, vn, kf, vf);
+            AttnAhead<HS, _Float16>::take(kn, vn, kf, vf);
         }
         BD_ATT_LOAD(min(kt + NW, ntile - 1) * BD_TILE);
         pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
@@ -305,32 +260,10 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_kernel(const float* _
     }
 }
 
-// the parts of (row, kv head) in part order: out = sum_p O_p e^(M_p - M) / sum_p L_p e^(M_p - M); part 0 is never empty
-template <int HS>
-__global__ __launch_bounds__(256) void bd_attn_merge_kernel(const float* __restrict__ po, const float2* __restrict__ pml,
-                                                            float* __restrict__ out, BdCaches bc, int kv_mul, int E, int parts) {
-    const int kvh = blockIdx.x, b = blockIdx.y, nkv = gridDim.x;
-    if (!bd_row_ok(bc, bc.rows[b])) return;
-    const size_t pbase = ((size_t)b * nkv + kvh) * parts;
-    for (int idx = threadIdx.x; idx < kv_mul * HS; idx += 256) {
-        const int q = idx / HS, d = idx % HS;
-        float M = -INFINITY;
-        for (int p = 0; p < parts; ++p) M = fmaxf(M, pml[(pbase + p) * BD_MAX_GROUP + q].x);
-        float L = 0.f, val = 0.f;
-        for (int p = 0; p < parts; ++p) {
-            const float2 ml = pml[(pbase + p) * BD_MAX_GROUP + q];
-            const float e = ml.x == -INFINITY ? 0.f : expf(ml.x - M);
-            L += ml.y * e;
-            val += po[((pbase + p) * BD_MAX_GROUP + q) * HS + d] * e;
-        }
-        out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
-    }
-}
-
 // ---- a shared prefix (llmk_prefix_*)                                                                                  ------------
 // A batch can hold ONE copy of the K/V rows of positions 1..P, [L][P][KV]; an ATTACHED slot's sequence is those rows and then its own
 // cache rows P .. pos-1 (still indexed by absolute position).  A pass with at least one attached row runs three kernels per layer
-// instead of bd_attn_kernel (+ merge); a pass with none runs exactly what it ran before.
+// instead of bd_attn_kernel (+ fold); a pass with none runs exactly what it ran before.
 //   bd_attn_prefix_kernel  the prefix rows against the query heads of up to RG attached rows at once: one read per column group
 //   bd_attn_own_kernel     bd_attn_kernel over a row's OWN rows first[slot] .. pos-1 (first = P attached, 0 not), never normalising
 //   bd_attn_fold_kernel    a (row, kv head)'s prefix parts in part order, then its own parts in part order
@@ -344,137 +277,6 @@ __host__ __device__ inline int bd_prefix_groups(int n_att, int kv_mul) { return 
 // longest row.  Tiles per part: bd_tiles_per_part(P, parts).
 __host__ __device__ inline int bd_prefix_parts(int n_att, int n_kv_heads, int kv_mul, int P, int n_cu) {
     return bd_parts(bd_prefix_groups(n_att, kv_mul), n_kv_heads, P, n_cu);
-}
-
-// bd_attn_kernel's tile loop for the kernels below: wave `wid` takes tiles t0 + wid, t0 + wid + 8, .. < t1 of the cache at kb / vb
-// (already at this lane's kv head and fragment); rows lo <= r < hi are visible, loads clamp the row index to hi - 1 (hi >= 1).
-template <int HS, class T>
-__device__ __forceinline__ void bd_attn_tiles(const float (&qf)[HS / 4], const T* __restrict__ kb, const T* __restrict__ vb, int KV,
-                                              int lo, int hi, int t0, int t1, int wid, int li, int g, float& m_run, float& l_run,
-                                              pf_v4f (&O)[HS / 16]) {
-    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
-    const float scale = sqrtf((float)HS);
-    const int ntile = (hi + BD_TILE - 1) / BD_TILE;
-    typename BdAhead<HS, T>::K kn;      // (as in bd_attn_kernel: the f32 statements are the ones this function always had)
-    typename BdAhead<HS, T>::V vn;
-    auto load = [&](int r0) {
-        if constexpr (std::is_same_v<T, float>) {
-            const float* kp = kb + (size_t)min(r0 + li, hi - 1) * KV;
-#pragma unroll
-            for (int m = 0; m < DG; m += 4) {
-                const float4 v = *reinterpret_cast<const float4*>(kp + m);
-                kn[m] = v.x; kn[m + 1] = v.y; kn[m + 2] = v.z; kn[m + 3] = v.w;
-            }
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const float* vp = vb + (size_t)min(r0 + 4 * g + v, hi - 1) * KV;
-                if constexpr (NT % 4 == 0) {
-#pragma unroll
-                    for (int t = 0; t < NT; t += 4) {
-                        const float4 x = *reinterpret_cast<const float4*>(vp + t);
-                        vn[v][t] = x.x; vn[v][t + 1] = x.y; vn[v][t + 2] = x.z; vn[v][t + 3] = x.w;
-                    }
-                } else if constexpr (NT == 2) {
-                    const float2 x = *reinterpret_cast<const float2*>(vp);
-                    vn[v][0] = x.x; vn[v][1] = x.y;
-                } else {
-                    vn[v][0] = vp[0];
-                }
-            }
-        } else {
-            BdHalfAhead<HS>::load(kn, vn, kb, vb, KV, r0, li, g, hi - 1);
-        }
-    };
-    load(min(t0 + wid, ntile - 1) * BD_TILE);
-    for (int kt = t0 + wid; kt < t1; kt += NW) {
-        const int r0 = kt * BD_TILE;
-        float kf[DG], vf[4][NT];
-        if constexpr (std::is_same_v<T, float>) {
-#pragma unroll
-            for (int m = 0; m < DG; ++m) kf[m] = kn[m];
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
-        } else {
-            BdHalfAhead<HS>::take(kn, vn, kf, vf);
-        }
-        load(min(kt + NW, ntile - 1) * BD_TILE);
-        pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < DG; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[m], qf[m], acc, 0, 0, 0);
-        float sc[4], mx = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int r = r0 + 4 * g + v;
-            sc[v] = (r >= lo && r < hi) ? acc[v] / scale : -INFINITY;
-            mx = fmaxf(mx, sc[v]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const bool any = m_new != -INFINITY;
-        const float alpha = !any ? 1.f : (m_run == -INFINITY ? 0.f : expf(m_run - m_new));
-        float p[4], rs = 0.f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            p[v] = (any && sc[v] != -INFINITY) ? expf(sc[v] - m_new) : 0.f;
-            rs += p[v];
-        }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float ar = __shfl(alpha, 4 * g + r, 64);                     // O rows are columns 4g+r
-#pragma unroll
-            for (int t = 0; t < NT; ++t) O[t][r] *= ar;
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) O[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(p[v], vf[v][t], O[t], 0, 0, 0);
-    }
-}
-
-// The waves' running states through LDS into ONE part state per live column: column c's goes to state index state_of(c)
-// (bd_attn_kernel's merge, never normalised).  A part without a visible row leaves M = -inf, L = 0, O = 0.
-template <int HS, class StateOf>
-__device__ __forceinline__ void bd_attn_leave(float m_run, float l_run, const pf_v4f (&O)[HS / 16], int live, float* __restrict__ po,
-                                              float2* __restrict__ pml, StateOf state_of) {
-    constexpr int NT = HS / 16, NW = BD_WAVES;
-    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
-    float* so = reinterpret_cast<float*>(pf_smem);   // [NW][16][HS]
-    float* sm = so + NW * 16 * HS;                    // [NW][16]
-    float* sl = sm + NW * 16;                         // [NW][16]
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
-    if (g == 0) {
-        sm[wid * 16 + li] = m_run;
-        sl[wid * 16 + li] = l_run;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) so[(size_t)(wid * 16 + 4 * g + r) * HS + NT * li + t] = O[t][r];
-    __syncthreads();
-    for (int idx = tid; idx < live * HS; idx += NW * WAVE) {
-        const int c = idx / HS, d = idx % HS;
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[w * 16 + c]);
-        float L = 0.f, val = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float mw = sm[w * 16 + c];
-            const float e = mw == -INFINITY ? 0.f : expf(mw - M);
-            L += sl[w * 16 + c] * e;
-            val += so[(size_t)(w * 16 + c) * HS + d] * e;
-        }
-        const size_t s = state_of(c);
-        po[s * HS + d] = val;
-        if (d == 0) pml[s] = make_float2(M, L);
-    }
 }
 
 // One workgroup per (kv head, column group, prefix part).  colmap [groups][RG]: the pass's attached rows, in row order, -1 behind the
@@ -494,27 +296,22 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const f
     if (nr == 0 || P < 1) return;                     // whole workgroup: no barrier is pending
     const int live = nr * kv_mul, c = min(li, live - 1);
     float qf[DG];
-    {
-        const float* qp = Q + (size_t)cm[c / kv_mul] * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG;
-#pragma unroll
-        for (int m = 0; m < DG; m += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(qp + m);
-            qf[m] = v.x; qf[m + 1] = v.y; qf[m + 2] = v.z; qf[m + 3] = v.w;
-        }
-    }
-    float m_run = -INFINITY, l_run = 0.f;
+    attn_load_q<HS>(qf, Q + (size_t)cm[c / kv_mul] * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG);
+    float m_run, l_run;
     pf_v4f O[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
     const int ntile = (P + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
-    bd_attn_tiles<HS, T>(qf, pk + (size_t)kvh * HS + g * DG, pv + (size_t)kvh * HS + NT * li, KV, 0, P, t0, t1, wid, li, g, m_run, l_run, O);
-    bd_attn_leave<HS>(m_run, l_run, O, live, po, pml, [&](int col) {
-        return (((size_t)cm[col / kv_mul] * nkv + kvh) * np + part) * kv_mul + col % kv_mul;
+    attn_tiles<HS, T, BD_WAVES>(qf, pk + (size_t)kvh * HS + g * DG, pv + (size_t)kvh * HS + NT * li, KV, P - 1, ntile, t0, t1, wid, li, g,
+                                [&](int r) { return r < P; }, m_run, l_run, O);
+    attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
+        const size_t s = (((size_t)cm[col / kv_mul] * nkv + kvh) * np + part) * kv_mul + col % kv_mul;
+        po[s * HS + d] = val;
+        if (d == 0) pml[s] = make_float2(M, L);
     });
 }
 
 // bd_attn_kernel for a pass with attached rows: the row's own cache rows first[slot] .. pos-1, tiles counted from the one that holds
-// row `first` (that tile masks the rows below it); part `part` leaves state p0 + part.  One workgroup per (kv head, row, own part).
+// row `first` (that tile masks the rows below it); part `part` leaves state p0 + part, never normalised.  One workgroup per (kv head,
+// row, own part).
 template <int HS, class T = float>
 __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
                                                                       const T* __restrict__ vc, float* __restrict__ po,
@@ -528,46 +325,47 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const floa
     const int lo = first[row.slot], nrows = row.pos;  // (the host refuses an attached row at pos <= P)
     const int h = kvh * kv_mul + min(li, kv_mul - 1);
     float qf[DG];
-    {
-        const float* qp = Q + (size_t)b * E + (size_t)h * HS + g * DG;
-#pragma unroll
-        for (int m = 0; m < DG; m += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(qp + m);
-            qf[m] = v.x; qf[m + 1] = v.y; qf[m + 2] = v.z; qf[m + 3] = v.w;
-        }
-    }
-    float m_run = -INFINITY, l_run = 0.f;
+    attn_load_q<HS>(qf, Q + (size_t)b * E + (size_t)h * HS + g * DG);
+    float m_run, l_run;
     pf_v4f O[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
     const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
     const size_t base = (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS;
-    bd_attn_tiles<HS, T>(qf, kc + base + g * DG, vc + base + NT * li, KV, lo, nrows, t0, t1, wid, li, g, m_run, l_run, O);
-    bd_attn_leave<HS>(m_run, l_run, O, kv_mul, po, pml, [&](int q) { return (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q; });
+    attn_tiles<HS, T, BD_WAVES>(qf, kc + base + g * DG, vc + base + NT * li, KV, nrows - 1, ntile, t0, t1, wid, li, g,
+                                [&](int r) { return lo <= r && r < nrows; }, m_run, l_run, O);
+    attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, kv_mul, [&](int q, int d, float M, float L, float val) {
+        const size_t s = (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q;
+        po[s * HS + d] = val;
+        if (d == 0) pml[s] = make_float2(M, L);
+    });
 }
 
-// (row, kv head): the prefix parts 0 .. p0-1 in part order -- an unattached row of a mixed pass has none: nothing wrote them, they are
-// skipped, which is what folding M = -inf, L = 0 does -- then the own parts p0 .. np-1 in part order.  The row's last own row is
-// always visible, so L > 0.
+// The part states of (row, kv head) folded in part order: out = sum_p O_p e^(M_p - M) / sum_p L_p e^(M_p - M).  State s of np, head q,
+// is pml[((b * nkv + kvh) * np + s) * stride + q], po that * HS.
+//   a pass without attached rows (launched only when it has more than one part): stride BD_MAX_GROUP, p0 = 0, first = null: parts
+//       0 .. np-1; part 0 is never empty;
+//   a pass with attached rows: stride kv_mul; the prefix parts 0 .. p0-1 -- an unattached row (first[slot] == 0) has none: nothing
+//       wrote them, they are skipped, which is what folding M = -inf, L = 0 does -- then the own parts p0 .. np-1.  The row's last
+//       own row is always visible.
+// Either way L > 0.
 template <int HS>
 __global__ __launch_bounds__(256) void bd_attn_fold_kernel(const float* __restrict__ po, const float2* __restrict__ pml,
                                                            float* __restrict__ out, BdCaches bc, const int* __restrict__ first,
-                                                           int kv_mul, int E, int np, int p0) {
+                                                           int kv_mul, int E, int stride, int np, int p0) {
     const int kvh = blockIdx.x, b = blockIdx.y, nkv = gridDim.x;
     const BdRow row = bc.rows[b];
     if (!bd_row_ok(bc, row)) return;
     const size_t sbase = ((size_t)b * nkv + kvh) * np;
-    const int pa = first[row.slot] > 0 ? 0 : p0;
+    const int pa = first && first[row.slot] > 0 ? 0 : p0;
     for (int idx = threadIdx.x; idx < kv_mul * HS; idx += 256) {
         const int q = idx / HS, d = idx % HS;
         float M = -INFINITY;
-        for (int p = pa; p < np; ++p) M = fmaxf(M, pml[(sbase + p) * kv_mul + q].x);
+        for (int p = pa; p < np; ++p) M = fmaxf(M, pml[(sbase + p) * stride + q].x);
         float L = 0.f, val = 0.f;
         for (int p = pa; p < np; ++p) {
-            const float2 ml = pml[(sbase + p) * kv_mul + q];
+            const float2 ml = pml[(sbase + p) * stride + q];
             const float e = ml.x == -INFINITY ? 0.f : expf(ml.x - M);
             L += ml.y * e;
-            val += po[((sbase + p) * kv_mul + q) * HS + d] * e;
+            val += po[((sbase + p) * stride + q) * HS + d] * e;
         }
         out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
     }

@@ -1123,7 +1123,6 @@ constexpr size_t pf_gemm_h_smem() {
     const size_t need = (size_t)4 * NG * 16 * PF_HP * sizeof(_Float16) + (size_t)NG * 16 * (64 * NR + PF_TPAD) * sizeof(float);
     return need > (size_t)84 * 1024 ? need : (size_t)84 * 1024;
 }
-constexpr size_t pf_attn_smem(int hs) { return ((size_t)PF_ATT_WAVES * 16 * hs + 2 * PF_ATT_WAVES * 16) * sizeof(float); }
 // The limits are raised ONCE, in pf_setup (as g_prepare does for the decode kernels): a launch is a launch, with no
 // runtime call in the 5 us gaps between the prefill's dependent kernels, and an LDS failure surfaces at setup.
 template <int NG, int WT>
@@ -1167,7 +1166,7 @@ hipError_t pf_prepare(const llmk_ctx* c) {
     if (ct != c->cfg.weight_type) HIPRET(pf_prepare_type(ct));
     return with_head_size(c->hs, [](auto hs) {
         constexpr int HS = decltype(hs)::value;
-        return hipFuncSetAttribute((const void*)pf_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pf_attn_smem(HS));
+        return hipFuncSetAttribute((const void*)pf_attn_kernel<HS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(PF_ATT_WAVES, HS));
     });
 }
 template <int NG, int NR>
@@ -1398,7 +1397,7 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
         // causal attention: position pos0+t sees cache rows 0 .. pos0+t-1
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
-            hipLaunchKernelGGL((pf_attn_kernel<HS>), dim3(c->nh, (T + 15) / 16), dim3(PF_ATT_WAVES * WAVE), pf_attn_smem(HS), w.stream,
+            hipLaunchKernelGGL((pf_attn_kernel<HS>), dim3(c->nh, (T + 15) / 16), dim3(PF_ATT_WAVES * WAVE), attn_smem(PF_ATT_WAVES, HS), w.stream,
                                w.Q, kc, vc, w.XB, KV, c->kv_mul, pos0, T, E);
             return hipGetLastError();
         });
@@ -1455,7 +1454,6 @@ int pf_run(llmk_ctx* c, const int* tokens, int n, int pos0, const ScoreJob* sj) 
 }
 // ---- batched decode (batch.h) -----------------------------------------------------------------------------------
 static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
-constexpr size_t bd_attn_smem(int hs) { return ((size_t)BD_WAVES * 16 * hs + 2 * BD_WAVES * 16) * sizeof(float); }
 
 // A batch's caches and prefix rows by element type (llmk_cache_create: float or _Float16, one type per batch), and f(T()) for the
 // type a batch has.  What differs between the types on the host: the buffers, the kernels' instantiation, and a converting kernel in
@@ -1534,20 +1532,21 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
             if (shared) {
                 const int np = pparts + parts;
                 const size_t px = (size_t)l * b->P * KV;
-                hipLaunchKernelGGL((bd_attn_prefix_kernel<HS, TC>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                hipLaunchKernelGGL((bd_attn_prefix_kernel<HS, TC>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
                                    w.Q, BdKv<TC>::pk(*b->px) + px, BdKv<TC>::pv(*b->px) + px, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
                 HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((bd_attn_own_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+                hipLaunchKernelGGL((bd_attn_own_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
                                    w.Q, kc, vc, b->px->d_xpo, b->px->d_xpml, bc, b->px->d_first, KV, c->kv_mul, E, tpp, np, pparts);
                 HIPRET(hipGetLastError());
                 hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->px->d_xpo, b->px->d_xpml, w.XB, bc, b->px->d_first,
-                                   c->kv_mul, E, np, pparts);
+                                   c->kv_mul, E, c->kv_mul, np, pparts);
                 return hipGetLastError();
             }
-            hipLaunchKernelGGL((bd_attn_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), bd_attn_smem(HS), w.stream,
+            hipLaunchKernelGGL((bd_attn_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
                                w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
             HIPRET(hipGetLastError());
-            if (parts > 1) hipLaunchKernelGGL((bd_attn_merge_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, c->kv_mul, E, parts);
+            if (parts > 1) hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, (const int*)nullptr,
+                                           c->kv_mul, E, BD_MAX_GROUP, parts, 0);
             return hipGetLastError();
         });
     }));
@@ -2847,7 +2846,7 @@ static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_ba
     HIPCHK(with_head_size(c->hs, [&](auto hs) {
         constexpr int HS = decltype(hs)::value;
         return with_kv_type(b.get(), [](auto t) {
-            return hipFuncSetAttribute((const void*)bd_attn_kernel<HS, decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+            return hipFuncSetAttribute((const void*)bd_attn_kernel<HS, decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
         });
     }));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2977,8 +2976,8 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
             constexpr int HS = decltype(hs)::value;
             return with_kv_type(b, [](auto t) -> hipError_t {
                 using TC = decltype(t);
-                HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS)));
-                return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bd_attn_smem(HS));
+                HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS)));
+                return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
             });
         }));
         b->px = std::move(px);

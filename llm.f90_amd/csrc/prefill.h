@@ -33,6 +33,12 @@ constexpr int PF_WAVES = 4;
 
 typedef float pf_v4f __attribute__((ext_vector_type(4)));
 
+}  // namespace llmk
+
+#include "attn_tiles.h"      // (behind pf_v4f: the attention of pf_attn_kernel below and of batch.h)
+
+namespace llmk {
+
 // Work of one GEMM = strips (64 weight rows) x nk (64-column steps) UNITS, strip-major.  Block b owns the U consecutive
 // units [b*U, (b+1)*U): every block multiplies the same number of 64x64 weight tiles whatever rows/K are, and the grid is
 // the number of workgroups the chip holds at once (1 or 2 per CU, pinned by the LDS request) -- with a strips x slices
@@ -751,16 +757,7 @@ __global__ __launch_bounds__(256) void pf_norm_kernel(const float* __restrict__ 
 // with its own running softmax (max m, sum l, unnormalised output O), and the workgroup merges the eight partial results
 // at the end:  out = sum_w O_w e^(m_w - M) / sum_w l_w e^(m_w - M).  The token-by-token kernel (kernels.h attn_kernel) is
 // launched per (head, position) and re-reads the cache for every position: 16x the L2 traffic of this one.
-//
-// Per tile and wave, with v_mfma_f32_16x16x4_f32 (D[i][j] += sum_k A[i][k] B[k][j]; lane l gives A[l%16][l/16] and
-// B[l/16][l%16], and receives D[4*(l/16)+v][l%16] in register v):
-//   S^T = K Q^T : A = K tile (i = cache row), B = Q (j = query), HS/4 steps; lane (q = l%16, g = l/16) holds head
-//         dimensions 16g' .. of both (the contraction index can be any permutation as long as A and B agree), and ends up
-//         with S[q][row 4g+v], v = 0..3 -- a query's 16 scores sit in 4 lanes x 4 registers: max and sum need two
-//         cross-lane steps (xor 16, 32);
-//   O += P V   : A = P (i = query): lane (q, g) feeds P[q][row 4g+v] in step v -- exactly the registers it holds, no
-//         transpose; B = V: lane (c = l%16, g) feeds V[row 4g+v][NT*c + t] for output tile t (NT = HS/16 adjacent floats:
-//         one vector load per row), and receives O[query 4g+r][NT*c + t] in register r.
+// The tile loop and the merge are attn_tiles.h's (the MFMA layout is described there); the 16 columns are prompt positions.
 constexpr int PF_ATT_WAVES = 8;
 
 template <int HS>
@@ -768,129 +765,21 @@ __global__ __launch_bounds__(PF_ATT_WAVES * WAVE) void pf_attn_kernel(const floa
                                                                       const float* __restrict__ vc, float* __restrict__ out,
                                                                       int KV, int kv_mul, int pos0, int T, int E) {
     constexpr int DG = HS / 4, NT = HS / 16, NW = PF_ATT_WAVES;
-    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
-    float* so = reinterpret_cast<float*>(pf_smem);   // [NW][16][HS]
-    float* sm = so + NW * 16 * HS;                    // [NW][16]
-    float* sl = sm + NW * 16;                         // [NW][16]
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
     const int h = blockIdx.x, kvh = h / kv_mul, q0 = blockIdx.y * 16;
     const int tq = q0 + li;                           // this lane's query (token index of the batch); row r is visible iff r < pos0 + tq
     const int nrows = pos0 + min(q0 + 15, T - 1);     // rows the tile's last query sees: 0 .. nrows-1
-    const float scale = sqrtf((float)HS);
     float qf[DG];
-    {
-        const float* qp = Q + (size_t)min(tq, T - 1) * E + (size_t)h * HS + g * DG;
-#pragma unroll
-        for (int m = 0; m < DG; m += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(qp + m);
-            qf[m] = v.x; qf[m + 1] = v.y; qf[m + 2] = v.z; qf[m + 3] = v.w;
-        }
-    }
-    float m_run = -INFINITY, l_run = 0.f;
+    attn_load_q<HS>(qf, Q + (size_t)min(tq, T - 1) * E + (size_t)h * HS + g * DG);
+    float m_run, l_run;
     pf_v4f O[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
-    const float* kb = kc + (size_t)kvh * HS + g * DG;
-    const float* vb = vc + (size_t)kvh * HS + NT * li;
     const int ntile = (nrows + 15) >> 4;
-    // K / V fragments of a tile are requested one tile ahead (unconditional loads of a clamped tile index): a tile's two
-    // dozen MFMAs and its softmax take far less than an L2 round trip
-    float kn[DG], vn[4][NT];
-#define PF_ATT_LOAD(R0_)                                                                                  \
-    do {                                                                                                  \
-        const float* kp_ = kb + (size_t)min((R0_) + li, nrows - 1) * KV;                                  \
-        _Pragma("unroll") for (int m = 0; m < DG; m += 4) {                                               \
-            const float4 v_ = *reinterpret_cast<const float4*>(kp_ + m);                                  \
-            kn[m] = v_.x; kn[m + 1] = v_.y; kn[m + 2] = v_.z; kn[m + 3] = v_.w;                           \
-        }                                                                                                 \
-        _Pragma("unroll") for (int v = 0; v < 4; ++v) {                                                   \
-            const float* vp_ = vb + (size_t)min((R0_) + 4 * g + v, nrows - 1) * KV;                       \
-            if constexpr (NT % 4 == 0) {                                                                  \
-                _Pragma("unroll") for (int t = 0; t < NT; t += 4) {                                       \
-                    const float4 x_ = *reinterpret_cast<const float4*>(vp_ + t);                          \
-                    vn[v][t] = x_.x; vn[v][t + 1] = x_.y; vn[v][t + 2] = x_.z; vn[v][t + 3] = x_.w;       \
-                }                                                                                         \
-            } else if constexpr (NT == 2) {                                                               \
-                const float2 x_ = *reinterpret_cast<const float2*>(vp_);                                  \
-                vn[v][0] = x_.x; vn[v][1] = x_.y;                                                         \
-            } else {                                                                                      \
-                vn[v][0] = vp_[0];                                                                        \
-            }                                                                                             \
-        }                                                                                                 \
-    } while (0)
-    PF_ATT_LOAD(min(wid, ntile - 1) << 4);
-    for (int kt = wid; kt < ntile; kt += NW) {
-        const int r0 = kt << 4;
-        float kf[DG], vf[4][NT];
-#pragma unroll
-        for (int m = 0; m < DG; ++m) kf[m] = kn[m];
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) vf[v][t] = vn[v][t];
-        PF_ATT_LOAD(min(kt + NW, ntile - 1) << 4);
-        pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < DG; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[m], qf[m], acc, 0, 0, 0);
-        float sc[4], mx = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const bool vis = r0 + 4 * g + v < pos0 + tq && tq < T;
-            sc[v] = vis ? acc[v] / scale : -INFINITY;
-            mx = fmaxf(mx, sc[v]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const bool any = m_new != -INFINITY;                                   // false: nothing of this query seen so far
-        const float alpha = !any ? 1.f : (m_run == -INFINITY ? 0.f : expf(m_run - m_new));
-        float p[4], rs = 0.f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            p[v] = (any && sc[v] != -INFINITY) ? expf(sc[v] - m_new) : 0.f;
-            rs += p[v];
-        }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float ar = __shfl(alpha, 4 * g + r, 64);                     // O rows are queries 4g+r
-#pragma unroll
-            for (int t = 0; t < NT; ++t) O[t][r] *= ar;
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) O[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(p[v], vf[v][t], O[t], 0, 0, 0);
-    }
-#undef PF_ATT_LOAD
-    if (g == 0) {
-        sm[wid * 16 + li] = m_run;
-        sl[wid * 16 + li] = l_run;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) so[(size_t)(wid * 16 + 4 * g + r) * HS + NT * li + t] = O[t][r];
-    __syncthreads();
-    for (int idx = tid; idx < 16 * HS; idx += NW * WAVE) {
-        const int q = idx / HS, d = idx % HS;
-        if (q0 + q >= T) continue;
-        float M = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) M = fmaxf(M, sm[w * 16 + q]);
-        float L = 0.f, val = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float mw = sm[w * 16 + q];
-            const float e = mw == -INFINITY ? 0.f : expf(mw - M);
-            L += sl[w * 16 + q] * e;
-            val += so[(size_t)(w * 16 + q) * HS + d] * e;
-        }
-        out[(size_t)(q0 + q) * E + (size_t)h * HS + d] = val / L;
-    }
+    attn_tiles<HS, float, NW>(qf, kc + (size_t)kvh * HS + g * DG, vc + (size_t)kvh * HS + NT * li, KV, nrows - 1, ntile, 0, ntile, wid, li, g,
+                              [&](int r) { return r < pos0 + tq && tq < T; }, m_run, l_run, O);
+    // (all 16 columns, a constant trip count; a ragged last tile's columns past T are dropped at the store)
+    attn_merge_waves<HS, NW>(m_run, l_run, O, 16, [&](int q, int d, float, float L, float val) {
+        if (q0 + q < T) out[(size_t)(q0 + q) * E + (size_t)h * HS + d] = val / L;
+    });
 }
 
 struct PfEpiArgs {

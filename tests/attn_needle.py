@@ -28,9 +28,9 @@ TK_NCU = 256        # csrc/token_kernel.h:155
 TK_WAVES = 8        # csrc/token_kernel.h:156
 TK_ATT_U = 8        # csrc/token_kernel.h:1108 (TkAtt::U)
 PF_TMAX = 128       # csrc/prefill.h:31   prompt positions per prefill / scoring batch
-PF_ATT_WAVES = 8    # csrc/prefill.h:697
-PF_ROWS = 16        # csrc/prefill.h:683-684: a workgroup owns 16 queries, a wave takes 16-row tiles of the cache round robin
-PF_STRIDE = PF_ROWS * PF_ATT_WAVES      # rows between two tiles of the same wave (prefill.h:755: kt += NW)
+PF_ATT_WAVES = 8    # csrc/prefill.h:761
+PF_ROWS = 16        # csrc/prefill.h:756-757: a workgroup owns 16 queries, a wave takes 16-row tiles of the cache round robin
+PF_STRIDE = PF_ROWS * PF_ATT_WAVES      # rows between two tiles of the same wave (attn_tiles.h:138: kt += NW)
 
 
 def attn_kernel_tiles(hs: int):

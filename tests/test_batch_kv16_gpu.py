@@ -1,6 +1,6 @@
 """A batch with f16 K/V caches (llmk_cache_*).  What is new on the device: the K/V write that rounds
 (bd_epi_qkv_h_kernel), the converting copy of fork and prefix (bd_to_half_kernel) and the half instantiations of the attention kernels
-(bd_attn_kernel / bd_attn_prefix_kernel / bd_attn_own_kernel over BdHalfAhead's packed loads).  Stored rows are compared BIT FOR BIT
+(bd_attn_kernel / bd_attn_prefix_kernel / bd_attn_own_kernel over AttnAhead's packed half loads).  Stored rows are compared BIT FOR BIT
 with clamp-then-round of what the f32 path stores; logits are compared at REL_TOL with kv16_ref.forward_fed, the float64 forward pass
 fed the rows the device stored (tests/test_batch_kv16_cpu.py shows why the oracle cannot judge such a batch, and that this can).
 

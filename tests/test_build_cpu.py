@@ -40,6 +40,63 @@ def test_persistent_kernels_do_not_spill():
             assert int(m.group(2)) <= 32, l
             k = re.search(r"scratch_ops_in_loops (-?\d+) of (\d+)", l)
             assert k and int(k.group(1)) == 0 and int(k.group(2)) <= 4, l
+    # the MFMA attention kernels (csrc/attn_tiles.h behind pf_attn_kernel and bd_attn_{,prefix_,own_}kernel): no scratch, and every
+    # instantiation inside the occupancy step it had with the tile loop written out per kernel.  Registers are allocated 8 at a time
+    # and waves per SIMD are min(8, 512 // allocation): head size 16 at 58 VGPRs at most -> 64, 32 at 76 -> 80, 64 at 118 -> 128,
+    # 128 at 194 -> 256
+    cap = {16: 64, 32: 80, 64: 128, 128: 256}
+    # (a line starts with the kernel's name and head size: "bd_attn_kernel<64, float>(", or still mangled where the demangler does
+    # not know _Float16: "_ZN4llmk14bd_attn_kernelILi64EDF16_EE")
+    head = re.compile(r"(?:_ZN4llmk\d+)?(?:pf_attn_kernel|bd_attn_(?:prefix_|own_)?kernel)(?:<|ILi)(\d+)")
+    attn = [l for l in r.stdout.splitlines() if head.match(l)]
+    assert len(attn) == 4 * (1 + 3 * 2), attn                    # 4 head sizes; the batch's three kernels for f32 and f16 caches
+    for l in attn:
+        m = re.search(r"VGPR\s+(\d+).*scratch\s+(\d+)", l)
+        assert m and int(m.group(2)) == 0 and int(m.group(1)) <= cap[int(head.match(l).group(1))], l
+    fold = [l for l in r.stdout.splitlines() if l.startswith("bd_attn_fold_kernel<")]
+    assert len(fold) == 4, fold
+    for l in fold:
+        m = re.search(r"scratch\s+(\d+)", l)
+        assert m and int(m.group(1)) == 0, l
+
+
+def _code_of(name):
+    """[(line number, the line without its // comment)] of a file of csrc/"""
+    with open(os.path.join(ROOT, "llm.f90_amd", "csrc", name)) as f:
+        return [(n, line.split("//", 1)[0]) for n, line in enumerate(f, 1)]
+
+
+def test_the_mfma_attention_is_written_once_and_in_one_named_exception():
+    """pf_attn_kernel (prefill.h), bd_attn_prefix_kernel and bd_attn_own_kernel (batch.h) are setup around ONE tile loop, ONE merge of
+    the waves and ONE look-ahead load per cache type, all in csrc/attn_tiles.h.  bd_attn_kernel alone keeps those statements written
+    out, because on the shared text its f32 instantiation measured slower (the reason stands at the kernel and in DESIGN.md 3i).
+    Outside comments: batch.h spells an MFMA builtin, defines a *_ATT_LOAD macro and spells the running softmax's rescale inside
+    bd_attn_kernel's body only -- one macro, one rescale -- prefill.h spells no MFMA builtin below its GEMM kernels and no such macro,
+    no other header has either, and llmk.hip reaches attn_tiles.h."""
+    csrc = os.path.join(ROOT, "llm.f90_amd", "csrc")
+    batch = _code_of("batch.h")
+    first = next(n for n, c in batch if "void bd_attn_kernel(" in c)
+    last = next(n for n, c in batch if n > first and c.startswith("}"))              # the kernel's closing brace
+    pf = _code_of("prefill.h")
+    below = next(n for n, c in pf if "PF_ATT_WAVES =" in c)
+    assert any("__builtin_amdgcn_mfma" in c for n, c in pf if n < below)              # (the GEMMs' own stay where they are)
+    hits = [f"prefill.h:{n}: {c.strip()}" for n, c in pf if n > below and "__builtin_amdgcn_mfma" in c]
+    macros, rescale = [], []
+    for name in sorted(f for f in os.listdir(csrc) if f.endswith(".h")):
+        for n, c in _code_of(name):
+            inside = name == "batch.h" and first < n < last
+            if name == "batch.h" and "__builtin_amdgcn_mfma" in c and not inside:
+                hits.append(f"{name}:{n}: {c.strip()}")
+            if re.search(r"#\s*define\s+\w*_ATT_LOAD\b", c):
+                (macros if inside else hits).append(f"{name}:{n}: {c.strip()}")
+            if "expf(m_run - m_new)" in c:
+                (rescale if inside or name == "attn_tiles.h" else hits).append(f"{name}:{n}")
+    assert not hits, "\n".join(hits)
+    assert len(macros) == 1, macros
+    assert sorted(r.split(":")[0] for r in rescale) == ["attn_tiles.h", "batch.h"], rescale
+    seen = set()
+    _quoted_includes(os.path.join(csrc, "llmk.hip"), seen)
+    assert os.path.normpath(os.path.join(csrc, "attn_tiles.h")) in seen
 
 
 def _quoted_includes(path, seen):
