@@ -531,6 +531,48 @@ int llmk_cache_type(llmk_batch *b);    /* LLMK_TYPE_F32 | LLMK_TYPE_F16, negativ
 int llmk_cache_bytes(llmk_batch *b, unsigned long long *out);   /* device bytes of the K/V caches + the prefix, if any */
 int llmk_cache_peek(llmk_batch *b, int which, int layer, int slot, int pos0, int n, float *out);
 
+/* Spans: SEVERAL consecutive positions of a slot in one pass -- a prompt chunk next to decoding rows, per-slot
+ * prompts, k drafted tokens checked in one pass over the weights.  ("span", not "batch": the llmk_batch_* list is closed;
+ * llmk_batch_forward keeps refusing two rows of one slot.)
+ *
+ * forward: one pass.  The rows of the pass are the spans' positions in span order, rows = sum of len; tokens[rows] are the 1-based ids
+ *          in that order.  Row j of a span feeds its token at position pos0+j of `slot`: that K/V row is written, and the row attends
+ *          over the slot's positions 1..pos0+j -- the prefix if the slot is attached, earlier cache rows, and the rows this same pass
+ *          wrote for columns <= j of the span; it sees none of the columns > j.
+ *          LLMK_E_ARG before anything runs or is allocated: a NULL batch, spans or tokens; n_spans < 1 or a len < 1; rows >
+ *          LLMK_MAX_BATCH; a slot out of range or named by two spans; pos0 < 1 or pos0+len-1 > the batch's seq_len; an attached slot
+ *          with pos0 <= P; a token outside [1, vocab_size]; flag bits other than LLMK_SPAN_LAST; both outputs NULL.  n_spans is bounded
+ *          by slot distinctness only, and rows may exceed n_slots.
+ *          logits_out [rows][vocab_size] and argmax_out [rows] (the 1-based first maximum, llmk_forward_greedy's rule) in row order;
+ *          with LLMK_SPAN_LAST they are [n_spans][vocab_size] and [n_spans]: ONE row per span, its last position, in span order (the
+ *          classifier still runs over all rows).  Either may be NULL.  A row with no finite logit: LLMK_E_NONFINITE.
+ *          A call whose spans all have len == 1 IS llmk_batch_forward: same code path, same launches, same bits.
+ * time:    measurement hook like llmk_batch_time: average milliseconds of one full pass (classifier and greedy pick included) of
+ *          n_spans spans of len rows each, slots 0..n_spans-1, all from pos0, with forward's range checks.  It OVERWRITES those rows.
+ * Parity: a row's logits are within the 1e-4 bar of llmk_forward's on that sequence alone, and of the same positions fed one per pass
+ * through llmk_batch_forward -- not bit-identical to either.  An f16 batch is defined as elsewhere: the f32 span pass over a cache that
+ * holds the rounded rows.  The same call on the same state returns the same bits (no float atomics, a fixed part order, no waiting
+ * across workgroups), and a row's bits do not depend on the tokens of LATER rows of its span.
+ * The f16-range rule of llmk_prefill applies: the call is redone on the f32 matrix instruction and its K/V rows are rewritten in the
+ * batch's type.
+ * REJECTED DRAFTS ARE FREE: cache rows beyond the position a caller accepts are dead.  No row of any later pass reads cache row r before
+ * a pass at position r+1 of that slot has rewritten it (a row at position p reads rows 0..p-1, and row p-1 is the one it writes), so a
+ * caller that accepts j of a span's rows simply continues the slot at position pos0+j; nothing is rolled back.
+ * Token records are NOT maintained: the caller records what it fed with llmk_rows_set_history, as after a fork.
+ * State the span passes need -- logits rows beyond n_slots, part states, the group table -- is allocated by the first span call that
+ * needs it: a batch that never calls these functions allocates and launches exactly what it did without them.
+ * In a span pass the slot's K/V rows are read once per GROUP of 16 / (query heads per kv head) consecutive rows of a span
+ * (bd_attn_span_kernel), not once per row.  LLMK_SPAN_ATTN=0 in the environment at llmk_batch_create / llmk_cache_create makes span
+ * passes run the per-row attention kernels of llmk_batch_forward instead (an A/B switch, like LLMK_PF_F32_MFMA for the prompt GEMMs);
+ * the results stay within the parity bar.
+ * Out of scope: draft models and acceptance policies (the host compares argmax_out itself), spans inside llmk_batch_decode /
+ * llmk_rows_decode, skipping classifier rows under LLMK_SPAN_LAST, more than LLMK_MAX_BATCH rows per pass. */
+typedef struct llmk_span { int32_t slot, pos0, len; } llmk_span;   /* positions pos0 .. pos0+len-1 (1-based) of `slot` */
+#define LLMK_SPAN_LAST 1   /* the outputs hold ONE row per span, its last position, in span order */
+int llmk_span_forward(llmk_batch *b, int n_spans, const llmk_span *spans, const int *tokens, int flags,
+                      float *logits_out, int *argmax_out);
+int llmk_span_time(llmk_batch *b, int n_spans, int len, int pos0, int iters, float *avg_ms);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

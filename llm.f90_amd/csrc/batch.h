@@ -8,7 +8,8 @@
 //   bd_attn_fold   the parts of a row folded in part order
 //   bd_advance     llmk_batch_decode: the picked id becomes the row's next token, its position moves on -- on the device
 //   bd_attn_prefix / bd_attn_own   a pass with rows ATTACHED to the batch's shared prefix (llmk_prefix_*, below)
-// bd_attn_prefix / bd_attn_own are setup around attn_tiles.h's tile loop, wave merge and look-ahead loads (shared with pf_attn_kernel);
+//   bd_attn_span   a pass with SEVERAL consecutive positions of a slot (llmk_span_*, below): (position, query head) pairs as columns
+// bd_attn_prefix / bd_attn_own / bd_attn_span are setup around attn_tiles.h's tile loop, wave merge and look-ahead loads (shared with pf_attn_kernel);
 // bd_attn keeps the same statements written out (the reason stands at the kernel).
 // The caches are [L][n_slots][seq_len][KV], f32 or -- a batch of llmk_cache_create(.., LLMK_TYPE_F16) -- IEEE half.
 #pragma once
@@ -339,13 +340,72 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const floa
     });
 }
 
+// ---- spans (llmk_span_*): several consecutive positions of a slot in one pass                                         ------------
+// The rows of a span pass are cut into COLUMN GROUPS of up to bd_prefix_rg(kv_mul) consecutive rows of one span (so of one slot, at
+// consecutive positions); the last group of a span may be shorter.  bd_attn_span_kernel is bd_attn_prefix_kernel's layout over the
+// slot's OWN cache: column c of a group is (row first + c / kv_mul, query head c % kv_mul of the kv head), columns from the last live
+// one on repeat it and are not written out, and the slot's K/V rows cross L2 once per group instead of once per row.  What is new is
+// the CAUSAL edge per column: the lane of column c sees cache row r iff lo <= r < pos(c's row), lo = first[slot] (P attached, 0 not).
+// bd_epi_qkv_kernel has written every row's K/V before this kernel runs, so the rows of the same pass at columns <= c are in the
+// cache and the predicate alone keeps the later ones out.
+struct BdGroup { int first, rows; };      // rows first .. first+rows-1 of the pass
+// groups a span of `len` rows is cut into
+__host__ __device__ inline int bd_span_groups(int len, int kv_mul) { return bd_prefix_groups(len, kv_mul); }
+// A group's tiles are [lo / BD_TILE, ceil(pos of its last row / BD_TILE)).  The split rule is ONE for the pass: bd_parts with the groups
+// in the place of the rows and the longest group's tile count (own_tiles) in the place of the longest row; part p of a group takes
+// tiles lo / BD_TILE + [p * tpp, (p + 1) * tpp), cut at the group's last tile -- possibly none.
+__host__ __device__ inline int bd_span_parts(int groups, int n_kv_heads, int own_tiles, int n_cu) {
+    return bd_parts(groups, n_kv_heads, own_tiles * BD_TILE, n_cu);
+}
+// One workgroup per (kv head, group, part).  direct (one part and no attached row in the pass): the normalised output goes to `out`.
+// Otherwise part `part` leaves state p0 + part of every (row, kv head) of the group in the layout of a pass with attached rows
+// (stride kv_mul, np states), and bd_attn_fold_kernel folds them.  A column all of whose rows lie before the part's tiles leaves
+// M = -inf, L = 0; the part that holds row lo is never empty for any column (pos > lo).
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_span_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                       const T* __restrict__ vc, float* __restrict__ out,
+                                                                       float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                       const BdGroup* __restrict__ groups, const int* __restrict__ first,
+                                                                       int n, int KV, int kv_mul, int E, int tpp, int np, int p0, int direct) {
+    constexpr int DG = HS / 4, NT = HS / 16;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x;
+    const BdGroup gr = groups[blockIdx.y];
+    if (gr.first < 0 || gr.rows < 1 || gr.rows > bd_prefix_rg(kv_mul) || gr.rows > n - gr.first) return;      // whole workgroup: no barrier is pending
+    const BdRow row0 = bc.rows[gr.first], rowl = bc.rows[gr.first + gr.rows - 1];
+    if (!bd_row_ok(bc, row0) || !bd_row_ok(bc, rowl) || rowl.slot != row0.slot || rowl.pos != row0.pos + gr.rows - 1) return;
+    const int lo = first ? first[row0.slot] : 0;      // (the host refuses an attached row at pos <= P)
+    const int live = gr.rows * kv_mul, c = min(li, live - 1);
+    const int vis = row0.pos + c / kv_mul;            // this lane's column sees cache rows lo .. vis-1
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)(gr.first + c / kv_mul) * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG);
+    float m_run, l_run;
+    pf_v4f O[NT];
+    const int ntile = (rowl.pos + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
+    const size_t base = (size_t)row0.slot * bc.slot_stride + (size_t)kvh * HS;
+    attn_tiles<HS, T, BD_WAVES>(qf, kc + base + g * DG, vc + base + NT * li, KV, rowl.pos - 1, ntile, t0, t1, wid, li, g,
+                                [&](int r) { return lo <= r && r < vis; }, m_run, l_run, O);
+    attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
+        const int b = gr.first + col / kv_mul, q = col % kv_mul;
+        if (direct) {
+            out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+        } else {
+            const size_t s = (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q;
+            po[s * HS + d] = val;
+            if (d == 0) pml[s] = make_float2(M, L);
+        }
+    });
+}
+
 // The part states of (row, kv head) folded in part order: out = sum_p O_p e^(M_p - M) / sum_p L_p e^(M_p - M).  State s of np, head q,
 // is pml[((b * nkv + kvh) * np + s) * stride + q], po that * HS.
 //   a pass without attached rows (launched only when it has more than one part): stride BD_MAX_GROUP, p0 = 0, first = null: parts
 //       0 .. np-1; part 0 is never empty;
 //   a pass with attached rows: stride kv_mul; the prefix parts 0 .. p0-1 -- an unattached row (first[slot] == 0) has none: nothing
 //       wrote them, they are skipped, which is what folding M = -inf, L = 0 does -- then the own parts p0 .. np-1.  The row's last
-//       own row is always visible.
+//       own row is always visible;
+//   a span pass (bd_attn_span_kernel; launched unless it ran one part with no attached row): stride kv_mul; p0 = 0 and first = null
+//       without attached rows, else as above.  The part that holds row first[slot] is never empty for any row.
 // Either way L > 0.
 template <int HS>
 __global__ __launch_bounds__(256) void bd_attn_fold_kernel(const float* __restrict__ po, const float2* __restrict__ pml,

@@ -279,6 +279,16 @@ struct llmk_batch {
     };
     std::unique_ptr<Prefix> px;
     int pass_att = 0;                            // attached rows among the rows bd_upload_rows uploaded last
+    // spans (llmk_span_*, batch.h), built by the first span call that runs bd_attn_span_kernel: a batch without one has none of it
+    struct Spans {
+        DevBuf<BdGroup> d_groups;                // [LLMK_MAX_BATCH] the pass's column groups ...
+        PinnedBuf<BdGroup> h_groups;             // ... and the pinned words they are copied from
+        DevBuf<float> d_spo;                     // part states of a span pass, in the layout of a pass with attached rows:
+        DevBuf<float2> d_spml;                   //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_spo that [hs]
+    };
+    std::unique_ptr<Spans> sn;
+    bool span_attn = true;                       // LLMK_SPAN_ATTN=0 at create: span passes run the per-row attention kernels
+    int pass_groups = 0;                         // column groups of the rows span_upload uploaded last; 0: not a span pass
 };
 
 namespace {
@@ -1514,6 +1524,17 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
         pparts = bd_prefix_parts(b->pass_att, c->nkv, c->kv_mul, b->P, c->n_cu);
         ptpp = bd_tiles_per_part(b->P, pparts);
     }
+    const int ngroups = b->pass_groups;
+    if (ngroups > 0) {
+        // a span pass (llmk_span_*): the split rule counts column groups, the longest group's tiles from the one that holds row `first`
+        int own = 0;
+        for (int k = 0; k < ngroups; ++k) {
+            const BdRow& r = b->h_rows[b->sn->h_groups[k].first + b->sn->h_groups[k].rows - 1];
+            own = std::max(own, (r.pos + step + BD_TILE - 1) / BD_TILE - (shared ? b->px->h_first[r.slot] : 0) / BD_TILE);
+        }
+        parts = bd_span_parts(ngroups, c->nkv, own, c->n_cu);
+        tpp = bd_tiles_per_part(own * BD_TILE, parts);
+    }
     PfEpiArgs e;
     // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
@@ -1529,6 +1550,23 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
         HIPRET(hipGetLastError());
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
+            if (ngroups > 0) {
+                // prefix (a pass with attached rows) + the groups' own rows + fold; one part and no attached row: straight to XB
+                const int np = pparts + parts, direct = !shared && parts == 1;
+                if (shared) {
+                    const size_t px = (size_t)l * b->P * KV;
+                    hipLaunchKernelGGL((bd_attn_prefix_kernel<HS, TC>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+                                       w.Q, BdKv<TC>::pk(*b->px) + px, BdKv<TC>::pv(*b->px) + px, b->sn->d_spo, b->sn->d_spml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
+                    HIPRET(hipGetLastError());
+                }
+                const int* first = shared ? b->px->d_first.get() : nullptr;
+                hipLaunchKernelGGL((bd_attn_span_kernel<HS, TC>), dim3(c->nkv, ngroups, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+                                   w.Q, kc, vc, w.XB, b->sn->d_spo, b->sn->d_spml, bc, b->sn->d_groups, first, T, KV, c->kv_mul, E, tpp, np, pparts, direct);
+                HIPRET(hipGetLastError());
+                if (!direct) hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->sn->d_spo, b->sn->d_spml, w.XB, bc, first,
+                                                c->kv_mul, E, c->kv_mul, np, pparts);
+                return hipGetLastError();
+            }
             if (shared) {
                 const int np = pparts + parts;
                 const size_t px = (size_t)l * b->P * KV;
@@ -1591,7 +1629,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 407; }
+int llmk_version(void) { return 408; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2760,6 +2798,7 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
     }
     hipStream_t st = b->ctx->stream;
     b->pass_att = 0;
+    b->pass_groups = 0;
     if (b->n_attached > 0) {
         // the column map: the attached rows in row order, -1 up to the end of the last column group
         for (int i = 0; i < n; ++i)
@@ -2814,6 +2853,7 @@ static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_ba
     // built aside: the caller gets the batch only after every step succeeded (a failure releases what was made)
     auto b = std::make_unique<llmk_batch>();
     b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len; b->kv_type = kv_type;
+    b->span_attn = !(getenv("LLMK_SPAN_ATTN") && getenv("LLMK_SPAN_ATTN")[0] == '0');
     ScPlan sp;
     if ((rc = bd_ready(b.get(), &sp, n_slots)) != LLMK_OK) return rc;
     const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV, nb = LLMK_MAX_BATCH;
@@ -3243,6 +3283,141 @@ int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     hipError_t pe = e1.create();
     if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
     for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, pos, false, sp);
+    if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
+    if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
+    float ms = 0.f;
+    if (pe == hipSuccess) pe = hipEventElapsedTime(&ms, e0, e1);
+    HIPCHK(hipMemsetAsync(c->pf->flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pe != hipSuccess) return LLMK_E_HIP + (int)pe;
+    *avg_ms = ms / (float)iters;
+    return LLMK_OK;
+}
+
+// ---- spans (batch.h): several consecutive positions of a slot in one pass ----
+// spans of a call: distinct slots, lengths and positions in range, at most LLMK_MAX_BATCH rows in all (*rows), ids in range
+// (tokens null: llmk_span_time, which feeds token 1)
+static bool span_ok(const llmk_batch* b, int n_spans, const llmk_span* spans, const int* tokens, bool fed, int* rows) {
+    if (!spans || (fed && !tokens) || n_spans < 1 || n_spans > LLMK_MAX_BATCH) return false;
+    bool seen[LLMK_MAX_BATCH] = {};
+    int n = 0;
+    for (int i = 0; i < n_spans; ++i) {
+        const llmk_span& s = spans[i];
+        if (s.slot < 0 || s.slot >= b->n_slots || seen[s.slot]) return false;
+        seen[s.slot] = true;
+        if (s.len < 1 || s.len > LLMK_MAX_BATCH - n) return false;
+        if (s.pos0 < 1 || s.pos0 > b->seq_len || s.len - 1 > b->seq_len - s.pos0) return false;
+        if (b->n_attached > 0 && s.pos0 <= b->px->h_first[s.slot]) return false;      // an attached slot's positions 1..P are the prefix
+        n += s.len;
+    }
+    for (int i = 0; fed && i < n; ++i)
+        if (tokens[i] < 1 || tokens[i] > b->ctx->V) return false;
+    *rows = n;
+    return true;
+}
+// what a span pass needs beyond a batch's own, by the first call that needs it: logits rows beyond n_slots; the group table and the
+// part states of bd_attn_span_kernel (not with LLMK_SPAN_ATTN=0: the per-row kernels have theirs)
+static int span_setup(llmk_batch* b, int rows) {
+    llmk_ctx* c = b->ctx;
+    if (rows > b->n_slots) {
+        const int rc = bd_alloc_rc(b->d_logits.reserve((size_t)LLMK_MAX_BATCH * c->V, c->stream));
+        if (rc) return rc;
+    }
+    if (!b->span_attn || b->sn) return LLMK_OK;
+    auto sn = std::make_unique<llmk_batch::Spans>();
+    const size_t nb = LLMK_MAX_BATCH, states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul;
+    HIPCHK(sn->d_groups.alloc(nb));
+    HIPCHK(sn->h_groups.alloc(nb));
+    int rc;
+    if ((rc = bd_alloc_rc(sn->d_spo.alloc(states * c->hs))) != LLMK_OK) return rc;
+    if ((rc = bd_alloc_rc(sn->d_spml.alloc(states))) != LLMK_OK) return rc;
+    HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
+        constexpr int HS = decltype(hs)::value;
+        return with_kv_type(b, [](auto t) -> hipError_t {
+            return hipFuncSetAttribute((const void*)bd_attn_span_kernel<HS, decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+        });
+    }));
+    b->sn = std::move(sn);
+    return LLMK_OK;
+}
+// the rows of the spans, in span order, as bd_upload_rows uploads them; then the group table (bd_attn_span_kernel), the way the column
+// map goes up.  tokens null: every row feeds token 1.
+static hipError_t span_upload(llmk_batch* b, int n_spans, const llmk_span* spans, const int* tokens) {
+    int slots[LLMK_MAX_BATCH], pos[LLMK_MAX_BATCH], ones[LLMK_MAX_BATCH], n = 0;
+    for (int i = 0; i < n_spans; ++i)
+        for (int j = 0; j < spans[i].len; ++j, ++n) { slots[n] = spans[i].slot; pos[n] = spans[i].pos0 + j; ones[n] = 1; }
+    HIPRET(bd_upload_rows(b, n, slots, tokens ? tokens : ones, pos));
+    if (!b->span_attn) return hipSuccess;
+    const int rg = bd_prefix_rg(b->ctx->kv_mul);
+    int row = 0, ng = 0;
+    for (int i = 0; i < n_spans; row += spans[i++].len)
+        for (int j = 0; j < spans[i].len; j += rg) b->sn->h_groups[ng++] = BdGroup{row + j, std::min(rg, spans[i].len - j)};
+    b->pass_groups = ng;
+    return hipMemcpyAsync(b->sn->d_groups, b->sn->h_groups, (size_t)ng * sizeof(BdGroup), hipMemcpyHostToDevice, b->ctx->stream);
+}
+
+int llmk_span_forward(llmk_batch* b, int n_spans, const llmk_span* spans, const int* tokens, int flags, float* logits_out, int* argmax_out) {
+    int n = 0;
+    if (!b || (!logits_out && !argmax_out) || (flags & ~LLMK_SPAN_LAST) || !span_ok(b, n_spans, spans, tokens, true, &n)) return LLMK_E_ARG;
+    if (n == n_spans) {
+        // one position per slot: this IS llmk_batch_forward
+        int slots[LLMK_MAX_BATCH], pos[LLMK_MAX_BATCH];
+        for (int i = 0; i < n; ++i) { slots[i] = spans[i].slot; pos[i] = spans[i].pos0; }
+        return llmk_batch_forward(b, n, slots, tokens, pos, logits_out, argmax_out);
+    }
+    llmk_ctx* c = b->ctx;
+    ScPlan sp;
+    int rc = bd_ready(b, &sp, n);
+    if (rc) return rc;
+    if ((rc = span_setup(b, n)) != LLMK_OK) return rc;
+    HIPCHK(span_upload(b, n_spans, spans, tokens));
+    int max_pos = 0;
+    for (int i = 0; i < n_spans; ++i) max_pos = std::max(max_pos, spans[i].pos0 + spans[i].len - 1);
+    HIPCHK(bd_pass(b, n, max_pos, logits_out != nullptr, sp));
+    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(pf_fetch_flag(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pf_flagged(c)) {
+        static bool told = false;
+        return pf_redo(c, "llmk_span_forward", &told, [&] { return llmk_span_forward(b, n_spans, spans, tokens, flags, logits_out, argmax_out); });
+    }
+    const int* ids = reinterpret_cast<const int*>(b->h_out + n);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 1 || ids[i] > c->V) return LLMK_E_NONFINITE;
+    if (!(flags & LLMK_SPAN_LAST)) {
+        if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
+        if (logits_out) HIPCHK(hipMemcpy(logits_out, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost));
+        return LLMK_OK;
+    }
+    for (int i = 0, last = -1; i < n_spans; ++i) {
+        last += spans[i].len;
+        if (argmax_out) argmax_out[i] = ids[last];
+        if (logits_out) HIPCHK(hipMemcpy(logits_out + (size_t)i * c->V, b->d_logits + (size_t)last * c->V, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return LLMK_OK;
+}
+
+int llmk_span_time(llmk_batch* b, int n_spans, int len, int pos0, int iters, float* avg_ms) {
+    if (!b || !avg_ms || iters < 1 || n_spans < 1 || n_spans > LLMK_MAX_BATCH) return LLMK_E_ARG;
+    llmk_span spans[LLMK_MAX_BATCH];
+    for (int i = 0; i < n_spans; ++i) spans[i] = llmk_span{i, pos0, len};
+    int n = 0;
+    if (!span_ok(b, n_spans, spans, nullptr, false, &n)) return LLMK_E_ARG;
+    if (len == 1) return llmk_batch_time(b, n_spans, pos0, iters, avg_ms);      // one position per slot: that pass
+    llmk_ctx* c = b->ctx;
+    ScPlan sp;
+    int rc = bd_ready(b, &sp, n);
+    if (rc) return rc;
+    if ((rc = span_setup(b, n)) != LLMK_OK) return rc;
+    HIPCHK(span_upload(b, n_spans, spans, nullptr));
+    const int max_pos = pos0 + len - 1;
+    HIPCHK(bd_pass(b, n, max_pos, false, sp));      // warm-up
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Event e0, e1;
+    HIPCHK(e0.create());
+    hipError_t pe = e1.create();
+    if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
+    for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, max_pos, false, sp);
     if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
     if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
     float ms = 0.f;

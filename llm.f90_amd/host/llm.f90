@@ -9,7 +9,7 @@
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
 !         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix] [--kv-f16]]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix] [--kv-f16] [--prompts FILE]]
 !
 ! --parallel N (1 .. 128, one GPU): N completions of the prompt decoded TOGETHER (llmk_batch_*, DESIGN.md section 3i) -- the prompt is
 ! prefilled once and forked into N slots, every pass over the weights serves all N; seeds seed, seed+1, ... at -t > 0 (the filter
@@ -18,6 +18,9 @@
 ! attention reads the prompt rows once per group of rows, not once per row.
 ! --kv-f16: the N slots' K/V caches -- and the shared prefix -- hold IEEE halves (llmk_cache_create): half the bytes per pass and per
 ! slot, the stored values rounded to nearest even and saturated at +-65504.  Refused without --parallel: the context's own cache is f32.
+! --prompts FILE: line j (0-based) of FILE is slot j's OWN prompt (fewer than N lines is an error).  The prompts are ingested through
+! the batch itself -- llmk_span_forward, the slots' chunks packed into passes of at most 128 rows -- and the N completions then run
+! together from their own positions.  Refused with -p and with --share-prefix (there is no common prompt).
 !
 ! --ngpu N (the 70B configuration, SURVEY.md section 8e): this process becomes rank 0 of N, starts N-1 copies of itself
 ! (one process per GPU, devices d..d+N-1), every rank loads the file and keeps its shard, the ranks meet through a
@@ -58,6 +61,7 @@ module arg_parse
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
      logical :: share_prefix      ! extension: --share-prefix: the --parallel slots share ONE copy of the prompt's K/V rows (llmk_prefix_*)
      logical :: kv_f16            ! extension: --kv-f16: the --parallel slots' K/V caches and the shared prefix are f16 (llmk_cache_create)
+     character(:), allocatable :: prompts_file   ! extension: --prompts FILE: one prompt per --parallel slot, a line each (llmk_span_*)
      integer :: parallel          ! extension: --parallel N (0 = off): N completions decoded together on one GPU (llmk_batch_*)
      integer :: logprobs          ! extension: --logprobs N (0 .. 20): the log-prob of every generated token and its N most likely
                                   ! alternatives, from the device (llmk_*_sample_lp); -1 = off
@@ -106,6 +110,7 @@ contains
     a%parallel = 0
     a%share_prefix = .false.
     a%kv_f16 = .false.
+    a%prompts_file = ""
 
     nargs = command_argument_count()
     i = 1
@@ -147,6 +152,7 @@ contains
        case ("--score");             a%score = .true.;         i = i + 1
        case ("--share-prefix");      a%share_prefix = .true.;  i = i + 1
        case ("--kv-f16");            a%kv_f16 = .true.;        i = i + 1
+       case ("--prompts");           a%prompts_file = trim(val); i = i + 2
        case ("--parallel")
           read (val, *) a%parallel
           if (a%parallel < 1 .or. a%parallel > 128) then
@@ -294,6 +300,14 @@ program llm
   type(llmk_sampler), allocatable, target :: par_samplers(:)
   type(c_ptr) :: par_sp
   integer :: par_steps
+  integer, allocatable :: par_k(:), par_fed(:)      ! --prompts: positions slot j's prompt fills (BOS + its first k-1 tokens); ingested so far
+  integer(c_int), allocatable :: par_first(:)       ! ... and the token each slot feeds at position k_j + 1
+  type(llmk_span), allocatable :: par_spans(:)
+  integer(c_int), allocatable :: par_feed(:)        ! the tokens of one ingest pass, [row]
+  integer(c_int), allocatable :: par_seq(:)         ! what the slots feed at their positions 1 .. k_j, slot after slot ...
+  integer, allocatable :: par_off(:)                ! ... slot j's at par_seq(par_off(j) + 1 : par_off(j) + par_k(j))
+  integer(c_int), allocatable, target :: par_am(:)  ! an ingest pass's first maxima, one per span (not used: the decode feeds the prompt's last token)
+  integer :: par_passes, n_sp, n_rows, take
 
   call parse_args(opts)
   ! --parallel N: what a batch does not do is said and stops here (include/llmk.h: penalties, logit bias and log-prob records are out
@@ -327,6 +341,20 @@ program llm
   if (opts%kv_f16 .and. opts%parallel == 0) then
      print *, "--kv-f16: only the K/V caches of --parallel N can be f16 (the context's own cache stays f32)"
      stop 1
+  end if
+  if (opts%prompts_file /= "") then
+     if (opts%parallel == 0) then
+        print *, "--prompts: one prompt per slot needs the slots: add --parallel N"
+        stop 1
+     end if
+     if (opts%prompt /= "") then
+        print *, "--prompts: every slot takes its own prompt from the file: drop -p"
+        stop 1
+     end if
+     if (opts%share_prefix) then
+        print *, "--prompts: own prompts leave no common prefix to share: drop --share-prefix"
+        stop 1
+     end if
   end if
   lead = opts%tp_rank == 0
   if (opts%ngpu > 1) call tp_launch_workers()
@@ -469,6 +497,7 @@ program llm
   ! maximum at -t 0.  Nothing is printed before the call returns; then the completions, one after another
   if (opts%parallel > 0) then
      k = size(prompt_tokens)
+     if (opts%prompts_file /= "") call read_prompts()      ! (k becomes the longest prompt's)
      if (k >= seq_len) then
         print *, "--parallel: the prompt (", k, "tokens ) leaves no position to generate within -n", seq_len
         stop 1
@@ -491,7 +520,10 @@ program llm
      end if
      t_start = clock_ticks()
      token = 2
-     if (k > 0) then
+     if (opts%prompts_file /= "") then
+        call ingest_prompts()
+        if (opts%verbose_ext) print '(A,I0,A)', " prompts ingested in ", par_passes, " span passes"
+     else if (k > 0) then
         allocate(batch(k))
         batch(1) = 2
         batch(2:) = int(prompt_tokens(1:k - 1), c_int)
@@ -515,7 +547,9 @@ program llm
      ! --share-prefix: one copy of the prompt's rows for all N slots (without a prompt there is nothing to share)
      if (opts%share_prefix .and. k > 0) call llmk_check(llmk_prefix_set(pbatch, int(k, c_int)), "llmk_prefix_set")
      do j = 1, opts%parallel
-        if (opts%share_prefix .and. k > 0) then
+        if (opts%prompts_file /= "") then
+           continue                                   ! (the slot holds its own prompt's rows: ingest_prompts)
+        else if (opts%share_prefix .and. k > 0) then
            call llmk_check(llmk_prefix_attach(pbatch, int(j - 1, c_int)), "llmk_prefix_attach")
         else
            call llmk_check(llmk_batch_fork(pbatch, int(j - 1, c_int), int(k, c_int)), "llmk_batch_fork")
@@ -523,6 +557,10 @@ program llm
         par_slots(j) = int(j - 1, c_int)
         par_tokens(j) = int(token, c_int)
         par_pos(j) = int(k + 1, c_int)
+        if (opts%prompts_file /= "") then
+           par_tokens(j) = par_first(j)
+           par_pos(j) = int(par_k(j) + 1, c_int)
+        end if
         par_samplers(j)%temperature = real(opts%temperature, c_float)
         par_samplers(j)%top_k = int(opts%top_k, c_int32_t)
         par_samplers(j)%top_p = real(opts%top_p, c_float)
@@ -776,6 +814,63 @@ program llm
   rc = llmk_destroy(ctx)
 
 contains
+
+  ! --prompts FILE: line j of the file is slot j's prompt.  Slot j's positions 1 .. k_j hold BOS and the first k_j - 1 tokens of its
+  ! prompt, and its last token (BOS for an empty line) is what the slot feeds at k_j + 1 -- `-p` for every slot.  k: the longest k_j.
+  subroutine read_prompts()
+    character(len=65536) :: line
+    integer, allocatable :: toks(:)
+    integer :: u, ios, jj
+    allocate(par_k(opts%parallel), par_fed(opts%parallel), par_first(opts%parallel), par_off(opts%parallel), par_seq(0))
+    open (newunit=u, file=opts%prompts_file, status="old", action="read", iostat=ios)
+    if (ios /= 0) then
+       print *, "--prompts: cannot open ", opts%prompts_file
+       stop 1
+    end if
+    do jj = 1, opts%parallel
+       read (u, '(A)', iostat=ios) line
+       if (ios /= 0) then
+          print '(A,A,A,I0,A,I0,A)', " --prompts: ", opts%prompts_file, " has ", jj - 1, " lines; --parallel ", opts%parallel, &
+               " needs one prompt per slot"
+          stop 1
+       end if
+       toks = bpe_encode(trim(line))
+       par_k(jj) = size(toks)
+       par_off(jj) = size(par_seq)
+       par_first(jj) = 2
+       if (par_k(jj) > 0) then
+          par_first(jj) = int(toks(par_k(jj)), c_int)
+          par_seq = [par_seq, 2_c_int, int(toks(1:par_k(jj) - 1), c_int)]
+       end if
+    end do
+    close (u)
+    k = maxval(par_k)
+  end subroutine read_prompts
+
+  ! the slots' prompts through the batch itself: every pass takes the next chunk of every slot that still has one, in slot order, up to
+  ! 128 rows in all (llmk_span_forward; LLMK_SPAN_LAST: one first maximum per span comes back)
+  subroutine ingest_prompts()
+    integer :: jj
+    allocate(par_spans(opts%parallel), par_feed(128), par_am(opts%parallel))
+    par_fed = 0
+    par_passes = 0
+    do while (any(par_fed < par_k))
+       n_sp = 0
+       n_rows = 0
+       do jj = 1, opts%parallel
+          take = min(par_k(jj) - par_fed(jj), 128 - n_rows)
+          if (take < 1) cycle
+          n_sp = n_sp + 1
+          par_spans(n_sp) = llmk_span(int(jj - 1, c_int32_t), int(par_fed(jj) + 1, c_int32_t), int(take, c_int32_t))
+          par_feed(n_rows + 1:n_rows + take) = par_seq(par_off(jj) + par_fed(jj) + 1:par_off(jj) + par_fed(jj) + take)
+          n_rows = n_rows + take
+          par_fed(jj) = par_fed(jj) + take
+       end do
+       call llmk_check(llmk_span_forward(pbatch, int(n_sp, c_int), par_spans, par_feed, LLMK_SPAN_LAST, c_null_ptr, c_loc(par_am)), &
+            "llmk_span_forward")
+       par_passes = par_passes + 1
+    end do
+  end subroutine ingest_prompts
 
   ! the request for the next n positions: the records go behind the `done` already there
   function lp_request(done, n) result(r)

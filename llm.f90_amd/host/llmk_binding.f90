@@ -17,6 +17,12 @@ module llmk_binding
   end type llmk_config
 
   ! the sampler of llmk_forward_sample_ex / llmk_decode_sample_ex: top_k = 0, top_p = 1, min_p = 0 are "off"
+  ! positions pos0 .. pos0+len-1 (1-based) of `slot`: a span of llmk_span_forward (include/llmk.h)
+  type, bind(C) :: llmk_span
+     integer(c_int32_t) :: slot, pos0, len
+  end type llmk_span
+  integer(c_int), parameter :: LLMK_SPAN_LAST = 1      ! the outputs hold ONE row per span, its last position
+
   type, bind(C) :: llmk_sampler
      real(c_float) :: temperature
      integer(c_int32_t) :: top_k
@@ -347,6 +353,23 @@ module llmk_binding
        type(c_ptr), value :: batch
        integer(c_int), value :: which, layer, slot, pos0, n
        real(c_float), intent(out) :: out(*)
+     end function
+     ! spans (include/llmk.h): several consecutive positions of a slot in one pass -- `--parallel N --prompts FILE`.  The outputs
+     ! travel as C addresses (c_loc of a `target` array, or c_null_ptr: not asked for)
+     integer(c_int) function llmk_span_forward(batch, n_spans, spans, tokens, flags, logits_out, argmax_out) &
+          bind(C, name="llmk_span_forward")
+       import :: c_int, c_ptr, llmk_span
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n_spans, flags
+       type(llmk_span), intent(in) :: spans(*)
+       integer(c_int), intent(in) :: tokens(*)
+       type(c_ptr), value :: logits_out, argmax_out
+     end function
+     integer(c_int) function llmk_span_time(batch, n_spans, len, pos0, iters, avg_ms) bind(C, name="llmk_span_time")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n_spans, len, pos0, iters
+       real(c_float), intent(out) :: avg_ms
      end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a

@@ -30,7 +30,7 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
            "llmk_batch_decode", "llmk_batch_time", "llmk_rows_set_history", "llmk_rows_get_history", "llmk_rows_decode",
            "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len",
-           "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_reset", "llmk_timings",
+           "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_span_forward", "llmk_span_time", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -38,6 +38,13 @@ PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-tok
 
 
 TOKEN_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_void_p)
+SPAN_LAST = 1          # LLMK_SPAN_LAST
+SPAN_CHUNK = 128       # rows of one pass (LLMK_MAX_BATCH): Batch.ingest's chunk
+
+
+class Span(C.Structure):
+    """llmk_span: positions pos0 .. pos0+len-1 (1-based) of `slot`"""
+    _fields_ = [("slot", C.c_int32), ("pos0", C.c_int32), ("len", C.c_int32)]
 
 
 class LlmkError(RuntimeError):
@@ -198,6 +205,9 @@ def lib():
             L.llmk_cache_type.argtypes = [vp]
             L.llmk_cache_bytes.argtypes = [vp, C.POINTER(C.c_ulonglong)]
             L.llmk_cache_peek.argtypes = [vp, ci, ci, ci, ci, ci, cf]
+        if hasattr(L, "llmk_span_forward"):
+            L.llmk_span_forward.argtypes = [vp, ci, C.POINTER(Span), C.POINTER(ci), ci, cf, C.POINTER(ci)]
+            L.llmk_span_time.argtypes = [vp, ci, ci, ci, ci, cf]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -678,6 +688,43 @@ class Batch:
                                      am.ctypes.data_as(C.POINTER(C.c_int)) if want_argmax else None))
         out = [x for x in (lg, am) if x is not None]
         return out[0] if len(out) == 1 else tuple(out)
+
+    def forward_spans(self, spans, tokens, last_only: bool = False, want_logits: bool = True, want_argmax: bool = True):
+        """one pass over several positions per slot (llmk_span_forward).  spans: [(slot, pos0, len)]; tokens: the rows' ids in span
+        order, sum of len of them.  (logits [rows][V], argmax [rows] 1-based), or the one that was asked for; last_only
+        (LLMK_SPAN_LAST): one row per span, its last position"""
+        spans = [tuple(int(x) for x in s) for s in spans]
+        if any(len(s) != 3 for s in spans):
+            raise ValueError("a span is (slot, pos0, len)")
+        tok = np.ascontiguousarray(tokens, np.int32)
+        if tok.ndim != 1 or len(tok) != sum(max(s[2], 0) for s in spans):
+            raise ValueError("one token per row: sum of the spans' len")
+        sp = (Span * max(1, len(spans)))(*[Span(*s) for s in spans])
+        n = len(spans) if last_only else len(tok)
+        lg = np.empty((n, self.V), np.float32) if want_logits else None
+        am = np.empty(n, np.int32) if want_argmax else None
+        _ck(lib().llmk_span_forward(self._h, len(spans), sp, tok.ctypes.data_as(C.POINTER(C.c_int)), SPAN_LAST if last_only else 0,
+                                    lg.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None,
+                                    am.ctypes.data_as(C.POINTER(C.c_int)) if want_argmax else None))
+        out = [x for x in (lg, am) if x is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def ingest(self, slot: int, tokens, pos0: int = 1) -> np.ndarray:
+        """a prompt into `slot` at positions pos0 .., in spans of at most 128 rows: the logits [V] of its last position"""
+        tok = np.ascontiguousarray(tokens, np.int32)
+        if tok.ndim != 1 or len(tok) < 1:
+            raise ValueError("at least one token")
+        for i in range(0, len(tok), SPAN_CHUNK):
+            chunk = tok[i:i + SPAN_CHUNK]
+            lg = self.forward_spans([(slot, pos0 + i, len(chunk))], chunk, last_only=True, want_argmax=False)
+        return lg[0]
+
+    def time_spans(self, n_spans: int, length: int, pos0: int, iters: int) -> float:
+        """average ms of one full pass of n_spans spans of `length` rows each, slots 0..n_spans-1, all from pos0 (llmk_span_time);
+        overwrites those rows"""
+        ms = C.c_float()
+        _ck(lib().llmk_span_time(self._h, n_spans, length, pos0, iters, C.byref(ms)))
+        return float(ms.value)
 
     def decode(self, slots, tokens, pos0, steps: int, samplers=None) -> np.ndarray:
         """`steps` passes, the picks fed back on the device (llmk_batch_decode): ids [n][steps].  samplers: None = greedy, else one

@@ -24,7 +24,14 @@ figures alone (--forked-only: the same from this build, no prefix ever set).
 
 times the pass at 8, 32 and 128 rows, at positions 25 and --pos, with f32 and with f16 K/V caches (llmk_cache_create): two batches in
 ONE process, the types alternating measurement by measurement; forked slots, and -- with --shared-prefix P, at --pos -- slots attached
-behind P positions.  --kv f32 | f16 measures one type alone."""
+behind P positions.  --kv f32 | f16 measures one type alone.
+
+    python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k --spans
+
+times span passes (llmk_span_*): (a) one span of 128 rows ending at --pos with bd_attn_span_kernel and with the per-row attention
+kernels (a second batch created under LLMK_SPAN_ATTN=0), on f32 and f16 caches, llmk_span_time, alternating; (b) a prompt of
+--pos - 24 tokens into one slot in spans of 128 against llmk_prefill + llmk_batch_fork, wall clock of the calls; (c) 112 decode rows
+at --pos with and without one 16-row chunk of another slot in the same pass, wall clock of the calls."""
 from __future__ import annotations
 
 import argparse
@@ -195,6 +202,92 @@ def kv_types(m, shape, kinds, P: int, pos: int, iters: int, repeats: int):
     return out
 
 
+def spans(m, shape, pos: int, iters: int, repeats: int):
+    """--spans: the three measurements of profiles/batch_spans.txt, every figure the median of `repeats` behind a warm-up"""
+    out = {"a": [], "b": {}, "c": {}}
+    pos0 = pos - 127
+    for kind in ("f32", "f16"):
+        os.environ["LLMK_SPAN_ATTN"] = "0"
+        try:
+            rows_b = llmk.Batch(m, 1, pos, kv_type=kind)
+        finally:
+            del os.environ["LLMK_SPAN_ATTN"]
+        span_b = llmk.Batch(m, 1, pos, kv_type=kind)
+        ms = {"span": [], "rows": []}
+        for _ in range(repeats):
+            for form, b in (("span", span_b), ("rows", rows_b)):
+                b.time_spans(1, 128, pos0, 3)
+                ms[form].append(b.time_spans(1, 128, pos0, iters))
+        row = {"kv": kind, "pos0": pos0, "len": 128}
+        for form, xs in ms.items():
+            row[form + "_ms"], row[form + "_spread"] = med_spread(xs)
+        out["a"].append(row)
+        rows_b.close()
+        span_b.close()
+    # (b) a prompt into one slot: spans against prefill + fork
+    n = pos - 24
+    prompt = [2] + [3 + i % (shape.vocab_size - 3) for i in range(n - 1)]
+    b = llmk.Batch(m, 1, pos)
+    ms = {"spans": [], "prefill_fork": []}
+    for r in range(repeats + 1):
+        t0 = time.perf_counter()
+        b.ingest(0, prompt)
+        t1 = time.perf_counter()
+        m.prefill(prompt, 1)
+        b.fork(0, n)
+        t2 = time.perf_counter()
+        if r:
+            ms["spans"].append((t1 - t0) * 1e3)
+            ms["prefill_fork"].append((t2 - t1) * 1e3)
+    out["b"] = {"tokens": n}
+    for form, xs in ms.items():
+        out["b"][form + "_ms"], out["b"][form + "_spread"] = med_spread(xs)
+    b.close()
+    # (c) 112 decode rows with and without a 16-row chunk of slot 112 in the same pass
+    slots, b = 113, None
+    for kind in ("f32", "f16"):
+        try:
+            b = llmk.Batch(m, slots, pos, kv_type=kind)
+            break
+        except llmk.LlmkError as e:
+            print(f"# (c): no room for {slots} slots of {kind} caches ({e})", file=sys.stderr)
+    if b is not None:
+        dec = [(j, pos, 1) for j in range(112)]
+        forms = {"decode": dec, "decode_chunk": dec + [(112, pos - 15, 16)]}
+        ms = {k: [] for k in forms}
+        for r in range(repeats + 1):
+            for form, sp in forms.items():
+                toks = [2] * sum(x[2] for x in sp)
+                b.forward_spans(sp, toks, want_logits=False)
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    b.forward_spans(sp, toks, want_logits=False)
+                if r:
+                    ms[form].append((time.perf_counter() - t0) * 1e3 / iters)
+        out["c"] = {"kv": b.kv_type, "pos": pos}
+        for form, xs in ms.items():
+            out["c"][form + "_ms"], out["c"][form + "_spread"] = med_spread(xs)
+        b.close()
+    return out
+
+
+def print_spans(shape_name, type_name, r, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# span passes, {shape_name} {type_name}: medians of {repeats} (spread = (max - min) / median)")
+    print(f"# (a) one span of 128 rows, llmk_span_time, {iters} passes per measurement, the forms alternating: bd_attn_span_kernel | LLMK_SPAN_ATTN=0")
+    print(f"{'kv':>5} {'pos0':>6} {'len':>4} {'span ms':>9} {'spread':>7} {'per-row ms':>11} {'spread':>7} {'per-row / span':>15}")
+    for x in r["a"]:
+        print(f"{x['kv']:>5} {x['pos0']:6d} {x['len']:4d} {x['span_ms']:9.3f} {x['span_spread']:7.3f} {x['rows_ms']:11.3f} {x['rows_spread']:7.3f} {x['rows_ms'] / x['span_ms']:15.2f}")
+    x = r["b"]
+    print(f"# (b) a prompt of {x['tokens']} tokens into one slot, wall clock of the calls (f32 caches)")
+    print(f"  spans of 128 (Batch.ingest) {x['spans_ms']:9.3f} ms (spread {x['spans_spread']:.3f})   llmk_prefill + llmk_batch_fork {x['prefill_fork_ms']:9.3f} ms (spread {x['prefill_fork_spread']:.3f})")
+    x = r["c"]
+    if x:
+        print(f"# (c) 112 decode rows at position {x['pos']} ({x['kv']} caches), wall clock of llmk_span_forward (argmax only), {iters} calls per measurement")
+        print(f"  alone {x['decode_ms']:9.3f} ms (spread {x['decode_spread']:.3f})   + one 16-row chunk of another slot {x['decode_chunk_ms']:9.3f} ms (spread {x['decode_chunk_spread']:.3f})"
+              f"   difference {x['decode_chunk_ms'] - x['decode_ms']:.3f} ms")
+
+
 def print_kv(shape_name, type_name, kinds, rows, iters, repeats):
     print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
     print(f"# batched decode by K/V cache type, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per type, "
@@ -250,10 +343,20 @@ def main():
     ap.add_argument("--kv", choices=["f32", "f16", "both"], default=None,
                     help="only the K/V-type table: the pass at 8, 32 and 128 rows at positions 25 and --pos on batches with f32 and / or f16 "
                          "K/V caches, alternating in one process; with --shared-prefix P also attached behind P positions at --pos")
+    ap.add_argument("--spans", action="store_true",
+                    help="only the span tables (llmk_span_*): a 128-row span ending at --pos with and without bd_attn_span_kernel, a prompt "
+                         "in spans against prefill + fork, 112 decode rows with and without a 16-row chunk")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
     m, shape = build(a.shape, a.type, a.cls_q6k)
+    if a.spans:
+        r = spans(m, shape, a.pos, a.iters, a.repeats)
+        m.close()
+        print_spans(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), r, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "spans": r}))
+        return
     if a.sampled:
         rows = sampled(m, shape, a.repeats)
         m.close()

@@ -89,6 +89,9 @@ SHAPES: Dict[str, LlamaShape] = {
     # kv head on the passes that have no token-by-token form (llmk_batch_*)
     "tiny-hs128w": LlamaShape(512, 1408, 2, 4, 4, 640, 40),
     "tiny-hs128w-long": LlamaShape(512, 1408, 2, 4, 4, 640, 320),
+    # three query heads per kv head (hs 32): the one kv_mul here that does not divide the 16 MFMA columns -- a span pass's column
+    # groups hold 5 rows and one padded column (llmk_span_*)
+    "tiny-kvmul3": LlamaShape(192, 512, 2, 6, 2, 400, 64),
 }
 
 
