@@ -40,7 +40,8 @@ extern "C" {
 #define LLMK_TYPE_F32 0
 #define LLMK_TYPE_F16 1
 #define LLMK_TYPE_Q4_0 2
-#define LLMK_TYPE_Q6_K 14 /* ggml block_q6_K (210 bytes per 256 weights): LLMK_WCLS only, see llmk_set_tensor_type */
+#define LLMK_TYPE_Q8_0 8 /* ggml block_q8_0 (34 bytes per 32 values): a batch's K/V caches only, see llmk_cache_create */
+#define LLMK_TYPE_Q6_K 14/* ggml block_q6_K (210 bytes per 256 weights): LLMK_WCLS only, see llmk_set_tensor_type */
 
 /* tensor ids for llmk_upload: one per component of TransformerWeights (weight_module.f90:13-26) */
 #define LLMK_TOKEN_EMBEDDING_TABLE 0 /* (E,V)        C [V][E]         always f32            */
@@ -505,15 +506,17 @@ int llmk_prefix_len(llmk_batch *b);
  * covers the slots' own caches AND the shared prefix -- no mixed types within a batch, no automatic choice.  The context's own cache,
  * llmk_prefill and the persistent kernel stay f32.
  *
- * create:  kv_type LLMK_TYPE_F32 or LLMK_TYPE_F16, anything else LLMK_E_TYPE; every other check is llmk_batch_create's, with the same
+ * create:  kv_type LLMK_TYPE_F32, LLMK_TYPE_F16 or LLMK_TYPE_Q8_0 (below), anything else -- 2, 14, .. -- LLMK_E_TYPE; LLMK_TYPE_Q8_0
+ *          on a model whose kv_dim is not a multiple of 32 is LLMK_E_SHAPE; every other check is llmk_batch_create's, with the same
  *          codes.  With LLMK_TYPE_F32 it IS llmk_batch_create: same code path, same allocations, same launches, same bits.  The handle
  *          is an llmk_batch: llmk_batch_*, llmk_rows_* and llmk_prefix_* take it with their contracts unchanged (the parity wording
  *          aside, below).  Caches the device has no room for: LLMK_E_NOMEM, nothing is left allocated.
- * type:    LLMK_TYPE_F32 | LLMK_TYPE_F16, a negative LLMK_E_* on error (as llmk_path).
- * bytes:   device bytes of the K/V caches plus the prefix rows, if the batch has any (as allocated: a prefix's blocks only grow).
+ * type:    LLMK_TYPE_F32 | LLMK_TYPE_F16 | LLMK_TYPE_Q8_0, a negative LLMK_E_* on error (as llmk_path).
+ * bytes:   device bytes of the K/V caches plus the prefix rows, if the batch has any (as allocated: a prefix's blocks only grow).  A
+ *          q8_0 batch: 34 bytes per 32 elements, 17/64 of the f32 batch's; its layout adds no padding.
  * peek:    verification hook, like llmk_peek: n cache rows of kv_dim floats each -- K (which 0) or V (1) of positions pos0 .. pos0+n-1
- *          (1-based) of `slot` in `layer`, converted to f32 (exact for f16); slot -1 reads the prefix, positions 1..P.  Out-of-range
- *          arguments: LLMK_E_ARG.  Both cache types.
+ *          (1-based) of `slot` in `layer`, converted to f32 (exact for f16; a q8_0 batch: value[] below, exact too); slot -1 reads the prefix,
+ *          positions 1..P.  Out-of-range arguments: LLMK_E_ARG.  Every cache type.
  * A NULL batch is LLMK_E_ARG (llmk_cache_type: -LLMK_E_ARG) before anything touches a device, in all of them.
  *
  * STORED VALUES of an f16 batch: h = (x != x) ? NaN : RNE_f16(clamp(x, -65504, 65504)) -- round to nearest even, f16 subnormals
@@ -525,9 +528,39 @@ int llmk_prefix_len(llmk_batch *b);
  * workgroups: the same call on the same state gives the same bits).  The f16-range redo rewrites the rows' K/V rows in the batch's type.
  * Parity: rounding K/V to f16 moves a row's logits by a few 1e-4 of max |logit| against llmk_forward's on that sequence (measured on
  * the test models), so an f16 batch is NOT within the 1e-4 bar of the f32 paths; it is within it of the float64 forward pass fed the
- * rows the batch stored (tests/kv16_ref.py). */
+ * rows the batch stored (tests/kv16_ref.py).
+ *
+ * A q8_0 BATCH (LLMK_TYPE_Q8_0 = 8, ggml's id; what llama.cpp's -ctk q8_0 -ctv q8_0 asks for): the slots' caches and the shared prefix
+ * hold q8_0 blocks of 32 CONSECUTIVE elements of a position's kv_dim row, K and V alike -- block j is elements 32j .. 32j+31 whatever
+ * the head size (at head size 16 one block spans two kv heads) -- 34 bytes per 32 values, 17/32 of f16.  On the device the int8
+ * quants [L][slots][seq_len][kv_dim] and the f16 scales [L][slots][seq_len][kv_dim / 32] are separate arrays of one allocation (not
+ * ggml's interleaved 34-byte records: a lane's fragment of quants loads naturally aligned); the contract is the VALUES.
+ * STORED VALUES: let x[0..32) be the f32 values the f32 batch stores at that place (the same expressions up to the store, as for
+ * f16; at llmk_batch_fork / llmk_prefix_set the context's f32 rows).
+ *     c[i] = clamp(x[i], -65504, 65504)                 (the saturation rule of the f16 cache: one outlier must not make anything infinite)
+ *     amax = max |c[i]|;  d32 = amax / 127.0f;  d = RNE_f16(d32)       (f16 subnormals kept; d32 <= 515.8, so it never overflows)
+ *     id   = d32 != 0 ? 1.0f / d32 : 0                  (from d32, not from the rounded d: ggml's quantize_row_q8_0_ref)
+ *     q[i] = (int8) clamp(roundf(c[i] * id), -127, 127) (nearest, ties away from zero); q[i] = 0 for all i when d == 0 (an amax
+ *                                                       below the f16 subnormals, f32 subnormals -- where id is infinite -- included)
+ *     a block with a NaN element: d = f16 NaN, every q = 0 (all 32 values read back NaN: the NaN is not hidden)
+ *     value[i] = (float)q[i] * (float)d                 (at most 7 x 11 significant bits: EXACT in f32; never -0.0)
+ * For finite inputs within +-65504 these are the values of ggml's quantize_row_q8_0_ref followed by dequantize_row_q8_0.  Every
+ * non-zero block holds a +-127 and the rule is idempotent: quantising stored values returns them bit for bit.  All divisions and
+ * products are IEEE f32, each rounded once.  A zeroed slot, and the rows beyond n_pos of a fork, hold q = 0, d = 0: +0.0.
+ * An attention pass of such a batch is DEFINED as the f32 pass over a cache that holds value[]: bytes and scales are converted in
+ * registers, then the f32 kernels' statements run unchanged; the determinism rules of the f16 batch carry over, the f16-range redo
+ * rewrites the rows in the batch's type, llmk_cache_type answers 8, llmk_cache_peek answers value[].  Everything that takes an
+ * llmk_batch keeps its contract on a q8_0 batch (llmk_batch_*, llmk_rows_*, llmk_prefix_*, llmk_span_*, the token records).
+ * Parity: q8_0 is about 25 times COARSER than f16.  Movement of the logits, of max |logit|, when the float64 forward pass quantises
+ * its own K/V rows by the rule above (63 positions, seed 777; tests/test_batch_kvq8_cpu.py prints it), next to the f16 figure:
+ *     tiny-hs64 0.81e-2 (f16 3.2e-4)   tk-small 1.08e-2 (3.4e-4)   tiny-gqa 1.30e-2 (4.5e-4)   tiny-hs128w 0.94e-2 (3.5e-4)
+ *     tiny-kvmul3 0.94e-2 (4.9e-4)
+ * (uniform-random test weights, which have near-ties everywhere).  So a q8_0 batch is NOT within the 1e-4 bar of the f32 or f16 paths;
+ * it is within it of the float64 forward pass fed the rows the batch stored (tests/kvq8_ref.py).  It is the caller's opt-in, never a
+ * default, and nothing chooses a cache type automatically.  Out of scope: q8_0 for the context's own cache, llmk_prefill or the
+ * persistent kernel; q4_0 / q5 caches; different K and V types; an int8 score product (Q stays f32); a raw-bits peek. */
 int llmk_cache_create(llmk_ctx *ctx, int n_slots, int seq_len, int kv_type, llmk_batch **out);
-int llmk_cache_type(llmk_batch *b);    /* LLMK_TYPE_F32 | LLMK_TYPE_F16, negative LLMK_E_* on error */
+int llmk_cache_type(llmk_batch *b);    /* LLMK_TYPE_F32 | LLMK_TYPE_F16 | LLMK_TYPE_Q8_0, negative LLMK_E_* on error */
 int llmk_cache_bytes(llmk_batch *b, unsigned long long *out);   /* device bytes of the K/V caches + the prefix, if any */
 int llmk_cache_peek(llmk_batch *b, int which, int layer, int slot, int pos0, int n, float *out);
 

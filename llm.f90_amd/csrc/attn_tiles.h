@@ -1,6 +1,7 @@
 // The MFMA attention the batched paths share (DESIGN.md sections 3c, 3i): pf_attn_kernel (prefill.h), bd_attn_prefix_kernel and
 // bd_attn_own_kernel (batch.h) are setup + attn_tiles + attn_merge_waves; bd_attn_kernel (batch.h) shares the look-ahead types and
-// keeps the loop and the merge written out (the reason stands at that kernel).  A workgroup owns 16 query COLUMNS
+// keeps the loop and the merge written out (the reason stands at that kernel); the four bd_q8_attn_* kernels of a q8_0 batch are
+// setup + these calls as well, over AttnAhead<HS, KvQ8>.  A workgroup owns 16 query COLUMNS
 // (prompt positions, or the query heads of a kv group) and a range of 16-row tiles of one K/V cache; its NW waves take the tiles round
 // robin, each with its own running softmax (max m, sum l, unnormalised output O), and merge through LDS at the end.
 //
@@ -18,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 
 namespace llmk {
 
@@ -39,6 +41,7 @@ struct AttnAhead;
 template <int HS>
 struct AttnAhead<HS, float> {
     static constexpr int DG = HS / 4, NT = HS / 16;
+    typedef const float* __restrict__ Ptr;
     typedef float K[DG];
     typedef float V[4][NT];
     static __device__ __forceinline__ void load(K& kn, V& vn, const float* kb, const float* vb, int KV, int r0, int li, int g, int last) {
@@ -81,6 +84,7 @@ struct AttnHalves<1> { typedef _Float16 type; };
 template <int HS>
 struct AttnAhead<HS, _Float16> {
     static constexpr int DG = HS / 4, NT = HS / 16, KW = DG < 8 ? DG : 8;      // KW: halves per K load
+    typedef const _Float16* __restrict__ Ptr;
     typedef typename AttnHalves<KW>::type K[DG / KW];
     typedef typename AttnHalves<NT>::type V[4];
     static __device__ __forceinline__ void load(K& kn, V& vn, const _Float16* kb, const _Float16* vb, int KV, int r0, int li, int g, int last) {
@@ -106,6 +110,79 @@ struct AttnAhead<HS, _Float16> {
     }
 };
 
+// q8_0 caches (llmk_cache_create(.., LLMK_TYPE_Q8_0)): a position's kv_dim row is blocks of 32 consecutive elements, a
+// block is 32 int8 quants and one f16 scale d, value = (float)q * (float)d (exact in f32: 7 x 11 significant bits).  Quants and scales
+// lie in SEPARATE arrays of the same index order -- quant of element e at q[e], its block's scale at d[e / 32] -- so that a fragment's
+// quants load at their natural width and alignment.  Q8Rows is a view of both at a block boundary; attn_at moves a view (or a plain
+// pointer) on by e elements.
+struct KvQ8 {};      // the element "type" of such a batch, where the f32 / f16 batches say float / _Float16
+struct Q8Rows {
+    int8_t* q;
+    _Float16* d;
+};
+__host__ __device__ __forceinline__ Q8Rows attn_at(Q8Rows p, size_t e) { return Q8Rows{p.q + e, p.d + (e >> 5)}; }      // (p at a block boundary)
+template <class T>
+__host__ __device__ __forceinline__ T* attn_at(T* p, size_t e) { return p + e; }
+// The look-ahead registers hold the PACKED bytes -- K: DG / 4 words, V: a word (two at head size 128) per row, the bytes in front
+// zero-extended -- and the scales as loaded: one for the K fragment (DG <= 32 elements inside one block; at head size 16 a block spans
+// two kv heads and the fragment still lies inside it), one per V row.  take dequantises in registers, each operand exactly
+// (float)q * (float)d.  Loads: K 4 | 8 | 16 | 2 x 16 bytes, V 1 | 2 | 4 | 8 bytes, naturally aligned (kv_dim % 32 == 0).
+template <int HS>
+struct AttnAhead<HS, KvQ8> {
+    static constexpr int DG = HS / 4, NT = HS / 16, KW = DG / 4, VW = (NT + 3) / 4;
+    static_assert(DG <= 32, "a K fragment lies inside one q8_0 block");
+    typedef Q8Rows Ptr;      // q at the lane's first quant, d at that quant's block
+    struct K { unsigned w[KW]; _Float16 d; };
+    struct V { unsigned w[4][VW]; _Float16 d[4]; };
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ void load(K& kn, V& vn, Q8Rows kb, Q8Rows vb, int KV, int r0, int li, int g, int last) {
+        const size_t rk = (size_t)min(r0 + li, last);
+        const int8_t* kp = kb.q + rk * KV;
+        kn.d = kb.d[rk * (KV >> 5)];
+        if constexpr (KW == 1) {
+            kn.w[0] = *reinterpret_cast<const unsigned*>(kp);
+        } else if constexpr (KW == 2) {
+            const u2 x = *reinterpret_cast<const u2*>(kp);
+            kn.w[0] = x.x; kn.w[1] = x.y;
+        } else {
+#pragma unroll
+            for (int m = 0; m < KW; m += 4) {
+                const u4 x = *reinterpret_cast<const u4*>(kp + 4 * m);
+                kn.w[m] = x.x; kn.w[m + 1] = x.y; kn.w[m + 2] = x.z; kn.w[m + 3] = x.w;
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const size_t rv = (size_t)min(r0 + 4 * g + v, last);
+            const int8_t* vp = vb.q + rv * KV;
+            vn.d[v] = vb.d[rv * (KV >> 5)];
+            if constexpr (NT == 1) {
+                vn.w[v][0] = *reinterpret_cast<const uint8_t*>(vp);
+            } else if constexpr (NT == 2) {
+                vn.w[v][0] = *reinterpret_cast<const uint16_t*>(vp);
+            } else if constexpr (NT == 4) {
+                vn.w[v][0] = *reinterpret_cast<const unsigned*>(vp);
+            } else {
+                const u2 x = *reinterpret_cast<const u2*>(vp);
+                vn.w[v][0] = x.x; vn.w[v][1] = x.y;
+            }
+        }
+    }
+    static __device__ __forceinline__ float value(unsigned w, int k, float d) { return (float)(int)(int8_t)(w >> (8 * k)) * d; }
+    static __device__ __forceinline__ void take(const K& kn, const V& vn, float (&kf)[DG], float (&vf)[4][NT]) {
+        const float dk = (float)kn.d;
+#pragma unroll
+        for (int m = 0; m < DG; ++m) kf[m] = value(kn.w[m / 4], m % 4, dk);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const float dv = (float)vn.d[v];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) vf[v][t] = value(vn.w[v][t / 4], t % 4, dv);
+        }
+    }
+};
+
 // lane (li, g)'s fragment of its query column: elements g * DG .. + DG of the column's head (qp points at the first)
 template <int HS>
 __device__ __forceinline__ void attn_load_q(float (&qf)[HS / 4], const float* __restrict__ qp) {
@@ -122,7 +199,7 @@ __device__ __forceinline__ void attn_load_q(float (&qf)[HS / 4], const float* __
 // index to `last` and the tile index to ntile - 1 (a tile's two dozen MFMAs and its softmax take far less than an L2 round trip, so
 // the next tile is requested before this one is multiplied).  A wave without a visible row leaves m = -inf, l = 0, O = 0.
 template <int HS, class T, int NW, class Visible>
-__device__ __forceinline__ void attn_tiles(const float (&qf)[HS / 4], const T* __restrict__ kb, const T* __restrict__ vb, int KV,
+__device__ __forceinline__ void attn_tiles(const float (&qf)[HS / 4], typename AttnAhead<HS, T>::Ptr kb, typename AttnAhead<HS, T>::Ptr vb, int KV,
                                            int last, int ntile, int t0, int t1, int wid, int li, int g, Visible visible, float& m_run,
                                            float& l_run, pf_v4f (&O)[HS / 16]) {
     constexpr int DG = HS / 4, NT = HS / 16;

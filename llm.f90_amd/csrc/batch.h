@@ -11,7 +11,8 @@
 //   bd_attn_span   a pass with SEVERAL consecutive positions of a slot (llmk_span_*, below): (position, query head) pairs as columns
 // bd_attn_prefix / bd_attn_own / bd_attn_span are setup around attn_tiles.h's tile loop, wave merge and look-ahead loads (shared with pf_attn_kernel);
 // bd_attn keeps the same statements written out (the reason stands at the kernel).
-// The caches are [L][n_slots][seq_len][KV], f32 or -- a batch of llmk_cache_create(.., LLMK_TYPE_F16) -- IEEE half.
+// The caches are [L][n_slots][seq_len][KV], f32 or -- a batch of llmk_cache_create(.., LLMK_TYPE_F16) -- IEEE half, or -- LLMK_TYPE_Q8_0 --
+// int8 quants in that order with the f16 scales of their blocks of 32 behind them (the q8_0 sections below).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,6 +97,109 @@ __global__ void bd_to_half_kernel(const float* __restrict__ sk, const float* __r
     for (size_t i = 4 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x); i < n; i += 4 * (size_t)gridDim.x * blockDim.x) {
         const float4 x = *reinterpret_cast<const float4*>(src + i);
         *reinterpret_cast<h4*>(dst + i) = (h4){pf_kv_half(x.x), pf_kv_half(x.y), pf_kv_half(x.z), pf_kv_half(x.w)};
+    }
+}
+
+// ---- q8_0 caches (llmk_cache_create(.., LLMK_TYPE_Q8_0); layout: attn_tiles.h Q8Rows)                                 ------------
+// THE stored-value rule (include/llmk.h), for the K/V write and the converting copy alike.  EIGHT ADJACENT LANES, the first at a
+// multiple of 8 in its wave, hold a block's 32 values, four each in element order; every lane of the eight must call (three xor
+// shuffles inside the group).  Leaves this lane's four quants packed in element order and the block's scale (the same in all eight).
+//   c = clamp(x, +-65504); amax = max |c|; d32 = amax / 127; d = RNE_f16(d32); id = d32 != 0 ? 1 / d32 : 0 (from d32, as ggml's
+//   quantize_row_q8_0_ref); q = clamp(roundf(c * id), +-127); d == 0 (amax below the f16 subnormals: id may be infinite): every q = 0;
+//   a NaN among the 32: d = NaN, every q = 0.
+// Every product and quotient is one IEEE f32 operation (no fast-math in this build; nothing here can be contracted).
+__device__ __forceinline__ void bd_q8_block(const float (&x)[4], unsigned& quants, _Float16& scale) {
+#pragma clang fp contract(off)
+    float c[4], amax = 0.f;
+    int nan = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        nan |= x[i] != x[i];
+        c[i] = fminf(fmaxf(x[i], -65504.f), 65504.f);
+        amax = fmaxf(amax, fabsf(c[i]));
+    }
+#pragma unroll
+    for (int s = 1; s < 8; s <<= 1) {
+        amax = fmaxf(amax, __shfl_xor(amax, s, 64));
+        nan |= __shfl_xor(nan, s, 64);
+    }
+    const float d32 = amax / 127.0f;
+    const _Float16 d = (_Float16)d32;
+    const float id = d32 != 0.f ? 1.0f / d32 : 0.f;
+    const bool zero = nan || (float)d == 0.f;
+    quants = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int q = zero ? 0 : (int)fminf(fmaxf(roundf(c[i] * id), -127.f), 127.f);
+        quants |= (unsigned)(q & 0xFF) << (8 * i);
+    }
+    scale = nan ? (_Float16)__builtin_nanf("") : d;
+}
+
+// bd_epi_qkv_h_kernel for a batch with q8_0 caches: Q goes out in f32, a K / V block is stored by the rule above from the values the
+// f32 kernel stores (the expressions of pf_epi_qkv_pair_h up to the store: keep them in step).  A thread owns rows 4 * p4 .. + 3 (two
+// RoPE pairs), so a block of 32 K or V elements is 8 adjacent threads: Q starts at row 0, K at E and V at E + KV, all multiples of 32
+// (E % 64 == 0: pf_shape_ok; KV % 32 == 0: llmk_cache_create), and a workgroup starts at a multiple of 4 * 256 rows -- a block never
+// straddles Q | K | V, a wave or the end of the rows (rows / 4 is a multiple of 8).  NO LANE RETURNS in front of bd_q8_block: a lane
+// beyond the rows, or of a bad row (uniform: the row is the workgroup's), computes on zeros and stores nothing, so the shuffles run
+// with the whole wave active.
+__global__ void bd_epi_qkv_q8_kernel(PfEpiArgs a, BdCaches bc, Q8Rows kc, Q8Rows vc) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y, r0 = 4 * p4;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    const BdRow r = bc.rows[t];
+    const bool live = p4 < a.rows / 4 && bd_row_ok(bc, r);
+    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) s4 = pf_sum4(a, t, r0);
+    const float xn = a.xn[t];
+    float x[4] = {s4.x / xn, s4.y / xn, s4.z / xn, s4.w / xn};
+    const int i0 = r0 < a.E ? r0 : r0 < a.E + a.KV ? r0 - a.E : r0 - a.E - a.KV;      // the element in Q, K or V
+    if (live && r0 < a.E + a.KV) {
+#pragma unroll
+        for (int k = 0; k < 4; k += 2) {
+            const float rval = (float)r.pos * a.rope[((i0 + k) % a.hs) >> 1];
+            const float fcr = cosf(rval), fci = sinf(rval);
+            {
+#pragma clang fp contract(off)
+                const float p00 = x[k] * fcr, p11 = x[k + 1] * fci, p01 = x[k] * fci, p10 = x[k + 1] * fcr;
+                x[k] = p00 - p11;
+                x[k + 1] = p01 + p10;
+            }
+        }
+    }
+    unsigned quants;
+    _Float16 scale;
+    bd_q8_block(x, quants, scale);
+    if (!live) return;
+    if (r0 < a.E) {
+        *reinterpret_cast<float4*>(a.out + (size_t)t * a.E + i0) = make_float4(x[0], x[1], x[2], x[3]);
+        return;
+    }
+    const Q8Rows dst = attn_at(r0 < a.E + a.KV ? kc : vc, (size_t)r.slot * bc.slot_stride + (size_t)(r.pos - 1) * a.KV + (i0 & ~31));
+    *reinterpret_cast<unsigned*>(dst.q + (i0 & 31)) = quants;
+    if ((i0 & 31) == 0) *dst.d = scale;
+}
+
+// f32 rows of the context's cache into a q8_0 batch (llmk_batch_fork, llmk_prefix_set), bd_to_half_kernel's arguments: n elements (a
+// multiple of 32: whole rows) of every layer and of K (blockIdx.z 0) and V (1), by the same rule.  The loop's bound is the
+// WORKGROUP's, so every lane of a wave runs every trip and the shuffles meet the whole wave; a lane beyond n converts zeros and
+// stores nothing (n % 32 == 0: the eight lanes of a block are beyond n together).
+__global__ void bd_to_q8_kernel(const float* __restrict__ sk, const float* __restrict__ sv, Q8Rows dk, Q8Rows dv, size_t n,
+                                size_t src_layer, size_t dst_layer) {
+    const float* src = (blockIdx.z ? sv : sk) + blockIdx.y * src_layer;
+    const Q8Rows dst = attn_at(blockIdx.z ? dv : dk, blockIdx.y * dst_layer);
+    for (size_t i0 = 4 * (size_t)blockIdx.x * blockDim.x; i0 < n; i0 += 4 * (size_t)gridDim.x * blockDim.x) {
+        const size_t i = i0 + 4 * threadIdx.x;
+        const bool live = i < n;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) v = *reinterpret_cast<const float4*>(src + i);
+        const float x[4] = {v.x, v.y, v.z, v.w};
+        unsigned quants;
+        _Float16 scale;
+        bd_q8_block(x, quants, scale);
+        if (live) {
+            *reinterpret_cast<unsigned*>(dst.q + i) = quants;
+            if ((i & 31) == 0) dst.d[i >> 5] = scale;
+        }
     }
 }
 
@@ -283,11 +387,12 @@ __host__ __device__ inline int bd_prefix_parts(int n_att, int n_kv_heads, int kv
 // One workgroup per (kv head, column group, prefix part).  colmap [groups][RG]: the pass's attached rows, in row order, -1 behind the
 // last.  Column c of a group is (row colmap[c / kv_mul], query head c % kv_mul of the kv head); columns from the last live one on
 // repeat it and are not written out.  Every attached row sees the whole prefix: the predicate is cache row < P alone.
-template <int HS, class T = float>
-__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const float* __restrict__ Q, const T* __restrict__ pk,
-                                                                         const T* __restrict__ pv, float* __restrict__ po,
-                                                                         float2* __restrict__ pml, const int* __restrict__ colmap, int n,
-                                                                         int P, int KV, int kv_mul, int E, int tpp, int np) {
+// (the kernels' text is a __device__ function over the cache type T and its view AttnAhead<HS, T>::Ptr, so that the q8_0 kernels below
+// -- __global__ names of their own -- are the same statements)
+template <int HS, class T>
+__device__ __forceinline__ void bd_attn_prefix_body(const float* __restrict__ Q, typename AttnAhead<HS, T>::Ptr pk, typename AttnAhead<HS, T>::Ptr pv,
+                                                    float* __restrict__ po, float2* __restrict__ pml, const int* __restrict__ colmap, int n,
+                                                    int P, int KV, int kv_mul, int E, int tpp, int np) {
     constexpr int DG = HS / 4, NT = HS / 16;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
     const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x, rg = bd_prefix_rg(kv_mul);
@@ -301,7 +406,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const f
     float m_run, l_run;
     pf_v4f O[NT];
     const int ntile = (P + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
-    attn_tiles<HS, T, BD_WAVES>(qf, pk + (size_t)kvh * HS + g * DG, pv + (size_t)kvh * HS + NT * li, KV, P - 1, ntile, t0, t1, wid, li, g,
+    attn_tiles<HS, T, BD_WAVES>(qf, attn_at(pk, (size_t)kvh * HS + g * DG), attn_at(pv, (size_t)kvh * HS + NT * li), KV, P - 1, ntile, t0, t1, wid, li, g,
                                 [&](int r) { return r < P; }, m_run, l_run, O);
     attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
         const size_t s = (((size_t)cm[col / kv_mul] * nkv + kvh) * np + part) * kv_mul + col % kv_mul;
@@ -309,15 +414,21 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const f
         if (d == 0) pml[s] = make_float2(M, L);
     });
 }
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_prefix_kernel(const float* __restrict__ Q, const T* __restrict__ pk,
+                                                                         const T* __restrict__ pv, float* __restrict__ po,
+                                                                         float2* __restrict__ pml, const int* __restrict__ colmap, int n,
+                                                                         int P, int KV, int kv_mul, int E, int tpp, int np) {
+    bd_attn_prefix_body<HS, T>(Q, pk, pv, po, pml, colmap, n, P, KV, kv_mul, E, tpp, np);
+}
 
 // bd_attn_kernel for a pass with attached rows: the row's own cache rows first[slot] .. pos-1, tiles counted from the one that holds
 // row `first` (that tile masks the rows below it); part `part` leaves state p0 + part, never normalised.  One workgroup per (kv head,
 // row, own part).
-template <int HS, class T = float>
-__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
-                                                                      const T* __restrict__ vc, float* __restrict__ po,
-                                                                      float2* __restrict__ pml, BdCaches bc, const int* __restrict__ first,
-                                                                      int KV, int kv_mul, int E, int tpp, int np, int p0) {
+template <int HS, class T>
+__device__ __forceinline__ void bd_attn_own_body(const float* __restrict__ Q, typename AttnAhead<HS, T>::Ptr kc, typename AttnAhead<HS, T>::Ptr vc,
+                                                 float* __restrict__ po, float2* __restrict__ pml, const BdCaches& bc, const int* __restrict__ first,
+                                                 int KV, int kv_mul, int E, int tpp, int np, int p0) {
     constexpr int DG = HS / 4, NT = HS / 16;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
     const int kvh = blockIdx.x, b = blockIdx.y, part = blockIdx.z, nkv = gridDim.x;
@@ -331,13 +442,20 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const floa
     pf_v4f O[NT];
     const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
     const size_t base = (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS;
-    attn_tiles<HS, T, BD_WAVES>(qf, kc + base + g * DG, vc + base + NT * li, KV, nrows - 1, ntile, t0, t1, wid, li, g,
+    attn_tiles<HS, T, BD_WAVES>(qf, attn_at(kc, base + g * DG), attn_at(vc, base + NT * li), KV, nrows - 1, ntile, t0, t1, wid, li, g,
                                 [&](int r) { return lo <= r && r < nrows; }, m_run, l_run, O);
     attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, kv_mul, [&](int q, int d, float M, float L, float val) {
         const size_t s = (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q;
         po[s * HS + d] = val;
         if (d == 0) pml[s] = make_float2(M, L);
     });
+}
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_own_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                      const T* __restrict__ vc, float* __restrict__ po,
+                                                                      float2* __restrict__ pml, BdCaches bc, const int* __restrict__ first,
+                                                                      int KV, int kv_mul, int E, int tpp, int np, int p0) {
+    bd_attn_own_body<HS, T>(Q, kc, vc, po, pml, bc, first, KV, kv_mul, E, tpp, np, p0);
 }
 
 // ---- spans (llmk_span_*): several consecutive positions of a slot in one pass                                         ------------
@@ -361,12 +479,11 @@ __host__ __device__ inline int bd_span_parts(int groups, int n_kv_heads, int own
 // Otherwise part `part` leaves state p0 + part of every (row, kv head) of the group in the layout of a pass with attached rows
 // (stride kv_mul, np states), and bd_attn_fold_kernel folds them.  A column all of whose rows lie before the part's tiles leaves
 // M = -inf, L = 0; the part that holds row lo is never empty for any column (pos > lo).
-template <int HS, class T = float>
-__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_span_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
-                                                                       const T* __restrict__ vc, float* __restrict__ out,
-                                                                       float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
-                                                                       const BdGroup* __restrict__ groups, const int* __restrict__ first,
-                                                                       int n, int KV, int kv_mul, int E, int tpp, int np, int p0, int direct) {
+template <int HS, class T>
+__device__ __forceinline__ void bd_attn_span_body(const float* __restrict__ Q, typename AttnAhead<HS, T>::Ptr kc, typename AttnAhead<HS, T>::Ptr vc,
+                                                  float* __restrict__ out, float* __restrict__ po, float2* __restrict__ pml, const BdCaches& bc,
+                                                  const BdGroup* __restrict__ groups, const int* __restrict__ first, int n, int KV, int kv_mul,
+                                                  int E, int tpp, int np, int p0, int direct) {
     constexpr int DG = HS / 4, NT = HS / 16;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
     const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x;
@@ -383,7 +500,7 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_span_kernel(const flo
     pf_v4f O[NT];
     const int ntile = (rowl.pos + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
     const size_t base = (size_t)row0.slot * bc.slot_stride + (size_t)kvh * HS;
-    attn_tiles<HS, T, BD_WAVES>(qf, kc + base + g * DG, vc + base + NT * li, KV, rowl.pos - 1, ntile, t0, t1, wid, li, g,
+    attn_tiles<HS, T, BD_WAVES>(qf, attn_at(kc, base + g * DG), attn_at(vc, base + NT * li), KV, rowl.pos - 1, ntile, t0, t1, wid, li, g,
                                 [&](int r) { return lo <= r && r < vis; }, m_run, l_run, O);
     attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
         const int b = gr.first + col / kv_mul, q = col % kv_mul;
@@ -395,6 +512,14 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_span_kernel(const flo
             if (d == 0) pml[s] = make_float2(M, L);
         }
     });
+}
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_span_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                       const T* __restrict__ vc, float* __restrict__ out,
+                                                                       float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                       const BdGroup* __restrict__ groups, const int* __restrict__ first,
+                                                                       int n, int KV, int kv_mul, int E, int tpp, int np, int p0, int direct) {
+    bd_attn_span_body<HS, T>(Q, kc, vc, out, po, pml, bc, groups, first, n, KV, kv_mul, E, tpp, np, p0, direct);
 }
 
 // The part states of (row, kv head) folded in part order: out = sum_p O_p e^(M_p - M) / sum_p L_p e^(M_p - M).  State s of np, head q,
@@ -430,6 +555,77 @@ __global__ __launch_bounds__(256) void bd_attn_fold_kernel(const float* __restri
         out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
     }
 }
+
+// ---- the attention of a batch with q8_0 caches                                                                        ------------
+// Four kernels with __global__ names of their own (tests/test_build_cpu.py counts the instantiations of the names above), each
+// setup + attn_tiles + attn_merge_waves over AttnAhead<HS, KvQ8>: the bytes and scales are converted in registers, then the f32
+// statements run unchanged.  prefix / own / span ARE the bodies above; the per-row kernel is bd_attn_kernel's setup and part states
+// (stride BD_MAX_GROUP; parts == 1: normalised to `out`) on the shared loop -- that kernel's exception is not extended.
+// bd_attn_fold_kernel folds the parts of either.
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_q8_attn_kernel(const float* __restrict__ Q, Q8Rows kc, Q8Rows vc, float* __restrict__ out,
+                                                                     float* __restrict__ po, float2* __restrict__ pml, BdCaches bc, int KV,
+                                                                     int kv_mul, int E, int tpp) {
+    constexpr int DG = HS / 4, NT = HS / 16;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, b = blockIdx.y, part = blockIdx.z, parts = gridDim.z, nkv = gridDim.x;
+    const BdRow row = bc.rows[b];
+    if (!bd_row_ok(bc, row)) return;                  // whole workgroup: no barrier is pending
+    const int nrows = row.pos;
+    const int h = kvh * kv_mul + min(li, kv_mul - 1);
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)b * E + (size_t)h * HS + g * DG);
+    float m_run, l_run;
+    pf_v4f O[NT];
+    const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
+    const size_t base = (size_t)row.slot * bc.slot_stride + (size_t)kvh * HS;
+    attn_tiles<HS, KvQ8, BD_WAVES>(qf, attn_at(kc, base + g * DG), attn_at(vc, base + NT * li), KV, nrows - 1, ntile, t0, t1, wid, li, g,
+                                   [&](int r) { return r < nrows; }, m_run, l_run, O);
+    const size_t pbase = ((size_t)b * nkv + kvh) * parts + part;
+    attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, kv_mul, [&](int q, int d, float M, float L, float val) {
+        if (parts == 1) {
+            out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+        } else {
+            po[(pbase * BD_MAX_GROUP + q) * HS + d] = val;
+            if (d == 0) pml[pbase * BD_MAX_GROUP + q] = make_float2(M, L);
+        }
+    });
+}
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_q8_attn_prefix_kernel(const float* __restrict__ Q, Q8Rows pk, Q8Rows pv, float* __restrict__ po,
+                                                                            float2* __restrict__ pml, const int* __restrict__ colmap, int n,
+                                                                            int P, int KV, int kv_mul, int E, int tpp, int np) {
+    bd_attn_prefix_body<HS, KvQ8>(Q, pk, pv, po, pml, colmap, n, P, KV, kv_mul, E, tpp, np);
+}
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_q8_attn_own_kernel(const float* __restrict__ Q, Q8Rows kc, Q8Rows vc, float* __restrict__ po,
+                                                                         float2* __restrict__ pml, BdCaches bc, const int* __restrict__ first,
+                                                                         int KV, int kv_mul, int E, int tpp, int np, int p0) {
+    bd_attn_own_body<HS, KvQ8>(Q, kc, vc, po, pml, bc, first, KV, kv_mul, E, tpp, np, p0);
+}
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_q8_attn_span_kernel(const float* __restrict__ Q, Q8Rows kc, Q8Rows vc, float* __restrict__ out,
+                                                                          float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                          const BdGroup* __restrict__ groups, const int* __restrict__ first,
+                                                                          int n, int KV, int kv_mul, int E, int tpp, int np, int p0, int direct) {
+    bd_attn_span_body<HS, KvQ8>(Q, kc, vc, out, po, pml, bc, groups, first, n, KV, kv_mul, E, tpp, np, p0, direct);
+}
+
+// The kernels by cache type, for the host's one dispatch (llmk.hip with_kv_type): T = float | _Float16 | KvQ8
+template <int HS, class T>
+struct BdAttn {
+    static constexpr auto row = bd_attn_kernel<HS, T>;
+    static constexpr auto prefix = bd_attn_prefix_kernel<HS, T>;
+    static constexpr auto own = bd_attn_own_kernel<HS, T>;
+    static constexpr auto span = bd_attn_span_kernel<HS, T>;
+};
+template <int HS>
+struct BdAttn<HS, KvQ8> {
+    static constexpr auto row = bd_q8_attn_kernel<HS>;
+    static constexpr auto prefix = bd_q8_attn_prefix_kernel<HS>;
+    static constexpr auto own = bd_q8_attn_own_kernel<HS>;
+    static constexpr auto span = bd_q8_attn_span_kernel<HS>;
+};
 
 // llmk_batch_decode, between two passes: row i's pick (1-based; greedy: the classifier's first maximum, else what the sampler left)
 // is recorded, becomes the token the row feeds next (0-based, as pf_embed_kernel reads it) and the row moves one position on.

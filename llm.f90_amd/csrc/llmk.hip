@@ -243,6 +243,7 @@ struct llmk_batch {
     int kv_type = LLMK_TYPE_F32;                 // the caches' and the prefix's element type (llmk_cache_create): ONE pair of each is allocated
     DevBuf<float> d_kc, d_vc;                    // [L][n_slots][seq_len][KV], an f32 batch's ...
     DevBuf<_Float16> d_kc16, d_vc16;             // ... and an f16 batch's (BdKv<T> below picks the pair by element type)
+    DevBuf<int8_t> d_kc8, d_vc8;                 // a q8_0 batch's: the quants in that order, then the scales [L][n_slots][seq_len][KV / 32] f16 (BdKv<KvQ8>)
     DevBuf<BdRow> d_rows;                        // [LLMK_MAX_BATCH] row words
     DevBuf<int> d_tok;                           // [LLMK_MAX_BATCH] 0-based fed ids
     DevBuf<float> d_out;                         // [2 * LLMK_MAX_BATCH]: (unused log-probs), then the rows' first maxima (1-based ints)
@@ -276,6 +277,7 @@ struct llmk_batch {
         DevBuf<float2> d_xpml;                   //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_xpo that [hs]
         DevBuf<float> d_pk, d_pv;                // [L][P][KV]: a snapshot of the context's rows of positions 1..P, grown by reserve
         DevBuf<_Float16> d_pk16, d_pv16;         // the same in an f16 batch: the prefix has the batch's type
+        DevBuf<int8_t> d_pk8, d_pv8;             // ... and in a q8_0 batch: quants [L][P][KV], then scales [L][P][KV / 32]
     };
     std::unique_ptr<Prefix> px;
     int pass_att = 0;                            // attached rows among the rows bd_upload_rows uploaded last
@@ -1465,26 +1467,42 @@ int pf_run(llmk_ctx* c, const int* tokens, int n, int pos0, const ScoreJob* sj) 
 // ---- batched decode (batch.h) -----------------------------------------------------------------------------------
 static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
 
-// A batch's caches and prefix rows by element type (llmk_cache_create: float or _Float16, one type per batch), and f(T()) for the
+// A batch's caches and prefix rows by element type (llmk_cache_create: float, _Float16 or KvQ8, one type per batch), and f(T()) for the
 // type a batch has.  What differs between the types on the host: the buffers, the kernels' instantiation, and a converting kernel in
-// the place of the device-to-device copy from the context's f32 rows.
+// the place of the device-to-device copy from the context's f32 rows.  A buffer of n ELEMENTS is units(n) units of its DevBuf; view(buf,
+// n) is what the kernels take for it -- the pointer, or for q8_0 the quants and the scales behind them (attn_tiles.h Q8Rows; nothing is
+// padded: n is a multiple of 32, so the scales start 32-byte aligned) -- and attn_at(view, e) moves it on by e elements.
+template <class T> struct BdKvPlain {
+    static size_t units(size_t n) { return n; }
+    static T* view(DevBuf<T>& buf, size_t) { return buf.get(); }
+};
 template <class T> struct BdKv;
-template <> struct BdKv<float> {
+template <> struct BdKv<KvQ8> {
+    static DevBuf<int8_t>& kc(llmk_batch* b) { return b->d_kc8; }
+    static DevBuf<int8_t>& vc(llmk_batch* b) { return b->d_vc8; }
+    static DevBuf<int8_t>& pk(llmk_batch::Prefix& p) { return p.d_pk8; }
+    static DevBuf<int8_t>& pv(llmk_batch::Prefix& p) { return p.d_pv8; }
+    static size_t units(size_t n) { return n + n / 32 * sizeof(_Float16); }      // bytes: 34 per 32 elements
+    static Q8Rows view(DevBuf<int8_t>& buf, size_t n) { return Q8Rows{buf.get(), reinterpret_cast<_Float16*>(buf.get() + n)}; }
+};
+template <> struct BdKv<float> : BdKvPlain<float> {
     static DevBuf<float>& kc(llmk_batch* b) { return b->d_kc; }
     static DevBuf<float>& vc(llmk_batch* b) { return b->d_vc; }
     static DevBuf<float>& pk(llmk_batch::Prefix& p) { return p.d_pk; }
     static DevBuf<float>& pv(llmk_batch::Prefix& p) { return p.d_pv; }
 };
-template <> struct BdKv<_Float16> {
+template <> struct BdKv<_Float16> : BdKvPlain<_Float16> {
     static DevBuf<_Float16>& kc(llmk_batch* b) { return b->d_kc16; }
     static DevBuf<_Float16>& vc(llmk_batch* b) { return b->d_vc16; }
     static DevBuf<_Float16>& pk(llmk_batch::Prefix& p) { return p.d_pk16; }
     static DevBuf<_Float16>& pv(llmk_batch::Prefix& p) { return p.d_pv16; }
 };
 template <class F>
-static auto with_kv_type(const llmk_batch* b, F f) { return b->kv_type == LLMK_TYPE_F16 ? f(_Float16()) : f(float()); }
+static auto with_kv_type(const llmk_batch* b, F f) {
+    return b->kv_type == LLMK_TYPE_Q8_0 ? f(KvQ8()) : b->kv_type == LLMK_TYPE_F16 ? f(_Float16()) : f(float());
+}
 // rows [n][KV] of every layer of the context's f32 caches into a batch's K and V buffers (dk, dv; layers dst_layer elements apart),
-// ENQUEUED: the copy an f32 batch always made, the converting kernel for an f16 one (batch.h bd_to_half_kernel)
+// ENQUEUED: the copy an f32 batch always made, the converting kernel for an f16 one (batch.h bd_to_half_kernel) or a q8_0 one (bd_to_q8_kernel)
 static hipError_t bd_copy_ctx_rows(llmk_ctx* c, float* dk, float* dv, size_t n, size_t dst_layer) {
     float* caches[2][2] = {{dk, c->d_kc}, {dv, c->d_vc}};
     for (auto& p : caches)
@@ -1495,6 +1513,12 @@ static hipError_t bd_copy_ctx_rows(llmk_ctx* c, float* dk, float* dv, size_t n, 
 static hipError_t bd_copy_ctx_rows(llmk_ctx* c, _Float16* dk, _Float16* dv, size_t n, size_t dst_layer) {
     const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
     hipLaunchKernelGGL(bd_to_half_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
+    return hipGetLastError();
+}
+
+static hipError_t bd_copy_ctx_rows(llmk_ctx* c, Q8Rows dk, Q8Rows dv, size_t n, size_t dst_layer) {
+    const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
+    hipLaunchKernelGGL(bd_to_q8_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
     return hipGetLastError();
 }
 
@@ -1538,29 +1562,38 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
     PfEpiArgs e;
     // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
-        TC* kc = BdKv<TC>::kc(b) + (size_t)l * b->n_slots * bc.slot_stride;
-        TC* vc = BdKv<TC>::vc(b) + (size_t)l * b->n_slots * bc.slot_stride;
+        const size_t cache = (size_t)c->L * b->n_slots * bc.slot_stride;
+        const auto kc = attn_at(BdKv<TC>::view(BdKv<TC>::kc(b), cache), (size_t)l * b->n_slots * bc.slot_stride);
+        const auto vc = attn_at(BdKv<TC>::view(BdKv<TC>::vc(b), cache), (size_t)l * b->n_slots * bc.slot_stride);
         if constexpr (std::is_same_v<TC, float>) {
             a.kc = kc; a.vc = vc;
             hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc);
+        } else if constexpr (std::is_same_v<TC, KvQ8>) {
+            a.kc = a.vc = nullptr;
+            hipLaunchKernelGGL(bd_epi_qkv_q8_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc, kc, vc);
         } else {
             a.kc = a.vc = nullptr;      // (the context's caches are not this pass's)
             hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc, kc, vc);
         }
         HIPRET(hipGetLastError());
+        // (the prefix rows of this layer: [L][P][KV] with the layers P rows apart, whatever the blocks' room)
+        auto pk = kc, pv = vc;
+        if (shared) {
+            pk = attn_at(BdKv<TC>::view(BdKv<TC>::pk(*b->px), (size_t)c->L * b->P * KV), (size_t)l * b->P * KV);
+            pv = attn_at(BdKv<TC>::view(BdKv<TC>::pv(*b->px), (size_t)c->L * b->P * KV), (size_t)l * b->P * KV);
+        }
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
             if (ngroups > 0) {
                 // prefix (a pass with attached rows) + the groups' own rows + fold; one part and no attached row: straight to XB
                 const int np = pparts + parts, direct = !shared && parts == 1;
                 if (shared) {
-                    const size_t px = (size_t)l * b->P * KV;
-                    hipLaunchKernelGGL((bd_attn_prefix_kernel<HS, TC>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                                       w.Q, BdKv<TC>::pk(*b->px) + px, BdKv<TC>::pv(*b->px) + px, b->sn->d_spo, b->sn->d_spml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
+                    hipLaunchKernelGGL((BdAttn<HS, TC>::prefix), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+                                       w.Q, pk, pv, b->sn->d_spo, b->sn->d_spml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
                     HIPRET(hipGetLastError());
                 }
                 const int* first = shared ? b->px->d_first.get() : nullptr;
-                hipLaunchKernelGGL((bd_attn_span_kernel<HS, TC>), dim3(c->nkv, ngroups, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+                hipLaunchKernelGGL((BdAttn<HS, TC>::span), dim3(c->nkv, ngroups, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
                                    w.Q, kc, vc, w.XB, b->sn->d_spo, b->sn->d_spml, bc, b->sn->d_groups, first, T, KV, c->kv_mul, E, tpp, np, pparts, direct);
                 HIPRET(hipGetLastError());
                 if (!direct) hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->sn->d_spo, b->sn->d_spml, w.XB, bc, first,
@@ -1569,18 +1602,17 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
             }
             if (shared) {
                 const int np = pparts + parts;
-                const size_t px = (size_t)l * b->P * KV;
-                hipLaunchKernelGGL((bd_attn_prefix_kernel<HS, TC>), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                                   w.Q, BdKv<TC>::pk(*b->px) + px, BdKv<TC>::pv(*b->px) + px, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
+                hipLaunchKernelGGL((BdAttn<HS, TC>::prefix), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+                                   w.Q, pk, pv, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
                 HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((bd_attn_own_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+                hipLaunchKernelGGL((BdAttn<HS, TC>::own), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
                                    w.Q, kc, vc, b->px->d_xpo, b->px->d_xpml, bc, b->px->d_first, KV, c->kv_mul, E, tpp, np, pparts);
                 HIPRET(hipGetLastError());
                 hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->px->d_xpo, b->px->d_xpml, w.XB, bc, b->px->d_first,
                                    c->kv_mul, E, c->kv_mul, np, pparts);
                 return hipGetLastError();
             }
-            hipLaunchKernelGGL((bd_attn_kernel<HS, TC>), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
+            hipLaunchKernelGGL((BdAttn<HS, TC>::row), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
                                w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
             HIPRET(hipGetLastError());
             if (parts > 1) hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, (const int*)nullptr,
@@ -1629,7 +1661,7 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
 
 extern "C" {
 
-int llmk_version(void) { return 408; }
+int llmk_version(void) { return 409; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2845,10 +2877,11 @@ static int bd_alloc_rc(hipError_t e) {
 static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) {
     if (!c || !out || n_slots < 1 || n_slots > LLMK_MAX_BATCH || seq_len < 1 || seq_len > c->S) return LLMK_E_ARG;
     *out = nullptr;
-    if (kv_type != LLMK_TYPE_F32 && kv_type != LLMK_TYPE_F16) return LLMK_E_TYPE;
+    if (kv_type != LLMK_TYPE_F32 && kv_type != LLMK_TYPE_F16 && kv_type != LLMK_TYPE_Q8_0) return LLMK_E_TYPE;
     int rc = check_ready(c);      // (an incomplete context is LLMK_E_STATE whatever its shape)
     if (rc) return rc;
     if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;
+    if (kv_type == LLMK_TYPE_Q8_0 && c->KV % 32 != 0) return LLMK_E_SHAPE;      // a q8_0 block is 32 elements of a position's row
     HIPCHK(hipSetDevice(c->cfg.device));
     // built aside: the caller gets the batch only after every step succeeded (a failure releases what was made)
     auto b = std::make_unique<llmk_batch>();
@@ -2860,8 +2893,8 @@ static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_ba
     rc = with_kv_type(b.get(), [&](auto t) -> int {
         using TC = decltype(t);
         int rc_;
-        if ((rc_ = bd_alloc_rc(BdKv<TC>::kc(b.get()).alloc(cache))) != LLMK_OK) return rc_;
-        if ((rc_ = bd_alloc_rc(BdKv<TC>::vc(b.get()).alloc(cache))) != LLMK_OK) return rc_;
+        if ((rc_ = bd_alloc_rc(BdKv<TC>::kc(b.get()).alloc(BdKv<TC>::units(cache)))) != LLMK_OK) return rc_;
+        if ((rc_ = bd_alloc_rc(BdKv<TC>::vc(b.get()).alloc(BdKv<TC>::units(cache)))) != LLMK_OK) return rc_;
         HIPCHK(BdKv<TC>::kc(b.get()).zero(c->stream));
         HIPCHK(BdKv<TC>::vc(b.get()).zero(c->stream));
         return LLMK_OK;
@@ -2886,7 +2919,7 @@ static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_ba
     HIPCHK(with_head_size(c->hs, [&](auto hs) {
         constexpr int HS = decltype(hs)::value;
         return with_kv_type(b.get(), [](auto t) {
-            return hipFuncSetAttribute((const void*)bd_attn_kernel<HS, decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+            return hipFuncSetAttribute((const void*)BdAttn<HS, decltype(t)>::row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
         });
     }));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2910,7 +2943,7 @@ int llmk_cache_bytes(llmk_batch* b, unsigned long long* out) {
         using TC = decltype(t);
         size_t n = BdKv<TC>::kc(b).size() + BdKv<TC>::vc(b).size();
         if (b->px) n += BdKv<TC>::pk(*b->px).size() + BdKv<TC>::pv(*b->px).size();
-        return (unsigned long long)n * sizeof(TC);
+        return (unsigned long long)n * sizeof(*BdKv<TC>::kc(b).get());
     });
     return LLMK_OK;
 }
@@ -2925,8 +2958,20 @@ int llmk_cache_peek(llmk_batch* b, int which, int layer, int slot, int pos0, int
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipStreamSynchronize(c->stream));
     const size_t row = (size_t)c->KV, cnt = (size_t)n * row;
+    if (b->kv_type == LLMK_TYPE_Q8_0) {
+        // value[i] = (float)q[i] * (float)d of i's block: one f32 product, exact (and never -0.0: d >= 0, or NaN)
+        const size_t elems = (size_t)c->L * (slot < 0 ? (size_t)b->P : (size_t)b->n_slots * b->seq_len) * row;
+        const size_t e0 = slot < 0 ? ((size_t)layer * b->P + (pos0 - 1)) * row : (((size_t)layer * b->n_slots + slot) * b->seq_len + (pos0 - 1)) * row;
+        const Q8Rows src = attn_at(BdKv<KvQ8>::view(slot < 0 ? (which ? b->px->d_pv8 : b->px->d_pk8) : (which ? b->d_vc8 : b->d_kc8), elems), e0);
+        std::vector<int8_t> q(cnt);
+        std::vector<uint16_t> d(cnt / 32);
+        HIPCHK(hipMemcpy(q.data(), src.q, cnt, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(d.data(), src.d, cnt / 32 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cnt; ++i) out[i] = (float)q[i] * bd_half_bits_to_float(d[i / 32]);
+        return LLMK_OK;
+    }
     return with_kv_type(b, [&](auto t) -> int {
-        using TC = decltype(t);
+        using TC = std::conditional_t<std::is_same_v<decltype(t), KvQ8>, float, decltype(t)>;      // (q8_0 is answered above)
         const TC* src = slot < 0 ? (which ? BdKv<TC>::pv(*b->px) : BdKv<TC>::pk(*b->px)) + ((size_t)layer * b->P + (pos0 - 1)) * row
                                  : (which ? BdKv<TC>::vc(b) : BdKv<TC>::kc(b)) + (((size_t)layer * b->n_slots + slot) * b->seq_len + (pos0 - 1)) * row;
         if constexpr (std::is_same_v<TC, float>) {
@@ -2958,6 +3003,20 @@ static hipError_t prefix_first(llmk_batch* b, int slot, int first) {
     return hipMemcpyAsync(b->px->d_first + slot, b->px->h_first + slot, sizeof(int), hipMemcpyHostToDevice, b->ctx->stream);
 }
 
+// rows n_pos .. seq_len-1 of `slot` in every layer of a q8_0 batch's caches: quants and scales zeroed, ENQUEUED
+static hipError_t bd_q8_zero(llmk_batch* b, int slot, int n_pos) {
+    llmk_ctx* c = b->ctx;
+    const size_t row = (size_t)c->KV, slot_rows = (size_t)b->seq_len * row, cache = (size_t)c->L * b->n_slots * slot_rows;
+    if (n_pos >= b->seq_len) return hipSuccess;
+    for (DevBuf<int8_t>* buf : {&b->d_kc8, &b->d_vc8})
+        for (int l = 0; l < c->L; ++l) {
+            const Q8Rows at = attn_at(BdKv<KvQ8>::view(*buf, cache), ((size_t)l * b->n_slots + slot) * slot_rows + (size_t)n_pos * row);
+            HIPRET(hipMemsetAsync(at.q, 0, slot_rows - (size_t)n_pos * row, c->stream));
+            HIPRET(hipMemsetAsync(at.d, 0, (slot_rows - (size_t)n_pos * row) / 32 * sizeof(_Float16), c->stream));
+        }
+    return hipSuccess;
+}
+
 int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
     if (!b || slot < 0 || slot >= b->n_slots || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S)) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
@@ -2974,7 +3033,7 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
                 if (n_pos > 0)
                     HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
             }
-    } else {
+    } else if (b->kv_type == LLMK_TYPE_F16) {
         // the same on the f16 caches: zero halves behind n_pos, the context's f32 rows converted (pf_kv_half) in the place of the copy
         for (_Float16* base : {b->d_kc16.get(), b->d_vc16.get()})
             for (int l = 0; l < c->L && (size_t)n_pos < (size_t)b->seq_len; ++l)
@@ -2982,6 +3041,13 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
                                       (slot_rows - (size_t)n_pos * row) * sizeof(_Float16), c->stream));
         if (n_pos > 0)
             HIPCHK(bd_copy_ctx_rows(c, b->d_kc16 + (size_t)slot * slot_rows, b->d_vc16 + (size_t)slot * slot_rows, (size_t)n_pos * row, (size_t)b->n_slots * slot_rows));
+    } else {
+        // ... and on the q8_0 caches: q = 0, d = 0 behind n_pos (which reads back +0.0), the context's rows quantised (bd_to_q8_kernel)
+        const size_t cache = (size_t)c->L * b->n_slots * slot_rows;
+        HIPCHK(bd_q8_zero(b, slot, n_pos));
+        if (n_pos > 0)
+            HIPCHK(bd_copy_ctx_rows(c, attn_at(BdKv<KvQ8>::view(b->d_kc8, cache), (size_t)slot * slot_rows),
+                                    attn_at(BdKv<KvQ8>::view(b->d_vc8, cache), (size_t)slot * slot_rows), (size_t)n_pos * row, (size_t)b->n_slots * slot_rows));
     }
     // a forked or emptied slot is a new sequence: no token fed yet (the caller records the prompt with llmk_rows_set_history)
     if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
@@ -3016,8 +3082,8 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
             constexpr int HS = decltype(hs)::value;
             return with_kv_type(b, [](auto t) -> hipError_t {
                 using TC = decltype(t);
-                HIPRET(hipFuncSetAttribute((const void*)bd_attn_prefix_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS)));
-                return hipFuncSetAttribute((const void*)bd_attn_own_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+                HIPRET(hipFuncSetAttribute((const void*)BdAttn<HS, TC>::prefix, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS)));
+                return hipFuncSetAttribute((const void*)BdAttn<HS, TC>::own, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
             });
         }));
         b->px = std::move(px);
@@ -3027,11 +3093,11 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
     rc = with_kv_type(b, [&](auto t) -> int {
         using TC = decltype(t);
         auto &pk = BdKv<TC>::pk(*b->px), &pv = BdKv<TC>::pv(*b->px);
-        if (pv.size() < px_rows) b->P = 0;
+        if (pv.size() < BdKv<TC>::units(px_rows)) b->P = 0;
         int rc_;
-        if ((rc_ = bd_alloc_rc(pk.reserve(px_rows, c->stream))) != LLMK_OK) return rc_;
-        if ((rc_ = bd_alloc_rc(pv.reserve(px_rows, c->stream))) != LLMK_OK) return rc_;
-        HIPCHK(bd_copy_ctx_rows(c, pk.get(), pv.get(), (size_t)n_pos * row, (size_t)n_pos * row));
+        if ((rc_ = bd_alloc_rc(pk.reserve(BdKv<TC>::units(px_rows), c->stream))) != LLMK_OK) return rc_;
+        if ((rc_ = bd_alloc_rc(pv.reserve(BdKv<TC>::units(px_rows), c->stream))) != LLMK_OK) return rc_;
+        HIPCHK(bd_copy_ctx_rows(c, BdKv<TC>::view(pk, px_rows), BdKv<TC>::view(pv, px_rows), (size_t)n_pos * row, (size_t)n_pos * row));
         return LLMK_OK;
     });
     if (rc) return rc;
@@ -3050,10 +3116,14 @@ int llmk_prefix_attach(llmk_batch* b, int slot) {
     const size_t slot_rows = (size_t)b->seq_len * c->KV;
     HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
         using TC = decltype(t);
-        for (TC* base : {BdKv<TC>::kc(b).get(), BdKv<TC>::vc(b).get()})
-            for (int l = 0; l < c->L; ++l)
-                HIPRET(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(TC), c->stream));
-        return hipSuccess;
+        if constexpr (std::is_same_v<TC, KvQ8>) {
+            return bd_q8_zero(b, slot, 0);
+        } else {
+            for (TC* base : {BdKv<TC>::kc(b).get(), BdKv<TC>::vc(b).get()})
+                for (int l = 0; l < c->L; ++l)
+                    HIPRET(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(TC), c->stream));
+            return hipSuccess;
+        }
     }));
     if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     HIPCHK(prefix_first(b, slot, b->P));
@@ -3334,7 +3404,7 @@ static int span_setup(llmk_batch* b, int rows) {
     HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
         constexpr int HS = decltype(hs)::value;
         return with_kv_type(b, [](auto t) -> hipError_t {
-            return hipFuncSetAttribute((const void*)bd_attn_span_kernel<HS, decltype(t)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+            return hipFuncSetAttribute((const void*)BdAttn<HS, decltype(t)>::span, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
         });
     }));
     b->sn = std::move(sn);

@@ -9,7 +9,7 @@
 !         [--ak] [-d device] [--device-argmax] [--device-sample] [--prefill] [--timings] [--seed N] [--stream-load] [--ngpu N]
 !         [--top-k N] [--top-p P] [--min-p M]
 !         [--repeat-penalty R] [--repeat-last-n N] [--presence-penalty P] [--frequency-penalty F] [--logit-bias ID:B]...
-!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix] [--kv-f16] [--prompts FILE]]
+!         [--ngpu N [--tp-rccl]] [--gguf-eps] [--gguf-rope-base] [--encode] [--score] [--logprobs N] [--parallel N [--share-prefix] [--kv-f16 | --kv-q8] [--prompts FILE]]
 !
 ! --parallel N (1 .. 128, one GPU): N completions of the prompt decoded TOGETHER (llmk_batch_*, DESIGN.md section 3i) -- the prompt is
 ! prefilled once and forked into N slots, every pass over the weights serves all N; seeds seed, seed+1, ... at -t > 0 (the filter
@@ -18,6 +18,9 @@
 ! attention reads the prompt rows once per group of rows, not once per row.
 ! --kv-f16: the N slots' K/V caches -- and the shared prefix -- hold IEEE halves (llmk_cache_create): half the bytes per pass and per
 ! slot, the stored values rounded to nearest even and saturated at +-65504.  Refused without --parallel: the context's own cache is f32.
+! --kv-q8: they hold ggml's q8_0 blocks instead (32 int8 quants and an f16 scale: 17/64 of the f32 bytes).  About 25 times coarser than
+! f16 -- the logits move by about 1e-2 of their largest (include/llmk.h) -- so it is the caller's opt-in; kv_dim must be a multiple of 32.
+! Refused without --parallel and together with --kv-f16 (a batch has one cache type).
 ! --prompts FILE: line j (0-based) of FILE is slot j's OWN prompt (fewer than N lines is an error).  The prompts are ingested through
 ! the batch itself -- llmk_span_forward, the slots' chunks packed into passes of at most 128 rows -- and the N completions then run
 ! together from their own positions.  Refused with -p and with --share-prefix (there is no common prompt).
@@ -60,6 +63,7 @@ module arg_parse
                                            ! 1e-5 and 10000, llama2.f90:454,545)
      logical :: encode_only       ! extension: print the prompt's 1-based token ids (bpe_encode) and stop -- no device needed
      logical :: share_prefix      ! extension: --share-prefix: the --parallel slots share ONE copy of the prompt's K/V rows (llmk_prefix_*)
+     logical :: kv_q8             ! extension: --kv-q8: they are q8_0 blocks (llmk_cache_create with LLMK_TYPE_Q8_0)
      logical :: kv_f16            ! extension: --kv-f16: the --parallel slots' K/V caches and the shared prefix are f16 (llmk_cache_create)
      character(:), allocatable :: prompts_file   ! extension: --prompts FILE: one prompt per --parallel slot, a line each (llmk_span_*)
      integer :: parallel          ! extension: --parallel N (0 = off): N completions decoded together on one GPU (llmk_batch_*)
@@ -110,6 +114,7 @@ contains
     a%parallel = 0
     a%share_prefix = .false.
     a%kv_f16 = .false.
+    a%kv_q8 = .false.
     a%prompts_file = ""
 
     nargs = command_argument_count()
@@ -152,6 +157,7 @@ contains
        case ("--score");             a%score = .true.;         i = i + 1
        case ("--share-prefix");      a%share_prefix = .true.;  i = i + 1
        case ("--kv-f16");            a%kv_f16 = .true.;        i = i + 1
+       case ("--kv-q8");             a%kv_q8 = .true.;         i = i + 1
        case ("--prompts");           a%prompts_file = trim(val); i = i + 2
        case ("--parallel")
           read (val, *) a%parallel
@@ -342,6 +348,14 @@ program llm
      print *, "--kv-f16: only the K/V caches of --parallel N can be f16 (the context's own cache stays f32)"
      stop 1
   end if
+  if (opts%kv_q8 .and. opts%parallel == 0) then
+     print *, "--kv-q8: only the K/V caches of --parallel N can be q8_0 (the context's own cache stays f32)"
+     stop 1
+  end if
+  if (opts%kv_q8 .and. opts%kv_f16) then
+     print *, "--kv-q8: a batch's K/V caches have one type: drop --kv-f16 or --kv-q8"
+     stop 1
+  end if
   if (opts%prompts_file /= "") then
      if (opts%parallel == 0) then
         print *, "--prompts: one prompt per slot needs the slots: add --parallel N"
@@ -504,18 +518,20 @@ program llm
      end if
      if (opts%kv_f16) then
         rc = llmk_cache_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), 1_c_int, pbatch)      ! LLMK_TYPE_F16
+     else if (opts%kv_q8) then
+        rc = llmk_cache_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), 8_c_int, pbatch)      ! LLMK_TYPE_Q8_0
      else
         rc = llmk_batch_create(ctx, int(opts%parallel, c_int), int(seq_len, c_int), pbatch)
      end if
      if (rc == 2) then                               ! LLMK_E_SHAPE
         print *, "--parallel: this model's shape has no batched pass (emb_dim and hidden_dim must be multiples of 64, kv_dim of 16, " // &
-             "at most 16 query heads per kv head)"
+             "at most 16 query heads per kv head; with --kv-q8 kv_dim must be a multiple of 32)"
         stop 1
      end if
      call llmk_check(rc, "llmk_batch_create")
      if (opts%verbose_ext) then
         call llmk_check(llmk_cache_bytes(pbatch, kv_bytes), "llmk_cache_bytes")
-        print '(A,A,A,I0,A,I0,A)', " batch K/V caches: ", merge("f16", "f32", llmk_cache_type(pbatch) == 1), ", ", opts%parallel, &
+        print '(A,A,A,I0,A,I0,A)', " batch K/V caches: ", trim(merge("q8_0", merge("f16 ", "f32 ", llmk_cache_type(pbatch) == 1), llmk_cache_type(pbatch) == 8)), ", ", opts%parallel, &
              " slots, ", kv_bytes, " bytes"
      end if
      t_start = clock_ticks()

@@ -332,7 +332,8 @@ module llmk_binding
        import :: c_int, c_ptr
        type(c_ptr), value :: batch
      end function
-     ! a batch whose K/V caches (and shared prefix) have the element type kv_type: 0 = f32 (llmk_batch_create itself), 1 = f16
+     ! a batch whose K/V caches (and shared prefix) have the element type kv_type: 0 = f32 (llmk_batch_create itself), 1 = f16,
+     ! 8 = q8_0 (ggml's blocks of 32 int8 quants and an f16 scale; kv_dim a multiple of 32)
      integer(c_int) function llmk_cache_create(ctx, n_slots, seq_len, kv_type, batch) bind(C, name="llmk_cache_create")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx

@@ -70,6 +70,7 @@ def sampler(temperature: float, seed: int, top_k: int = 0, top_p: float = 1.0, m
 MAX_LOGIT_BIAS = 256
 MAX_BATCH = 128
 KV_TYPES = {"f32": 0, "f16": 1}             # a batch's K/V cache types (llmk_cache_create): LLMK_TYPE_F32 / LLMK_TYPE_F16
+KV_CACHE_TYPES = {**KV_TYPES, "q8_0": 8}    # ... and all of them: LLMK_TYPE_Q8_0 (blocks of 32 int8 quants and an f16 scale) joins
 CLS_NONE, CLS_GEMM, CLS_ROWS = 0, 1, 2      # llmk_cls_form: LLMK_CLS_*
 
 
@@ -616,8 +617,10 @@ class Batch:
     Llmk context `model`; every pass takes one position of up to n_slots of them.  Slots count from 0; tokens and positions are
     1-based.  Calls on a batch and on its context must not overlap.  Close the batch before its context.
     kv_type "f16": the slots' caches and the shared prefix hold IEEE halves (llmk_cache_create) -- half the bytes, the stored values
-    rounded to nearest even and saturated at +-65504 (include/llmk.h); "f32" is llmk_batch_create, as before.  An int is passed
-    through as the LLMK_TYPE_* id it is."""
+    rounded to nearest even and saturated at +-65504 (include/llmk.h); "f32" is llmk_batch_create, as before.  "q8_0": ggml's q8_0
+    blocks, 17/64 of the f32 bytes -- about 25 times coarser than f16 (the logits move by about 1e-2 of max |logit| on the test
+    models: include/llmk.h), the caller's opt-in and never a default; kv_dim must be a multiple of 32.  An int is passed through as
+    the LLMK_TYPE_* id it is."""
 
     def __init__(self, model: Llmk, n_slots: int, seq_len: int | None = None, kv_type="f32"):
         self.model, self.n_slots, self.V = model, n_slots, model.V
@@ -625,17 +628,17 @@ class Batch:
         if kv_type == "f32":
             _ck(lib().llmk_batch_create(model._h, n_slots, seq_len or model.shape.seq_len, C.byref(self._h)))
         else:
-            if isinstance(kv_type, str) and kv_type not in KV_TYPES:
-                raise ValueError(f"kv_type {kv_type!r}: one of {sorted(KV_TYPES)}")
-            _ck(lib().llmk_cache_create(model._h, n_slots, seq_len or model.shape.seq_len, KV_TYPES.get(kv_type, kv_type), C.byref(self._h)))
+            if isinstance(kv_type, str) and kv_type not in KV_CACHE_TYPES:
+                raise ValueError(f"kv_type {kv_type!r}: one of {sorted(KV_CACHE_TYPES)}")
+            _ck(lib().llmk_cache_create(model._h, n_slots, seq_len or model.shape.seq_len, KV_CACHE_TYPES.get(kv_type, kv_type), C.byref(self._h)))
 
     @property
     def kv_type(self) -> str:
-        """"f32" or "f16": the element type of the batch's K/V caches and prefix (llmk_cache_type)"""
+        """"f32", "f16" or "q8_0": the element type of the batch's K/V caches and prefix (llmk_cache_type)"""
         t = lib().llmk_cache_type(self._h)
         if t < 0:
             _ck(-t)
-        return {v: k for k, v in KV_TYPES.items()}[t]
+        return {v: k for k, v in KV_CACHE_TYPES.items()}[t]
 
     def cache_bytes(self) -> int:
         """device bytes of the K/V caches plus the prefix rows, if any (llmk_cache_bytes)"""

@@ -24,7 +24,7 @@ figures alone (--forked-only: the same from this build, no prefix ever set).
 
 times the pass at 8, 32 and 128 rows, at positions 25 and --pos, with f32 and with f16 K/V caches (llmk_cache_create): two batches in
 ONE process, the types alternating measurement by measurement; forked slots, and -- with --shared-prefix P, at --pos -- slots attached
-behind P positions.  --kv f32 | f16 measures one type alone.
+behind P positions.  --kv f32 | f16 | q8_0 measures one type alone, --kv all the three (q8_0: llmk_cache_create with LLMK_TYPE_Q8_0).
 
     python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k --spans
 
@@ -206,7 +206,9 @@ def spans(m, shape, pos: int, iters: int, repeats: int):
     """--spans: the three measurements of profiles/batch_spans.txt, every figure the median of `repeats` behind a warm-up"""
     out = {"a": [], "b": {}, "c": {}}
     pos0 = pos - 127
-    for kind in ("f32", "f16"):
+    for kind in ("f32", "f16", "q8_0"):
+        if kind == "q8_0" and shape.kv_dim % 32:      # (no q8_0 caches on this shape)
+            continue
         os.environ["LLMK_SPAN_ATTN"] = "0"
         try:
             rows_b = llmk.Batch(m, 1, pos, kv_type=kind)
@@ -292,10 +294,11 @@ def print_kv(shape_name, type_name, kinds, rows, iters, repeats):
     print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
     print(f"# batched decode by K/V cache type, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per type, "
           f"the types alternating in one process (spread = (max - min) / median)")
-    print(f"{'n':>5} {'pos':>6} {'form':>9} {'behind':>7} " + " ".join(f"{k + ' ms':>10} {'spread':>7}" for k in kinds) + (f" {'f32 / f16':>10}" if len(kinds) == 2 else ""))
+    ratios = [(a, b) for a, b in (("f32", "f16"), ("f16", "q8_0")) if a in kinds and b in kinds]
+    print(f"{'n':>5} {'pos':>6} {'form':>9} {'behind':>7} " + " ".join(f"{k + ' ms':>10} {'spread':>7}" for k in kinds) + "".join(f" {a + ' / ' + b:>11}" for a, b in ratios))
     for r in rows:
         cells = " ".join(f"{r[k + '_ms']:10.3f} {r[k + '_spread']:7.3f}" for k in kinds)
-        ratio = f" {r['f32_ms'] / r['f16_ms']:10.2f}" if len(kinds) == 2 else ""
+        ratio = "".join(f" {r[a + '_ms'] / r[b + '_ms']:11.2f}" for a, b in ratios)
         print(f"{r['n']:5d} {r['pos']:6d} {r['form']:>9} {r['behind']:7d} {cells}{ratio}")
 
 
@@ -340,9 +343,10 @@ def main():
     ap.add_argument("--forked-only", action="store_true",
                     help="with --shared-prefix: only the forked figures, no prefix is ever set (what another build selected with LLMK_LIB "
                          "that has no llmk_prefix_* measures: the like-for-like baseline of the unshared path)")
-    ap.add_argument("--kv", choices=["f32", "f16", "both"], default=None,
-                    help="only the K/V-type table: the pass at 8, 32 and 128 rows at positions 25 and --pos on batches with f32 and / or f16 "
-                         "K/V caches, alternating in one process; with --shared-prefix P also attached behind P positions at --pos")
+    ap.add_argument("--kv", choices=["f32", "f16", "q8_0", "both", "all"], default=None,
+                    help="only the K/V-type table: the pass at 8, 32 and 128 rows at positions 25 and --pos on batches with f32, f16 and / or "
+                         "q8_0 K/V caches (both: f32 and f16; all: the three), alternating in one process; with --shared-prefix P also "
+                         "attached behind P positions at --pos")
     ap.add_argument("--spans", action="store_true",
                     help="only the span tables (llmk_span_*): a 128-row span ending at --pos with and without bd_attn_span_kernel, a prompt "
                          "in spans against prefill + fork, 112 decode rows with and without a 16-row chunk")
@@ -365,7 +369,7 @@ def main():
             print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "sampled": rows}))
         return
     if a.kv:
-        kinds = ("f32", "f16") if a.kv == "both" else (a.kv,)
+        kinds = {"both": ("f32", "f16"), "all": ("f32", "f16", "q8_0")}.get(a.kv, (a.kv,))
         rows = kv_types(m, shape, kinds, a.shared_prefix, a.pos, a.iters, a.repeats)
         m.close()
         print_kv(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), kinds, rows, a.iters, a.repeats)
