@@ -1120,13 +1120,18 @@ template <class SH>
 struct TkAtt {
     static constexpr int HS = SH::HS, LPT = HS / 4, TPW = 64 / LPT, TPB = TK_WAVES * TPW, U = 8, TILE = TPB * U;
     float4 kv[U], vv[U];
+    int lane;   // (laundered per layer in prefetch: what tk_attention derives from it -- LDS and cross-lane addresses, timestep indices -- is
+                // recomputed there, a handful of VALU instructions, instead of being hoisted out of the layer loop into registers that
+                // would then be live through the whole kernel; the kernels sit at the register ceiling)
     // K and V rows of the first TILE (= 256) timesteps (written by earlier launches) are requested at the START of
     // the layer's attention, long before q exists: by the time q arrives they have crossed the loaded memory system.
     // (The 64 registers are the two ring entries the QKV phase has just consumed and not yet refilled; an attention
     // CU streams no QKV / wo tiles, so nothing else of its own is queued ahead of the q poll.)
     // Only contexts longer than TILE pay exposed round trips.
     __device__ __forceinline__ void prefetch(const TokenArgs& a, int l, int h, int pos, int tid, int t0 = 0) {
-        const int lane = tid & 63, wid = tid >> 6;
+        const int wid = tid >> 6;
+        lane = tid & 63;
+        asm volatile("" : "+v"(lane));
         const int g = h / SH::KVMUL, sub = lane % LPT, tl = lane / LPT;
         const __amdgpu_buffer_rsrc_t rk = tk_rsrc(a.kc + (size_t)l * a.S * SH::KV, a.S * SH::KV * 4);
         const __amdgpu_buffer_rsrc_t rv = tk_rsrc(a.vc + (size_t)l * a.S * SH::KV, a.S * SH::KV * 4);
@@ -1187,6 +1192,103 @@ __device__ __forceinline__ float tstep_sum(float v) {
     return v;
 }
 
+// The scores of the first NB batches of a tile as straight-line code: NB independent chains (dot4, the DPP tree, the scale)
+// that the scheduler interleaves, and one predicated store per batch.  NB is the tile's live batches rounded up to 1, 2, 4
+// or 8 (tk_att_scores): a dead batch holds clamped rows and its timesteps are >= tcache, so it is computed and not stored.
+// t = the lane's timestep in batch 0; last = the lane that holds the timestep's sum (tstep_sum).
+template <class SH, int NB, int U0 = 0>
+__device__ __forceinline__ void tk_att_scores_nb(const float4& qv, const float4 (&kv)[TkAtt<SH>::U], float* att, int t, int tcache, bool last) {
+    constexpr int LPT = SH::HS / 4, TPB = TkAtt<SH>::TPB;
+    const float scale = sqrtf((float)SH::HS);
+    float d[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) d[u] = dot4(qv, kv[U0 + u], 0.f);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) d[u] = tstep_sum<LPT>(d[u]);
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+        if (last && t + (U0 + u) * TPB < tcache) att[t + (U0 + u) * TPB] = d[u] / scale;              // :582
+}
+// (eight batches as two groups of four: four chains already hide the DPP wait states, and eight at once cost registers)
+template <class SH, int NB, int U0 = 0>
+__device__ __forceinline__ void tk_att_scores_grp(const float4& qv, const float4 (&kv)[TkAtt<SH>::U], float* att, int t, int tcache, bool last) {
+    if constexpr (NB > 4) {
+        tk_att_scores_nb<SH, 4, U0>(qv, kv, att, t, tcache, last);
+        tk_att_scores_grp<SH, NB - 4, U0 + 4>(qv, kv, att, t, tcache, last);
+    } else {
+        tk_att_scores_nb<SH, NB, U0>(qv, kv, att, t, tcache, last);
+    }
+}
+// n = the timesteps from the tile's first one to the end of the part (block-uniform)
+template <class SH>
+__device__ __forceinline__ void tk_att_scores(const float4& qv, const float4 (&kv)[TkAtt<SH>::U], float* att, int t, int n, int tcache, bool last) {
+    constexpr int TPB = TkAtt<SH>::TPB;
+    static_assert(TkAtt<SH>::U == 8, "the variants are 1, 2, 4 and 8 batches");
+    if (n > 4 * TPB) tk_att_scores_grp<SH, 8>(qv, kv, att, t, tcache, last);
+    else if (n > 2 * TPB) tk_att_scores_grp<SH, 4>(qv, kv, att, t, tcache, last);
+    else if (n > TPB) tk_att_scores_grp<SH, 2>(qv, kv, att, t, tcache, last);
+    else tk_att_scores_grp<SH, 1>(qv, kv, att, t, tcache, last);
+}
+
+// Softmax and V accumulation of a part that is ONE tile, from the scores in LDS to the wave's partial output (tk_attention).
+// NB = the live batches rounded up to 1, 2, 4 or 8: more than NB / 2 of them are live.
+template <class SH, int NB>
+__device__ __forceinline__ float4 tk_att_one_tile(const float* att, const float4* vcur, const float4 (&vv)[TkAtt<SH>::U], int t0, int t1, bool own, int npast,
+                                                  int lane, int tb, int sub, unsigned long long* dbg, float& m_out, float& s_out) {
+    constexpr int TPB = TkAtt<SH>::TPB;
+    const int n = t1 - t0;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    constexpr int NS = (NB * TPB + WAVE - 1) / WAVE;                 // score registers of a lane
+    float sc[NS], w[NS];
+    bool lv[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int t = t0 + lane + i * WAVE;
+        lv[i] = t < t1;
+        sc[i] = att[min(t, t1 - 1)];
+    }
+    float4 vc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (own) vc = vcur[sub];                                         // (requested with the scores: one round trip)
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) m = fmaxf(m, lv[i] ? sc[i] : -INFINITY);
+    m = wave_max(m);
+    if (TK_DEBUG && dbg) dbg[3] = wall_clock64();
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        w[i] = 0.f;
+        if (i == 0 || i * WAVE < n) w[i] = lv[i] ? expf(sc[i] - m) : 0.f;
+        s += w[i];
+    }
+    s = wave_sum(s);
+    m_out = m;
+    s_out = s;
+    if (TK_DEBUG && dbg) dbg[4] = wall_clock64();
+    // xi/sum(xi) (:476) once per timestep, in the lane that holds it
+#pragma unroll
+    for (int i = 0; i < NS; ++i)
+        if (i == 0 || i * WAVE < n) w[i] = lv[i] ? w[i] / s : 0.f;
+    float p[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) p[u] = __shfl(w[(u * TPB) / WAVE], (u * TPB) % WAVE + tb, WAVE);
+    const int o = own ? npast - t0 : -1;   // the one V row that is this token's own comes from LDS
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        if (u < NB / 2 || u * TPB < n) {
+            float4 v4 = vv[u];
+            if (u == o / TPB) {      // (block-uniform: one batch pays the select)
+                if (tb == o % TPB) v4 = vc;
+            }
+            acc.x = fmaf(p[u], v4.x, acc.x);
+            acc.y = fmaf(p[u], v4.y, acc.y);
+            acc.z = fmaf(p[u], v4.z, acc.z);
+            acc.w = fmaf(p[u], v4.w, acc.w);
+        }
+    }
+    return acc;
+}
+
 template <class SH>
 __device__ __forceinline__ void tk_attention(const TokenArgs& a, char* lds, int l, int h, int pos, int tid, TkAtt<SH>& pa,
                                              unsigned long long* dbg = nullptr, int t0 = 0, int t1 = -1, float* m_out = nullptr,
@@ -1194,9 +1296,10 @@ __device__ __forceinline__ void tk_attention(const TokenArgs& a, char* lds, int 
     if (t1 < 0) t1 = pos;           // timesteps [t0, t1) of the pos in all (TkAttPlan); t1 == pos includes this token's own
     constexpr int HS = SH::HS, LPT = HS / 4, TPW = 64 / LPT, TPB = TK_WAVES * TPW, U = TkAtt<SH>::U, TILE = TPB * U;
     static_assert(LPT == 16 || LPT == 32, "a timestep is one or two DPP rows");
+    static_assert(WAVE % TPB == 0, "a batch of timesteps lies within one 64-lane stride of the scores (the one-tile weights)");
     float4 (&kv)[U] = pa.kv;
     float4 (&vv)[U] = pa.vv;
-    const int lane = tid & 63, wid = tid >> 6;
+    const int lane = pa.lane, wid = tid >> 6;
     const int g = h / SH::KVMUL;
     const float* qs = reinterpret_cast<const float*>(lds + TkLds<SH>::ATT_Q);
     const float4* kcur = reinterpret_cast<const float4*>(qs + HS);
@@ -1215,70 +1318,81 @@ __device__ __forceinline__ void tk_attention(const TokenArgs& a, char* lds, int 
     const int tmax = max(npast - 1, 0);
     const int tcache = min(npast, t1);
 
-    float* ex = att + a.S;                                                      // exp(score - max), written per wave
-    float* pw = reinterpret_cast<float*>(lds + TkLds<SH>::ATT_P) + wid * 32;    // this wave's U*TPW (<= 32) weights of a batch
+    const int n = t1 - t0;                                                      // this part's timesteps (block-uniform)
+    const bool own = t1 == pos;                                                 // ... of which the last is this token's own
     for (int base = t0; base < t1; base += TILE) {
         if (base > t0) {
 #pragma unroll
             for (int u = 0; u < U; ++u) kv[u] = tk_ldkv(rk, min(base + u * TPB + tb, tmax) * rowb + col);
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (base + u * TPB < t1) {   // block-uniform: short contexts skip the empty batches
-                const int t = base + u * TPB + tb;
-                // rows >= pos-1 read a clamped (wrong) row: t = pos-1 is redone from LDS below, later ones are never used
-                const float d = tstep_sum<LPT>(dot4(qv, kv[u], 0.f));
-                if (sub == LPT - 1 && t < tcache) att[t] = d / scale;              // :582
-            }
-        }
+        // rows >= pos-1 read a clamped (wrong) row: t = pos-1 is redone from LDS below, later ones are never stored
+        tk_att_scores<SH>(qv, kv, att, base + tb, t1 - base, tcache, sub == LPT - 1);
     }
-    if (t1 == pos) {   // this token's own key never went through the cache
+    if (own) {   // this token's own key never went through the cache
         const float d = tstep_sum<LPT>(dot4(qv, kcur[sub], 0.f));
         if (wid == 0 && lane == LPT - 1) att[npast] = d / scale;
     }
     if (TK_DEBUG && dbg) dbg[0] = wall_clock64();
     tk_barrier();
     if (TK_DEBUG && dbg) dbg[1] = wall_clock64();
-    // every wave folds max and sum over ALL scores itself: no cross-wave reduction, no extra barriers.  exp() is
-    // evaluated once per score here (each wave keeps its own copy of what it wrote: same values, benign overlap)
-    float m = -INFINITY;
-    for (int t = t0 + lane; t < t1; t += WAVE) m = fmaxf(m, att[t]);
-    m = wave_max(m);
-    if (TK_DEBUG && dbg) dbg[3] = wall_clock64();
-    float s = 0.f;
-    for (int t = t0 + lane; t < t1; t += WAVE) {
-        const float e = expf(att[t] - m);
-        ex[t] = e;
-        s += e;
-    }
-    s = wave_sum(s);
-    if (m_out) { *m_out = m; *s_out = s; }
-    if (TK_DEBUG && dbg) dbg[4] = wall_clock64();
-
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int base = t0; base < t1; base += TILE) {
-        if (base > t0) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) vv[u] = tk_ldkv(rv, min(base + u * TPB + tb, tmax) * rowb + col);
+    float pmax, psum;                                                           // the part's maximum and sum of exponentials
+    if (n <= TILE) {
+        // ONE TILE (every part up to seq_len 2048 at head size 64, 1024 at head size 128): a lane's scores t0 + lane, + 64, ...
+        // are at most TILE / 64 registers.  They are read from LDS once, all reads in flight together; the maximum, the
+        // exponentials, the sum and the weights ex / s stay in those registers, and a lane fetches the weights of ITS
+        // timesteps (batch u: t0 + u * TPB + tb, held by lane (u * TPB) % 64 + tb in register u * TPB / 64) with one round of
+        // cross-lane reads: no exp[] and no weight table in LDS, no LDS round trip between the sum and the first V FMA.
+        // Same values, same operations, same order as the loops of the general path below.
+        if (n > 4 * TPB) acc = tk_att_one_tile<SH, 8>(att, vcur, vv, t0, t1, own, npast, lane, tb, sub, dbg, pmax, psum);
+        else if (n > 2 * TPB) acc = tk_att_one_tile<SH, 4>(att, vcur, vv, t0, t1, own, npast, lane, tb, sub, dbg, pmax, psum);
+        else if (n > TPB) acc = tk_att_one_tile<SH, 2>(att, vcur, vv, t0, t1, own, npast, lane, tb, sub, dbg, pmax, psum);
+        else acc = tk_att_one_tile<SH, 1>(att, vcur, vv, t0, t1, own, npast, lane, tb, sub, dbg, pmax, psum);
+    } else {
+        // longer parts: every wave folds max and sum over ALL scores itself: no cross-wave reduction, no extra barriers.  exp() is
+        // evaluated once per score here (each wave keeps its own copy of what it wrote: same values, benign overlap)
+        float* ex = att + a.S;                                                      // exp(score - max), written per wave
+        float* pw = reinterpret_cast<float*>(lds + TkLds<SH>::ATT_P) + wid * 32;    // this wave's U*TPW (<= 32) weights of a batch
+        float m = -INFINITY;
+        for (int t = t0 + lane; t < t1; t += WAVE) m = fmaxf(m, att[t]);
+        m = wave_max(m);
+        if (TK_DEBUG && dbg) dbg[3] = wall_clock64();
+        float s = 0.f;
+        for (int t = t0 + lane; t < t1; t += WAVE) {
+            const float e = expf(att[t] - m);
+            ex[t] = e;
+            s += e;
         }
-        // xi/sum(xi) (:476) once per timestep: lane i < U*TPW owns timestep (u = i / TPW, tl = i % TPW) of this wave
-        if (lane < U * TPW) {
-            const int t = base + (lane / TPW) * TPB + wid * TPW + (lane % TPW);
-            pw[lane] = (t < t1) ? ex[t] / s : 0.f;
-        }
+        s = wave_sum(s);
+        pmax = m;
+        psum = s;
+        if (TK_DEBUG && dbg) dbg[4] = wall_clock64();
+
+        for (int base = t0; base < t1; base += TILE) {
+            if (base > t0) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (base + u * TPB < t1) {
-                const int t = base + u * TPB + tb;
-                const float4 v4 = (t == npast) ? vcur[sub] : vv[u];
-                const float p = pw[u * TPW + tl];
-                acc.x = fmaf(p, v4.x, acc.x);
-                acc.y = fmaf(p, v4.y, acc.y);
-                acc.z = fmaf(p, v4.z, acc.z);
-                acc.w = fmaf(p, v4.w, acc.w);
+                for (int u = 0; u < U; ++u) vv[u] = tk_ldkv(rv, min(base + u * TPB + tb, tmax) * rowb + col);
+            }
+            // xi/sum(xi) (:476) once per timestep: lane i < U*TPW owns timestep (u = i / TPW, tl = i % TPW) of this wave
+            if (lane < U * TPW) {
+                const int t = base + (lane / TPW) * TPB + wid * TPW + (lane % TPW);
+                pw[lane] = (t < t1) ? ex[t] / s : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (base + u * TPB < t1) {
+                    const int t = base + u * TPB + tb;
+                    const float4 v4 = (t == npast) ? vcur[sub] : vv[u];
+                    const float p = pw[u * TPW + tl];
+                    acc.x = fmaf(p, v4.x, acc.x);
+                    acc.y = fmaf(p, v4.y, acc.y);
+                    acc.z = fmaf(p, v4.z, acc.z);
+                    acc.w = fmaf(p, v4.w, acc.w);
+                }
             }
         }
     }
+    if (m_out) { *m_out = pmax; *s_out = psum; }
     red[(wid * TPW + tl) * LPT + sub] = acc;   // the service wave folds the waves*TPW partials per dim
     if (TK_DEBUG && dbg) dbg[2] = wall_clock64();
 }
@@ -1550,6 +1664,9 @@ __device__ __forceinline__ void tk_service(const TokenArgs& a, char* lds, int c,
             tk_barrier();
             float pm, ps;       // this part's maximum and sum of exponentials
             tk_attention<SH>(a, lds, l, my_head, pos, tid, pa, (tr && lane == 0 && l < 22) ? tr + (32 + l) * 16 + 10 : nullptr, at0, at1, &pm, &ps);
+            // (wave-uniform, and opaque to the optimiser from here on: with the part's maximum and sum traced back into tk_attention's variants hipcc
+            // contracts the part merge below into other multiply-adds than it did before them -- other bits from 257 timesteps on)
+            asm volatile("" : "+s"(pm), "+s"(ps));
             tk_barrier();
             TK_STAMP(6);
             // fold the waves*TPW partial output vectors: lane = output dim, one conflict-free ds_read_b32 per partial
