@@ -234,16 +234,17 @@ struct llmk_ctx {
 };
 typedef llmk_ctx::PfLane PfLane;
 
+// a K block and a V block in a batch's element type: the bytes are owned here, BdKv<T> (below) is the one place that says what they hold
+struct BdStore { DevBuf<char> k, v; };
+
 // Batched decode (batch.h): K/V caches of its own for n_slots sequences on the context's weights.  A pass runs on
 // the context's stream through lane 0 of its prefill workspaces and the scoring partials (calls on a batch and on its context are
 // serialised by the caller, as all calls on a context are); what a pass needs beyond them is here.
 struct llmk_batch {
     llmk_ctx* ctx = nullptr;
     int n_slots = 0, seq_len = 0;
-    int kv_type = LLMK_TYPE_F32;                 // the caches' and the prefix's element type (llmk_cache_create): ONE pair of each is allocated
-    DevBuf<float> d_kc, d_vc;                    // [L][n_slots][seq_len][KV], an f32 batch's ...
-    DevBuf<_Float16> d_kc16, d_vc16;             // ... and an f16 batch's (BdKv<T> below picks the pair by element type)
-    DevBuf<int8_t> d_kc8, d_vc8;                 // a q8_0 batch's: the quants in that order, then the scales [L][n_slots][seq_len][KV / 32] f16 (BdKv<KvQ8>)
+    int kv_type = LLMK_TYPE_F32;                 // the caches' and the prefix's element type (llmk_cache_create)
+    BdStore cache;                               // [L][n_slots][seq_len][KV] in that type (BdKv<T> below says what the bytes hold)
     DevBuf<BdRow> d_rows;                        // [LLMK_MAX_BATCH] row words
     DevBuf<int> d_tok;                           // [LLMK_MAX_BATCH] 0-based fed ids
     DevBuf<float> d_out;                         // [2 * LLMK_MAX_BATCH]: (unused log-probs), then the rows' first maxima (1-based ints)
@@ -273,11 +274,7 @@ struct llmk_batch {
         PinnedBuf<int> h_first;                  // ... and the pinned words it is copied from
         DevBuf<int> d_colmap;                    // [LLMK_MAX_BATCH + BD_MAX_GROUP] bd_attn_prefix_kernel's column map
         PinnedBuf<int> h_colmap;
-        DevBuf<float> d_xpo;                     // part states of a pass with attached rows:
-        DevBuf<float2> d_xpml;                   //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_xpo that [hs]
-        DevBuf<float> d_pk, d_pv;                // [L][P][KV]: a snapshot of the context's rows of positions 1..P, grown by reserve
-        DevBuf<_Float16> d_pk16, d_pv16;         // the same in an f16 batch: the prefix has the batch's type
-        DevBuf<int8_t> d_pk8, d_pv8;             // ... and in a q8_0 batch: quants [L][P][KV], then scales [L][P][KV / 32]
+        BdStore rows;                            // [L][P][KV] in the batch's type: a snapshot of the context's rows of positions 1..P, grown by reserve
     };
     std::unique_ptr<Prefix> px;
     int pass_att = 0;                            // attached rows among the rows bd_upload_rows uploaded last
@@ -285,10 +282,15 @@ struct llmk_batch {
     struct Spans {
         DevBuf<BdGroup> d_groups;                // [LLMK_MAX_BATCH] the pass's column groups ...
         PinnedBuf<BdGroup> h_groups;             // ... and the pinned words they are copied from
-        DevBuf<float> d_spo;                     // part states of a span pass, in the layout of a pass with attached rows:
-        DevBuf<float2> d_spml;                   //   [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L}, d_spo that [hs]
     };
     std::unique_ptr<Spans> sn;
+    // part states of a pass with attached rows and of a span pass (one purpose per pass, on the context's one stream), built by
+    // whichever of llmk_prefix_set and span_setup needs them first (bd_part_states)
+    struct PartStates {
+        DevBuf<float2> d_ml;                     // [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L} ...
+        DevBuf<float> d_o;                       // ... and that [hs] unnormalised outputs
+    };
+    std::unique_ptr<PartStates> ps;
     bool span_attn = true;                       // LLMK_SPAN_ATTN=0 at create: span passes run the per-row attention kernels
     int pass_groups = 0;                         // column groups of the rows span_upload uploaded last; 0: not a span pass
 };
@@ -1467,156 +1469,231 @@ int pf_run(llmk_ctx* c, const int* tokens, int n, int pos0, const ScoreJob* sj) 
 // ---- batched decode (batch.h) -----------------------------------------------------------------------------------
 static_assert(LLMK_MAX_BATCH == PF_TMAX, "a batch's rows are the rows of one prefill pass");
 
-// A batch's caches and prefix rows by element type (llmk_cache_create: float, _Float16 or KvQ8, one type per batch), and f(T()) for the
-// type a batch has.  What differs between the types on the host: the buffers, the kernels' instantiation, and a converting kernel in
-// the place of the device-to-device copy from the context's f32 rows.  A buffer of n ELEMENTS is units(n) units of its DevBuf; view(buf,
-// n) is what the kernels take for it -- the pointer, or for q8_0 the quants and the scales behind them (attn_tiles.h Q8Rows; nothing is
-// padded: n is a multiple of 32, so the scales start 32-byte aligned) -- and attn_at(view, e) moves it on by e elements.
+// an IEEE half's bits as the f32 of the same value (host side of llmk_cache_peek; subnormals, infinities and NaN included)
+static float bd_half_bits_to_float(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
+    uint32_t u;
+    if (ex == 0x1Fu) {
+        u = sign | 0x7F800000u | (man << 13);
+    } else if (ex != 0) {
+        u = sign | ((ex + 112u) << 23) | (man << 13);
+    } else {
+        // man * 2^-24, exact in f32
+        float f = (float)man * 5.9604644775390625e-8f;
+        memcpy(&u, &f, sizeof u);
+        u |= sign;
+    }
+    float f;
+    memcpy(&f, &u, sizeof f);
+    return f;
+}
+
+// What a BdStore's bytes hold, by element type (llmk_cache_create: float, _Float16 or KvQ8, one type per batch), and f(T()) for the
+// type a batch has: the ONE place where the types differ on the host.  For a block of n ELEMENTS:
+//   bytes(n)                          its size; view(buf, n) is what the kernels take for it -- the pointer, or for q8_0 the quants and
+//                                     the scales behind them (attn_tiles.h Q8Rows; nothing is padded: n is a multiple of 32, so the scales
+//                                     start 32-byte aligned) -- and attn_at(view, e) moves it on by e elements;
+//   shape_ok(KV)                      may a position's row have KV elements?
+//   zero(view, n, st)                 n elements read back +0.0, ENQUEUED;
+//   from_ctx(c, dk, dv, n, dst_layer) rows [n / KV][KV] of every layer of the context's f32 caches into K and V blocks (layers dst_layer
+//                                     elements apart), ENQUEUED: the device-to-device copy an f32 batch always made, the converting
+//                                     kernel for the others (batch.h bd_to_half_kernel, bd_to_q8_kernel);
+//   read(view, n, out)                n elements as f32 on the host, exact; synchronous;
+//   epi_qkv(a, bc, kc, vc, QKV, T, st) a layer's QKV epilogue of T rows, which writes the rows' K and V into the layer's blocks.
 template <class T> struct BdKvPlain {
-    static size_t units(size_t n) { return n; }
-    static T* view(DevBuf<T>& buf, size_t) { return buf.get(); }
+    static size_t bytes(size_t n) { return n * sizeof(T); }
+    static T* view(const DevBuf<char>& buf, size_t) { return reinterpret_cast<T*>(buf.get()); }
+    static bool shape_ok(int) { return true; }
+    static hipError_t zero(T* at, size_t n, hipStream_t st) { return hipMemsetAsync(at, 0, n * sizeof(T), st); }
 };
 template <class T> struct BdKv;
-template <> struct BdKv<KvQ8> {
-    static DevBuf<int8_t>& kc(llmk_batch* b) { return b->d_kc8; }
-    static DevBuf<int8_t>& vc(llmk_batch* b) { return b->d_vc8; }
-    static DevBuf<int8_t>& pk(llmk_batch::Prefix& p) { return p.d_pk8; }
-    static DevBuf<int8_t>& pv(llmk_batch::Prefix& p) { return p.d_pv8; }
-    static size_t units(size_t n) { return n + n / 32 * sizeof(_Float16); }      // bytes: 34 per 32 elements
-    static Q8Rows view(DevBuf<int8_t>& buf, size_t n) { return Q8Rows{buf.get(), reinterpret_cast<_Float16*>(buf.get() + n)}; }
-};
 template <> struct BdKv<float> : BdKvPlain<float> {
-    static DevBuf<float>& kc(llmk_batch* b) { return b->d_kc; }
-    static DevBuf<float>& vc(llmk_batch* b) { return b->d_vc; }
-    static DevBuf<float>& pk(llmk_batch::Prefix& p) { return p.d_pk; }
-    static DevBuf<float>& pv(llmk_batch::Prefix& p) { return p.d_pv; }
+    static hipError_t from_ctx(llmk_ctx* c, float* dk, float* dv, size_t n, size_t dst_layer) {
+        float* caches[2][2] = {{dk, c->d_kc}, {dv, c->d_vc}};
+        for (auto& p : caches)
+            for (int l = 0; l < c->L; ++l)
+                HIPRET(hipMemcpyAsync(p[0] + (size_t)l * dst_layer, p[1] + (size_t)l * c->S * c->KV, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        return hipSuccess;
+    }
+    static hipError_t read(const float* at, size_t n, float* out) { return hipMemcpy(out, at, n * sizeof(float), hipMemcpyDeviceToHost); }
+    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, float* kc, float* vc, int QKV, int T, hipStream_t st) {
+        a.kc = kc; a.vc = vc;
+        hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc);
+        return hipGetLastError();
+    }
 };
 template <> struct BdKv<_Float16> : BdKvPlain<_Float16> {
-    static DevBuf<_Float16>& kc(llmk_batch* b) { return b->d_kc16; }
-    static DevBuf<_Float16>& vc(llmk_batch* b) { return b->d_vc16; }
-    static DevBuf<_Float16>& pk(llmk_batch::Prefix& p) { return p.d_pk16; }
-    static DevBuf<_Float16>& pv(llmk_batch::Prefix& p) { return p.d_pv16; }
+    static hipError_t from_ctx(llmk_ctx* c, _Float16* dk, _Float16* dv, size_t n, size_t dst_layer) {
+        const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
+        hipLaunchKernelGGL(bd_to_half_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
+        return hipGetLastError();
+    }
+    static hipError_t read(const _Float16* at, size_t n, float* out) {
+        std::vector<uint16_t> h(n);
+        HIPRET(hipMemcpy(h.data(), at, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) out[i] = bd_half_bits_to_float(h[i]);
+        return hipSuccess;
+    }
+    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, _Float16* kc, _Float16* vc, int QKV, int T, hipStream_t st) {
+        a.kc = a.vc = nullptr;      // (the context's caches are not this pass's)
+        hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
+        return hipGetLastError();
+    }
 };
+template <> struct BdKv<KvQ8> {
+    static size_t bytes(size_t n) { return n + n / 32 * sizeof(_Float16); }      // 34 per 32 elements: the quants, then the scales
+    static Q8Rows view(const DevBuf<char>& buf, size_t n) {
+        return Q8Rows{reinterpret_cast<int8_t*>(buf.get()), reinterpret_cast<_Float16*>(buf.get() + n)};
+    }
+    static bool shape_ok(int KV) { return KV % 32 == 0; }      // a q8_0 block is 32 elements of a position's row
+    // q = 0, d = 0, which reads back +0.0
+    static hipError_t zero(Q8Rows at, size_t n, hipStream_t st) {
+        HIPRET(hipMemsetAsync(at.q, 0, n, st));
+        return hipMemsetAsync(at.d, 0, n / 32 * sizeof(_Float16), st);
+    }
+    static hipError_t from_ctx(llmk_ctx* c, Q8Rows dk, Q8Rows dv, size_t n, size_t dst_layer) {
+        const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
+        hipLaunchKernelGGL(bd_to_q8_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
+        return hipGetLastError();
+    }
+    // value[i] = (float)q[i] * (float)d of i's block: one f32 product, exact (and never -0.0: d >= 0, or NaN)
+    static hipError_t read(Q8Rows at, size_t n, float* out) {
+        std::vector<int8_t> q(n);
+        std::vector<uint16_t> d(n / 32);
+        HIPRET(hipMemcpy(q.data(), at.q, n, hipMemcpyDeviceToHost));
+        HIPRET(hipMemcpy(d.data(), at.d, n / 32 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) out[i] = (float)q[i] * bd_half_bits_to_float(d[i / 32]);
+        return hipSuccess;
+    }
+    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, Q8Rows kc, Q8Rows vc, int QKV, int T, hipStream_t st) {
+        a.kc = a.vc = nullptr;
+        hipLaunchKernelGGL(bd_epi_qkv_q8_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
+        return hipGetLastError();
+    }
+};
+static bool kv_type_ok(int kv_type) { return kv_type == LLMK_TYPE_F32 || kv_type == LLMK_TYPE_F16 || kv_type == LLMK_TYPE_Q8_0; }
 template <class F>
 static auto with_kv_type(const llmk_batch* b, F f) {
     return b->kv_type == LLMK_TYPE_Q8_0 ? f(KvQ8()) : b->kv_type == LLMK_TYPE_F16 ? f(_Float16()) : f(float());
 }
-// rows [n][KV] of every layer of the context's f32 caches into a batch's K and V buffers (dk, dv; layers dst_layer elements apart),
-// ENQUEUED: the copy an f32 batch always made, the converting kernel for an f16 one (batch.h bd_to_half_kernel) or a q8_0 one (bd_to_q8_kernel)
-static hipError_t bd_copy_ctx_rows(llmk_ctx* c, float* dk, float* dv, size_t n, size_t dst_layer) {
-    float* caches[2][2] = {{dk, c->d_kc}, {dv, c->d_vc}};
-    for (auto& p : caches)
-        for (int l = 0; l < c->L; ++l)
-            HIPRET(hipMemcpyAsync(p[0] + (size_t)l * dst_layer, p[1] + (size_t)l * c->S * c->KV, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    return hipSuccess;
+
+// The two element offsets of the store: layer l, slot s, position p (0-based) of a cache block, and layer l, position p of a prefix
+// block ([L][P][KV] with the layers P rows apart, whatever the block's room).  (L, 0, 0) and (L, 0) are the blocks' element counts.
+static size_t bd_cache_at(const llmk_batch* b, int l, int slot, int p) { return (((size_t)l * b->n_slots + slot) * b->seq_len + p) * b->ctx->KV; }
+static size_t bd_prefix_at(const llmk_batch* b, int l, int p) { return ((size_t)l * b->P + p) * b->ctx->KV; }
+// ... and the kernels' views of a block there
+template <class TC>
+static auto bd_cache_view(const llmk_batch* b, const DevBuf<char>& buf, int l, int slot, int p) {
+    return attn_at(BdKv<TC>::view(buf, bd_cache_at(b, b->ctx->L, 0, 0)), bd_cache_at(b, l, slot, p));
 }
-static hipError_t bd_copy_ctx_rows(llmk_ctx* c, _Float16* dk, _Float16* dv, size_t n, size_t dst_layer) {
-    const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
-    hipLaunchKernelGGL(bd_to_half_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
-    return hipGetLastError();
+template <class TC>
+static auto bd_prefix_view(const llmk_batch* b, const DevBuf<char>& buf, int l, int p) {
+    return attn_at(BdKv<TC>::view(buf, bd_prefix_at(b, b->ctx->L, 0)), bd_prefix_at(b, l, p));
 }
 
-static hipError_t bd_copy_ctx_rows(llmk_ctx* c, Q8Rows dk, Q8Rows dv, size_t n, size_t dst_layer) {
-    const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
-    hipLaunchKernelGGL(bd_to_q8_kernel, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, n, (size_t)c->S * c->KV, dst_layer);
-    return hipGetLastError();
+// rows n_pos .. seq_len-1 (0-based) of `slot` in every layer of both caches read back +0.0, as in a fresh slot; ENQUEUED
+template <class TC>
+static hipError_t bd_zero_slot(llmk_batch* b, int slot, int n_pos) {
+    if (n_pos >= b->seq_len) return hipSuccess;
+    for (const DevBuf<char>* buf : {&b->cache.k, &b->cache.v})
+        for (int l = 0; l < b->ctx->L; ++l)
+            HIPRET(BdKv<TC>::zero(bd_cache_view<TC>(b, *buf, l, slot, n_pos), (size_t)(b->seq_len - n_pos) * b->ctx->KV, b->ctx->stream));
+    return hipSuccess;
+}
+
+// The attention of one pass, computed once for all layers: the split rules, which kernel serves the rows' own ranges, whether a fold
+// follows, and the part states it goes through.
+//   ROW   no attached row, no span: bd_attn_kernel, parts of the rows' whole ranges; more than one part: states in d_po / d_pml
+//         (stride BD_MAX_GROUP), folded;
+//   OWN   attached rows (pass_att > 0, llmk_prefix_*): the prefix kernel, then bd_attn_own_kernel from row `first` on; always folded;
+//   SPAN  a span pass (pass_groups > 0, llmk_span_*): the prefix kernel if it has attached rows, then bd_attn_span_kernel over column
+//         groups; one part and no attached row: straight to XB (direct), else folded.
+// OWN and SPAN leave np = pparts + parts states per (row, kv head) in the batch's PartStates (stride kv_mul): the prefix parts first.
+struct BdAttnPlan {
+    enum Kind { ROW, OWN, SPAN } kind;
+    bool shared, fold;              // attached rows in the pass: the prefix kernel runs; the fold kernel runs
+    int units;                      // grid.y of the rows' kernel: rows, or column groups of a span pass
+    int parts, tpp;                 // own parts and their tiles
+    int groups, pparts, ptpp;       // the prefix kernel's column groups, parts and tiles per part (0 without attached rows)
+    int np, direct;
+    float* po;
+    float2* pml;
+    int stride;
+    const int* first;               // the slots' first own rows (d_first) in a pass with attached rows, else null
+};
+static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step) {
+    const llmk_ctx* c = b->ctx;
+    BdAttnPlan p{};
+    p.shared = b->pass_att > 0;
+    p.kind = b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
+    p.units = p.kind == BdAttnPlan::SPAN ? b->pass_groups : n;
+    // The split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`.  Without
+    // attached rows every range starts at tile 0 and the longest is the longest row's
+    int own = (max_pos + BD_TILE - 1) / BD_TILE;
+    if (p.shared) {
+        own = 0;
+        for (int i = 0; i < n; ++i)
+            own = std::max(own, (b->h_rows[i].pos + step + BD_TILE - 1) / BD_TILE - b->px->h_first[b->h_rows[i].slot] / BD_TILE);
+        p.groups = bd_prefix_groups(b->pass_att, c->kv_mul);
+        p.pparts = bd_prefix_parts(b->pass_att, c->nkv, c->kv_mul, b->P, c->n_cu);
+        p.ptpp = bd_tiles_per_part(b->P, p.pparts);
+        p.first = b->px->d_first;
+    }
+    p.parts = bd_parts(p.units, c->nkv, own * BD_TILE, c->n_cu);
+    p.tpp = bd_tiles_per_part(own * BD_TILE, p.parts);
+    p.np = p.pparts + p.parts;
+    p.direct = p.kind == BdAttnPlan::SPAN && !p.shared && p.parts == 1;
+    p.fold = p.kind == BdAttnPlan::ROW ? p.parts > 1 : !p.direct;
+    if (p.kind == BdAttnPlan::ROW) {
+        p.po = b->d_po; p.pml = b->d_pml; p.stride = BD_MAX_GROUP;
+    } else {
+        p.po = b->ps->d_o; p.pml = b->ps->d_ml; p.stride = c->kv_mul;
+    }
+    return p;
 }
 
 // One pass, ENQUEUED on the context's stream: the n rows in d_rows / d_tok through every layer, the classifier and the per-row first
 // maximum (into d_out + n); the logits of every row into d_logits when asked for.  max_pos: the longest row (the attention's split rule).
-// With attached rows among them (pass_att > 0, llmk_prefix_*) the attention is the three kernels of batch.h's prefix section; `step`:
-// the rows stand `step` positions behind the uploaded ones (a decode's later passes).
+// `step`: the rows stand `step` positions behind the uploaded ones (a decode's later passes).
 template <class TC>      // TC: the caches' element type
 static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, int step) {
     llmk_ctx* c = b->ctx;
     PfLane& w = c->pf->lane[0];
     const int E = c->E, KV = c->KV, QKV = E + 2 * KV, T = n;
     const BdCaches bc{b->d_rows, (size_t)b->seq_len * KV, b->n_slots, b->seq_len};
-    int parts = bd_parts(n, c->nkv, max_pos, c->n_cu), tpp = bd_tiles_per_part(max_pos, parts);
-    const bool shared = b->pass_att > 0;
-    int groups = 0, pparts = 0, ptpp = 0;
-    if (shared) {
-        // the own parts' split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`
-        int own = 0;
-        for (int i = 0; i < n; ++i) {
-            const int pos = b->h_rows[i].pos + step;
-            own = std::max(own, (pos + BD_TILE - 1) / BD_TILE - b->px->h_first[b->h_rows[i].slot] / BD_TILE);
-        }
-        parts = bd_parts(n, c->nkv, own * BD_TILE, c->n_cu);
-        tpp = bd_tiles_per_part(own * BD_TILE, parts);
-        groups = bd_prefix_groups(b->pass_att, c->kv_mul);
-        pparts = bd_prefix_parts(b->pass_att, c->nkv, c->kv_mul, b->P, c->n_cu);
-        ptpp = bd_tiles_per_part(b->P, pparts);
-    }
-    const int ngroups = b->pass_groups;
-    if (ngroups > 0) {
-        // a span pass (llmk_span_*): the split rule counts column groups, the longest group's tiles from the one that holds row `first`
-        int own = 0;
-        for (int k = 0; k < ngroups; ++k) {
-            const BdRow& r = b->h_rows[b->sn->h_groups[k].first + b->sn->h_groups[k].rows - 1];
-            own = std::max(own, (r.pos + step + BD_TILE - 1) / BD_TILE - (shared ? b->px->h_first[r.slot] : 0) / BD_TILE);
-        }
-        parts = bd_span_parts(ngroups, c->nkv, own, c->n_cu);
-        tpp = bd_tiles_per_part(own * BD_TILE, parts);
-    }
+    const BdAttnPlan p = bd_attn_plan(b, n, max_pos, step);
     PfEpiArgs e;
     // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
-        const size_t cache = (size_t)c->L * b->n_slots * bc.slot_stride;
-        const auto kc = attn_at(BdKv<TC>::view(BdKv<TC>::kc(b), cache), (size_t)l * b->n_slots * bc.slot_stride);
-        const auto vc = attn_at(BdKv<TC>::view(BdKv<TC>::vc(b), cache), (size_t)l * b->n_slots * bc.slot_stride);
-        if constexpr (std::is_same_v<TC, float>) {
-            a.kc = kc; a.vc = vc;
-            hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc);
-        } else if constexpr (std::is_same_v<TC, KvQ8>) {
-            a.kc = a.vc = nullptr;
-            hipLaunchKernelGGL(bd_epi_qkv_q8_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc, kc, vc);
-        } else {
-            a.kc = a.vc = nullptr;      // (the context's caches are not this pass's)
-            hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, w.stream, a, bc, kc, vc);
-        }
-        HIPRET(hipGetLastError());
-        // (the prefix rows of this layer: [L][P][KV] with the layers P rows apart, whatever the blocks' room)
-        auto pk = kc, pv = vc;
-        if (shared) {
-            pk = attn_at(BdKv<TC>::view(BdKv<TC>::pk(*b->px), (size_t)c->L * b->P * KV), (size_t)l * b->P * KV);
-            pv = attn_at(BdKv<TC>::view(BdKv<TC>::pv(*b->px), (size_t)c->L * b->P * KV), (size_t)l * b->P * KV);
-        }
+        const auto kc = bd_cache_view<TC>(b, b->cache.k, l, 0, 0), vc = bd_cache_view<TC>(b, b->cache.v, l, 0, 0);
+        HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, QKV, T, w.stream));
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
-            if (ngroups > 0) {
-                // prefix (a pass with attached rows) + the groups' own rows + fold; one part and no attached row: straight to XB
-                const int np = pparts + parts, direct = !shared && parts == 1;
-                if (shared) {
-                    hipLaunchKernelGGL((BdAttn<HS, TC>::prefix), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                                       w.Q, pk, pv, b->sn->d_spo, b->sn->d_spml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
-                    HIPRET(hipGetLastError());
-                }
-                const int* first = shared ? b->px->d_first.get() : nullptr;
-                hipLaunchKernelGGL((BdAttn<HS, TC>::span), dim3(c->nkv, ngroups, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                                   w.Q, kc, vc, w.XB, b->sn->d_spo, b->sn->d_spml, bc, b->sn->d_groups, first, T, KV, c->kv_mul, E, tpp, np, pparts, direct);
+            const dim3 block(BD_WAVES * WAVE), grid(c->nkv, p.units, p.parts);
+            const size_t smem = attn_smem(BD_WAVES, HS);
+            if (p.shared) {
+                hipLaunchKernelGGL((BdAttn<HS, TC>::prefix), dim3(c->nkv, p.groups, p.pparts), block, smem, w.stream, w.Q,
+                                   bd_prefix_view<TC>(b, b->px->rows.k, l, 0), bd_prefix_view<TC>(b, b->px->rows.v, l, 0), p.po, p.pml,
+                                   b->px->d_colmap, T, b->P, KV, c->kv_mul, E, p.ptpp, p.np);
                 HIPRET(hipGetLastError());
-                if (!direct) hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->sn->d_spo, b->sn->d_spml, w.XB, bc, first,
-                                                c->kv_mul, E, c->kv_mul, np, pparts);
-                return hipGetLastError();
             }
-            if (shared) {
-                const int np = pparts + parts;
-                hipLaunchKernelGGL((BdAttn<HS, TC>::prefix), dim3(c->nkv, groups, pparts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                                   w.Q, pk, pv, b->px->d_xpo, b->px->d_xpml, b->px->d_colmap, T, b->P, KV, c->kv_mul, E, ptpp, np);
-                HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((BdAttn<HS, TC>::own), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                                   w.Q, kc, vc, b->px->d_xpo, b->px->d_xpml, bc, b->px->d_first, KV, c->kv_mul, E, tpp, np, pparts);
-                HIPRET(hipGetLastError());
-                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->px->d_xpo, b->px->d_xpml, w.XB, bc, b->px->d_first,
-                                   c->kv_mul, E, c->kv_mul, np, pparts);
-                return hipGetLastError();
+            switch (p.kind) {
+                case BdAttnPlan::ROW:
+                    hipLaunchKernelGGL((BdAttn<HS, TC>::row), grid, block, smem, w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc, KV, c->kv_mul, E, p.tpp);
+                    break;
+                case BdAttnPlan::OWN:
+                    hipLaunchKernelGGL((BdAttn<HS, TC>::own), grid, block, smem, w.stream, w.Q, kc, vc, p.po, p.pml, bc, p.first, KV, c->kv_mul, E, p.tpp,
+                                       p.np, p.pparts);
+                    break;
+                case BdAttnPlan::SPAN:
+                    hipLaunchKernelGGL((BdAttn<HS, TC>::span), grid, block, smem, w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc, b->sn->d_groups, p.first, T,
+                                       KV, c->kv_mul, E, p.tpp, p.np, p.pparts, p.direct);
+                    break;
             }
-            hipLaunchKernelGGL((BdAttn<HS, TC>::row), dim3(c->nkv, T, parts), dim3(BD_WAVES * WAVE), attn_smem(BD_WAVES, HS), w.stream,
-                               w.Q, kc, vc, w.XB, b->d_po, b->d_pml, bc, KV, c->kv_mul, E, tpp);
             HIPRET(hipGetLastError());
-            if (parts > 1) hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, b->d_po, b->d_pml, w.XB, bc, (const int*)nullptr,
-                                           c->kv_mul, E, BD_MAX_GROUP, parts, 0);
+            if (p.fold)
+                hipLaunchKernelGGL((bd_attn_fold_kernel<HS>), dim3(c->nkv, T), dim3(256), 0, w.stream, p.po, p.pml, w.XB, bc, p.first, c->kv_mul, E,
+                                   p.stride, p.np, p.pparts);
             return hipGetLastError();
         });
     }));
@@ -1655,6 +1732,46 @@ int pf_redo(llmk_ctx* c, const char* who, bool* told, F again) {
     rc = again();
     if (!for_good) c->pf.reset();          // (the next call sets the f16 instruction up again)
     return rc;
+}
+
+// The tail of a forward call (`who`) whose rows are uploaded: the pass, its first maxima and the f16-range flag fetched, the stream
+// synchronised.  A raised flag: the whole call is redone (`again`, which delivers) and *ids stays null.  Else *ids are the n rows'
+// first maxima, all in range (or LLMK_E_NONFINITE), and the logits the caller asked for are in d_logits: the caller delivers.
+template <class F>
+static int bd_forward_sync(llmk_batch* b, int n, int max_pos, bool want_logits, const ScPlan& sp, const char* who, F again, const int** ids) {
+    static bool told = false;      // one per F: every public function passes a closure of its own, and says so once
+    llmk_ctx* c = b->ctx;
+    *ids = nullptr;
+    HIPCHK(bd_pass(b, n, max_pos, want_logits, sp));
+    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(pf_fetch_flag(c));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pf_flagged(c)) return pf_redo(c, who, &told, again);
+    const int* got = reinterpret_cast<const int*>(b->h_out + n);
+    for (int i = 0; i < n; ++i)
+        if (got[i] < 1 || got[i] > c->V) return LLMK_E_NONFINITE;
+    *ids = got;
+    return LLMK_OK;
+}
+// The timing loop of llmk_batch_time and llmk_span_time on the uploaded rows: a warm-up pass, then `iters` passes between two events
+static int bd_time(llmk_batch* b, int n, int max_pos, int iters, const ScPlan& sp, float* avg_ms) {
+    llmk_ctx* c = b->ctx;
+    HIPCHK(bd_pass(b, n, max_pos, false, sp));      // warm-up
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Event e0, e1;
+    HIPCHK(e0.create());
+    hipError_t pe = e1.create();
+    if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
+    for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, max_pos, false, sp);
+    if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
+    if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
+    float ms = 0.f;
+    if (pe == hipSuccess) pe = hipEventElapsedTime(&ms, e0, e1);
+    HIPCHK(hipMemsetAsync(c->pf->flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (pe != hipSuccess) return LLMK_E_HIP + (int)pe;
+    *avg_ms = ms / (float)iters;
+    return LLMK_OK;
 }
 
 }  // namespace
@@ -2809,17 +2926,22 @@ static int bd_ready(llmk_batch* b, ScPlan* sp, int rows) {
     if (ct != LLMK_TYPE_Q6_K && sp->R == 0) return LLMK_E_SHAPE;      // no chunk of the classifier fits the workspace: there is no token-by-token form
     return LLMK_OK;
 }
-// rows of a call: n in [1, n_slots], distinct slots, ids and positions in range (last_pos: the last position the call writes)
+// One slot's share of a call, on the host: the slot in range and not yet `seen` in this call (it is marked), its positions
+// pos0 .. pos0+len-1 (len >= 1) in range and not inside an attached slot's prefix (its positions 1..P are the prefix's)
+static bool bd_slot_ok(const llmk_batch* b, bool* seen, int slot, int pos0, int len) {
+    if (slot < 0 || slot >= b->n_slots || seen[slot]) return false;
+    seen[slot] = true;
+    if (pos0 < 1 || pos0 > b->seq_len || len - 1 > b->seq_len - pos0) return false;
+    return !(b->n_attached > 0 && pos0 <= b->px->h_first[slot]);
+}
+// rows of a call: n in [1, n_slots], distinct slots, ids and positions in range (span: the positions a row of the call writes)
 // (fed = false: rows that feed no token -- the hook of the rows functions; `tokens` is not read)
 static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos, int span, bool fed = true) {
     if (!slots || (fed && !tokens) || !pos || n < 1 || n > b->n_slots || span < 1) return false;
     bool seen[LLMK_MAX_BATCH] = {};
     for (int i = 0; i < n; ++i) {
-        if (slots[i] < 0 || slots[i] >= b->n_slots || seen[slots[i]]) return false;
-        seen[slots[i]] = true;
         if (fed && (tokens[i] < 1 || tokens[i] > b->ctx->V)) return false;
-        if (pos[i] < 1 || pos[i] > b->seq_len || span - 1 > b->seq_len - pos[i]) return false;
-        if (b->n_attached > 0 && pos[i] <= b->px->h_first[slots[i]]) return false;      // an attached slot's positions 1..P are the prefix
+        if (!bd_slot_ok(b, seen, slots[i], pos[i], span)) return false;
     }
     return true;
 }
@@ -2845,25 +2967,6 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
     return hipMemcpyAsync(b->d_tok, b->h_tok, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
 }
 
-// an IEEE half's bits as the f32 of the same value (host side of llmk_cache_peek; subnormals, infinities and NaN included)
-static float bd_half_bits_to_float(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 0x1Fu, man = h & 0x3FFu;
-    uint32_t u;
-    if (ex == 0x1Fu) {
-        u = sign | 0x7F800000u | (man << 13);
-    } else if (ex != 0) {
-        u = sign | ((ex + 112u) << 23) | (man << 13);
-    } else {
-        // man * 2^-24, exact in f32
-        float f = (float)man * 5.9604644775390625e-8f;
-        memcpy(&u, &f, sizeof u);
-        u |= sign;
-    }
-    float f;
-    memcpy(&f, &u, sizeof f);
-    return f;
-}
-
 // an allocation the device has no room for is the caller's to handle (llmk_cache_create sizes caches by n_slots x seq_len), not a HIP fault
 static int bd_alloc_rc(hipError_t e) {
     if (e == hipErrorOutOfMemory) {
@@ -2877,29 +2980,25 @@ static int bd_alloc_rc(hipError_t e) {
 static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) {
     if (!c || !out || n_slots < 1 || n_slots > LLMK_MAX_BATCH || seq_len < 1 || seq_len > c->S) return LLMK_E_ARG;
     *out = nullptr;
-    if (kv_type != LLMK_TYPE_F32 && kv_type != LLMK_TYPE_F16 && kv_type != LLMK_TYPE_Q8_0) return LLMK_E_TYPE;
+    if (!kv_type_ok(kv_type)) return LLMK_E_TYPE;
     int rc = check_ready(c);      // (an incomplete context is LLMK_E_STATE whatever its shape)
     if (rc) return rc;
     if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;
-    if (kv_type == LLMK_TYPE_Q8_0 && c->KV % 32 != 0) return LLMK_E_SHAPE;      // a q8_0 block is 32 elements of a position's row
-    HIPCHK(hipSetDevice(c->cfg.device));
     // built aside: the caller gets the batch only after every step succeeded (a failure releases what was made)
     auto b = std::make_unique<llmk_batch>();
     b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len; b->kv_type = kv_type;
+    if (!with_kv_type(b.get(), [&](auto t) { return BdKv<decltype(t)>::shape_ok(c->KV); })) return LLMK_E_SHAPE;
+    HIPCHK(hipSetDevice(c->cfg.device));
     b->span_attn = !(getenv("LLMK_SPAN_ATTN") && getenv("LLMK_SPAN_ATTN")[0] == '0');
     ScPlan sp;
     if ((rc = bd_ready(b.get(), &sp, n_slots)) != LLMK_OK) return rc;
-    const size_t cache = (size_t)c->L * n_slots * seq_len * c->KV, nb = LLMK_MAX_BATCH;
-    rc = with_kv_type(b.get(), [&](auto t) -> int {
-        using TC = decltype(t);
-        int rc_;
-        if ((rc_ = bd_alloc_rc(BdKv<TC>::kc(b.get()).alloc(BdKv<TC>::units(cache)))) != LLMK_OK) return rc_;
-        if ((rc_ = bd_alloc_rc(BdKv<TC>::vc(b.get()).alloc(BdKv<TC>::units(cache)))) != LLMK_OK) return rc_;
-        HIPCHK(BdKv<TC>::kc(b.get()).zero(c->stream));
-        HIPCHK(BdKv<TC>::vc(b.get()).zero(c->stream));
-        return LLMK_OK;
-    });
-    if (rc) return rc;
+    const size_t nb = LLMK_MAX_BATCH;
+    // the caches: one block each for K and V, all bytes zero (every type reads that back as +0.0)
+    const size_t cache_bytes = with_kv_type(b.get(), [&](auto t) { return BdKv<decltype(t)>::bytes(bd_cache_at(b.get(), c->L, 0, 0)); });
+    for (DevBuf<char>* buf : {&b->cache.k, &b->cache.v})
+        if ((rc = bd_alloc_rc(buf->alloc(cache_bytes))) != LLMK_OK) return rc;
+    HIPCHK(b->cache.k.zero(c->stream));
+    HIPCHK(b->cache.v.zero(c->stream));
     HIPCHK(b->d_rows.alloc(nb));
     HIPCHK(b->d_tok.alloc(nb));
     HIPCHK(b->d_out.alloc(2 * nb));
@@ -2939,12 +3038,9 @@ int llmk_cache_type(llmk_batch* b) {
 // device bytes of the K/V caches and of the prefix rows (the blocks as they are allocated: a prefix's only grow)
 int llmk_cache_bytes(llmk_batch* b, unsigned long long* out) {
     if (!b || !out) return LLMK_E_ARG;
-    *out = with_kv_type(b, [&](auto t) -> unsigned long long {
-        using TC = decltype(t);
-        size_t n = BdKv<TC>::kc(b).size() + BdKv<TC>::vc(b).size();
-        if (b->px) n += BdKv<TC>::pk(*b->px).size() + BdKv<TC>::pv(*b->px).size();
-        return (unsigned long long)n * sizeof(*BdKv<TC>::kc(b).get());
-    });
+    size_t n = b->cache.k.size() + b->cache.v.size();
+    if (b->px) n += b->px->rows.k.size() + b->px->rows.v.size();
+    *out = n;
     return LLMK_OK;
 }
 
@@ -2957,32 +3053,13 @@ int llmk_cache_peek(llmk_batch* b, int which, int layer, int slot, int pos0, int
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipStreamSynchronize(c->stream));
-    const size_t row = (size_t)c->KV, cnt = (size_t)n * row;
-    if (b->kv_type == LLMK_TYPE_Q8_0) {
-        // value[i] = (float)q[i] * (float)d of i's block: one f32 product, exact (and never -0.0: d >= 0, or NaN)
-        const size_t elems = (size_t)c->L * (slot < 0 ? (size_t)b->P : (size_t)b->n_slots * b->seq_len) * row;
-        const size_t e0 = slot < 0 ? ((size_t)layer * b->P + (pos0 - 1)) * row : (((size_t)layer * b->n_slots + slot) * b->seq_len + (pos0 - 1)) * row;
-        const Q8Rows src = attn_at(BdKv<KvQ8>::view(slot < 0 ? (which ? b->px->d_pv8 : b->px->d_pk8) : (which ? b->d_vc8 : b->d_kc8), elems), e0);
-        std::vector<int8_t> q(cnt);
-        std::vector<uint16_t> d(cnt / 32);
-        HIPCHK(hipMemcpy(q.data(), src.q, cnt, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(d.data(), src.d, cnt / 32 * sizeof(uint16_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < cnt; ++i) out[i] = (float)q[i] * bd_half_bits_to_float(d[i / 32]);
-        return LLMK_OK;
-    }
-    return with_kv_type(b, [&](auto t) -> int {
-        using TC = std::conditional_t<std::is_same_v<decltype(t), KvQ8>, float, decltype(t)>;      // (q8_0 is answered above)
-        const TC* src = slot < 0 ? (which ? BdKv<TC>::pv(*b->px) : BdKv<TC>::pk(*b->px)) + ((size_t)layer * b->P + (pos0 - 1)) * row
-                                 : (which ? BdKv<TC>::vc(b) : BdKv<TC>::kc(b)) + (((size_t)layer * b->n_slots + slot) * b->seq_len + (pos0 - 1)) * row;
-        if constexpr (std::is_same_v<TC, float>) {
-            HIPCHK(hipMemcpy(out, src, cnt * sizeof(float), hipMemcpyDeviceToHost));
-        } else {
-            std::vector<uint16_t> h(cnt);
-            HIPCHK(hipMemcpy(h.data(), src, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < cnt; ++i) out[i] = bd_half_bits_to_float(h[i]);
-        }
-        return LLMK_OK;
-    });
+    HIPCHK(with_kv_type(b, [&](auto t) {
+        using TC = decltype(t);
+        const auto src = slot < 0 ? bd_prefix_view<TC>(b, which ? b->px->rows.v : b->px->rows.k, layer, pos0 - 1)
+                                  : bd_cache_view<TC>(b, which ? b->cache.v : b->cache.k, layer, slot, pos0 - 1);
+        return BdKv<TC>::read(src, (size_t)n * c->KV, out);
+    }));
+    return LLMK_OK;
 }
 
 int llmk_batch_destroy(llmk_batch* b) {
@@ -3003,57 +3080,37 @@ static hipError_t prefix_first(llmk_batch* b, int slot, int first) {
     return hipMemcpyAsync(b->px->d_first + slot, b->px->h_first + slot, sizeof(int), hipMemcpyHostToDevice, b->ctx->stream);
 }
 
-// rows n_pos .. seq_len-1 of `slot` in every layer of a q8_0 batch's caches: quants and scales zeroed, ENQUEUED
-static hipError_t bd_q8_zero(llmk_batch* b, int slot, int n_pos) {
-    llmk_ctx* c = b->ctx;
-    const size_t row = (size_t)c->KV, slot_rows = (size_t)b->seq_len * row, cache = (size_t)c->L * b->n_slots * slot_rows;
-    if (n_pos >= b->seq_len) return hipSuccess;
-    for (DevBuf<int8_t>* buf : {&b->d_kc8, &b->d_vc8})
-        for (int l = 0; l < c->L; ++l) {
-            const Q8Rows at = attn_at(BdKv<KvQ8>::view(*buf, cache), ((size_t)l * b->n_slots + slot) * slot_rows + (size_t)n_pos * row);
-            HIPRET(hipMemsetAsync(at.q, 0, slot_rows - (size_t)n_pos * row, c->stream));
-            HIPRET(hipMemsetAsync(at.d, 0, (slot_rows - (size_t)n_pos * row) / 32 * sizeof(_Float16), c->stream));
-        }
-    return hipSuccess;
-}
-
 int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
     if (!b || slot < 0 || slot >= b->n_slots || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S)) return LLMK_E_ARG;
     llmk_ctx* c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
-    const size_t row = (size_t)c->KV, slot_rows = (size_t)b->seq_len * row;
-    if (b->kv_type == LLMK_TYPE_F32) {
-        float* caches[2][2] = {{b->d_kc, c->d_kc}, {b->d_vc, c->d_vc}};
-        for (auto& p : caches)
-            for (int l = 0; l < c->L; ++l) {
-                float* dst = p[0] + ((size_t)l * b->n_slots + slot) * slot_rows;
-                if ((size_t)n_pos < (size_t)b->seq_len)      // rows beyond n_pos: as in a fresh slot
-                    HIPCHK(hipMemsetAsync(dst + (size_t)n_pos * row, 0, (slot_rows - (size_t)n_pos * row) * sizeof(float), c->stream));
-                if (n_pos > 0)
-                    HIPCHK(hipMemcpyAsync(dst, p[1] + (size_t)l * c->S * row, (size_t)n_pos * row * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-            }
-    } else if (b->kv_type == LLMK_TYPE_F16) {
-        // the same on the f16 caches: zero halves behind n_pos, the context's f32 rows converted (pf_kv_half) in the place of the copy
-        for (_Float16* base : {b->d_kc16.get(), b->d_vc16.get()})
-            for (int l = 0; l < c->L && (size_t)n_pos < (size_t)b->seq_len; ++l)
-                HIPCHK(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows + (size_t)n_pos * row, 0,
-                                      (slot_rows - (size_t)n_pos * row) * sizeof(_Float16), c->stream));
-        if (n_pos > 0)
-            HIPCHK(bd_copy_ctx_rows(c, b->d_kc16 + (size_t)slot * slot_rows, b->d_vc16 + (size_t)slot * slot_rows, (size_t)n_pos * row, (size_t)b->n_slots * slot_rows));
-    } else {
-        // ... and on the q8_0 caches: q = 0, d = 0 behind n_pos (which reads back +0.0), the context's rows quantised (bd_to_q8_kernel)
-        const size_t cache = (size_t)c->L * b->n_slots * slot_rows;
-        HIPCHK(bd_q8_zero(b, slot, n_pos));
-        if (n_pos > 0)
-            HIPCHK(bd_copy_ctx_rows(c, attn_at(BdKv<KvQ8>::view(b->d_kc8, cache), (size_t)slot * slot_rows),
-                                    attn_at(BdKv<KvQ8>::view(b->d_vc8, cache), (size_t)slot * slot_rows), (size_t)n_pos * row, (size_t)b->n_slots * slot_rows));
-    }
+    // rows beyond n_pos: as in a fresh slot; the context's f32 rows in front of them, copied or converted by the batch's type
+    HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
+        using TC = decltype(t);
+        HIPRET(bd_zero_slot<TC>(b, slot, n_pos));
+        if (n_pos == 0) return hipSuccess;
+        return BdKv<TC>::from_ctx(c, bd_cache_view<TC>(b, b->cache.k, 0, slot, 0), bd_cache_view<TC>(b, b->cache.v, 0, slot, 0), (size_t)n_pos * c->KV,
+                                  bd_cache_at(b, 1, 0, 0));
+    }));
     // a forked or emptied slot is a new sequence: no token fed yet (the caller records the prompt with llmk_rows_set_history)
     if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     if (b->px && b->px->h_first[slot] > 0) HIPCHK(prefix_first(b, slot, 0));      // a forked slot is self-contained: it leaves the prefix
     HIPCHK(hipStreamSynchronize(c->stream));
     return LLMK_OK;
+}
+
+// The part states of a pass with attached rows and of a span pass (BdAttnPlan OWN, SPAN): built aside by whichever of llmk_prefix_set
+// and span_setup needs them first, and kept.  A pass uses them for one purpose, and passes are ordered by the context's one stream.
+static hipError_t bd_part_states(llmk_batch* b) {
+    if (b->ps) return hipSuccess;
+    const llmk_ctx* c = b->ctx;
+    const size_t nb = LLMK_MAX_BATCH, states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul;
+    auto ps = std::make_unique<llmk_batch::PartStates>();
+    HIPRET(ps->d_o.alloc(states * c->hs));
+    HIPRET(ps->d_ml.alloc(states));
+    b->ps = std::move(ps);
+    return hipSuccess;
 }
 
 // ---- a shared prefix (batch.h): one copy of the K/V rows of positions 1..P, the slots attached to it keep their own rows behind it ----
@@ -3069,15 +3126,14 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
     if (!b->px) {
         // what a pass with attached rows needs beyond the prefix rows, built aside by the first call that sets a prefix
         auto px = std::make_unique<llmk_batch::Prefix>();
-        const size_t states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul, words = (size_t)b->n_slots;
+        const size_t words = (size_t)b->n_slots;
         HIPCHK(px->d_first.alloc(words));
         HIPCHK(px->d_first.zero(c->stream));
         HIPCHK(px->h_first.alloc(words));
         memset(px->h_first, 0, words * sizeof(int));
         HIPCHK(px->d_colmap.alloc(nb + BD_MAX_GROUP));
         HIPCHK(px->h_colmap.alloc(nb + BD_MAX_GROUP));
-        HIPCHK(px->d_xpo.alloc(states * c->hs));
-        HIPCHK(px->d_xpml.alloc(states));
+        HIPCHK(bd_part_states(b));
         HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
             constexpr int HS = decltype(hs)::value;
             return with_kv_type(b, [](auto t) -> hipError_t {
@@ -3092,12 +3148,13 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
     const size_t px_rows = (size_t)c->L * n_pos * row;
     rc = with_kv_type(b, [&](auto t) -> int {
         using TC = decltype(t);
-        auto &pk = BdKv<TC>::pk(*b->px), &pv = BdKv<TC>::pv(*b->px);
-        if (pv.size() < BdKv<TC>::units(px_rows)) b->P = 0;
-        int rc_;
-        if ((rc_ = bd_alloc_rc(pk.reserve(BdKv<TC>::units(px_rows), c->stream))) != LLMK_OK) return rc_;
-        if ((rc_ = bd_alloc_rc(pv.reserve(BdKv<TC>::units(px_rows), c->stream))) != LLMK_OK) return rc_;
-        HIPCHK(bd_copy_ctx_rows(c, BdKv<TC>::view(pk, px_rows), BdKv<TC>::view(pv, px_rows), (size_t)n_pos * row, (size_t)n_pos * row));
+        BdStore& rows = b->px->rows;
+        if (rows.v.size() < BdKv<TC>::bytes(px_rows)) b->P = 0;
+        for (DevBuf<char>* buf : {&rows.k, &rows.v}) {
+            const int rc_ = bd_alloc_rc(buf->reserve(BdKv<TC>::bytes(px_rows), c->stream));
+            if (rc_) return rc_;
+        }
+        HIPCHK(BdKv<TC>::from_ctx(c, BdKv<TC>::view(rows.k, px_rows), BdKv<TC>::view(rows.v, px_rows), (size_t)n_pos * row, (size_t)n_pos * row));
         return LLMK_OK;
     });
     if (rc) return rc;
@@ -3113,18 +3170,7 @@ int llmk_prefix_attach(llmk_batch* b, int slot) {
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     // a new sequence behind the prefix: own rows and token record as llmk_batch_fork(b, slot, 0) leaves them
-    const size_t slot_rows = (size_t)b->seq_len * c->KV;
-    HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
-        using TC = decltype(t);
-        if constexpr (std::is_same_v<TC, KvQ8>) {
-            return bd_q8_zero(b, slot, 0);
-        } else {
-            for (TC* base : {BdKv<TC>::kc(b).get(), BdKv<TC>::vc(b).get()})
-                for (int l = 0; l < c->L; ++l)
-                    HIPRET(hipMemsetAsync(base + ((size_t)l * b->n_slots + slot) * slot_rows, 0, slot_rows * sizeof(TC), c->stream));
-            return hipSuccess;
-        }
-    }));
+    HIPCHK(with_kv_type(b, [&](auto t) { return bd_zero_slot<decltype(t)>(b, slot, 0); }));
     if (b->pen.hist) HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
     HIPCHK(prefix_first(b, slot, b->P));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3143,17 +3189,10 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos));
-    HIPCHK(bd_pass(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp));
-    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(pf_fetch_flag(c));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (pf_flagged(c)) {
-        static bool told = false;
-        return pf_redo(c, "llmk_batch_forward", &told, [&] { return llmk_batch_forward(b, n, slots, tokens, pos, logits_out, argmax_out); });
-    }
-    const int* ids = reinterpret_cast<const int*>(b->h_out + n);
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 1 || ids[i] > c->V) return LLMK_E_NONFINITE;
+    const int* ids;
+    rc = bd_forward_sync(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp, "llmk_batch_forward",
+                         [&] { return llmk_batch_forward(b, n, slots, tokens, pos, logits_out, argmax_out); }, &ids);
+    if (!ids) return rc;
     if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
     if (logits_out) HIPCHK(hipMemcpy(logits_out, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost));
     return LLMK_OK;
@@ -3336,32 +3375,17 @@ int llmk_rows_get_history(llmk_batch* b, int slot, int* tokens_out, int n, int p
 }
 
 int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
-    if (!b || !avg_ms || n < 1 || n > b->n_slots || pos < 1 || pos > b->seq_len || iters < 1) return LLMK_E_ARG;
-    for (int i = 0; i < n && b->n_attached > 0; ++i)
-        if (pos <= b->px->h_first[i]) return LLMK_E_ARG;      // (slots 0..n-1: an attached one's positions 1..P are the prefix)
-    llmk_ctx* c = b->ctx;
+    if (!b || !avg_ms || n < 1 || n > b->n_slots || iters < 1) return LLMK_E_ARG;
+    bool seen[LLMK_MAX_BATCH] = {};
+    for (int i = 0; i < n; ++i)
+        if (!bd_slot_ok(b, seen, i, pos, 1)) return LLMK_E_ARG;      // (slots 0..n-1)
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     int slots[LLMK_MAX_BATCH], tokens[LLMK_MAX_BATCH], posv[LLMK_MAX_BATCH];
     for (int i = 0; i < n; ++i) { slots[i] = i; tokens[i] = 1; posv[i] = pos; }
     HIPCHK(bd_upload_rows(b, n, slots, tokens, posv));
-    HIPCHK(bd_pass(b, n, pos, false, sp));      // warm-up
-    HIPCHK(hipStreamSynchronize(c->stream));
-    Event e0, e1;
-    HIPCHK(e0.create());
-    hipError_t pe = e1.create();
-    if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
-    for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, pos, false, sp);
-    if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
-    if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
-    float ms = 0.f;
-    if (pe == hipSuccess) pe = hipEventElapsedTime(&ms, e0, e1);
-    HIPCHK(hipMemsetAsync(c->pf->flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (pe != hipSuccess) return LLMK_E_HIP + (int)pe;
-    *avg_ms = ms / (float)iters;
-    return LLMK_OK;
+    return bd_time(b, n, pos, iters, sp, avg_ms);
 }
 
 // ---- spans (batch.h): several consecutive positions of a slot in one pass ----
@@ -3373,11 +3397,7 @@ static bool span_ok(const llmk_batch* b, int n_spans, const llmk_span* spans, co
     int n = 0;
     for (int i = 0; i < n_spans; ++i) {
         const llmk_span& s = spans[i];
-        if (s.slot < 0 || s.slot >= b->n_slots || seen[s.slot]) return false;
-        seen[s.slot] = true;
-        if (s.len < 1 || s.len > LLMK_MAX_BATCH - n) return false;
-        if (s.pos0 < 1 || s.pos0 > b->seq_len || s.len - 1 > b->seq_len - s.pos0) return false;
-        if (b->n_attached > 0 && s.pos0 <= b->px->h_first[s.slot]) return false;      // an attached slot's positions 1..P are the prefix
+        if (s.len < 1 || s.len > LLMK_MAX_BATCH - n || !bd_slot_ok(b, seen, s.slot, s.pos0, s.len)) return false;
         n += s.len;
     }
     for (int i = 0; fed && i < n; ++i)
@@ -3395,12 +3415,10 @@ static int span_setup(llmk_batch* b, int rows) {
     }
     if (!b->span_attn || b->sn) return LLMK_OK;
     auto sn = std::make_unique<llmk_batch::Spans>();
-    const size_t nb = LLMK_MAX_BATCH, states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul;
-    HIPCHK(sn->d_groups.alloc(nb));
-    HIPCHK(sn->h_groups.alloc(nb));
-    int rc;
-    if ((rc = bd_alloc_rc(sn->d_spo.alloc(states * c->hs))) != LLMK_OK) return rc;
-    if ((rc = bd_alloc_rc(sn->d_spml.alloc(states))) != LLMK_OK) return rc;
+    HIPCHK(sn->d_groups.alloc(LLMK_MAX_BATCH));
+    HIPCHK(sn->h_groups.alloc(LLMK_MAX_BATCH));
+    const int rc = bd_alloc_rc(bd_part_states(b));
+    if (rc) return rc;
     HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
         constexpr int HS = decltype(hs)::value;
         return with_kv_type(b, [](auto t) -> hipError_t {
@@ -3443,17 +3461,10 @@ int llmk_span_forward(llmk_batch* b, int n_spans, const llmk_span* spans, const 
     HIPCHK(span_upload(b, n_spans, spans, tokens));
     int max_pos = 0;
     for (int i = 0; i < n_spans; ++i) max_pos = std::max(max_pos, spans[i].pos0 + spans[i].len - 1);
-    HIPCHK(bd_pass(b, n, max_pos, logits_out != nullptr, sp));
-    HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(pf_fetch_flag(c));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (pf_flagged(c)) {
-        static bool told = false;
-        return pf_redo(c, "llmk_span_forward", &told, [&] { return llmk_span_forward(b, n_spans, spans, tokens, flags, logits_out, argmax_out); });
-    }
-    const int* ids = reinterpret_cast<const int*>(b->h_out + n);
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 1 || ids[i] > c->V) return LLMK_E_NONFINITE;
+    const int* ids;
+    rc = bd_forward_sync(b, n, max_pos, logits_out != nullptr, sp, "llmk_span_forward",
+                         [&] { return llmk_span_forward(b, n_spans, spans, tokens, flags, logits_out, argmax_out); }, &ids);
+    if (!ids) return rc;
     if (!(flags & LLMK_SPAN_LAST)) {
         if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
         if (logits_out) HIPCHK(hipMemcpy(logits_out, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost));
@@ -3474,29 +3485,12 @@ int llmk_span_time(llmk_batch* b, int n_spans, int len, int pos0, int iters, flo
     int n = 0;
     if (!span_ok(b, n_spans, spans, nullptr, false, &n)) return LLMK_E_ARG;
     if (len == 1) return llmk_batch_time(b, n_spans, pos0, iters, avg_ms);      // one position per slot: that pass
-    llmk_ctx* c = b->ctx;
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     if ((rc = span_setup(b, n)) != LLMK_OK) return rc;
     HIPCHK(span_upload(b, n_spans, spans, nullptr));
-    const int max_pos = pos0 + len - 1;
-    HIPCHK(bd_pass(b, n, max_pos, false, sp));      // warm-up
-    HIPCHK(hipStreamSynchronize(c->stream));
-    Event e0, e1;
-    HIPCHK(e0.create());
-    hipError_t pe = e1.create();
-    if (pe == hipSuccess) pe = hipEventRecord(e0, c->stream);
-    for (int k = 0; k < iters && pe == hipSuccess; ++k) pe = bd_pass(b, n, max_pos, false, sp);
-    if (pe == hipSuccess) pe = hipEventRecord(e1, c->stream);
-    if (pe == hipSuccess) pe = hipStreamSynchronize(c->stream);
-    float ms = 0.f;
-    if (pe == hipSuccess) pe = hipEventElapsedTime(&ms, e0, e1);
-    HIPCHK(hipMemsetAsync(c->pf->flag, 0, sizeof(unsigned), c->stream));      // (token 1 at every row: whatever the range check said is not a call's)
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (pe != hipSuccess) return LLMK_E_HIP + (int)pe;
-    *avg_ms = ms / (float)iters;
-    return LLMK_OK;
+    return bd_time(b, n, pos0 + len - 1, iters, sp, avg_ms);
 }
 
 int llmk_reset(llmk_ctx* c) {

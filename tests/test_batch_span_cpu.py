@@ -71,7 +71,9 @@ def test_mirrors_follow_the_kernel_s_rule():
     assert "t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);" in src
     hip = open(os.path.join(ROOT, "llm.f90_amd", "csrc", "llmk.hip")).read()
     assert "b->sn->h_groups[ng++] = BdGroup{row + j, std::min(rg, spans[i].len - j)};" in hip
-    assert hip.count("states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul") == 2      # the span part states are sized as the prefix's
+    # the span part states ARE the prefix's: one pair (llmk_batch::PartStates), sized once, built by whichever needs it first
+    assert hip.count("states = nb * c->nkv * 2 * BD_MAX_PARTS * c->kv_mul") == 1
+    assert hip.count("bd_part_states(b)") == 2 and "bd_alloc_rc(bd_part_states(b))" in hip     # llmk_prefix_set and span_setup call it
 
 
 def random_spans(rng, kv_mul, lo, seq_len=400):

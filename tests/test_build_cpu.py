@@ -161,6 +161,38 @@ def test_the_shim_allocates_and_releases_through_its_owners_only():
     assert os.path.normpath(os.path.join(csrc, "owned.h")) in seen
 
 
+def test_the_batch_s_host_code_has_one_store_one_attention_plan_and_one_call_tail():
+    """A batch's K and V blocks and its prefix rows are a BdStore each, whatever the element type: llmk.hip declares none of the typed
+    buffer pairs again, nor the two part-state pairs that one lazily built pair replaced.  The element types differ on the host inside
+    the BdKv specialisations and with_kv_type ALONE: below the "batched decode" banner and above llmk_reset no other line compares
+    kv_type or asks std::is_same_v about an element type.  A pass launches the prefix kernel and the fold kernel at one site each
+    (bd_attn_plan decides), and the batch functions share one timing loop.  All outside comments."""
+    shim = _code_of("llmk.hip")
+    gone = re.compile(r"\b(d_kc16|d_vc16|d_kc8|d_vc8|d_pk16|d_pv16|d_pk8|d_pv8|d_xpo|d_spo)\b")
+    hits = [f"llmk.hip:{n}: {c.strip()}" for n, c in shim if gone.search(c)]
+    assert not hits, "\n".join(hits)
+    launches = re.findall(r"hipLaunchKernelGGL\((.*?)\);", "\n".join(c for _, c in shim), re.S)
+    assert len(launches) > 50, len(launches)
+    for what in ("::prefix)", "bd_attn_fold_kernel"):
+        assert sum(what in l for l in launches) == 1, what
+    raw = open(os.path.join(ROOT, "llm.f90_amd", "csrc", "llmk.hip")).read().splitlines()
+    banner = next(n for n, line in enumerate(raw, 1) if line.startswith("// ---- batched decode"))
+    reset = next(n for n, c in shim if c.startswith("int llmk_reset("))
+    create = next(n for n, c in shim if "llmk_batch_create" in c)
+    assert banner < create < reset
+    assert sum("hipEventElapsedTime" in c for n, c in shim if create <= n < reset) <= 1
+    assert sum("hipEventElapsedTime" in c for n, c in shim if banner <= n < reset) == 1
+    # the one place: from the first BdKv line to the closing brace of with_kv_type
+    first = next(n for n, c in shim if "struct BdKv" in c)
+    with_ = next(n for n, c in shim if "static auto with_kv_type(" in c)
+    last = next(n for n, c in shim if n > with_ and c.startswith("}"))
+    assert banner < first < with_ < last < reset
+    typed = re.compile(r"is_same_v<[^>]*(KvQ8|_Float16|float)|kv_type\s*[!=]=")
+    assert any(typed.search(c) for n, c in shim if first <= n <= last)
+    hits = [f"llmk.hip:{n}: {c.strip()}" for n, c in shim if banner <= n < reset and not first <= n <= last and typed.search(c)]
+    assert not hits, "\n".join(hits)
+
+
 def test_the_sticky_error_word_has_one_vocabulary_and_one_policy():
     """The persistent kernel's sticky error word is spelled in csrc/tk_recover.h alone, and the host's reaction to it is that
     header's TkRecovery, carried out by llmk.hip's tk_perform.  Outside comments, neither llmk.hip nor token_kernel.h spells the
