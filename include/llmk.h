@@ -606,6 +606,49 @@ int llmk_span_forward(llmk_batch *b, int n_spans, const llmk_span *spans, const 
                       float *logits_out, int *argmax_out);
 int llmk_span_time(llmk_batch *b, int n_spans, int len, int pos0, int iters, float *avg_ms);
 
+/* Trees: SEVERAL drafted continuations of a slot that share a stem, checked in one pass -- top-k alternatives
+ * per step, several draft heads, n-gram lookups with more than one candidate.  A span verifies a chain; a tree verifies every
+ * root-to-node path at once, the stem computed and its K/V rows read once.  ("tree": the llmk_batch_* and llmk_span_* lists are closed.)
+ *
+ * forward: a tree is an llmk_span {slot, pos0, len}: len NODES in row order; tokens[rows] and parent[rows] run over all trees in tree
+ *          order.  parent of node j is LLMK_TREE_ROOT or an index in [0, j-1] of the same tree (parents come before children);
+ *          depth(j) is 0 for a child of the root, else depth(parent) + 1.  Node j feeds its token at POSITION pos0 + depth(j) -- the
+ *          RoPE angle of its Q and K -- and its K/V row is written at the cache row of position pos0 + j, its PLACE.  It attends over
+ *          the slot's positions 1..pos0-1 (the prefix if the slot is attached, then its own rows) and over the places of its
+ *          ancestors and itself, nothing else: its logits are what the sequence "the slot's first pos0-1 tokens, then the tokens
+ *          along root -> j" gives at its last position, within the 1e-4 bar of llmk_forward on that sequence alone (not bit-identical).
+ *          LLMK_E_ARG before anything runs or is allocated: a NULL batch, trees, tokens or parent; n_trees < 1 or a len < 1; rows >
+ *          LLMK_MAX_BATCH; a slot out of range or named twice; pos0 < 1 or pos0+len-1 > the batch's seq_len (PLACES count, not
+ *          positions); an attached slot with pos0 <= P; a token outside [1, vocab_size]; a parent outside {-1} u [0, j-1]; both
+ *          outputs NULL.  logits_out [rows][vocab_size] and argmax_out [rows] (the 1-based first maximum) in row order; either may
+ *          be NULL.  A row with no finite logit: LLMK_E_NONFINITE.  The f16-range rule of llmk_prefill applies as for spans.
+ *          Every cache type is served.  The same call on the same state returns the same bits, and a node's bits do not depend on the
+ *          tokens of nodes that are not its ancestors.
+ *          A call all of whose trees are chains (parent[j] == j-1 for every node) IS llmk_span_forward with flags 0: same code path,
+ *          same launches, same bits.
+ * accept:  makes path[0..n) the slot's positions pos0 .. pos0+n-1; path[k] is the node accepted at depth k.  In every layer, for K
+ *          and V, the cache row of place pos0+path[k] is copied to the cache row of position pos0+k, bit for bit in the batch's type
+ *          (f32 words, halves, q8_0 quants with their block scales).  The rows were rotated for position pos0+depth, so nothing is
+ *          recomputed: the slot continues at pos0+n exactly as if those tokens had been fed in order, and everything behind is dead
+ *          by the span rule.  LLMK_E_ARG: a NULL batch; a slot out of range; n < 0, or a NULL path with n > 0; path not strictly
+ *          increasing or path[0] < 0; pos0 < 1 or pos0+path[n-1] > seq_len; an attached slot with pos0 <= P.  n == 0 succeeds and
+ *          does nothing; so does a path with path[k] == k throughout (a chain's rows are where they belong).  The function does not
+ *          know the tree: a path that is not a root-to-node chain of the last forward is the caller's error and leaves the cache of
+ *          some other sequence.
+ * time:    measurement hook like llmk_span_time: n_trees trees of len nodes each, slots 0..n_trees-1, all from pos0, in the shape of
+ *          a binary heap -- parent[j] = (j-1)/2, node 0 under the root -- with forward's range checks.  It OVERWRITES those rows.
+ * Token records are NOT maintained, as for spans.  State that only trees need -- a pass's RoPE positions, masks and group bases, the
+ * path -- is allocated by the first tree call that is not a chain: a batch that never makes one allocates and launches exactly what
+ * it did without these functions.  A tree pass costs what a span pass of the same rows costs: the same column groups of 16 / (query
+ * heads per kv head) consecutive rows read the slot's K/V rows once each (bd_attn_tree_kernel).
+ * Out of scope: draft models and acceptance policies (the host compares argmax_out itself), trees inside llmk_batch_decode /
+ * llmk_rows_decode, LLMK_SPAN_LAST for trees, more than LLMK_MAX_BATCH rows per pass, more than one tree per slot per call. */
+#define LLMK_TREE_ROOT (-1)
+int llmk_tree_forward(llmk_batch *b, int n_trees, const llmk_span *trees, const int *tokens, const int *parent,
+                      float *logits_out, int *argmax_out);
+int llmk_tree_accept(llmk_batch *b, int slot, int pos0, int n, const int *path);
+int llmk_tree_time(llmk_batch *b, int n_trees, int len, int pos0, int iters, float *avg_ms);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

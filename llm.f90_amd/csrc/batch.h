@@ -9,7 +9,9 @@
 //   bd_advance     llmk_batch_decode: the picked id becomes the row's next token, its position moves on -- on the device
 //   bd_attn_prefix / bd_attn_own   a pass with rows ATTACHED to the batch's shared prefix (llmk_prefix_*, below)
 //   bd_attn_span   a pass with SEVERAL consecutive positions of a slot (llmk_span_*, below): (position, query head) pairs as columns
-// bd_attn_prefix / bd_attn_own / bd_attn_span are setup around attn_tiles.h's tile loop, wave merge and look-ahead loads (shared with pf_attn_kernel);
+//   bd_attn_tree   a pass over TREES of drafted tokens (llmk_tree_*, below): a span pass whose rows are rotated at one position, stored
+//                  at another and see their ancestors only; bd_tree_move moves an accepted path down to consecutive positions
+// bd_attn_prefix / bd_attn_own / bd_attn_span / bd_attn_tree are setup around attn_tiles.h's tile loop, wave merge and look-ahead loads (shared with pf_attn_kernel);
 // bd_attn keeps the same statements written out (the reason stands at the kernel).
 // The caches are [L][n_slots][seq_len][KV], f32 or -- a batch of llmk_cache_create(.., LLMK_TYPE_F16) -- IEEE half, or -- LLMK_TYPE_Q8_0 --
 // int8 quants in that order with the f16 scales of their blocks of 32 behind them (the q8_0 sections below).
@@ -611,6 +613,175 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_q8_attn_span_kernel(const 
     bd_attn_span_body<HS, KvQ8>(Q, kc, vc, out, po, pml, bc, groups, first, n, KV, kv_mul, E, tpp, np, p0, direct);
 }
 
+// ---- trees (llmk_tree_*): drafted continuations that share a stem, in one pass                                        ------------
+// A tree is a span {slot, pos0, len} whose row j -- NODE j -- has a parent among the nodes before it, or the root.  A node has two
+// positions: it is ROTATED at pos0 + depth(j) (rope_pos[row]: what the sequence root -> j says) and STORED at its PLACE pos0 + j (the
+// row words, as in a span: bd_row_ok, the fold, the samplers and the argmax read places and need not know).  Cache row base + j,
+// base = pos0 - 1, is node j's; a node sees the slot's rows below `base` and, of the tree's rows, its ancestors' and its own: bit i
+// of the row's 128-bit mask m[4] says that node i is one of those (LLMK_MAX_BATCH nodes at most).  Ancestors come first, so the
+// span's bound r < place still holds and the tiles behind the group's last place are never needed.  llmk_tree_accept then moves the
+// rows of the accepted path down to positions pos0, pos0 + 1, ..: they were rotated for exactly those positions.
+static_assert(PF_TMAX <= 128, "a tree's nodes are the bits of four mask words");
+typedef unsigned bd_mask __attribute__((ext_vector_type(4)));      // (a native vector: HIP's uint4, captured by the predicate, went to scratch)
+struct BdTreeArgs {
+    const int* rope_pos;      // [rows] the position a row is rotated at, <= its place
+    const bd_mask* mask;      // [rows] ancestor-or-self bits over the row's tree
+    const int* base;          // [groups] pos0 - 1 of the group's tree: the cache row of node 0
+};
+
+// The QKV epilogues with two positions.  pf_epi_qkv_pair[_h] rotate by a.pos0 + t and store at cache row a.pos0 + t - 1: handed the
+// RoPE position and caches moved on by (place - RoPE position) rows they store at the place, with their arithmetic untouched -- a
+// chain's rows (place == RoPE position) are bd_epi_qkv[_h]_kernel's bit for bit.  A row whose RoPE position is not in [1, place]
+// is not written (the host checks every parent before a pass).
+__device__ __forceinline__ bool bd_tree_row_ok(const BdCaches& bc, const BdRow& r, int rpos) { return bd_row_ok(bc, r) && rpos >= 1 && rpos <= r.pos; }
+__global__ void bd_epi_qkv_tree_kernel(PfEpiArgs a, BdCaches bc, const int* __restrict__ rope_pos) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    if (p4 >= a.rows / 4) return;
+    const BdRow r = bc.rows[t];
+    const int rpos = rope_pos[t];
+    if (!bd_tree_row_ok(bc, r, rpos)) return;
+    const float4 s4 = pf_sum4(a, t, 4 * p4);
+    a.pos0 = rpos - t;
+    a.kc += (size_t)r.slot * bc.slot_stride + (size_t)(r.pos - rpos) * a.KV;
+    a.vc += (size_t)r.slot * bc.slot_stride + (size_t)(r.pos - rpos) * a.KV;
+    pf_epi_qkv_pair(a, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
+    pf_epi_qkv_pair(a, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
+}
+__global__ void bd_epi_qkv_tree_h_kernel(PfEpiArgs a, BdCaches bc, _Float16* __restrict__ kc, _Float16* __restrict__ vc,
+                                         const int* __restrict__ rope_pos) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    if (p4 >= a.rows / 4) return;
+    const BdRow r = bc.rows[t];
+    const int rpos = rope_pos[t];
+    if (!bd_tree_row_ok(bc, r, rpos)) return;
+    const float4 s4 = pf_sum4(a, t, 4 * p4);
+    a.pos0 = rpos - t;
+    kc += (size_t)r.slot * bc.slot_stride + (size_t)(r.pos - rpos) * a.KV;
+    vc += (size_t)r.slot * bc.slot_stride + (size_t)(r.pos - rpos) * a.KV;
+    pf_epi_qkv_pair_h(a, kc, vc, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
+    pf_epi_qkv_pair_h(a, kc, vc, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
+}
+// q8_0: bd_epi_qkv_q8_kernel's statements (keep the two in step) with the rotation by rope_pos[t]; the block goes to the row's place
+__global__ void bd_epi_qkv_tree_q8_kernel(PfEpiArgs a, BdCaches bc, Q8Rows kc, Q8Rows vc, const int* __restrict__ rope_pos) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y, r0 = 4 * p4;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    const BdRow r = bc.rows[t];
+    const int rpos = rope_pos[t];
+    const bool live = p4 < a.rows / 4 && bd_tree_row_ok(bc, r, rpos);
+    float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) s4 = pf_sum4(a, t, r0);
+    const float xn = a.xn[t];
+    float x[4] = {s4.x / xn, s4.y / xn, s4.z / xn, s4.w / xn};
+    const int i0 = r0 < a.E ? r0 : r0 < a.E + a.KV ? r0 - a.E : r0 - a.E - a.KV;      // the element in Q, K or V
+    if (live && r0 < a.E + a.KV) {
+#pragma unroll
+        for (int k = 0; k < 4; k += 2) {
+            const float rval = (float)rpos * a.rope[((i0 + k) % a.hs) >> 1];
+            const float fcr = cosf(rval), fci = sinf(rval);
+            {
+#pragma clang fp contract(off)
+                const float p00 = x[k] * fcr, p11 = x[k + 1] * fci, p01 = x[k] * fci, p10 = x[k + 1] * fcr;
+                x[k] = p00 - p11;
+                x[k + 1] = p01 + p10;
+            }
+        }
+    }
+    unsigned quants;
+    _Float16 scale;
+    bd_q8_block(x, quants, scale);
+    if (!live) return;
+    if (r0 < a.E) {
+        *reinterpret_cast<float4*>(a.out + (size_t)t * a.E + i0) = make_float4(x[0], x[1], x[2], x[3]);
+        return;
+    }
+    const Q8Rows dst = attn_at(r0 < a.E + a.KV ? kc : vc, (size_t)r.slot * bc.slot_stride + (size_t)(r.pos - 1) * a.KV + (i0 & ~31));
+    *reinterpret_cast<unsigned*>(dst.q + (i0 & 31)) = quants;
+    if ((i0 & 31) == 0) *dst.d = scale;
+}
+
+// bd_attn_span_kernel's work split -- one workgroup per (kv head, column group, part), the groups cut from the trees as from spans, the
+// slot's K/V rows across L2 once per group -- with the ancestor predicate per lane: the lane of a column whose row has place `vis`
+// and mask m sees cache row r iff lo <= r < vis and (r < base or bit r - base of m).  The four mask words stay in registers; the
+// word is picked by two compares on the bit index (no indexed local array, hence no scratch).  A column need not see the row its
+// part starts at (a child of the root at pos0 == lo + 1 sees itself alone), so ANY part of a column may be empty: M = -inf, L = 0,
+// which the merge and the fold skip; the part with the column's own place never is.
+template <int HS, class T>
+__device__ __forceinline__ void bd_attn_tree_body(const float* __restrict__ Q, typename AttnAhead<HS, T>::Ptr kc, typename AttnAhead<HS, T>::Ptr vc,
+                                                  float* __restrict__ out, float* __restrict__ po, float2* __restrict__ pml, const BdCaches& bc,
+                                                  const BdGroup* __restrict__ groups, const BdTreeArgs& tr, const int* __restrict__ first, int n,
+                                                  int KV, int kv_mul, int E, int tpp, int np, int p0, int direct) {
+    constexpr int DG = HS / 4, NT = HS / 16;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x;
+    const BdGroup gr = groups[blockIdx.y];
+    if (gr.first < 0 || gr.rows < 1 || gr.rows > bd_prefix_rg(kv_mul) || gr.rows > n - gr.first) return;      // whole workgroup: no barrier is pending
+    const BdRow row0 = bc.rows[gr.first], rowl = bc.rows[gr.first + gr.rows - 1];
+    if (!bd_row_ok(bc, row0) || !bd_row_ok(bc, rowl) || rowl.slot != row0.slot || rowl.pos != row0.pos + gr.rows - 1) return;
+    const int lo = first ? first[row0.slot] : 0, base = tr.base[blockIdx.y];
+    if (base < lo || base >= row0.pos || rowl.pos - base > PF_TMAX) return;      // the group's nodes are row0.pos - 1 - base .. rowl.pos - 1 - base
+    const int live = gr.rows * kv_mul, c = min(li, live - 1);
+    const int vis = row0.pos + c / kv_mul;            // this lane's column sees nothing from its own place on
+    const bd_mask m = tr.mask[gr.first + c / kv_mul];
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)(gr.first + c / kv_mul) * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG);
+    float m_run, l_run;
+    pf_v4f O[NT];
+    const int ntile = (rowl.pos + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
+    const size_t at = (size_t)row0.slot * bc.slot_stride + (size_t)kvh * HS;
+    attn_tiles<HS, T, BD_WAVES>(qf, attn_at(kc, at + g * DG), attn_at(vc, at + NT * li), KV, rowl.pos - 1, ntile, t0, t1, wid, li, g,
+                                [&](int r) {
+                                    const unsigned j = (unsigned)(r - base);      // the node stored at cache row r (r < base: beyond every word)
+                                    const unsigned w = j < 64u ? (j < 32u ? m.x : m.y) : (j < 96u ? m.z : m.w);
+                                    return lo <= r && r < vis && (r < base || ((w >> (j & 31u)) & 1u));
+                                },
+                                m_run, l_run, O);
+    attn_merge_waves<HS, BD_WAVES>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
+        const int b = gr.first + col / kv_mul, q = col % kv_mul;
+        if (direct) {
+            out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+        } else {
+            const size_t s = (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q;
+            po[s * HS + d] = val;
+            if (d == 0) pml[s] = make_float2(M, L);
+        }
+    });
+}
+template <int HS, class T = float>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_tree_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                       const T* __restrict__ vc, float* __restrict__ out,
+                                                                       float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                       const BdGroup* __restrict__ groups, BdTreeArgs tr,
+                                                                       const int* __restrict__ first, int n, int KV, int kv_mul, int E,
+                                                                       int tpp, int np, int p0, int direct) {
+    bd_attn_tree_body<HS, T>(Q, kc, vc, out, po, pml, bc, groups, tr, first, n, KV, kv_mul, E, tpp, np, p0, direct);
+}
+template <int HS>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_q8_attn_tree_kernel(const float* __restrict__ Q, Q8Rows kc, Q8Rows vc, float* __restrict__ out,
+                                                                          float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                          const BdGroup* __restrict__ groups, BdTreeArgs tr,
+                                                                          const int* __restrict__ first, int n, int KV, int kv_mul, int E,
+                                                                          int tpp, int np, int p0, int direct) {
+    bd_attn_tree_body<HS, KvQ8>(Q, kc, vc, out, po, pml, bc, groups, tr, first, n, KV, kv_mul, E, tpp, np, p0, direct);
+}
+
+// llmk_tree_accept: the rows of the accepted nodes path[0] < path[1] < .. become the rows of positions pos0, pos0 + 1, ..  k / v point
+// at the cache row of position pos0 in layer 0 of the slot, as arrays of W (4-byte words of f32 | f16 | q8_0 quant rows, or the 2-byte
+// scales of q8_0 rows); `row` W per cache row, `layer` W between layers, `room` rows from there to the slot's end.  One thread per
+// (column of W, layer, K | V) walks k upwards: path[k] >= k and strictly increasing, so step k reads a row no earlier step of this
+// thread wrote, and no other thread touches the column -- an in-place move without a barrier.  path[k] == k: nothing to move.
+template <class W>
+__global__ void bd_tree_move_kernel(W* __restrict__ k, W* __restrict__ v, size_t layer, int row, int room, const int* __restrict__ path, int n) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= row) return;
+    W* p = (blockIdx.z ? v : k) + blockIdx.y * layer + col;
+    for (int i = 0; i < n; ++i) {
+        const int s = path[i];
+        if (s > i && s < room) p[(size_t)i * row] = p[(size_t)s * row];
+    }
+}
+
 // The kernels by cache type, for the host's one dispatch (llmk.hip with_kv_type): T = float | _Float16 | KvQ8
 template <int HS, class T>
 struct BdAttn {
@@ -618,6 +789,7 @@ struct BdAttn {
     static constexpr auto prefix = bd_attn_prefix_kernel<HS, T>;
     static constexpr auto own = bd_attn_own_kernel<HS, T>;
     static constexpr auto span = bd_attn_span_kernel<HS, T>;
+    static constexpr auto tree = bd_attn_tree_kernel<HS, T>;
 };
 template <int HS>
 struct BdAttn<HS, KvQ8> {
@@ -625,6 +797,7 @@ struct BdAttn<HS, KvQ8> {
     static constexpr auto prefix = bd_q8_attn_prefix_kernel<HS>;
     static constexpr auto own = bd_q8_attn_own_kernel<HS>;
     static constexpr auto span = bd_q8_attn_span_kernel<HS>;
+    static constexpr auto tree = bd_q8_attn_tree_kernel<HS>;
 };
 
 // llmk_batch_decode, between two passes: row i's pick (1-based; greedy: the classifier's first maximum, else what the sampler left)

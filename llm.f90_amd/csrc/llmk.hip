@@ -293,6 +293,18 @@ struct llmk_batch {
     std::unique_ptr<PartStates> ps;
     bool span_attn = true;                       // LLMK_SPAN_ATTN=0 at create: span passes run the per-row attention kernels
     int pass_groups = 0;                         // column groups of the rows span_upload uploaded last; 0: not a span pass
+    // trees (llmk_tree_*, batch.h), built by the first tree call that is not a chain: a batch without one has none of it
+    struct Trees {
+        // one block of words per pass, [TR_WORDS]: the rows' RoPE positions, the groups' pos0 - 1, the rows' four mask words
+        static constexpr size_t ROPE = 0, BASE = LLMK_MAX_BATCH, MASK = 2 * LLMK_MAX_BATCH, TR_WORDS = 6 * LLMK_MAX_BATCH;
+        DevBuf<int> d_words;
+        PinnedBuf<int> h_words;
+        DevBuf<int> d_path;                      // [seq_len] llmk_tree_accept's path ...
+        PinnedBuf<int> h_path;                   // ... and the pinned words it is copied from
+        BdTreeArgs args() const { return BdTreeArgs{d_words + ROPE, reinterpret_cast<const bd_mask*>(d_words + MASK), d_words + BASE}; }
+    };
+    std::unique_ptr<Trees> tr;
+    bool pass_tree = false;                      // the rows uploaded last are the nodes of trees (tree_upload): BdAttnPlan TREE
 };
 
 namespace {
@@ -1499,9 +1511,24 @@ static float bd_half_bits_to_float(uint16_t h) {
 //                                     elements apart), ENQUEUED: the device-to-device copy an f32 batch always made, the converting
 //                                     kernel for the others (batch.h bd_to_half_kernel, bd_to_q8_kernel);
 //   read(view, n, out)                n elements as f32 on the host, exact; synchronous;
-//   epi_qkv(a, bc, kc, vc, QKV, T, st) a layer's QKV epilogue of T rows, which writes the rows' K and V into the layer's blocks.
+//   epi_qkv(a, bc, kc, vc, rope_pos, QKV, T, st) a layer's QKV epilogue of T rows, which writes the rows' K and V into the layer's
+//                                     blocks; rope_pos (a tree pass, else null): the rows' RoPE positions apart from their places;
+//   move(k, v, b, pos0, path, n, st)  llmk_tree_accept: cache rows pos0 - 1 + path[i] onto rows pos0 - 1 + i of k / v (views of layer 0
+//                                     of a slot at position pos0) in every layer, bit for bit, ENQUEUED (batch.h bd_tree_move_kernel).
+// bd_tree_move_kernel over columns of W that hold `per` cache elements each
+template <class W>
+static hipError_t bd_tree_move(W* k, W* v, const llmk_batch* b, int per, int pos0, const int* path, int n, hipStream_t st) {
+    const llmk_ctx* c = b->ctx;
+    const int row = c->KV / per;
+    hipLaunchKernelGGL(bd_tree_move_kernel<W>, dim3((row + 255) / 256, c->L, 2), dim3(256), 0, st, k, v, (size_t)b->n_slots * b->seq_len * row, row,
+                       b->seq_len - pos0 + 1, path, n);
+    return hipGetLastError();
+}
 template <class T> struct BdKvPlain {
     static size_t bytes(size_t n) { return n * sizeof(T); }
+    static hipError_t move(T* k, T* v, const llmk_batch* b, int pos0, const int* path, int n, hipStream_t st) {
+        return bd_tree_move(reinterpret_cast<unsigned*>(k), reinterpret_cast<unsigned*>(v), b, (int)(sizeof(unsigned) / sizeof(T)), pos0, path, n, st);
+    }
     static T* view(const DevBuf<char>& buf, size_t) { return reinterpret_cast<T*>(buf.get()); }
     static bool shape_ok(int) { return true; }
     static hipError_t zero(T* at, size_t n, hipStream_t st) { return hipMemsetAsync(at, 0, n * sizeof(T), st); }
@@ -1516,9 +1543,10 @@ template <> struct BdKv<float> : BdKvPlain<float> {
         return hipSuccess;
     }
     static hipError_t read(const float* at, size_t n, float* out) { return hipMemcpy(out, at, n * sizeof(float), hipMemcpyDeviceToHost); }
-    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, float* kc, float* vc, int QKV, int T, hipStream_t st) {
+    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, float* kc, float* vc, const int* rope_pos, int QKV, int T, hipStream_t st) {
         a.kc = kc; a.vc = vc;
-        hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc);
+        if (rope_pos) hipLaunchKernelGGL(bd_epi_qkv_tree_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, rope_pos);
+        else hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc);
         return hipGetLastError();
     }
 };
@@ -1534,9 +1562,10 @@ template <> struct BdKv<_Float16> : BdKvPlain<_Float16> {
         for (size_t i = 0; i < n; ++i) out[i] = bd_half_bits_to_float(h[i]);
         return hipSuccess;
     }
-    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, _Float16* kc, _Float16* vc, int QKV, int T, hipStream_t st) {
+    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, _Float16* kc, _Float16* vc, const int* rope_pos, int QKV, int T, hipStream_t st) {
         a.kc = a.vc = nullptr;      // (the context's caches are not this pass's)
-        hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
+        if (rope_pos) hipLaunchKernelGGL(bd_epi_qkv_tree_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc, rope_pos);
+        else hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
         return hipGetLastError();
     }
 };
@@ -1565,10 +1594,16 @@ template <> struct BdKv<KvQ8> {
         for (size_t i = 0; i < n; ++i) out[i] = (float)q[i] * bd_half_bits_to_float(d[i / 32]);
         return hipSuccess;
     }
-    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, Q8Rows kc, Q8Rows vc, int QKV, int T, hipStream_t st) {
+    static hipError_t epi_qkv(PfEpiArgs& a, const BdCaches& bc, Q8Rows kc, Q8Rows vc, const int* rope_pos, int QKV, int T, hipStream_t st) {
         a.kc = a.vc = nullptr;
-        hipLaunchKernelGGL(bd_epi_qkv_q8_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
+        if (rope_pos) hipLaunchKernelGGL(bd_epi_qkv_tree_q8_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc, rope_pos);
+        else hipLaunchKernelGGL(bd_epi_qkv_q8_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
         return hipGetLastError();
+    }
+    // the quant words, then the scales: 2-byte columns (a row has KV / 32 of them, which may be odd)
+    static hipError_t move(Q8Rows k, Q8Rows v, const llmk_batch* b, int pos0, const int* path, int n, hipStream_t st) {
+        HIPRET(bd_tree_move(reinterpret_cast<unsigned*>(k.q), reinterpret_cast<unsigned*>(v.q), b, 4, pos0, path, n, st));
+        return bd_tree_move(reinterpret_cast<uint16_t*>(k.d), reinterpret_cast<uint16_t*>(v.d), b, 32, pos0, path, n, st);
     }
 };
 static bool kv_type_ok(int kv_type) { return kv_type == LLMK_TYPE_F32 || kv_type == LLMK_TYPE_F16 || kv_type == LLMK_TYPE_Q8_0; }
@@ -1607,10 +1642,13 @@ static hipError_t bd_zero_slot(llmk_batch* b, int slot, int n_pos) {
 //         (stride BD_MAX_GROUP), folded;
 //   OWN   attached rows (pass_att > 0, llmk_prefix_*): the prefix kernel, then bd_attn_own_kernel from row `first` on; always folded;
 //   SPAN  a span pass (pass_groups > 0, llmk_span_*): the prefix kernel if it has attached rows, then bd_attn_span_kernel over column
-//         groups; one part and no attached row: straight to XB (direct), else folded.
-// OWN and SPAN leave np = pparts + parts states per (row, kv head) in the batch's PartStates (stride kv_mul): the prefix parts first.
+//         groups; one part and no attached row: straight to XB (direct), else folded;
+//   TREE  a tree pass (pass_tree, llmk_tree_*): a span pass whose rows are rotated at rope_pos and whose column groups run
+//         bd_attn_tree_kernel -- the same groups, split rule, part states and fold.
+// OWN, SPAN and TREE leave np = pparts + parts states per (row, kv head) in the batch's PartStates (stride kv_mul): the prefix parts first.
 struct BdAttnPlan {
-    enum Kind { ROW, OWN, SPAN } kind;
+    enum Kind { ROW, OWN, SPAN, TREE } kind;
+    bool grouped;                   // SPAN or TREE: the rows' kernel runs over column groups
     bool shared, fold;              // attached rows in the pass: the prefix kernel runs; the fold kernel runs
     int units;                      // grid.y of the rows' kernel: rows, or column groups of a span pass
     int parts, tpp;                 // own parts and their tiles
@@ -1625,8 +1663,9 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
     const llmk_ctx* c = b->ctx;
     BdAttnPlan p{};
     p.shared = b->pass_att > 0;
-    p.kind = b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
-    p.units = p.kind == BdAttnPlan::SPAN ? b->pass_groups : n;
+    p.kind = b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
+    p.grouped = p.kind == BdAttnPlan::SPAN || p.kind == BdAttnPlan::TREE;
+    p.units = p.grouped ? b->pass_groups : n;
     // The split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`.  Without
     // attached rows every range starts at tile 0 and the longest is the longest row's
     int own = (max_pos + BD_TILE - 1) / BD_TILE;
@@ -1642,7 +1681,7 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
     p.parts = bd_parts(p.units, c->nkv, own * BD_TILE, c->n_cu);
     p.tpp = bd_tiles_per_part(own * BD_TILE, p.parts);
     p.np = p.pparts + p.parts;
-    p.direct = p.kind == BdAttnPlan::SPAN && !p.shared && p.parts == 1;
+    p.direct = p.grouped && !p.shared && p.parts == 1;
     p.fold = p.kind == BdAttnPlan::ROW ? p.parts > 1 : !p.direct;
     if (p.kind == BdAttnPlan::ROW) {
         p.po = b->d_po; p.pml = b->d_pml; p.stride = BD_MAX_GROUP;
@@ -1666,7 +1705,7 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
     // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
         const auto kc = bd_cache_view<TC>(b, b->cache.k, l, 0, 0), vc = bd_cache_view<TC>(b, b->cache.v, l, 0, 0);
-        HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, QKV, T, w.stream));
+        HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, p.kind == BdAttnPlan::TREE ? b->tr->args().rope_pos : nullptr, QKV, T, w.stream));
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
             const dim3 block(BD_WAVES * WAVE), grid(c->nkv, p.units, p.parts);
@@ -1688,6 +1727,10 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
                 case BdAttnPlan::SPAN:
                     hipLaunchKernelGGL((BdAttn<HS, TC>::span), grid, block, smem, w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc, b->sn->d_groups, p.first, T,
                                        KV, c->kv_mul, E, p.tpp, p.np, p.pparts, p.direct);
+                    break;
+                case BdAttnPlan::TREE:
+                    hipLaunchKernelGGL((BdAttn<HS, TC>::tree), grid, block, smem, w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc, b->sn->d_groups, b->tr->args(),
+                                       p.first, T, KV, c->kv_mul, E, p.tpp, p.np, p.pparts, p.direct);
                     break;
             }
             HIPRET(hipGetLastError());
@@ -2953,6 +2996,7 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
     hipStream_t st = b->ctx->stream;
     b->pass_att = 0;
     b->pass_groups = 0;
+    b->pass_tree = false;
     if (b->n_attached > 0) {
         // the column map: the attached rows in row order, -1 up to the end of the last column group
         for (int i = 0; i < n; ++i)
@@ -3407,13 +3451,14 @@ static bool span_ok(const llmk_batch* b, int n_spans, const llmk_span* spans, co
 }
 // what a span pass needs beyond a batch's own, by the first call that needs it: logits rows beyond n_slots; the group table and the
 // part states of bd_attn_span_kernel (not with LLMK_SPAN_ATTN=0: the per-row kernels have theirs)
-static int span_setup(llmk_batch* b, int rows) {
+// (groups: the table and the states are needed -- a tree pass always runs over column groups)
+static int span_setup(llmk_batch* b, int rows, bool groups) {
     llmk_ctx* c = b->ctx;
     if (rows > b->n_slots) {
         const int rc = bd_alloc_rc(b->d_logits.reserve((size_t)LLMK_MAX_BATCH * c->V, c->stream));
         if (rc) return rc;
     }
-    if (!b->span_attn || b->sn) return LLMK_OK;
+    if (!groups || b->sn) return LLMK_OK;
     auto sn = std::make_unique<llmk_batch::Spans>();
     HIPCHK(sn->d_groups.alloc(LLMK_MAX_BATCH));
     HIPCHK(sn->h_groups.alloc(LLMK_MAX_BATCH));
@@ -3430,12 +3475,12 @@ static int span_setup(llmk_batch* b, int rows) {
 }
 // the rows of the spans, in span order, as bd_upload_rows uploads them; then the group table (bd_attn_span_kernel), the way the column
 // map goes up.  tokens null: every row feeds token 1.
-static hipError_t span_upload(llmk_batch* b, int n_spans, const llmk_span* spans, const int* tokens) {
+static hipError_t span_upload(llmk_batch* b, int n_spans, const llmk_span* spans, const int* tokens, bool groups) {
     int slots[LLMK_MAX_BATCH], pos[LLMK_MAX_BATCH], ones[LLMK_MAX_BATCH], n = 0;
     for (int i = 0; i < n_spans; ++i)
         for (int j = 0; j < spans[i].len; ++j, ++n) { slots[n] = spans[i].slot; pos[n] = spans[i].pos0 + j; ones[n] = 1; }
     HIPRET(bd_upload_rows(b, n, slots, tokens ? tokens : ones, pos));
-    if (!b->span_attn) return hipSuccess;
+    if (!groups) return hipSuccess;
     const int rg = bd_prefix_rg(b->ctx->kv_mul);
     int row = 0, ng = 0;
     for (int i = 0; i < n_spans; row += spans[i++].len)
@@ -3457,8 +3502,8 @@ int llmk_span_forward(llmk_batch* b, int n_spans, const llmk_span* spans, const 
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
-    if ((rc = span_setup(b, n)) != LLMK_OK) return rc;
-    HIPCHK(span_upload(b, n_spans, spans, tokens));
+    if ((rc = span_setup(b, n, b->span_attn)) != LLMK_OK) return rc;
+    HIPCHK(span_upload(b, n_spans, spans, tokens, b->span_attn));
     int max_pos = 0;
     for (int i = 0; i < n_spans; ++i) max_pos = std::max(max_pos, spans[i].pos0 + spans[i].len - 1);
     const int* ids;
@@ -3488,8 +3533,132 @@ int llmk_span_time(llmk_batch* b, int n_spans, int len, int pos0, int iters, flo
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
-    if ((rc = span_setup(b, n)) != LLMK_OK) return rc;
-    HIPCHK(span_upload(b, n_spans, spans, nullptr));
+    if ((rc = span_setup(b, n, b->span_attn)) != LLMK_OK) return rc;
+    HIPCHK(span_upload(b, n_spans, spans, nullptr, b->span_attn));
+    return bd_time(b, n, pos0 + len - 1, iters, sp, avg_ms);
+}
+
+// ---- trees (batch.h): drafted continuations that share a stem in one pass; the accepted path becomes the slot's next positions ----
+// parents of a call's trees, rows in tree order: node j's is the root or a node before it; *chain: every node hangs under the one before
+static bool tree_ok(int n_trees, const llmk_span* trees, const int* parent, bool* chain) {
+    *chain = true;
+    for (int i = 0, row = 0; i < n_trees; row += trees[i++].len)
+        for (int j = 0; j < trees[i].len; ++j) {
+            const int p = parent[row + j];
+            if (p < LLMK_TREE_ROOT || p >= j) return false;
+            *chain = *chain && p == j - 1;
+        }
+    return true;
+}
+// what trees need beyond a span pass's, by the first call that needs it: the words of a pass and llmk_tree_accept's path
+static int tree_setup(llmk_batch* b) {
+    if (b->tr) return LLMK_OK;
+    llmk_ctx* c = b->ctx;
+    auto tr = std::make_unique<llmk_batch::Trees>();
+    HIPCHK(tr->d_words.alloc(llmk_batch::Trees::TR_WORDS));
+    HIPCHK(tr->h_words.alloc(llmk_batch::Trees::TR_WORDS));
+    HIPCHK(tr->d_path.alloc(b->seq_len));
+    HIPCHK(tr->h_path.alloc(b->seq_len));
+    HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
+        constexpr int HS = decltype(hs)::value;
+        return with_kv_type(b, [](auto t) -> hipError_t {
+            return hipFuncSetAttribute((const void*)BdAttn<HS, decltype(t)>::tree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+        });
+    }));
+    b->tr = std::move(tr);
+    return LLMK_OK;
+}
+// the nodes as span_upload uploads a span's rows (their places) and groups; then a row's RoPE position pos0 + depth and its
+// ancestor-or-self mask -- the parent's with the node's own bit -- and a group's pos0 - 1, in one block of words.  tokens null: token 1.
+static hipError_t tree_upload(llmk_batch* b, int n_trees, const llmk_span* trees, const int* tokens, const int* parent) {
+    typedef llmk_batch::Trees Tr;
+    HIPRET(span_upload(b, n_trees, trees, tokens, true));
+    const int rg = bd_prefix_rg(b->ctx->kv_mul);
+    int* w = b->tr->h_words;
+    for (int i = 0, row = 0, ng = 0; i < n_trees; row += trees[i++].len) {
+        int depth[LLMK_MAX_BATCH];
+        for (int j = 0; j < trees[i].len; ++j) {
+            const int p = parent[row + j];
+            int* m = w + Tr::MASK + 4 * (row + j);
+            for (int k = 0; k < 4; ++k) m[k] = p < 0 ? 0 : w[Tr::MASK + 4 * (row + p) + k];
+            m[j >> 5] |= (int)(1u << (j & 31));
+            depth[j] = p < 0 ? 0 : depth[p] + 1;
+            w[Tr::ROPE + row + j] = trees[i].pos0 + depth[j];
+        }
+        for (int j = 0; j < trees[i].len; j += rg) w[Tr::BASE + ng++] = trees[i].pos0 - 1;
+    }
+    b->pass_tree = true;
+    return hipMemcpyAsync(b->tr->d_words, b->tr->h_words, Tr::TR_WORDS * sizeof(int), hipMemcpyHostToDevice, b->ctx->stream);
+}
+// a checked call up to its pass: the context's side, the lazy state, the rows
+static int tree_begin(llmk_batch* b, int n_trees, const llmk_span* trees, const int* tokens, const int* parent, int n, ScPlan* sp) {
+    int rc = bd_ready(b, sp, n);
+    if (rc) return rc;
+    if ((rc = span_setup(b, n, true)) != LLMK_OK) return rc;
+    if ((rc = tree_setup(b)) != LLMK_OK) return rc;
+    HIPCHK(tree_upload(b, n_trees, trees, tokens, parent));
+    return LLMK_OK;
+}
+
+int llmk_tree_forward(llmk_batch* b, int n_trees, const llmk_span* trees, const int* tokens, const int* parent, float* logits_out, int* argmax_out) {
+    int n = 0;
+    bool chain;
+    if (!b || (!logits_out && !argmax_out) || !parent || !span_ok(b, n_trees, trees, tokens, true, &n) || !tree_ok(n_trees, trees, parent, &chain))
+        return LLMK_E_ARG;
+    if (chain) return llmk_span_forward(b, n_trees, trees, tokens, 0, logits_out, argmax_out);      // chains ARE spans
+    llmk_ctx* c = b->ctx;
+    ScPlan sp;
+    int rc = tree_begin(b, n_trees, trees, tokens, parent, n, &sp);
+    if (rc) return rc;
+    int max_pos = 0;
+    for (int i = 0; i < n_trees; ++i) max_pos = std::max(max_pos, trees[i].pos0 + trees[i].len - 1);
+    const int* ids;
+    rc = bd_forward_sync(b, n, max_pos, logits_out != nullptr, sp, "llmk_tree_forward",
+                         [&] { return llmk_tree_forward(b, n_trees, trees, tokens, parent, logits_out, argmax_out); }, &ids);
+    if (!ids) return rc;
+    if (argmax_out) memcpy(argmax_out, ids, (size_t)n * sizeof(int));
+    if (logits_out) HIPCHK(hipMemcpy(logits_out, b->d_logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost));
+    return LLMK_OK;
+}
+
+int llmk_tree_accept(llmk_batch* b, int slot, int pos0, int n, const int* path) {
+    if (!b || slot < 0 || slot >= b->n_slots || n < 0 || (n > 0 && !path) || pos0 < 1) return LLMK_E_ARG;
+    if (b->n_attached > 0 && pos0 <= b->px->h_first[slot]) return LLMK_E_ARG;
+    bool moves = false;
+    for (int k = 0; k < n; ++k) {
+        if (path[k] < (k ? path[k - 1] + 1 : 0)) return LLMK_E_ARG;
+        moves = moves || path[k] != k;
+    }
+    if (n > 0 && path[n - 1] > b->seq_len - pos0) return LLMK_E_ARG;
+    if (!moves) return LLMK_OK;      // a chain (or nothing) accepted: every row is where it belongs
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
+    const int rc = tree_setup(b);
+    if (rc) return rc;
+    memcpy(b->tr->h_path.get(), path, (size_t)n * sizeof(int));      // (n <= seq_len: strictly increasing, the last one checked)
+    HIPCHK(hipMemcpyAsync(b->tr->d_path, b->tr->h_path, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(with_kv_type(b, [&](auto t) {
+        using TC = decltype(t);
+        return BdKv<TC>::move(bd_cache_view<TC>(b, b->cache.k, 0, slot, pos0 - 1), bd_cache_view<TC>(b, b->cache.v, 0, slot, pos0 - 1), b, pos0,
+                              b->tr->d_path, n, c->stream);
+    }));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+
+int llmk_tree_time(llmk_batch* b, int n_trees, int len, int pos0, int iters, float* avg_ms) {
+    if (!b || !avg_ms || iters < 1 || n_trees < 1 || n_trees > LLMK_MAX_BATCH) return LLMK_E_ARG;
+    llmk_span trees[LLMK_MAX_BATCH];
+    for (int i = 0; i < n_trees; ++i) trees[i] = llmk_span{i, pos0, len};
+    int n = 0;
+    if (!span_ok(b, n_trees, trees, nullptr, false, &n)) return LLMK_E_ARG;
+    if (len <= 2) return llmk_span_time(b, n_trees, len, pos0, iters, avg_ms);      // a heap of one or two nodes is a chain: that pass
+    int parent[LLMK_MAX_BATCH];
+    for (int i = 0; i < n; ++i) parent[i] = i % len ? (i % len - 1) / 2 : LLMK_TREE_ROOT;
+    ScPlan sp;
+    const int rc = tree_begin(b, n_trees, trees, nullptr, parent, n, &sp);
+    if (rc) return rc;
     return bd_time(b, n, pos0 + len - 1, iters, sp, avg_ms);
 }
 

@@ -372,6 +372,29 @@ module llmk_binding
        integer(c_int), value :: n_spans, len, pos0, iters
        real(c_float), intent(out) :: avg_ms
      end function
+     ! trees (include/llmk.h): drafted continuations that share a stem in one pass; parent(j) = -1 (the root) or an earlier node of
+     ! the same tree (0-based).  No flag of the CLI reaches them: this host has no drafter
+     integer(c_int) function llmk_tree_forward(batch, n_trees, trees, tokens, parent, logits_out, argmax_out) &
+          bind(C, name="llmk_tree_forward")
+       import :: c_int, c_ptr, llmk_span
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n_trees
+       type(llmk_span), intent(in) :: trees(*)
+       integer(c_int), intent(in) :: tokens(*), parent(*)
+       type(c_ptr), value :: logits_out, argmax_out
+     end function
+     integer(c_int) function llmk_tree_accept(batch, slot, pos0, n, path) bind(C, name="llmk_tree_accept")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot, pos0, n
+       integer(c_int), intent(in) :: path(*)
+     end function
+     integer(c_int) function llmk_tree_time(batch, n_trees, len, pos0, iters, avg_ms) bind(C, name="llmk_tree_time")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n_trees, len, pos0, iters
+       real(c_float), intent(out) :: avg_ms
+     end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
      ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too

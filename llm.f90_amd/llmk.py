@@ -30,7 +30,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_logprob_logits", "llmk_score", "llmk_batch_create", "llmk_batch_destroy", "llmk_batch_fork", "llmk_batch_forward",
            "llmk_batch_decode", "llmk_batch_time", "llmk_rows_set_history", "llmk_rows_get_history", "llmk_rows_decode",
            "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len",
-           "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_span_forward", "llmk_span_time", "llmk_reset", "llmk_timings",
+           "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_span_forward", "llmk_span_time",
+           "llmk_tree_forward", "llmk_tree_accept", "llmk_tree_time", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -209,6 +210,10 @@ def lib():
         if hasattr(L, "llmk_span_forward"):
             L.llmk_span_forward.argtypes = [vp, ci, C.POINTER(Span), C.POINTER(ci), ci, cf, C.POINTER(ci)]
             L.llmk_span_time.argtypes = [vp, ci, ci, ci, ci, cf]
+        if hasattr(L, "llmk_tree_forward"):
+            L.llmk_tree_forward.argtypes = [vp, ci, C.POINTER(Span), C.POINTER(ci), C.POINTER(ci), cf, C.POINTER(ci)]
+            L.llmk_tree_accept.argtypes = [vp, ci, ci, ci, C.POINTER(ci)]
+            L.llmk_tree_time.argtypes = [vp, ci, ci, ci, ci, cf]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -727,6 +732,39 @@ class Batch:
         overwrites those rows"""
         ms = C.c_float()
         _ck(lib().llmk_span_time(self._h, n_spans, length, pos0, iters, C.byref(ms)))
+        return float(ms.value)
+
+    def forward_tree(self, trees, tokens, parent, want_logits: bool = True, want_argmax: bool = True):
+        """one pass over trees of drafted tokens (llmk_tree_forward).  trees: [(slot, pos0, len)], len nodes each; tokens and parent:
+        one per node in tree order, parent -1 (the root) or an earlier node of the same tree.  Node j is fed at position
+        pos0 + depth(j) and stored at place pos0 + j; it sees the slot's positions 1..pos0-1, its ancestors and itself.  (logits
+        [rows][V], argmax [rows] 1-based), or the one that was asked for"""
+        trees = [tuple(int(x) for x in s) for s in trees]
+        if any(len(s) != 3 for s in trees):
+            raise ValueError("a tree is (slot, pos0, len)")
+        tok, par = np.ascontiguousarray(tokens, np.int32), np.ascontiguousarray(parent, np.int32)
+        if tok.ndim != 1 or par.shape != tok.shape or len(tok) != sum(max(s[2], 0) for s in trees):
+            raise ValueError("one token and one parent per node: sum of the trees' len")
+        sp = (Span * max(1, len(trees)))(*[Span(*s) for s in trees])
+        lg = np.empty((len(tok), self.V), np.float32) if want_logits else None
+        am = np.empty(len(tok), np.int32) if want_argmax else None
+        _ck(lib().llmk_tree_forward(self._h, len(trees), sp, tok.ctypes.data_as(C.POINTER(C.c_int)), par.ctypes.data_as(C.POINTER(C.c_int)),
+                                    lg.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None,
+                                    am.ctypes.data_as(C.POINTER(C.c_int)) if want_argmax else None))
+        out = [x for x in (lg, am) if x is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def accept(self, slot: int, pos0: int, path):
+        """the nodes path[0] < path[1] < .. of the tree fed at pos0 become `slot`'s positions pos0, pos0 + 1, .. (llmk_tree_accept):
+        their K/V rows are moved down bit for bit; the slot continues at pos0 + len(path)"""
+        p = np.ascontiguousarray(path, np.int32).reshape(-1)
+        _ck(lib().llmk_tree_accept(self._h, slot, pos0, len(p), p.ctypes.data_as(C.POINTER(C.c_int)) if len(p) else None))
+
+    def time_tree(self, n_trees: int, length: int, pos0: int, iters: int) -> float:
+        """average ms of one full pass of n_trees binary-heap trees of `length` nodes each, slots 0..n_trees-1, all from pos0
+        (llmk_tree_time); overwrites those rows"""
+        ms = C.c_float()
+        _ck(lib().llmk_tree_time(self._h, n_trees, length, pos0, iters, C.byref(ms)))
         return float(ms.value)
 
     def decode(self, slots, tokens, pos0, steps: int, samplers=None) -> np.ndarray:

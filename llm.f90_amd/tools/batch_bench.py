@@ -273,6 +273,73 @@ def spans(m, shape, pos: int, iters: int, repeats: int):
     return out
 
 
+TREE_ROWS = (16, 64, 128)
+
+
+def trees(m, shape, pos: int, iters: int, repeats: int):
+    """--trees: profiles/batch_tree.txt.  One binary-heap tree of n nodes behind pos0 - 1 positions, for pos0 in (25, --pos): the pass
+    (llmk_tree_time) against a span pass of the same rows (llmk_span_time), alternating; the wall clock of llmk_tree_forward (argmax
+    only) against the way without trees -- every root-to-leaf path of the heap as a span of a slot of its own, in passes of at most
+    128 rows; and llmk_tree_accept of the path to the last node."""
+    out = []
+    for pos0 in (25, pos):
+        for n in TREE_ROWS:
+            parent = [(j - 1) // 2 for j in range(n)]
+            paths = []
+            for leaf in range(n // 2, n):              # the nodes without a child
+                p, j = [], leaf
+                while j >= 0:
+                    p.append(j)
+                    j = parent[j]
+                paths.append(p[::-1])
+            passes, cur = [], []
+            for p in paths:                            # greedy packing of the paths into passes of <= 128 rows
+                if sum(len(x) for x in cur) + len(p) > 128:
+                    passes.append(cur)
+                    cur = []
+                cur.append(p)
+            passes.append(cur)
+            b = llmk.Batch(m, max(len(x) for x in passes), pos0 + n - 1)
+            calls = [([(s, pos0, len(p)) for s, p in enumerate(ps)], [2] * sum(len(p) for p in ps)) for ps in passes]
+            ms = {"tree": [], "span": [], "tree_call": [], "paths_call": [], "accept": []}
+            for r in range(repeats + 1):
+                t = [b.time_tree(1, n, pos0, iters if r else 3), b.time_spans(1, n, pos0, iters if r else 3)]
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    b.forward_tree([(0, pos0, n)], [2] * n, parent, want_logits=False)
+                t1 = time.perf_counter()
+                for _ in range(iters):
+                    for sp, toks in calls:
+                        b.forward_spans(sp, toks, want_logits=False)
+                t2 = time.perf_counter()
+                for _ in range(iters):
+                    b.accept(0, pos0, paths[-1])
+                t3 = time.perf_counter()
+                if r:
+                    for k, v in zip(ms, t + [(t1 - t0) * 1e3 / iters, (t2 - t1) * 1e3 / iters, (t3 - t2) * 1e3 / iters]):
+                        ms[k].append(v)
+            row = {"pos0": pos0, "rows": n, "paths": len(paths), "path_rows": sum(len(p) for p in paths), "passes": len(passes)}
+            for k, xs in ms.items():
+                row[k + "_ms"], row[k + "_spread"] = med_spread(xs)
+            out.append(row)
+            b.close()
+    return out
+
+
+def print_trees(shape_name, type_name, rows, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# tree passes, {shape_name} {type_name}, f32 caches, one heap tree in one slot: medians of {repeats} x {iters} (spread = (max - min) / median)")
+    print("# tree | span: llmk_tree_time | llmk_span_time of the same rows, alternating.  tree call | paths: wall clock of llmk_tree_forward |")
+    print("# of the heap's root-to-leaf paths as one span each in slots of their own (passes of <= 128 rows), argmax only.  accept: llmk_tree_accept")
+    print(f"{'pos0':>5} {'rows':>5} {'tree ms':>9} {'spread':>7} {'span ms':>9} {'spread':>7} {'tree/span':>10} {'tree call':>10} {'spread':>7} "
+          f"{'paths':>6} {'rows':>5} {'passes':>7} {'paths ms':>9} {'spread':>7} {'paths/tree':>11} {'accept ms':>10} {'spread':>7}")
+    for x in rows:
+        print(f"{x['pos0']:5d} {x['rows']:5d} {x['tree_ms']:9.3f} {x['tree_spread']:7.3f} {x['span_ms']:9.3f} {x['span_spread']:7.3f} "
+              f"{x['tree_ms'] / x['span_ms']:10.3f} {x['tree_call_ms']:10.3f} {x['tree_call_spread']:7.3f} {x['paths']:6d} {x['path_rows']:5d} "
+              f"{x['passes']:7d} {x['paths_call_ms']:9.3f} {x['paths_call_spread']:7.3f} {x['paths_call_ms'] / x['tree_call_ms']:11.2f} "
+              f"{x['accept_ms']:10.4f} {x['accept_spread']:7.3f}")
+
+
 def print_spans(shape_name, type_name, r, iters, repeats):
     print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
     print(f"# span passes, {shape_name} {type_name}: medians of {repeats} (spread = (max - min) / median)")
@@ -350,10 +417,20 @@ def main():
     ap.add_argument("--spans", action="store_true",
                     help="only the span tables (llmk_span_*): a 128-row span ending at --pos with and without bd_attn_span_kernel, a prompt "
                          "in spans against prefill + fork, 112 decode rows with and without a 16-row chunk")
+    ap.add_argument("--trees", action="store_true",
+                    help="only the tree table (llmk_tree_*): a heap tree of 16, 64 and 128 nodes behind positions 25 and --pos against a span "
+                         "pass of the same rows and against its root-to-leaf paths as spans; llmk_tree_accept")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
     m, shape = build(a.shape, a.type, a.cls_q6k)
+    if a.trees:
+        rows = trees(m, shape, a.pos, a.iters, a.repeats)
+        m.close()
+        print_trees(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "trees": rows}))
+        return
     if a.spans:
         r = spans(m, shape, a.pos, a.iters, a.repeats)
         m.close()
