@@ -649,6 +649,37 @@ int llmk_tree_forward(llmk_batch *b, int n_trees, const llmk_span *trees, const 
 int llmk_tree_accept(llmk_batch *b, int slot, int pos0, int n, const int *path);
 int llmk_tree_time(llmk_batch *b, int n_trees, int len, int pos0, int iters, float *avg_ms);
 
+/* Adapters: a LoRA per slot of a batch, y += scale * B (A x) beside every adapted base GEMM, in the ONE pass
+ * over the base weights -- several fine-tunes of one base model share a batch, a q4_0 base (which cannot be merged with an adapter on
+ * the host) included.  A slot without an adapter runs the base model and costs nothing.
+ *
+ * create:  rank in [1, 64] and a finite scale (= alpha / rank), else LLMK_E_ARG.  LLMK_E_SHAPE for a context llmk_batch_create refuses.
+ *          The adapter belongs to the context: llmk_destroy with live adapters is LLMK_E_STATE, as with live batches.
+ * upload:  one PIECE: rows row0 .. row0+rows-1 of layer `layer` of the fused tensor tensor_id (LLMK_WQKV, LLMK_WO, LLMK_W13, LLMK_W2).
+ *          A [rank][K] and B [rows][rank], row-major, K the tensor's row length (hidden_dim for LLMK_W2, else emb_dim); ggml_type
+ *          LLMK_TYPE_F32 or LLMK_TYPE_F16 (anything else LLMK_E_TYPE); both are copied and kept as f32 on the device.  A llama.cpp
+ *          adapter's attn_q / attn_k / attn_v are rows 0..E, E..E+KV, E+KV..E+2KV of LLMK_WQKV (E emb_dim, KV kv_dim); ffn_gate /
+ *          ffn_up are rows 0..H, H..2H of LLMK_W13.  An adapter may leave any piece out (q and v only is the classic one).  row0 and
+ *          rows are multiples of 4, rows >= 4, inside the tensor; a tensor and layer hold at most 4 pieces, which must not overlap;
+ *          else LLMK_E_ARG, and nothing changes.  A piece with the very range of an existing one replaces it.
+ * destroy: LLMK_E_STATE while a slot of a live batch is assigned to it.
+ * assign:  the slot's rows run `ad` from the next pass on, in every call kind (llmk_batch_forward / _decode, llmk_rows_decode,
+ *          llmk_span_forward, llmk_tree_forward); NULL: the base model, the default.  LLMK_E_ARG: a NULL batch, a slot out of range, an
+ *          adapter of another context.  A pass may mix any adapters and the base model; rows of one adapter are computed 16 at a time,
+ *          so 128 rows on 128 adapters are slow and correct.  A row's logits are those of the model W + scale * B A within the 1e-4 bar
+ *          (not bit-identical to a merged model); the same call on the same state returns the same bits; a pass in which no row has
+ *          an adapter enqueues exactly what it did without these functions and returns the same bits.
+ *          The K/V CACHE IS NOT GUARDED: llmk_batch_fork, llmk_prefix_attach and an assign in mid-sequence all keep working, and a
+ *          slot's K/V rows are whatever model wrote them (the context's rows and a shared prefix: the base model's).  A caller who
+ *          wants a prompt's keys and values under the adapter feeds the prompt through the batch (llmk_span_forward) after the assign.
+ * Out of scope: llmk_forward, llmk_prefill, llmk_score and the persistent kernel; tensor-parallel contexts; adapters on the embedding
+ * table or the classifier; quantised adapter storage.  ("lora": the llmk_batch_* list is closed, as for spans and trees.) */
+typedef struct llmk_lora llmk_lora;
+int llmk_lora_create(llmk_ctx *ctx, int rank, float scale, llmk_lora **out);
+int llmk_lora_upload(llmk_lora *ad, int tensor_id, int layer, int row0, int rows, const void *A, const void *B, int ggml_type);
+int llmk_lora_destroy(llmk_lora *ad);
+int llmk_lora_assign(llmk_batch *b, int slot, llmk_lora *ad);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

@@ -16,6 +16,7 @@
 #include "token_kernel.h"
 #include "prefill.h"
 #include "batch.h"
+#include "lora.h"
 #include "tp_p2p.h"
 #include "forward_ahead.h"
 #include "tk_recover.h"
@@ -219,6 +220,7 @@ struct llmk_ctx {
     };
     std::unique_ptr<Score> sc;
     int n_batches = 0;                     // live llmk_batch objects on this context (llmk_destroy refuses while there are any)
+    int n_loras = 0;                       // ... and live llmk_lora objects (their device tables are read by the batches' passes)
     // llmk_forward with the next greedy position in flight (forward_ahead.h).  Position p's logits go to pinned
     // buffer p & 1 -- [0] is h_logits, whose error word and ids() serve both -- so the host copies out of one while the next launch
     // fills the other; fa_ev[p & 1] is recorded right behind position p's launch
@@ -305,6 +307,31 @@ struct llmk_batch {
     };
     std::unique_ptr<Trees> tr;
     bool pass_tree = false;                      // the rows uploaded last are the nodes of trees (tree_upload): BdAttnPlan TREE
+    // adapters (llmk_lora_*, lora.h), built by the first llmk_lora_assign that assigns one: a batch without one has none of it
+    struct Lora {
+        std::vector<llmk_lora*> slot;            // [n_slots] a slot's adapter; null: the base model
+        int n_assigned = 0;                      // slots with one
+        DevBuf<LoraGroup> d_groups;              // [LLMK_MAX_BATCH] the pass's column groups ...
+        PinnedBuf<LoraGroup> h_groups;           // ... and the pinned words they are copied from
+        DevBuf<float> d_s;                       // the shrink's partials [chunks][groups][LORA_MAX_PIECES][LORA_S], grown by the pass that needs more (reserve)
+        std::vector<llmk_lora*> in_pass;         // the distinct adapters of the rows bd_upload_rows uploaded last ...
+        int groups = 0;                          // ... and their column groups; 0: every row runs the base model
+    };
+    std::unique_ptr<Lora> lo;
+};
+
+// One adapter (lora.h): per layer and fused tensor up to LORA_MAX_PIECES row ranges, each with A [R16][K] and B [rows][R16] in f32 on
+// the device, the rank padded to R16 with zeros.  The kernels find the pieces through d_table, the image of h_table.
+struct llmk_lora {
+    llmk_ctx* ctx = nullptr;
+    int rank = 0, r16 = 0;
+    float scale = 0.f;
+    int uses = 0;                                // slots of live batches that are assigned to it (llmk_lora_destroy refuses while there are any)
+    struct Piece { DevBuf<float> A, B; };
+    std::vector<Piece> pieces;                   // [L][LORA_TENSORS][LORA_MAX_PIECES], as the tables
+    std::vector<LoraPiece> h_table;
+    DevBuf<LoraPiece> d_table;
+    static int at(int layer, int ti) { return (layer * LORA_TENSORS + ti) * LORA_MAX_PIECES; }
 };
 
 namespace {
@@ -1354,13 +1381,34 @@ hipError_t sc_batch(llmk_ctx* c, const PfLane& w, int lane, PfEpiArgs& e, const 
     return sc_merge(c, lane, w.stream, sj, sp.nparts, T, i0);
 }
 
+// The adapters' share of one base GEMM of a pass (lora.h), ENQUEUED on the lane's stream behind that GEMM: layer l of tensor tid read X
+// [T][K] and left `prows` rows per pass row in w.P.  The grids cover the most pieces and the longest piece any adapter of the pass has
+// here; a tensor and layer none of them touches gets no launch.
+hipError_t lora_enqueue(const llmk_batch::Lora& lo, const PfLane& w, int tid, int l, const float* X, int K, int prows) {
+    const int at = llmk_lora::at(l, tid - LLMK_WQKV);
+    int np = 0, rows = 0;
+    for (const llmk_lora* ad : lo.in_pass)
+        for (int p = 0; p < LORA_MAX_PIECES; ++p)
+            if (ad->h_table[at + p].rows > 0) { np = std::max(np, p + 1); rows = std::max(rows, ad->h_table[at + p].rows); }
+    if (np == 0) return hipSuccess;
+    const int nch = lora_nchunks(K);
+    hipLaunchKernelGGL(lora_shrink_kernel, dim3(nch, lo.groups, np), dim3(LORA_WAVES * WAVE), 0, w.stream, lo.d_groups.get(), at / LORA_MAX_PIECES, X, K,
+                       lora_chunk(K), lo.d_s.get());
+    HIPRET(hipGetLastError());
+    hipLaunchKernelGGL(lora_expand_kernel, dim3((rows + LORA_STRIP - 1) / LORA_STRIP, lo.groups, np), dim3(LORA_WAVES * WAVE), 0, w.stream,
+                       lo.d_groups.get(), at / LORA_MAX_PIECES, lo.d_s.get(), nch, w.P.get(), prows);
+    return hipGetLastError();
+}
+
 // The layers of one pass, shared by the prefill (pf_batch) and the batched decode (bd_pass): T <= PF_TMAX rows, the ids in `tok` (0-based,
 // device memory), through the embedding and every layer on the lane's stream; X ends up in w.X.  What a row's POSITION touches is the
 // caller's: qkv_attn(l, e) follows layer l's QKV GEMM (e.rows / e.out are set for its epilogue) and enqueues RoPE, the K/V write and
 // the attention into w.XB.  final_gains: the gains the last residual's kernel normalises w.Xs with (null: none).  `e` is left as the
-// classifier's epilogue needs it.
+// classifier's epilogue needs it.  lo (a batch's pass with rows on adapters, else null): behind each base GEMM and in front of its epilogue
+// the adapters' correction is added into the GEMM's partial tiles (lora_enqueue); null enqueues nothing.
 template <class QkvAttn>
-hipError_t pf_layers(llmk_ctx* c, PfLane& w, const int* tok, int T, int pos0, const float* final_gains, PfEpiArgs& e, QkvAttn&& qkv_attn) {
+hipError_t pf_layers(llmk_ctx* c, PfLane& w, const int* tok, int T, int pos0, const float* final_gains, PfEpiArgs& e, const llmk_batch::Lora* lo,
+                     QkvAttn&& qkv_attn) {
     const int E = c->E, H = c->H, KV = c->KV, QKV = E + 2 * KV, Tp = (T + 15) / 16 * 16;
     const float* emb = (const float*)c->t[LLMK_TOKEN_EMBEDDING_TABLE].data;
     hipLaunchKernelGGL(pf_embed_kernel, dim3((E + 255) / 256, T), dim3(256), 0, w.stream, emb, tok, w.X, E);
@@ -1373,7 +1421,8 @@ hipError_t pf_layers(llmk_ctx* c, PfLane& w, const int* tok, int T, int pos0, co
         auto gemm = [&](int tid, int rows_per_layer, const float* X, int K) -> hipError_t {
             const DevTensor& dt = c->t[tid];
             const char* wt = (const char*)dt.data + (size_t)l * rows_per_layer * dt.row_bytes;
-            return pf_gemm(c, w, wt, (int)dt.row_bytes, X, rows_per_layer, K, T, &e);
+            HIPRET(pf_gemm(c, w, wt, (int)dt.row_bytes, X, rows_per_layer, K, T, &e));
+            return lo ? lora_enqueue(*lo, w, tid, l, X, K, rows_per_layer) : hipSuccess;
         };
         // rmsnorm (layer 0 here, later layers in the previous residual's kernel) + QKV + RoPE + KV write   llama2.f90:527-565
         if (l == 0) {
@@ -1412,7 +1461,7 @@ hipError_t pf_batch(llmk_ctx* c, PfLane& w, const PfLane* prev, const int* tok, 
     const int E = c->E, KV = c->KV, QKV = E + 2 * KV;
     PfEpiArgs e;
     // (scoring: the FINAL rmsnorm of every row)
-    HIPRET(pf_layers(c, w, tok, T, pos0, sj ? (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data : nullptr, e, [&](int l, PfEpiArgs& a) -> hipError_t {
+    HIPRET(pf_layers(c, w, tok, T, pos0, sj ? (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data : nullptr, e, nullptr, [&](int l, PfEpiArgs& a) -> hipError_t {
         float* kc = c->d_kc + (size_t)l * c->S * KV;
         float* vc = c->d_vc + (size_t)l * c->S * KV;
         a.kc = kc; a.vc = vc;
@@ -1703,7 +1752,8 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
     const BdAttnPlan p = bd_attn_plan(b, n, max_pos, step);
     PfEpiArgs e;
     // (every pass ends in the classifier: the FINAL rmsnorm of every row; pos0 = 0: a row's position is in its row words)
-    HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, [&](int l, PfEpiArgs& a) -> hipError_t {
+    HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, b->lo && b->lo->groups > 0 ? b->lo.get() : nullptr,
+                     [&](int l, PfEpiArgs& a) -> hipError_t {
         const auto kc = bd_cache_view<TC>(b, b->cache.k, l, 0, 0), vc = bd_cache_view<TC>(b, b->cache.v, l, 0, 0);
         HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, p.kind == BdAttnPlan::TREE ? b->tr->args().rope_pos : nullptr, QKV, T, w.stream));
         return with_head_size(c->hs, [&](auto hs) {
@@ -1821,7 +1871,7 @@ static int bd_time(llmk_batch* b, int n, int max_pos, int iters, const ScPlan& s
 
 extern "C" {
 
-int llmk_version(void) { return 409; }
+int llmk_version(void) { return 410; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2988,6 +3038,35 @@ static bool bd_rows_ok(const llmk_batch* b, int n, const int* slots, const int* 
     }
     return true;
 }
+// The column groups of a pass (lora.h): the rows in h_rows that run an adapter, sorted by adapter in order of first appearance and in row
+// order within one, 16 to a group; uploaded once per call (a multi-step decode keeps its rows, so its groups stay).
+static hipError_t lora_groups(llmk_batch* b, int n) {
+    llmk_batch::Lora& lo = *b->lo;
+    lo.groups = 0;
+    lo.in_pass.clear();
+    if (lo.n_assigned == 0) return hipSuccess;
+    for (int i = 0; i < n; ++i) {
+        llmk_lora* ad = lo.slot[b->h_rows[i].slot];
+        if (ad && std::find(lo.in_pass.begin(), lo.in_pass.end(), ad) == lo.in_pass.end()) lo.in_pass.push_back(ad);
+    }
+    for (const llmk_lora* ad : lo.in_pass) {
+        int k = 0;
+        for (int i = 0; i < n; ++i) {
+            if (lo.slot[b->h_rows[i].slot] != ad) continue;
+            if (k % LORA_COLS == 0) {
+                LoraGroup& g = lo.h_groups[lo.groups++];
+                g.table = ad->d_table; g.scale = ad->scale; g.r16 = ad->r16;
+                for (int& col : g.col) col = -1;
+            }
+            lo.h_groups[lo.groups - 1].col[k++ % LORA_COLS] = i;
+        }
+    }
+    if (lo.groups == 0) return hipSuccess;
+    const llmk_ctx* c = b->ctx;
+    const size_t chunks = (size_t)std::max(lora_nchunks(c->E), lora_nchunks(c->H));
+    HIPRET(lo.d_s.reserve(chunks * lo.groups * LORA_MAX_PIECES * LORA_S, c->stream));
+    return hipMemcpyAsync(lo.d_groups, lo.h_groups, (size_t)lo.groups * sizeof(LoraGroup), hipMemcpyHostToDevice, c->stream);
+}
 static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const int* tokens, const int* pos) {
     for (int i = 0; i < n; ++i) {
         b->h_rows[i] = BdRow{slots[i], pos[i]};
@@ -3007,6 +3086,7 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
             HIPRET(hipMemcpyAsync(b->px->d_colmap, b->px->h_colmap, (size_t)cells * sizeof(int), hipMemcpyHostToDevice, st));
         }
     }
+    if (b->lo) HIPRET(lora_groups(b, n));
     HIPRET(hipMemcpyAsync(b->d_rows, b->h_rows, (size_t)n * sizeof(BdRow), hipMemcpyHostToDevice, st));
     return hipMemcpyAsync(b->d_tok, b->h_tok, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st);
 }
@@ -3113,7 +3193,101 @@ int llmk_batch_destroy(llmk_batch* b) {
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     hipStreamSynchronize(c->stream);
     --c->n_batches;
+    if (b->lo)
+        for (llmk_lora* ad : b->lo->slot)
+            if (ad) --ad->uses;
     delete b;
+    return LLMK_OK;
+}
+
+// ---- adapters (lora.h): a LoRA per slot in the one pass over the base weights ----
+int llmk_lora_create(llmk_ctx* c, int rank, float scale, llmk_lora** out) {
+    if (!c || !out || rank < 1 || rank > LORA_MAX_RANK || !std::isfinite(scale)) return LLMK_E_ARG;
+    *out = nullptr;
+    if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;      // (what llmk_batch_create refuses)
+    HIPCHK(hipSetDevice(c->cfg.device));
+    auto ad = std::make_unique<llmk_lora>();
+    ad->ctx = c; ad->rank = rank; ad->r16 = (rank + 15) / 16 * 16; ad->scale = scale;
+    const size_t n = (size_t)llmk_lora::at(c->L, 0);
+    ad->pieces.resize(n);
+    ad->h_table.assign(n, LoraPiece{nullptr, nullptr, 0, 0});
+    HIPCHK(ad->d_table.alloc(n));
+    HIPCHK(hipMemcpy(ad->d_table, ad->h_table.data(), n * sizeof(LoraPiece), hipMemcpyHostToDevice));
+    ++c->n_loras;
+    *out = ad.release();
+    return LLMK_OK;
+}
+
+int llmk_lora_upload(llmk_lora* ad, int tensor_id, int layer, int row0, int rows, const void* A, const void* B, int ggml_type) {
+    if (!ad || !A || !B || tensor_id < LLMK_WQKV || tensor_id > LLMK_W2 || layer < 0 || layer >= ad->ctx->L) return LLMK_E_ARG;
+    if (ggml_type != LLMK_TYPE_F32 && ggml_type != LLMK_TYPE_F16) return LLMK_E_TYPE;
+    llmk_ctx* c = ad->ctx;
+    const int trows = tensor_id == LLMK_WQKV ? c->E + 2 * c->KV : tensor_id == LLMK_W13 ? 2 * c->H : c->E, K = tensor_id == LLMK_W2 ? c->H : c->E;
+    if (row0 < 0 || rows < 4 || (row0 | rows) % 4 || rows > trows - row0) return LLMK_E_ARG;
+    // the piece's place: the one with this very range (replaced), else a free one; a range that meets another piece's is refused
+    const int at = llmk_lora::at(layer, tensor_id - LLMK_WQKV);
+    int place = -1, same = -1;
+    for (int p = 0; p < LORA_MAX_PIECES; ++p) {
+        const LoraPiece& h = ad->h_table[at + p];
+        if (h.rows == 0) place = place < 0 ? p : place;
+        else if (h.row0 == row0 && h.rows == rows) same = p;
+        else if (row0 < h.row0 + h.rows && h.row0 < row0 + rows) return LLMK_E_ARG;
+    }
+    if (same >= 0) place = same;
+    if (place < 0) return LLMK_E_ARG;      // (LORA_MAX_PIECES pieces are there)
+    HIPCHK(hipSetDevice(c->cfg.device));
+    // staged as the device holds them: A [R16][K], B [rows][R16], f32, the rank padded with zeros
+    const int r = ad->rank, r16 = ad->r16;
+    auto at_f32 = [&](const void* src, size_t i) {
+        return ggml_type == LLMK_TYPE_F32 ? static_cast<const float*>(src)[i] : bd_half_bits_to_float(static_cast<const uint16_t*>(src)[i]);
+    };
+    std::vector<float> ha((size_t)r16 * K, 0.f), hb((size_t)rows * r16, 0.f);
+    for (size_t i = 0; i < (size_t)r * K; ++i) ha[i] = at_f32(A, i);
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < r; ++j) hb[(size_t)i * r16 + j] = at_f32(B, (size_t)i * r + j);
+    llmk_lora::Piece fresh;
+    int rc = bd_alloc_rc(fresh.A.alloc(ha.size()));
+    if (rc == LLMK_OK) rc = bd_alloc_rc(fresh.B.alloc(hb.size()));
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(fresh.A, ha.data(), ha.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(fresh.B, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
+    HIPCHK(hipStreamSynchronize(c->stream));      // (no pass reads the piece this one replaces any more)
+    ad->pieces[at + place] = std::move(fresh);
+    ad->h_table[at + place] = LoraPiece{ad->pieces[at + place].A, ad->pieces[at + place].B, row0, rows};
+    HIPCHK(hipMemcpy(ad->d_table + at + place, &ad->h_table[at + place], sizeof(LoraPiece), hipMemcpyHostToDevice));
+    return LLMK_OK;
+}
+
+int llmk_lora_destroy(llmk_lora* ad) {
+    if (!ad) return LLMK_E_ARG;
+    if (ad->uses > 0) return LLMK_E_STATE;
+    llmk_ctx* c = ad->ctx;
+    hipSetDevice(c->cfg.device);
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
+    hipStreamSynchronize(c->stream);
+    --c->n_loras;
+    delete ad;
+    return LLMK_OK;
+}
+
+// The slot's K/V rows stay what they are: rows written under another adapter, forked from the context or read from a shared prefix are
+// the caller's business (include/llmk.h)
+int llmk_lora_assign(llmk_batch* b, int slot, llmk_lora* ad) {
+    if (!b || slot < 0 || slot >= b->n_slots || (ad && ad->ctx != b->ctx)) return LLMK_E_ARG;
+    if (!b->lo) {
+        if (!ad) return LLMK_OK;
+        HIPCHK(hipSetDevice(b->ctx->cfg.device));
+        auto lo = std::make_unique<llmk_batch::Lora>();
+        lo->slot.assign(b->n_slots, nullptr);
+        HIPCHK(lo->d_groups.alloc(LLMK_MAX_BATCH));
+        HIPCHK(lo->h_groups.alloc(LLMK_MAX_BATCH));
+        b->lo = std::move(lo);
+    }
+    llmk_lora*& cur = b->lo->slot[slot];
+    if (cur) { --cur->uses; --b->lo->n_assigned; }
+    cur = ad;
+    if (cur) { ++cur->uses; ++b->lo->n_assigned; }
     return LLMK_OK;
 }
 
@@ -4200,7 +4374,7 @@ int llmk_tp_ranks_seen(llmk_ctx* c) {
 
 int llmk_destroy(llmk_ctx* c) {
     if (!c) return LLMK_E_ARG;
-    if (c->n_batches > 0) return LLMK_E_STATE;      // its batches go first (llmk_batch_destroy): they run on this context's weights and stream
+    if (c->n_batches > 0 || c->n_loras > 0) return LLMK_E_STATE;      // its batches and adapters go first (llmk_batch_destroy, llmk_lora_destroy): they run on this context's weights and stream
     hipSetDevice(c->cfg.device);
     if (c->stream) spec_settle(c);
     if (c->stream) hipStreamSynchronize(c->stream);

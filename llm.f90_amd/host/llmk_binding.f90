@@ -395,6 +395,32 @@ module llmk_binding
        integer(c_int), value :: n_trees, len, pos0, iters
        real(c_float), intent(out) :: avg_ms
      end function
+     ! adapters (include/llmk.h): a LoRA per slot of a batch.  A and B travel as C addresses (c_loc of `target` arrays, row-major as
+     ! C sees them: A(K, rank), B(rank, rows) in Fortran order); ad = c_null_ptr in llmk_lora_assign: the base model
+     integer(c_int) function llmk_lora_create(ctx, rank, scale, ad) bind(C, name="llmk_lora_create")
+       import :: c_int, c_ptr, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: rank
+       real(c_float), value :: scale
+       type(c_ptr), intent(out) :: ad
+     end function
+     integer(c_int) function llmk_lora_upload(ad, tensor_id, layer, row0, rows, a, b, ggml_type) bind(C, name="llmk_lora_upload")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ad
+       integer(c_int), value :: tensor_id, layer, row0, rows
+       type(c_ptr), value :: a, b
+       integer(c_int), value :: ggml_type
+     end function
+     integer(c_int) function llmk_lora_destroy(ad) bind(C, name="llmk_lora_destroy")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ad
+     end function
+     integer(c_int) function llmk_lora_assign(batch, slot, ad) bind(C, name="llmk_lora_assign")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot
+       type(c_ptr), value :: ad
+     end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
      ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too

@@ -31,7 +31,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_batch_decode", "llmk_batch_time", "llmk_rows_set_history", "llmk_rows_get_history", "llmk_rows_decode",
            "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len",
            "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_span_forward", "llmk_span_time",
-           "llmk_tree_forward", "llmk_tree_accept", "llmk_tree_time", "llmk_reset", "llmk_timings",
+           "llmk_tree_forward", "llmk_tree_accept", "llmk_tree_time",
+           "llmk_lora_create", "llmk_lora_upload", "llmk_lora_destroy", "llmk_lora_assign", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -214,6 +215,11 @@ def lib():
             L.llmk_tree_forward.argtypes = [vp, ci, C.POINTER(Span), C.POINTER(ci), C.POINTER(ci), cf, C.POINTER(ci)]
             L.llmk_tree_accept.argtypes = [vp, ci, ci, ci, C.POINTER(ci)]
             L.llmk_tree_time.argtypes = [vp, ci, ci, ci, ci, cf]
+        if hasattr(L, "llmk_lora_create"):
+            L.llmk_lora_create.argtypes = [vp, ci, C.c_float, C.POINTER(vp)]
+            L.llmk_lora_upload.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci]
+            L.llmk_lora_destroy.argtypes = [vp]
+            L.llmk_lora_assign.argtypes = [vp, ci, vp]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -617,6 +623,54 @@ class Llmk:
             pass
 
 
+class Lora:
+    """One LoRA adapter on the context `model` (llmk_lora_*): y += scale * B (A x) beside the base GEMMs of the
+    slots Batch.set_lora assigns to it.  scale = alpha / rank.  Close it after the batches that use it and before its context."""
+
+    def __init__(self, model: Llmk, rank: int, scale: float):
+        self.model, self.rank, self.scale = model, rank, scale
+        self._h = C.c_void_p()
+        _ck(lib().llmk_lora_create(model._h, rank, scale, C.byref(self._h)))
+
+    def upload(self, name: str, layer: int, row0: int, A, B):
+        """one piece: rows row0 .. of layer `layer` of the fused tensor `name` ("wqkv", "wo", "w13", "w2"); A [rank][K], B [rows][rank],
+        float32 or float16 (anything else is converted to float32)"""
+        A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
+        if not (A.dtype == B.dtype and A.dtype in (np.float32, np.float16)):
+            A, B = A.astype(np.float32), B.astype(np.float32)
+        if A.ndim != 2 or B.ndim != 2 or A.shape[0] != self.rank or B.shape[1] != self.rank:
+            raise ValueError(f"A is [rank][K] and B [rows][rank] with rank {self.rank}: got {A.shape} and {B.shape}")
+        s = self.model.shape
+        if A.shape[1] != (s.hidden_dim if name == "w2" else s.emb_dim):
+            raise ValueError(f"A of {name} has {s.hidden_dim if name == 'w2' else s.emb_dim} columns, not {A.shape[1]}")
+        _ck(lib().llmk_lora_upload(self._h, TENSOR_IDS[name], layer, row0, B.shape[0], A.ctypes.data, B.ctypes.data, 0 if A.dtype == np.float32 else 1))
+
+    @classmethod
+    def from_gguf(cls, model: Llmk, path: str) -> "Lora":
+        """a llama.cpp adapter file (general.type = "adapter"): scale = adapter.lora.alpha / rank, every blk.N.<target>.weight.lora_a /
+        .lora_b pair a piece of the fused tensor its target lies in (tools/gguf.py lora_piece)"""
+        from .tools import gguf
+        alpha, rank, pieces = gguf.read_lora_gguf(path)
+        ad = cls(model, rank, alpha / rank)
+        for (target, layer), (A, B) in sorted(pieces.items()):
+            name, row0, rows = gguf.lora_piece(model.shape, target)
+            if B.shape[0] != rows:
+                raise ValueError(f"{path}: blk.{layer}.{target} has {B.shape[0]} rows, the model {rows}")
+            ad.upload(name, layer, row0, A, B)
+        return ad
+
+    def close(self):
+        if self._h:
+            _ck(lib().llmk_lora_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Batch:
     """Batched decode (llmk_batch_*): n_slots sequences with K/V caches of their own on the weights of the
     Llmk context `model`; every pass takes one position of up to n_slots of them.  Slots count from 0; tokens and positions are
@@ -664,6 +718,11 @@ class Batch:
         if not (a[0].ndim == 1 and a[0].shape == a[1].shape == a[2].shape):
             raise ValueError("one slot, one token and one position per row")
         return a, [x.ctypes.data_as(C.POINTER(C.c_int)) for x in a]
+
+    def set_lora(self, slot: int, lora: "Lora | None"):
+        """`slot` runs the adapter `lora` from the next pass on, None: the base model (llmk_lora_assign).  The slot's K/V rows stay
+        what they are: feed the prompt through the batch (ingest) AFTER this call to have its keys and values under the adapter."""
+        _ck(lib().llmk_lora_assign(self._h, slot, lora._h if lora is not None else None))
 
     def fork(self, slot: int, n_pos: int):
         """the context's K/V rows of positions 1..n_pos into `slot` (llmk_batch_fork); n_pos = 0 empties the slot"""

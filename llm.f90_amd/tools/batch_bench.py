@@ -31,7 +31,13 @@ behind P positions.  --kv f32 | f16 | q8_0 measures one type alone, --kv all the
 times span passes (llmk_span_*): (a) one span of 128 rows ending at --pos with bd_attn_span_kernel and with the per-row attention
 kernels (a second batch created under LLMK_SPAN_ATTN=0), on f32 and f16 caches, llmk_span_time, alternating; (b) a prompt of
 --pos - 24 tokens into one slot in spans of 128 against llmk_prefill + llmk_batch_fork, wall clock of the calls; (c) 112 decode rows
-at --pos with and without one 16-row chunk of another slot in the same pass, wall clock of the calls."""
+at --pos with and without one 16-row chunk of another slot in the same pass, wall clock of the calls.
+
+    python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k --lora 8,16,64,16:8,16:0
+
+times the pass at 8, 32 and 128 rows at position 25 with no adapter assigned and with every row on an adapter (llmk_lora_*): rank 8, 16
+and 64 on one shared adapter, rank 16 on 8 adapters and on one adapter per row; beside each the bytes per layer the two adapter kernels
+move, from shapes."""
 from __future__ import annotations
 
 import argparse
@@ -107,6 +113,80 @@ def sampled(m, shape, repeats: int):
             out.append({"n": n, "sampler": name, "ms_per_step": med, "spread": spread, "tok_s": n / med * 1e3})
     b.close()
     return out
+
+
+def lora_bytes(shape, rank: int, rows: int, adapters: int):
+    """bytes per LAYER that lora_shrink_kernel and lora_expand_kernel move for `rows` pass rows spread evenly over `adapters` adapters of
+    all seven pieces (csrc/lora.h), from shapes: (shrink, expand).  Shrink: A once per group and piece, the group's input rows once
+    per piece, the partials written.  Expand: the partials read by every 256-row strip, B once per group, 16 bytes read and written
+    per (pass row, 4 output rows)."""
+    E, H, KV, r16 = shape.emb_dim, shape.hidden_dim, shape.kv_dim, (rank + 15) // 16 * 16
+    groups = adapters * -(-(rows // adapters) // 16)
+    def chunks(K):      # lora_nchunks
+        kc = -(-(-(-K // min(-(-K // 256), 16))) // 64) * 64
+        return -(-K // kc)
+    shrink = expand = 0
+    for K, out in ((E, E), (E, KV), (E, KV), (E, E), (E, H), (E, H), (H, E)):      # q k v o gate up down
+        s_bytes = chunks(K) * groups * r16 * 16 * 4
+        shrink += groups * r16 * K * 4 + rows * K * 4 + s_bytes
+        expand += -(-out // 256) * s_bytes + groups * out * r16 * 4 + 2 * rows * out * 4
+    return shrink, expand
+
+
+LORA_POS = 25
+
+
+def lora(m, shape, specs: str, iters: int, repeats: int):
+    """--lora RANK[:ADAPTERS][,..]: llmk_batch_time at SAMPLED_ROWS rows, all at LORA_POS, with no adapter assigned and -- where the
+    library has llmk_lora_* -- with every row on one of ADAPTERS adapters (default 1; 0: one per row) of rank RANK and all seven
+    pieces.  Every adapter is uploaded from the same host arrays (the device copies are its own).  Each figure behind a warm-up of
+    its shape."""
+    import numpy as np
+    have = hasattr(llmk.lib(), "llmk_lora_create")
+    b = llmk.Batch(m, max(SAMPLED_ROWS), LORA_POS)
+    rng = np.random.default_rng(7)
+
+    def timed(n):
+        b.time(n, LORA_POS, 3)
+        med, spread = med_spread([b.time(n, LORA_POS, iters) for _ in range(repeats)])
+        return {"n": n, "ms_per_pass": med, "spread": spread}
+    out = [dict(timed(n), rank=0, adapters=0) for n in SAMPLED_ROWS]
+    for spec in (specs.split(",") if have else ()):
+        rank, _, count = spec.partition(":")
+        rank, count = int(rank), int(count or 1)
+        pieces = {}
+        for t in gguf.LORA_TARGETS:
+            name, row0, rows = gguf.lora_piece(shape, t)
+            K = shape.hidden_dim if name == "w2" else shape.emb_dim
+            pieces[name, row0] = ((rng.normal(size=(rank, K)) / K ** 0.5).astype(np.float32), (rng.normal(size=(rows, rank)) / rank ** 0.5).astype(np.float32))
+        ads = []
+        for n in SAMPLED_ROWS:
+            k = min(count or n, n)
+            while len(ads) < k:
+                ads.append(llmk.Lora(m, rank, 0.3))
+                for l in range(shape.n_layers):
+                    for (name, row0), (A, B) in pieces.items():
+                        ads[-1].upload(name, l, row0, A, B)
+            for j in range(n):
+                b.set_lora(j, ads[j % k])
+            sh, ex = lora_bytes(shape, rank, n, k)
+            out.append(dict(timed(n), rank=rank, adapters=k, shrink_bytes_per_layer=sh, expand_bytes_per_layer=ex))
+        for j in range(max(SAMPLED_ROWS)):
+            b.set_lora(j, None)
+        for ad in ads:
+            ad.close()
+    b.close()
+    return out
+
+
+def print_lora(shape_name, type_name, rows, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# adapters, {shape_name} {type_name}: llmk_batch_time at position {LORA_POS}, median of {repeats} x {iters} passes; x none = against no adapter assigned")
+    print(f"{'n':>5} {'rank':>5} {'adapters':>9} {'ms/pass':>10} {'spread':>8} {'x none':>8} {'shrink MB/layer':>16} {'expand MB/layer':>16}")
+    none = {r["n"]: r["ms_per_pass"] for r in rows if r["rank"] == 0}
+    for r in rows:
+        print(f"{r['n']:5d} {r['rank']:5d} {r['adapters']:9d} {r['ms_per_pass']:10.3f} {r['spread']:8.3f} {r['ms_per_pass'] / none[r['n']]:8.3f} "
+              f"{r.get('shrink_bytes_per_layer', 0) / 1e6:16.2f} {r.get('expand_bytes_per_layer', 0) / 1e6:16.2f}")
 
 
 def shared_prefix(m, shape, P: int, pos: int, iters: int, repeats: int, forked_only: bool = False):
@@ -420,10 +500,21 @@ def main():
     ap.add_argument("--trees", action="store_true",
                     help="only the tree table (llmk_tree_*): a heap tree of 16, 64 and 128 nodes behind positions 25 and --pos against a span "
                          "pass of the same rows and against its root-to-leaf paths as spans; llmk_tree_accept")
+    ap.add_argument("--lora", default=None, metavar="RANK[:ADAPTERS][,..]",
+                    help="only the adapter table (llmk_lora_*): the pass at 8, 32 and 128 rows at position 25 with no adapter and with every "
+                         "row on one of ADAPTERS adapters of rank RANK (default 1; 0: one per row); another build selected with LLMK_LIB "
+                         "that has no llmk_lora_* measures the first alone")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
     m, shape = build(a.shape, a.type, a.cls_q6k)
+    if a.lora:
+        rows = lora(m, shape, a.lora, a.iters, a.repeats)
+        m.close()
+        print_lora(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "lora": rows}))
+        return
     if a.trees:
         rows = trees(m, shape, a.pos, a.iters, a.repeats)
         m.close()

@@ -767,6 +767,65 @@ def load_fused(path: str, dequant_cls: bool = False) -> FusedWeights:
     return fw
 
 
+# ----------------------------------------------------------------------------------------------
+# llama.cpp LoRA adapter files: general.type = "adapter", adapter.type = "lora", adapter.lora.alpha, and per adapted matrix
+# blk.N.<target>.weight.lora_a [r][in] and .lora_b [out][r] (f32 or f16)
+# ----------------------------------------------------------------------------------------------
+LORA_TARGETS = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")
+
+
+def lora_piece(shape: LlamaShape, target: str) -> Tuple[str, int, int]:
+    """(fused tensor, row0, rows) of a GGUF target: where its rows lie in the fused weight_module tensors"""
+    E, H, KV = shape.emb_dim, shape.hidden_dim, shape.kv_dim
+    return {"attn_q": ("wqkv", 0, E), "attn_k": ("wqkv", E, KV), "attn_v": ("wqkv", E + KV, KV), "attn_output": ("wo", 0, E),
+            "ffn_gate": ("w13", 0, H), "ffn_up": ("w13", H, H), "ffn_down": ("w2", 0, E)}[target]
+
+
+def write_lora_gguf(path: str, alpha: float, pieces: Dict[Tuple[str, int], Tuple[np.ndarray, np.ndarray]], alignment: int = 32) -> None:
+    """pieces: {(target, layer): (A [r][in], B [out][r])}, float32 or float16 arrays, written as they are"""
+    tensors = []
+    for (target, layer), ab in sorted(pieces.items()):
+        for a, suffix in zip(ab, ("lora_a", "lora_b")):
+            a = np.ascontiguousarray(a)
+            tensors.append((f"blk.{layer}.{target}.weight.{suffix}", a, {np.dtype("float32"): GGML_F32, np.dtype("float16"): GGML_F16}[a.dtype]))
+    kvs = [("general.architecture", T_STR, b"llama"), ("general.type", T_STR, b"adapter"), ("adapter.type", T_STR, b"lora"),
+           ("adapter.lora.alpha", T_F32, float(alpha)), ("general.alignment", T_U32, alignment)]
+    with open(path, "wb") as f:
+        f.write(struct.pack("<IIqq", GGUF_MAGIC, 3, len(tensors), len(kvs)))
+        for k, t, v in kvs:
+            _w_str(f, k.encode())
+            f.write(struct.pack("<I", t))
+            _w_str(f, v) if t == T_STR else f.write(struct.pack(_SCALAR_FMT[t], v))
+        offset = 0
+        for name, a, tt in tensors:
+            _w_str(f, name.encode())
+            f.write(struct.pack("<IQQIQ", 2, a.shape[1], a.shape[0], tt, offset))      # (ne[0] = the innermost dimension)
+            offset += (a.nbytes + alignment - 1) // alignment * alignment
+        f.write(b"\0" * ((-f.tell()) % alignment))
+        for name, a, tt in tensors:
+            f.write(a.data)
+            f.write(b"\0" * ((-a.nbytes) % alignment))
+
+
+def read_lora_gguf(path: str):
+    """(alpha, rank, {(target, layer): (A [r][in], B [out][r])}) of a llama.cpp adapter file, the arrays in the file's types"""
+    g = read_gguf(path)
+    if g.kv.get("general.type") != b"adapter" or g.kv.get("adapter.type", b"lora") != b"lora":
+        raise ValueError(f"{path}: not a LoRA adapter file (general.type = {g.kv.get('general.type')!r})")
+    pieces = {}
+    for name in g.tensors:
+        if not name.endswith(".weight.lora_a"):
+            continue
+        _, layer, target = name[:-len(".weight.lora_a")].split(".", 2)
+        if target not in LORA_TARGETS:
+            raise ValueError(f"{path}: {name}: only the layers' seven matrices take an adapter")
+        pieces[(target, int(layer))] = tuple(g.read_tensor(f"blk.{layer}.{target}.weight.{s}")[0] for s in ("lora_a", "lora_b"))
+    ranks = {a.shape[0] for a, _ in pieces.values()} | {b.shape[1] for _, b in pieces.values()}
+    if len(ranks) != 1:
+        raise ValueError(f"{path}: one rank per adapter, found {sorted(ranks)}")
+    return float(g.kv["adapter.lora.alpha"]), ranks.pop(), pieces
+
+
 if __name__ == "__main__":
     import argparse
 
