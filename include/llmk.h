@@ -680,6 +680,42 @@ int llmk_lora_upload(llmk_lora *ad, int tensor_id, int layer, int row0, int rows
 int llmk_lora_destroy(llmk_lora *ad);
 int llmk_lora_assign(llmk_batch *b, int slot, llmk_lora *ad);
 
+/* Pages: a batch whose slots share ONE pool of fixed-size pages instead of owning seq_len rows each, so the
+ * memory follows the positions in use and any number of slots can hold the pages of a common stem.  ("pages": the llmk_batch_* and
+ * llmk_cache_* lists are closed.)  The pool is [layers][n_pages][page_len][kv_dim] per K and V; a slot has a table of
+ * ceil(seq_len / page_len) entries, entry i the physical page of its positions i * page_len + 1 .. (i + 1) * page_len.  The handle is
+ * an llmk_batch.
+ *
+ * create:  kv_type LLMK_TYPE_F32 or LLMK_TYPE_F16 (the stored-value rule of the f16 paragraph above is unchanged); LLMK_TYPE_Q8_0 and
+ *          any other type: LLMK_E_TYPE.  page_len a multiple of 16 in [16, 256] and n_pages >= 1, else LLMK_E_ARG; every other check is
+ *          llmk_cache_create's.  seq_len still bounds a slot.  All tables start empty.
+ * The allocator is the host's and deterministic: a fresh page is the lowest-numbered free one, and every page has a reference count.
+ * Before a pass the host makes every page the pass writes present and owned by its slot alone -- for llmk_batch_decode and
+ * llmk_rows_decode all `steps` positions of every row, so no decode step comes back to the host -- and every page of the slot in
+ * front of them present; a write into a page that other slots hold too first copies it to a fresh page (copy on write).  Not enough
+ * free pages: LLMK_E_NOMEM before anything is launched, with the tables, the counts and the caches as they were.  Rows of a page
+ * behind its slot's last written position hold whatever the page's last owner left; no pass reads them.
+ * release: the slot keeps positions 1..n_keep; the pages wholly behind them go back to the pool (0: all of them).
+ * share:   dst lets go of what it held and becomes src's positions 1..n_pos: src's full pages by reference, and -- n_pos not a multiple
+ *          of page_len -- a fresh page with a bit-for-bit copy of the last page's rows in use (LLMK_E_NOMEM without one: nothing
+ *          changed).  src must hold a page for every one of those positions, dst != src, else LLMK_E_ARG.  dst's token record becomes
+ *          src's.  N completions of a prompt, or a tree of stems, in one copy of the stem's pages.
+ * free:    the pages free right now, or a negative LLMK_E_* code.
+ * table:   verification hook: the slot's physical pages in table order into pages_out[0 .. cap), returns how many it holds.
+ * On such a batch llmk_batch_forward / _decode / _fork / _time / _destroy, llmk_rows_*, llmk_lora_assign, llmk_cache_type, llmk_cache_bytes
+ * (the pool's bytes) and llmk_cache_peek (through the table; a position without a page reads +0.0) keep their contracts, and
+ * llmk_batch_fork takes fresh pages for the slot (LLMK_E_NOMEM: the slot keeps what it had).  llmk_span_forward, llmk_span_time and a
+ * chain-only llmk_tree_forward run the per-row attention kernel (the form LLMK_SPAN_ATTN=0 selects).  llmk_prefix_*, a llmk_tree_forward
+ * that is not a chain and llmk_tree_accept are LLMK_E_ARG before anything runs.  A pass's arithmetic does not depend on where a slot's
+ * pages lie: the same sequence gives the same bits on any table.  llmk_pages_* on a batch of llmk_batch_create / llmk_cache_create, or
+ * on NULL: LLMK_E_ARG (llmk_pages_free, llmk_pages_table: -LLMK_E_ARG).
+ * Out of scope: q8_0 pages; the prefix, span and tree column-group kernels over pages; swapping pages to the host; any scheduler. */
+int llmk_pages_create(llmk_ctx *ctx, int n_slots, int seq_len, int kv_type, int page_len, int n_pages, llmk_batch **out);
+int llmk_pages_release(llmk_batch *b, int slot, int n_keep);
+int llmk_pages_share(llmk_batch *b, int dst_slot, int src_slot, int n_pos);
+int llmk_pages_free(llmk_batch *b);    /* free pages now; negative LLMK_E_* on error */
+int llmk_pages_table(llmk_batch *b, int slot, int *pages_out, int cap);
+
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);
 

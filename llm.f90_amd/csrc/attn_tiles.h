@@ -1,7 +1,8 @@
 // The MFMA attention the batched paths share (DESIGN.md sections 3c, 3i): pf_attn_kernel (prefill.h), bd_attn_prefix_kernel and
 // bd_attn_own_kernel (batch.h) are setup + attn_tiles + attn_merge_waves; bd_attn_kernel (batch.h) shares the look-ahead types and
 // keeps the loop and the merge written out (the reason stands at that kernel); the four bd_q8_attn_* kernels of a q8_0 batch are
-// setup + these calls as well, over AttnAhead<HS, KvQ8>.  A workgroup owns 16 query COLUMNS
+// setup + these calls as well, over AttnAhead<HS, KvQ8>, and so is bd_attn_paged_kernel (paged.h), which tells the loop where each
+// tile of a slot's pages lies.  A workgroup owns 16 query COLUMNS
 // (prompt positions, or the query heads of a kv group) and a range of 16-row tiles of one K/V cache; its NW waves take the tiles round
 // robin, each with its own running softmax (max m, sum l, unnormalised output O), and merge through LDS at the end.
 //
@@ -198,10 +199,16 @@ __device__ __forceinline__ void attn_load_q(float (&qf)[HS / 4], const float* __
 // and leaves its running state in m_run, l_run, O.  visible(r): does this lane's query column see cache row r?  Loads clamp the row
 // index to `last` and the tile index to ntile - 1 (a tile's two dozen MFMAs and its softmax take far less than an L2 round trip, so
 // the next tile is requested before this one is multiplied).  A wave without a visible row leaves m = -inf, l = 0, O = 0.
-template <int HS, class T, int NW, class Visible>
+// where(p, tile): the pointer a tile's loads start from, for a cache whose 16-row tiles do not lie one behind the other (paged.h: the
+// pages of a slot); AttnDense, the default, is the cache as it stands: p itself, and nothing of it is left in the code.
+struct AttnDense {
+    template <class P>
+    __device__ __forceinline__ P operator()(P p, int) const { return p; }
+};
+template <int HS, class T, int NW, class Visible, class Where = AttnDense>
 __device__ __forceinline__ void attn_tiles(const float (&qf)[HS / 4], typename AttnAhead<HS, T>::Ptr kb, typename AttnAhead<HS, T>::Ptr vb, int KV,
                                            int last, int ntile, int t0, int t1, int wid, int li, int g, Visible visible, float& m_run,
-                                           float& l_run, pf_v4f (&O)[HS / 16]) {
+                                           float& l_run, pf_v4f (&O)[HS / 16], Where where = Where()) {
     constexpr int DG = HS / 4, NT = HS / 16;
     typedef AttnAhead<HS, T> Ahead;
     const float scale = sqrtf((float)HS);
@@ -211,12 +218,16 @@ __device__ __forceinline__ void attn_tiles(const float (&qf)[HS / 4], typename A
     for (int t = 0; t < NT; ++t) O[t] = (pf_v4f){0.f, 0.f, 0.f, 0.f};
     typename Ahead::K kn;
     typename Ahead::V vn;
-    Ahead::load(kn, vn, kb, vb, KV, min(t0 + wid, ntile - 1) * 16, li, g, last);
+    {
+        const int tn = min(t0 + wid, ntile - 1);
+        Ahead::load(kn, vn, where(kb, tn), where(vb, tn), KV, tn * 16, li, g, last);
+    }
     for (int kt = t0 + wid; kt < t1; kt += NW) {
         const int r0 = kt * 16;
         float kf[DG], vf[4][NT];
         Ahead::take(kn, vn, kf, vf);
-        Ahead::load(kn, vn, kb, vb, KV, min(kt + NW, ntile - 1) * 16, li, g, last);
+        const int tn = min(kt + NW, ntile - 1);
+        Ahead::load(kn, vn, where(kb, tn), where(vb, tn), KV, tn * 16, li, g, last);
         pf_v4f acc = (pf_v4f){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int m = 0; m < DG; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[m], qf[m], acc, 0, 0, 0);

@@ -16,6 +16,7 @@
 #include "token_kernel.h"
 #include "prefill.h"
 #include "batch.h"
+#include "paged.h"
 #include "lora.h"
 #include "tp_p2p.h"
 #include "forward_ahead.h"
@@ -318,6 +319,17 @@ struct llmk_batch {
         int groups = 0;                          // ... and their column groups; 0: every row runs the base model
     };
     std::unique_ptr<Lora> lo;
+    // pages (llmk_pages_*, paged.h): a batch of llmk_pages_create keeps the pool [L][n_pages][page_len][KV] in `cache` and this; any
+    // other batch has none of it
+    struct Pages {
+        PagePool pool;                           // the host's tables and counts: what the device's table follows
+        DevBuf<int> d_table;                     // [n_slots][width]
+        PinnedBuf<int> h_table;                  // the pinned words a changed table row is copied from
+        std::vector<PagePool::Copy> copies;      // the copies on write of the call in hand
+        BdStore peek;                            // llmk_cache_peek's gathered rows (k alone), grown by reserve
+        BdPages view() const { return BdPages{d_table, pool.width, pool.page_len, pool.n_pages}; }
+    };
+    std::unique_ptr<Pages> pg;
 };
 
 // One adapter (lora.h): per layer and fused tensor up to LORA_MAX_PIECES row ranges, each with A [R16][K] and B [rows][R16] in f32 on
@@ -1581,6 +1593,29 @@ template <class T> struct BdKvPlain {
     static T* view(const DevBuf<char>& buf, size_t) { return reinterpret_cast<T*>(buf.get()); }
     static bool shape_ok(int) { return true; }
     static hipError_t zero(T* at, size_t n, hipStream_t st) { return hipMemsetAsync(at, 0, n * sizeof(T), st); }
+    // a batch of llmk_pages_create may hold this type (paged.h); k / v / src: layer 0 of the pools.  All ENQUEUED:
+    //   page_copy   the first `rows` rows of page src onto page dst, every layer, K and V, bit for bit;
+    //   to_pages    rows [n / KV][KV] of every layer of the context's f32 caches into the pages of `slot`;
+    //   from_pages  n elements of `slot` from cache row row0 on, out of one layer's pool into the block dst, as stored.
+    static constexpr bool pageable = true;
+    static hipError_t page_copy(T* k, T* v, const llmk_batch* b, int src, int dst, int rows, hipStream_t st) {
+        const PagePool& pl = b->pg->pool;
+        const size_t per = sizeof(uint4) / sizeof(T), page = (size_t)pl.page_len * b->ctx->KV / per, n = (size_t)rows * b->ctx->KV / per;
+        hipLaunchKernelGGL(bd_page_copy_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 64), b->ctx->L, 2), dim3(256), 0, st,
+                           reinterpret_cast<uint4*>(k), reinterpret_cast<uint4*>(v), page * pl.n_pages, page, src, dst, n);
+        return hipGetLastError();
+    }
+    static hipError_t to_pages(llmk_ctx* c, T* dk, T* dv, const llmk_batch* b, int slot, size_t n, size_t dst_layer) {
+        const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
+        hipLaunchKernelGGL(bd_to_pages_kernel<T>, dim3(blocks, c->L, 2), dim3(256), 0, c->stream, c->d_kc.get(), c->d_vc.get(), dk, dv, b->pg->view(), slot, n,
+                           c->KV, (size_t)c->S * c->KV, dst_layer);
+        return hipGetLastError();
+    }
+    static hipError_t from_pages(const T* src, T* dst, const llmk_batch* b, int slot, int row0, size_t n, hipStream_t st) {
+        const unsigned blocks = (unsigned)std::min<size_t>((n / 4 + 255) / 256, 1024);
+        hipLaunchKernelGGL(bd_from_pages_kernel<T>, dim3(blocks), dim3(256), 0, st, src, dst, b->pg->view(), slot, row0, n, b->ctx->KV);
+        return hipGetLastError();
+    }
 };
 template <class T> struct BdKv;
 template <> struct BdKv<float> : BdKvPlain<float> {
@@ -1596,6 +1631,12 @@ template <> struct BdKv<float> : BdKvPlain<float> {
         a.kc = kc; a.vc = vc;
         if (rope_pos) hipLaunchKernelGGL(bd_epi_qkv_tree_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, rope_pos);
         else hipLaunchKernelGGL(bd_epi_qkv_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc);
+        return hipGetLastError();
+    }
+    // ... of a paged batch: kc / vc are the layer's pools, a row's K and V go where the table says (paged.h)
+    static hipError_t epi_qkv_paged(PfEpiArgs& a, const BdCaches& bc, const BdPages& pg, float* kc, float* vc, int QKV, int T, hipStream_t st) {
+        a.kc = kc; a.vc = vc;
+        hipLaunchKernelGGL(bd_epi_qkv_paged_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, pg);
         return hipGetLastError();
     }
 };
@@ -1617,8 +1658,14 @@ template <> struct BdKv<_Float16> : BdKvPlain<_Float16> {
         else hipLaunchKernelGGL(bd_epi_qkv_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, kc, vc);
         return hipGetLastError();
     }
+    static hipError_t epi_qkv_paged(PfEpiArgs& a, const BdCaches& bc, const BdPages& pg, _Float16* kc, _Float16* vc, int QKV, int T, hipStream_t st) {
+        a.kc = a.vc = nullptr;
+        hipLaunchKernelGGL(bd_epi_qkv_paged_h_kernel, dim3((QKV / 4 + 255) / 256, T), dim3(256), 0, st, a, bc, pg, kc, vc);
+        return hipGetLastError();
+    }
 };
 template <> struct BdKv<KvQ8> {
+    static constexpr bool pageable = false;      // (q8_0 pages: not built; llmk_pages_create answers LLMK_E_TYPE)
     static size_t bytes(size_t n) { return n + n / 32 * sizeof(_Float16); }      // 34 per 32 elements: the quants, then the scales
     static Q8Rows view(const DevBuf<char>& buf, size_t n) {
         return Q8Rows{reinterpret_cast<int8_t*>(buf.get()), reinterpret_cast<_Float16*>(buf.get() + n)};
@@ -1663,7 +1710,11 @@ static auto with_kv_type(const llmk_batch* b, F f) {
 
 // The two element offsets of the store: layer l, slot s, position p (0-based) of a cache block, and layer l, position p of a prefix
 // block ([L][P][KV] with the layers P rows apart, whatever the block's room).  (L, 0, 0) and (L, 0) are the blocks' element counts.
-static size_t bd_cache_at(const llmk_batch* b, int l, int slot, int p) { return (((size_t)l * b->n_slots + slot) * b->seq_len + p) * b->ctx->KV; }
+// (a paged batch's block is [L][n_pages * page_len][KV]: slot 0, p = page * page_len + the row in the page)
+static size_t bd_layer_rows(const llmk_batch* b) {
+    return b->pg ? (size_t)b->pg->pool.n_pages * b->pg->pool.page_len : (size_t)b->n_slots * b->seq_len;
+}
+static size_t bd_cache_at(const llmk_batch* b, int l, int slot, int p) { return ((size_t)l * bd_layer_rows(b) + (size_t)slot * b->seq_len + p) * b->ctx->KV; }
 static size_t bd_prefix_at(const llmk_batch* b, int l, int p) { return ((size_t)l * b->P + p) * b->ctx->KV; }
 // ... and the kernels' views of a block there
 template <class TC>
@@ -1685,6 +1736,56 @@ static hipError_t bd_zero_slot(llmk_batch* b, int slot, int n_pos) {
     return hipSuccess;
 }
 
+// ---- a paged batch (paged.h): the device follows the host's tables ----
+// What the pool's log holds since the call began goes to the device, ENQUEUED in front of whatever the call launches next: the copies on
+// write, then the table rows of the slots that changed (as the row words go up).  The log and the copies are then done with.
+static hipError_t pg_commit(llmk_batch* b) {
+    llmk_batch::Pages& pg = *b->pg;
+    hipStream_t st = b->ctx->stream;
+    for (const PagePool::Copy& cp : pg.copies)
+        HIPRET(with_kv_type(b, [&](auto t) -> hipError_t {
+            using TC = decltype(t);
+            if constexpr (BdKv<TC>::pageable)
+                return BdKv<TC>::page_copy(bd_cache_view<TC>(b, b->cache.k, 0, 0, 0), bd_cache_view<TC>(b, b->cache.v, 0, 0, 0), b, cp.src, cp.dst, pg.pool.page_len, st);
+            return hipErrorNotSupported;
+        }));
+    bool seen[LLMK_MAX_BATCH] = {};
+    const size_t w = (size_t)pg.pool.width;
+    for (const PagePool::Change& ch : pg.pool.log) {
+        const size_t slot = ch.at / w;
+        if (seen[slot]) continue;
+        seen[slot] = true;
+        memcpy(pg.h_table + slot * w, pg.pool.of((int)slot), w * sizeof(int));
+        HIPRET(hipMemcpyAsync(pg.d_table + slot * w, pg.h_table + slot * w, w * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    pg.pool.log.clear();
+    pg.copies.clear();
+    return hipSuccess;
+}
+// Before a pass: every page the spans' positions lie in is present and owned by its slot alone, and every page of the slot in front of
+// them is present.  Not enough free pages: LLMK_E_NOMEM with tables and counts as they were, nothing launched.  A dense batch: nothing.
+static int pg_prepare(llmk_batch* b, int n_spans, const llmk_span* spans) {
+    if (!b->pg) return LLMK_OK;
+    llmk_batch::Pages& pg = *b->pg;
+    pg.pool.log.clear();
+    pg.copies.clear();
+    for (int i = 0; i < n_spans; ++i)
+        if (!pg.pool.ensure(spans[i].slot, spans[i].pos0, spans[i].len, pg.copies)) {
+            pg.pool.undo(0);
+            pg.copies.clear();
+            return LLMK_E_NOMEM;
+        }
+    HIPCHK(pg_commit(b));
+    return LLMK_OK;
+}
+// ... for rows that write `span` positions each from pos[i] on
+static int pg_prepare(llmk_batch* b, int n, const int* slots, const int* pos, int span) {
+    if (!b->pg) return LLMK_OK;
+    llmk_span spans[LLMK_MAX_BATCH];
+    for (int i = 0; i < n; ++i) spans[i] = llmk_span{slots[i], pos[i], span};
+    return pg_prepare(b, n, spans);
+}
+
 // The attention of one pass, computed once for all layers: the split rules, which kernel serves the rows' own ranges, whether a fold
 // follows, and the part states it goes through.
 //   ROW   no attached row, no span: bd_attn_kernel, parts of the rows' whole ranges; more than one part: states in d_po / d_pml
@@ -1694,9 +1795,12 @@ static hipError_t bd_zero_slot(llmk_batch* b, int slot, int n_pos) {
 //         groups; one part and no attached row: straight to XB (direct), else folded;
 //   TREE  a tree pass (pass_tree, llmk_tree_*): a span pass whose rows are rotated at rope_pos and whose column groups run
 //         bd_attn_tree_kernel -- the same groups, split rule, part states and fold.
+//   PAGED a pass of a paged batch (llmk_pages_*): ROW's split, states and fold with bd_attn_paged_kernel in bd_attn_kernel's place --
+//         span passes too (such a batch has no shared prefix, no column groups and no trees).
 // OWN, SPAN and TREE leave np = pparts + parts states per (row, kv head) in the batch's PartStates (stride kv_mul): the prefix parts first.
 struct BdAttnPlan {
-    enum Kind { ROW, OWN, SPAN, TREE } kind;
+    enum Kind { ROW, OWN, SPAN, TREE, PAGED } kind;
+    bool per_row;                   // ROW or PAGED: one workgroup per (kv head, row, part), states in d_po / d_pml
     bool grouped;                   // SPAN or TREE: the rows' kernel runs over column groups
     bool shared, fold;              // attached rows in the pass: the prefix kernel runs; the fold kernel runs
     int units;                      // grid.y of the rows' kernel: rows, or column groups of a span pass
@@ -1712,7 +1816,8 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
     const llmk_ctx* c = b->ctx;
     BdAttnPlan p{};
     p.shared = b->pass_att > 0;
-    p.kind = b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
+    p.kind = b->pg ? BdAttnPlan::PAGED : b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
+    p.per_row = p.kind == BdAttnPlan::ROW || p.kind == BdAttnPlan::PAGED;
     p.grouped = p.kind == BdAttnPlan::SPAN || p.kind == BdAttnPlan::TREE;
     p.units = p.grouped ? b->pass_groups : n;
     // The split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`.  Without
@@ -1731,8 +1836,8 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
     p.tpp = bd_tiles_per_part(own * BD_TILE, p.parts);
     p.np = p.pparts + p.parts;
     p.direct = p.grouped && !p.shared && p.parts == 1;
-    p.fold = p.kind == BdAttnPlan::ROW ? p.parts > 1 : !p.direct;
-    if (p.kind == BdAttnPlan::ROW) {
+    p.fold = p.per_row ? p.parts > 1 : !p.direct;
+    if (p.per_row) {
         p.po = b->d_po; p.pml = b->d_pml; p.stride = BD_MAX_GROUP;
     } else {
         p.po = b->ps->d_o; p.pml = b->ps->d_ml; p.stride = c->kv_mul;
@@ -1755,7 +1860,11 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, b->lo && b->lo->groups > 0 ? b->lo.get() : nullptr,
                      [&](int l, PfEpiArgs& a) -> hipError_t {
         const auto kc = bd_cache_view<TC>(b, b->cache.k, l, 0, 0), vc = bd_cache_view<TC>(b, b->cache.v, l, 0, 0);
-        HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, p.kind == BdAttnPlan::TREE ? b->tr->args().rope_pos : nullptr, QKV, T, w.stream));
+        if (p.kind == BdAttnPlan::PAGED) {
+            if constexpr (BdKv<TC>::pageable) HIPRET(BdKv<TC>::epi_qkv_paged(a, bc, b->pg->view(), kc, vc, QKV, T, w.stream));
+        } else {
+            HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, p.kind == BdAttnPlan::TREE ? b->tr->args().rope_pos : nullptr, QKV, T, w.stream));
+        }
         return with_head_size(c->hs, [&](auto hs) {
             constexpr int HS = decltype(hs)::value;
             const dim3 block(BD_WAVES * WAVE), grid(c->nkv, p.units, p.parts);
@@ -1781,6 +1890,11 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
                 case BdAttnPlan::TREE:
                     hipLaunchKernelGGL((BdAttn<HS, TC>::tree), grid, block, smem, w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc, b->sn->d_groups, b->tr->args(),
                                        p.first, T, KV, c->kv_mul, E, p.tpp, p.np, p.pparts, p.direct);
+                    break;
+                case BdAttnPlan::PAGED:
+                    if constexpr (BdKv<TC>::pageable)
+                        hipLaunchKernelGGL((bd_attn_paged_kernel<HS, TC>), grid, block, pg_attn_smem(HS, b->seq_len), w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc,
+                                           b->pg->view(), KV, c->kv_mul, E, p.tpp);
                     break;
             }
             HIPRET(hipGetLastError());
@@ -1871,7 +1985,7 @@ static int bd_time(llmk_batch* b, int n, int max_pos, int iters, const ScPlan& s
 
 extern "C" {
 
-int llmk_version(void) { return 410; }
+int llmk_version(void) { return 411; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -3101,19 +3215,29 @@ static int bd_alloc_rc(hipError_t e) {
 }
 
 // llmk_batch_create IS this with LLMK_TYPE_F32: the caches of an f32 batch are allocated, zeroed and used as they always were
-static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) {
+// page_len > 0: llmk_pages_create -- the block is a pool of n_pages pages and the batch gets its tables (paged.h), all entries none
+static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, int page_len, int n_pages, llmk_batch** out) {
     if (!c || !out || n_slots < 1 || n_slots > LLMK_MAX_BATCH || seq_len < 1 || seq_len > c->S) return LLMK_E_ARG;
     *out = nullptr;
     if (!kv_type_ok(kv_type)) return LLMK_E_TYPE;
+    const bool paged = page_len > 0;
     int rc = check_ready(c);      // (an incomplete context is LLMK_E_STATE whatever its shape)
     if (rc) return rc;
     if (!pf_shape_ok(c) || c->kv_mul > BD_MAX_GROUP) return LLMK_E_SHAPE;
     // built aside: the caller gets the batch only after every step succeeded (a failure releases what was made)
     auto b = std::make_unique<llmk_batch>();
     b->ctx = c; b->n_slots = n_slots; b->seq_len = seq_len; b->kv_type = kv_type;
+    if (paged) {
+        if (!with_kv_type(b.get(), [](auto t) { return BdKv<decltype(t)>::pageable; })) return LLMK_E_TYPE;
+        if (page_len < PG_MIN_LEN || page_len > PG_MAX_LEN || page_len % BD_TILE || n_pages < 1 || n_pages > INT_MAX / page_len) return LLMK_E_ARG;
+        if (pg_attn_smem(c->hs, seq_len) > PG_MAX_SMEM) return LLMK_E_SHAPE;
+        b->pg = std::make_unique<llmk_batch::Pages>();
+        b->pg->pool.init(n_slots, seq_len, page_len, n_pages);
+    }
     if (!with_kv_type(b.get(), [&](auto t) { return BdKv<decltype(t)>::shape_ok(c->KV); })) return LLMK_E_SHAPE;
     HIPCHK(hipSetDevice(c->cfg.device));
-    b->span_attn = !(getenv("LLMK_SPAN_ATTN") && getenv("LLMK_SPAN_ATTN")[0] == '0');
+    // (a paged batch's span passes run the per-row attention kernel: the column-group kernels do not read through a table)
+    b->span_attn = !paged && !(getenv("LLMK_SPAN_ATTN") && getenv("LLMK_SPAN_ATTN")[0] == '0');
     ScPlan sp;
     if ((rc = bd_ready(b.get(), &sp, n_slots)) != LLMK_OK) return rc;
     const size_t nb = LLMK_MAX_BATCH;
@@ -3141,18 +3265,103 @@ static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_ba
     HIPCHK(b->h_err.alloc(1));
     HIPCHK(with_head_size(c->hs, [&](auto hs) {
         constexpr int HS = decltype(hs)::value;
-        return with_kv_type(b.get(), [](auto t) {
-            return hipFuncSetAttribute((const void*)BdAttn<HS, decltype(t)>::row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+        return with_kv_type(b.get(), [&](auto t) -> hipError_t {
+            using TC = decltype(t);
+            if constexpr (BdKv<TC>::pageable)
+                if (paged)
+                    return hipFuncSetAttribute((const void*)bd_attn_paged_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_attn_smem(HS, seq_len));
+            return hipFuncSetAttribute((const void*)BdAttn<HS, TC>::row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
         });
     }));
+    if (paged) {
+        // the tables: every entry none, here and on the device
+        llmk_batch::Pages& pg = *b->pg;
+        HIPCHK(pg.d_table.alloc(pg.pool.table.size()));
+        HIPCHK(pg.h_table.alloc(pg.pool.table.size()));
+        memcpy(pg.h_table, pg.pool.table.data(), pg.pool.table.size() * sizeof(int));
+        HIPCHK(hipMemcpyAsync(pg.d_table, pg.h_table, pg.pool.table.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     ++c->n_batches;
     *out = b.release();
     return LLMK_OK;
 }
 
-int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) { return bd_create(c, n_slots, seq_len, LLMK_TYPE_F32, out); }
-int llmk_cache_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) { return bd_create(c, n_slots, seq_len, kv_type, out); }
+int llmk_batch_create(llmk_ctx* c, int n_slots, int seq_len, llmk_batch** out) { return bd_create(c, n_slots, seq_len, LLMK_TYPE_F32, 0, 0, out); }
+int llmk_cache_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, llmk_batch** out) { return bd_create(c, n_slots, seq_len, kv_type, 0, 0, out); }
+
+// ---- pages (paged.h): one pool of pages for all slots, a table per slot ----
+int llmk_pages_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, int page_len, int n_pages, llmk_batch** out) {
+    if (out) *out = nullptr;
+    if (page_len < 1) return LLMK_E_ARG;      // (0 is bd_create's word for a dense batch)
+    return bd_create(c, n_slots, seq_len, kv_type, page_len, n_pages, out);
+}
+
+int llmk_pages_release(llmk_batch* b, int slot, int n_keep) {
+    if (!b || !b->pg || slot < 0 || slot >= b->n_slots || n_keep < 0 || n_keep > b->seq_len) return LLMK_E_ARG;
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
+    b->pg->pool.log.clear();
+    b->pg->pool.release(slot, n_keep);
+    HIPCHK(pg_commit(b));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+
+int llmk_pages_share(llmk_batch* b, int dst_slot, int src_slot, int n_pos) {
+    if (!b || !b->pg || dst_slot < 0 || dst_slot >= b->n_slots || src_slot < 0 || src_slot >= b->n_slots || dst_slot == src_slot) return LLMK_E_ARG;
+    llmk_batch::Pages& pg = *b->pg;
+    PagePool& pl = pg.pool;
+    const int full = n_pos / pl.page_len, part = n_pos % pl.page_len;
+    if (n_pos < 0 || n_pos > b->seq_len || pl.count(src_slot) < full + (part > 0)) return LLMK_E_ARG;      // (src has a page for every position)
+    llmk_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    { const int rc_ = spec_settle(c); if (rc_) return rc_; }
+    // dst lets go of what it held; src's full pages by reference; the partial page is a fresh one with a copy of the rows in use
+    pl.log.clear();
+    pg.copies.clear();
+    pl.release(dst_slot, 0);
+    for (int i = 0; i < full; ++i) pl.set(dst_slot * pl.width + i, pl.of(src_slot)[i]);
+    int fresh = -1;
+    if (part > 0) {
+        if ((fresh = pl.lowest_free()) < 0) {
+            pl.undo(0);
+            return LLMK_E_NOMEM;
+        }
+        pl.set(dst_slot * pl.width + full, fresh);
+    }
+    HIPCHK(pg_commit(b));
+    if (part > 0)
+        HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
+            using TC = decltype(t);
+            if constexpr (BdKv<TC>::pageable)
+                return BdKv<TC>::page_copy(bd_cache_view<TC>(b, b->cache.k, 0, 0, 0), bd_cache_view<TC>(b, b->cache.v, 0, 0, 0), b, pl.of(src_slot)[full], fresh, part,
+                                           c->stream);
+            return hipErrorNotSupported;
+        }));
+    // dst's token record is src's up to n_pos, and empty behind it
+    if (b->pen.hist) {
+        HIPCHK(hipMemsetAsync(b->pen.hist + (size_t)dst_slot * b->seq_len, 0, (size_t)b->seq_len * sizeof(int), c->stream));
+        if (n_pos > 0)
+            HIPCHK(hipMemcpyAsync(b->pen.hist + (size_t)dst_slot * b->seq_len, b->pen.hist + (size_t)src_slot * b->seq_len, (size_t)n_pos * sizeof(int),
+                                  hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LLMK_OK;
+}
+
+int llmk_pages_free(llmk_batch* b) {
+    if (!b || !b->pg) return -LLMK_E_ARG;
+    return b->pg->pool.n_free;
+}
+
+int llmk_pages_table(llmk_batch* b, int slot, int* pages_out, int cap) {
+    if (!b || !b->pg || slot < 0 || slot >= b->n_slots || cap < 0 || (cap > 0 && !pages_out)) return -LLMK_E_ARG;
+    const int n = b->pg->pool.count(slot);
+    for (int i = 0; i < std::min(n, cap); ++i) pages_out[i] = b->pg->pool.of(slot)[i];
+    return n;
+}
 
 int llmk_cache_type(llmk_batch* b) {
     if (!b) return -LLMK_E_ARG;
@@ -3177,6 +3386,23 @@ int llmk_cache_peek(llmk_batch* b, int which, int layer, int slot, int pos0, int
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (b->pg) {
+        // the rows are gathered through the slot's table into a block of their own, then read as a dense batch's
+        const size_t ne = (size_t)n * c->KV;
+        return with_kv_type(b, [&](auto t) -> int {
+            using TC = decltype(t);
+            if constexpr (BdKv<TC>::pageable) {
+                const int rc = bd_alloc_rc(b->pg->peek.k.reserve(BdKv<TC>::bytes(ne), c->stream));
+                if (rc) return rc;
+                const auto dst = BdKv<TC>::view(b->pg->peek.k, ne);
+                HIPCHK(BdKv<TC>::from_pages(bd_cache_view<TC>(b, which ? b->cache.v : b->cache.k, layer, 0, 0), dst, b, slot, pos0 - 1, ne, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));
+                HIPCHK(BdKv<TC>::read(dst, ne, out));
+                return LLMK_OK;
+            }
+            return LLMK_E_TYPE;
+        });
+    }
     HIPCHK(with_kv_type(b, [&](auto t) {
         using TC = decltype(t);
         const auto src = slot < 0 ? bd_prefix_view<TC>(b, which ? b->px->rows.v : b->px->rows.k, layer, pos0 - 1)
@@ -3303,8 +3529,28 @@ int llmk_batch_fork(llmk_batch* b, int slot, int n_pos) {
     llmk_ctx* c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     { const int rc_ = spec_settle(c); if (rc_) return rc_; }
-    // rows beyond n_pos: as in a fresh slot; the context's f32 rows in front of them, copied or converted by the batch's type
-    HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
+    if (b->pg) {
+        // a paged slot lets go of its pages and takes fresh ones for positions 1..n_pos (LLMK_E_NOMEM: it keeps what it had)
+        llmk_batch::Pages& pg = *b->pg;
+        pg.pool.log.clear();
+        pg.copies.clear();
+        pg.pool.release(slot, 0);
+        if (n_pos > 0 && !pg.pool.ensure(slot, 1, n_pos, pg.copies)) {
+            pg.pool.undo(0);
+            return LLMK_E_NOMEM;
+        }
+        HIPCHK(pg_commit(b));
+        if (n_pos > 0)
+            HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
+                using TC = decltype(t);
+                if constexpr (BdKv<TC>::pageable)
+                    return BdKv<TC>::to_pages(c, bd_cache_view<TC>(b, b->cache.k, 0, 0, 0), bd_cache_view<TC>(b, b->cache.v, 0, 0, 0), b, slot, (size_t)n_pos * c->KV,
+                                              bd_cache_at(b, 1, 0, 0));
+                return hipErrorNotSupported;
+            }));
+    }
+    // (a dense slot) rows beyond n_pos: as in a fresh slot; the context's f32 rows in front of them, copied or converted by the batch's type
+    if (!b->pg) HIPCHK(with_kv_type(b, [&](auto t) -> hipError_t {
         using TC = decltype(t);
         HIPRET(bd_zero_slot<TC>(b, slot, n_pos));
         if (n_pos == 0) return hipSuccess;
@@ -3333,7 +3579,7 @@ static hipError_t bd_part_states(llmk_batch* b) {
 
 // ---- a shared prefix (batch.h): one copy of the K/V rows of positions 1..P, the slots attached to it keep their own rows behind it ----
 int llmk_prefix_set(llmk_batch* b, int n_pos) {
-    if (!b || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S) - 1) return LLMK_E_ARG;
+    if (!b || b->pg || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S) - 1) return LLMK_E_ARG;      // (a paged batch shares pages: llmk_pages_share)
     if (b->n_attached > 0) return LLMK_E_STATE;
     llmk_ctx* c = b->ctx;
     if (n_pos == 0) { b->P = 0; return LLMK_OK; }      // (the buffers stay for the next prefix)
@@ -3382,7 +3628,7 @@ int llmk_prefix_set(llmk_batch* b, int n_pos) {
 }
 
 int llmk_prefix_attach(llmk_batch* b, int slot) {
-    if (!b || slot < 0 || slot >= b->n_slots) return LLMK_E_ARG;
+    if (!b || b->pg || slot < 0 || slot >= b->n_slots) return LLMK_E_ARG;
     if (b->P < 1) return LLMK_E_STATE;
     llmk_ctx* c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -3396,7 +3642,7 @@ int llmk_prefix_attach(llmk_batch* b, int slot) {
 }
 
 int llmk_prefix_len(llmk_batch* b) {
-    if (!b) return -LLMK_E_ARG;
+    if (!b || b->pg) return -LLMK_E_ARG;
     return b->P;
 }
 
@@ -3406,6 +3652,7 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
     ScPlan sp;
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
+    if ((rc = pg_prepare(b, n, slots, pos, 1)) != LLMK_OK) return rc;
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos));
     const int* ids;
     rc = bd_forward_sync(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp, "llmk_batch_forward",
@@ -3495,6 +3742,7 @@ static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, 
     if (rc) return rc;
     ScPlan sp;
     if ((rc = bd_ready(b, &sp, n)) != LLMK_OK) return rc;
+    if ((rc = pg_prepare(b, n, slots, pos0, steps)) != LLMK_OK) return rc;      // (every step's page up front: no host round trip inside a decode)
     HIPCHK(b->d_ids.reserve(nids, c->stream));
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos0));
     HIPCHK(rows_upload_words(b, n, samplers != nullptr, pen, lp != nullptr));
@@ -3602,6 +3850,7 @@ int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     if (rc) return rc;
     int slots[LLMK_MAX_BATCH], tokens[LLMK_MAX_BATCH], posv[LLMK_MAX_BATCH];
     for (int i = 0; i < n; ++i) { slots[i] = i; tokens[i] = 1; posv[i] = pos; }
+    if ((rc = pg_prepare(b, n, slots, posv, 1)) != LLMK_OK) return rc;
     HIPCHK(bd_upload_rows(b, n, slots, tokens, posv));
     return bd_time(b, n, pos, iters, sp, avg_ms);
 }
@@ -3677,6 +3926,7 @@ int llmk_span_forward(llmk_batch* b, int n_spans, const llmk_span* spans, const 
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     if ((rc = span_setup(b, n, b->span_attn)) != LLMK_OK) return rc;
+    if ((rc = pg_prepare(b, n_spans, spans)) != LLMK_OK) return rc;
     HIPCHK(span_upload(b, n_spans, spans, tokens, b->span_attn));
     int max_pos = 0;
     for (int i = 0; i < n_spans; ++i) max_pos = std::max(max_pos, spans[i].pos0 + spans[i].len - 1);
@@ -3708,6 +3958,7 @@ int llmk_span_time(llmk_batch* b, int n_spans, int len, int pos0, int iters, flo
     int rc = bd_ready(b, &sp, n);
     if (rc) return rc;
     if ((rc = span_setup(b, n, b->span_attn)) != LLMK_OK) return rc;
+    if ((rc = pg_prepare(b, n_spans, spans)) != LLMK_OK) return rc;
     HIPCHK(span_upload(b, n_spans, spans, nullptr, b->span_attn));
     return bd_time(b, n, pos0 + len - 1, iters, sp, avg_ms);
 }
@@ -3780,6 +4031,7 @@ int llmk_tree_forward(llmk_batch* b, int n_trees, const llmk_span* trees, const 
     if (!b || (!logits_out && !argmax_out) || !parent || !span_ok(b, n_trees, trees, tokens, true, &n) || !tree_ok(n_trees, trees, parent, &chain))
         return LLMK_E_ARG;
     if (chain) return llmk_span_forward(b, n_trees, trees, tokens, 0, logits_out, argmax_out);      // chains ARE spans
+    if (b->pg) return LLMK_E_ARG;                                                                   // (the tree kernels do not read through a table)
     llmk_ctx* c = b->ctx;
     ScPlan sp;
     int rc = tree_begin(b, n_trees, trees, tokens, parent, n, &sp);
@@ -3796,7 +4048,7 @@ int llmk_tree_forward(llmk_batch* b, int n_trees, const llmk_span* trees, const 
 }
 
 int llmk_tree_accept(llmk_batch* b, int slot, int pos0, int n, const int* path) {
-    if (!b || slot < 0 || slot >= b->n_slots || n < 0 || (n > 0 && !path) || pos0 < 1) return LLMK_E_ARG;
+    if (!b || b->pg || slot < 0 || slot >= b->n_slots || n < 0 || (n > 0 && !path) || pos0 < 1) return LLMK_E_ARG;
     if (b->n_attached > 0 && pos0 <= b->px->h_first[slot]) return LLMK_E_ARG;
     bool moves = false;
     for (int k = 0; k < n; ++k) {
@@ -3828,6 +4080,7 @@ int llmk_tree_time(llmk_batch* b, int n_trees, int len, int pos0, int iters, flo
     int n = 0;
     if (!span_ok(b, n_trees, trees, nullptr, false, &n)) return LLMK_E_ARG;
     if (len <= 2) return llmk_span_time(b, n_trees, len, pos0, iters, avg_ms);      // a heap of one or two nodes is a chain: that pass
+    if (b->pg) return LLMK_E_ARG;
     int parent[LLMK_MAX_BATCH];
     for (int i = 0; i < n; ++i) parent[i] = i % len ? (i % len - 1) / 2 : LLMK_TREE_ROOT;
     ScPlan sp;

@@ -1,0 +1,232 @@
+// Paged K/V caches (llmk_pages_*): a batch made by llmk_pages_create keeps ONE pool of pages,
+// [L][n_pages][page_len][KV] per K and V in f32 or f16, and a table per slot, [n_slots][width] with width = ceil(seq_len / page_len):
+// entry i of a slot is the physical page of its positions i * page_len + 1 .. (i + 1) * page_len, -1 for none.  page_len is a multiple
+// of BD_TILE, so a 16-row MFMA tile never straddles a page.  Here:
+//   PagePool                 the host's allocator: lowest free page first, a reference count per page, every change undoable
+//   bd_attn_paged_kernel     bd_attn_kernel's work split over a slot's pages: the tiles' physical rows staged in LDS, then the shared
+//                            tile loop of attn_tiles.h with the tile's pointer taken from there
+//   bd_epi_qkv_paged[_h]     bd_epi_qkv[_h]_kernel with the store row taken through the table
+//   bd_page_copy / bd_to_pages / bd_from_pages      copy on write and the partial page of a share; llmk_batch_fork; llmk_cache_peek
+// The rows of a page behind its slot's position hold whatever the page's last owner left: no kernel reads them (the tile loop clamps
+// every row index to the row's last position).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstddef>
+#include <vector>
+
+#include "batch.h"
+
+namespace llmk {
+
+constexpr int PG_MIN_LEN = BD_TILE, PG_MAX_LEN = 256;
+
+// what the kernels know of the tables
+struct BdPages {
+    const int* table;      // [n_slots][width]
+    int width, page_len, n_pages;
+};
+// the physical cache row of position row + 1 of `slot`, -1 where the slot has no page there
+__device__ __forceinline__ int pg_row(const BdPages& pg, int slot, int row) {
+    const int e = pg.table[(size_t)slot * pg.width + row / pg.page_len];
+    return (unsigned)e < (unsigned)pg.n_pages ? e * pg.page_len + row % pg.page_len : -1;
+}
+
+// ---- the allocator (host, plain C++: nothing here touches the device)                                                  ------------
+// Deterministic: a fresh page is the lowest-numbered free one.  A page's count is the table entries that name it.  Every change of an
+// entry goes through set(), which keeps the counts and writes the undo log; undo() takes the tables and counts back to a mark, so a
+// call that runs out of pages leaves them exactly as it found them.
+struct PagePool {
+    struct Copy { int src, dst; };                 // page src is to be copied onto the fresh page dst (copy on write)
+    struct Change { int at, was, now; };
+    int page_len = 0, n_pages = 0, width = 0, n_free = 0;
+    std::vector<int> table, ref;                   // [n_slots][width], -1: none; [n_pages]
+    std::vector<Change> log;
+
+    void init(int n_slots, int seq_len, int page_len_, int n_pages_) {
+        page_len = page_len_; n_pages = n_free = n_pages_;
+        width = (seq_len + page_len - 1) / page_len;
+        table.assign((size_t)n_slots * width, -1);
+        ref.assign(n_pages, 0);
+        log.clear();
+    }
+    int* of(int slot) { return table.data() + (size_t)slot * width; }
+    int lowest_free() const {
+        for (int p = 0; p < n_pages; ++p)
+            if (ref[p] == 0) return p;
+        return -1;
+    }
+    void set(int at, int now) {
+        const int was = table[at];
+        if (was == now) return;
+        if (was >= 0 && --ref[was] == 0) ++n_free;
+        if (now >= 0 && ref[now]++ == 0) --n_free;
+        table[at] = now;
+        log.push_back(Change{at, was, now});
+    }
+    size_t mark() const { return log.size(); }
+    void undo(size_t to) {
+        while (log.size() > to) {
+            const Change c = log.back();
+            log.pop_back();
+            if (c.now >= 0 && --ref[c.now] == 0) ++n_free;
+            if (c.was >= 0 && ref[c.was]++ == 0) --n_free;
+            table[c.at] = c.was;
+        }
+    }
+    // Positions pos0 .. pos0+len-1 (1-based) of `slot` are about to be written: every page up to the last of them becomes present,
+    // and those the positions lie in exclusively owned -- a shared one is replaced by a fresh page and the copy is noted.  false: out
+    // of pages (the caller undoes).
+    bool ensure(int slot, int pos0, int len, std::vector<Copy>& copies) {
+        const int first = (pos0 - 1) / page_len, last = (pos0 + len - 2) / page_len;
+        for (int i = 0; i <= last; ++i) {
+            const int at = slot * width + i, was = table[at];
+            if (was >= 0 && (i < first || ref[was] == 1)) continue;
+            const int fresh = lowest_free();
+            if (fresh < 0) return false;
+            set(at, fresh);
+            if (was >= 0) copies.push_back(Copy{was, fresh});
+        }
+        return true;
+    }
+    // the slot keeps positions 1..n_keep: the pages wholly behind them go
+    void release(int slot, int n_keep) {
+        for (int i = (n_keep + page_len - 1) / page_len; i < width; ++i) set(slot * width + i, -1);
+    }
+    // mapped entries of a slot: always a run from entry 0 (ensure fills from there, release cuts a tail)
+    int count(int slot) const {
+        int n = 0;
+        while (n < width && table[(size_t)slot * width + n] >= 0) ++n;
+        return n;
+    }
+};
+
+// ---- decode attention through the table                                                                                ------------
+// bd_attn_kernel's work split: one workgroup per (kv head, row, part), bd_parts / bd_tiles_per_part, 8 waves round robin, the kv group's
+// query heads as the 16 columns, the part states and the fold of that kernel (stride BD_MAX_GROUP; parts == 1: normalised to `out`).
+// What is new is where a tile lies: logical tile kt of the row's slot starts at physical row table[slot][kt / tpg] * page_len +
+// (kt % tpg) * 16, tpg = page_len / 16.  The K/V loads would hang on a table load each; so the workgroup first stages the physical rows
+// of ITS tiles -- [t0, t1) and the NW look-ahead tiles behind them, clamped as the loop clamps -- in LDS behind the merge's block (the
+// merge of a fast wave must not overwrite what a slow one still reads), one global round trip next to the Q load, and the loop takes a
+// tile's pointer from an LDS word, the same for the whole wave.  The tile loop IS attn_tiles (the statements of bd_attn_kernel in that
+// order): a row's arithmetic does not depend on where its pages lie.  An entry out of range reads page n_pages - 1 (the host maps every
+// page of a row before a pass).  Dynamic LDS: pg_attn_smem.
+constexpr size_t pg_attn_smem(int hs, int seq_len) { return attn_smem(BD_WAVES, hs) + (size_t)((seq_len + BD_TILE - 1) / BD_TILE) * sizeof(int); }
+constexpr size_t PG_MAX_SMEM = 160 * 1024;      // a gfx950 workgroup's LDS: llmk_pages_create refuses a seq_len whose tiles do not fit behind the merge
+template <int HS, class T>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_paged_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                        const T* __restrict__ vc, float* __restrict__ out,
+                                                                        float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                        BdPages pg, int KV, int kv_mul, int E, int tpp) {
+    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
+    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
+    int* tile_row = reinterpret_cast<int*>(pf_smem + attn_smem(NW, HS));      // [tiles of seq_len], this workgroup's filled in
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, b = blockIdx.y, part = blockIdx.z, parts = gridDim.z, nkv = gridDim.x;
+    const BdRow row = bc.rows[b];
+    if (!bd_row_ok(bc, row)) return;                  // whole workgroup: no barrier is pending
+    const int nrows = row.pos;
+    const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
+    {
+        const int tpg = pg.page_len / BD_TILE;
+        const int* tab = pg.table + (size_t)row.slot * pg.width;
+        for (int t = min(t0, ntile - 1) + tid; t < min(t1 + NW, ntile); t += NW * WAVE) {
+            const unsigned e = min((unsigned)tab[t / tpg], (unsigned)(pg.n_pages - 1));
+            tile_row[t] = (int)e * pg.page_len + (t % tpg) * BD_TILE;
+        }
+    }
+    const int h = kvh * kv_mul + min(li, kv_mul - 1);
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)b * E + (size_t)h * HS + g * DG);
+    __syncthreads();
+    float m_run, l_run;
+    pf_v4f O[NT];
+    attn_tiles<HS, T, NW>(qf, kc + (size_t)kvh * HS + g * DG, vc + (size_t)kvh * HS + NT * li, KV, nrows - 1, ntile, t0, t1, wid, li, g,
+                          [&](int r) { return r < nrows; }, m_run, l_run, O,
+                          [&](const T* p, int tile) { return p + (ptrdiff_t)(tile_row[tile] - tile * BD_TILE) * KV; });
+    const size_t pbase = ((size_t)b * nkv + kvh) * parts + part;
+    attn_merge_waves<HS, NW>(m_run, l_run, O, kv_mul, [&](int q, int d, float M, float L, float val) {
+        if (parts == 1) {
+            out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+        } else {
+            po[(pbase * BD_MAX_GROUP + q) * HS + d] = val;
+            if (d == 0) pml[pbase * BD_MAX_GROUP + q] = make_float2(M, L);
+        }
+    });
+}
+
+// ---- the QKV epilogues through the table                                                                               ------------
+// bd_epi_qkv[_h]_kernel: rotated at the row's position, stored at the physical row of that position -- pf_epi_qkv_pair[_h] store at cache
+// row a.pos0 + t - 1, so they are handed the layer's pool moved on by (physical row - logical row) rows, as the tree epilogues are
+// (batch.h), with their arithmetic untouched.  A row without a page there is not written (the host maps it before the pass).
+__global__ void bd_epi_qkv_paged_kernel(PfEpiArgs a, BdCaches bc, BdPages pg) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    if (p4 >= a.rows / 4) return;
+    const BdRow r = bc.rows[t];
+    if (!bd_row_ok(bc, r)) return;
+    const int at = pg_row(pg, r.slot, r.pos - 1);
+    if (at < 0) return;
+    const float4 s4 = pf_sum4(a, t, 4 * p4);
+    a.pos0 = r.pos - t;
+    a.kc += (ptrdiff_t)(at - (r.pos - 1)) * a.KV;
+    a.vc += (ptrdiff_t)(at - (r.pos - 1)) * a.KV;
+    pf_epi_qkv_pair(a, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
+    pf_epi_qkv_pair(a, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
+}
+__global__ void bd_epi_qkv_paged_h_kernel(PfEpiArgs a, BdCaches bc, BdPages pg, _Float16* __restrict__ kc, _Float16* __restrict__ vc) {
+    const int p4 = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    pf_low_check(a, blockIdx.x == 0 && blockIdx.y == 0);
+    if (p4 >= a.rows / 4) return;
+    const BdRow r = bc.rows[t];
+    if (!bd_row_ok(bc, r)) return;
+    const int at = pg_row(pg, r.slot, r.pos - 1);
+    if (at < 0) return;
+    const float4 s4 = pf_sum4(a, t, 4 * p4);
+    a.pos0 = r.pos - t;
+    kc += (ptrdiff_t)(at - (r.pos - 1)) * a.KV;
+    vc += (ptrdiff_t)(at - (r.pos - 1)) * a.KV;
+    pf_epi_qkv_pair_h(a, kc, vc, t, 4 * p4, s4.x / a.xn[t], s4.y / a.xn[t]);
+    pf_epi_qkv_pair_h(a, kc, vc, t, 4 * p4 + 2, s4.z / a.xn[t], s4.w / a.xn[t]);
+}
+
+// ---- copies                                                                                                            ------------
+// The first n 16-byte words of page src onto page dst in every layer (blockIdx.y) of K (blockIdx.z 0) and V (1), bit for bit: a whole
+// page for copy on write, the rows in use for the partial page of llmk_pages_share.  k / v: the pools as 16-byte words, `layer` and
+// `page` of them per layer and per page.
+__global__ void bd_page_copy_kernel(uint4* __restrict__ k, uint4* __restrict__ v, size_t layer, size_t page, int src, int dst, size_t n) {
+    uint4* p = (blockIdx.z ? v : k) + blockIdx.y * layer;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[dst * page + i] = p[src * page + i];
+}
+
+// four elements on their way into a pool: f32 as they are, f16 by the stored-value rule (pf_kv_half, as bd_to_half_kernel)
+__device__ __forceinline__ void pg_store4(float* dst, const float4& x) { *reinterpret_cast<float4*>(dst) = x; }
+__device__ __forceinline__ void pg_store4(_Float16* dst, const float4& x) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    *reinterpret_cast<h4*>(dst) = (h4){pf_kv_half(x.x), pf_kv_half(x.y), pf_kv_half(x.z), pf_kv_half(x.w)};
+}
+// llmk_batch_fork: rows 0 .. n / KV - 1 of the context's f32 caches (layers src_layer elements apart) into the pages of `slot`, every
+// layer and K (blockIdx.z 0) and V (1); n elements, a multiple of KV, KV a multiple of 4
+template <class T>
+__global__ void bd_to_pages_kernel(const float* __restrict__ sk, const float* __restrict__ sv, T* __restrict__ dk, T* __restrict__ dv,
+                                   BdPages pg, int slot, size_t n, int KV, size_t src_layer, size_t dst_layer) {
+    const float* src = (blockIdx.z ? sv : sk) + blockIdx.y * src_layer;
+    T* dst = (blockIdx.z ? dv : dk) + blockIdx.y * dst_layer;
+    for (size_t i = 4 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x); i < n; i += 4 * (size_t)gridDim.x * blockDim.x) {
+        const int at = pg_row(pg, slot, (int)(i / KV));
+        if (at >= 0) pg_store4(dst + (size_t)at * KV + i % KV, *reinterpret_cast<const float4*>(src + i));
+    }
+}
+// llmk_cache_peek: n elements (whole rows) of `slot` from cache row row0 on, out of one layer's pool `src` into the block `dst`, as
+// they are stored; a position without a page reads +0.0, as in a fresh slot of a dense batch
+template <class T>
+__global__ void bd_from_pages_kernel(const T* __restrict__ src, T* __restrict__ dst, BdPages pg, int slot, int row0, size_t n, int KV) {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    for (size_t i = 4 * ((size_t)blockIdx.x * blockDim.x + threadIdx.x); i < n; i += 4 * (size_t)gridDim.x * blockDim.x) {
+        const int at = pg_row(pg, slot, row0 + (int)(i / KV));
+        *reinterpret_cast<t4*>(dst + i) = at >= 0 ? *reinterpret_cast<const t4*>(src + (size_t)at * KV + i % KV) : (t4){0, 0, 0, 0};
+    }
+}
+
+}  // namespace llmk

@@ -421,6 +421,34 @@ module llmk_binding
        integer(c_int), value :: slot
        type(c_ptr), value :: ad
      end function
+     ! pages (include/llmk.h): a batch whose slots share one pool of pages; the handle is a batch's.  llmk_pages_free and
+     ! llmk_pages_table answer a count, or a negative LLMK_E_* code; pages_out may be c_null_ptr with cap = 0
+     integer(c_int) function llmk_pages_create(ctx, n_slots, seq_len, kv_type, page_len, n_pages, batch) bind(C, name="llmk_pages_create")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: n_slots, seq_len, kv_type, page_len, n_pages
+       type(c_ptr), intent(out) :: batch
+     end function
+     integer(c_int) function llmk_pages_release(batch, slot, n_keep) bind(C, name="llmk_pages_release")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot, n_keep
+     end function
+     integer(c_int) function llmk_pages_share(batch, dst_slot, src_slot, n_pos) bind(C, name="llmk_pages_share")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: dst_slot, src_slot, n_pos
+     end function
+     integer(c_int) function llmk_pages_free(batch) bind(C, name="llmk_pages_free")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+     end function
+     integer(c_int) function llmk_pages_table(batch, slot, pages_out, cap) bind(C, name="llmk_pages_table")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: slot, cap
+       type(c_ptr), value :: pages_out
+     end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
      ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too

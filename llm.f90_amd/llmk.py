@@ -32,7 +32,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_rows_sample_logits", "llmk_prefix_set", "llmk_prefix_attach", "llmk_prefix_len",
            "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_span_forward", "llmk_span_time",
            "llmk_tree_forward", "llmk_tree_accept", "llmk_tree_time",
-           "llmk_lora_create", "llmk_lora_upload", "llmk_lora_destroy", "llmk_lora_assign", "llmk_reset", "llmk_timings",
+           "llmk_lora_create", "llmk_lora_upload", "llmk_lora_destroy", "llmk_lora_assign",
+           "llmk_pages_create", "llmk_pages_release", "llmk_pages_share", "llmk_pages_free", "llmk_pages_table", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -220,6 +221,12 @@ def lib():
             L.llmk_lora_upload.argtypes = [vp, ci, ci, ci, ci, vp, vp, ci]
             L.llmk_lora_destroy.argtypes = [vp]
             L.llmk_lora_assign.argtypes = [vp, ci, vp]
+        if hasattr(L, "llmk_pages_create"):
+            L.llmk_pages_create.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(vp)]
+            L.llmk_pages_release.argtypes = [vp, ci, ci]
+            L.llmk_pages_share.argtypes = [vp, ci, ci, ci]
+            L.llmk_pages_free.argtypes = [vp]
+            L.llmk_pages_table.argtypes = [vp, ci, C.POINTER(ci), ci]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -679,12 +686,23 @@ class Batch:
     rounded to nearest even and saturated at +-65504 (include/llmk.h); "f32" is llmk_batch_create, as before.  "q8_0": ggml's q8_0
     blocks, 17/64 of the f32 bytes -- about 25 times coarser than f16 (the logits move by about 1e-2 of max |logit| on the test
     models: include/llmk.h), the caller's opt-in and never a default; kv_dim must be a multiple of 32.  An int is passed through as
-    the LLMK_TYPE_* id it is."""
+    the LLMK_TYPE_* id it is.
+    page_len and n_pages (both or neither): the slots share one pool of n_pages pages of page_len positions each (llmk_pages_create;
+    "f32" or "f16") -- memory follows the positions in use, share() maps a stem's pages into another slot, release() gives pages back.
+    set_prefix / attach, accept and a forward_tree that is not a chain are refused on such a batch."""
 
-    def __init__(self, model: Llmk, n_slots: int, seq_len: int | None = None, kv_type="f32"):
+    def __init__(self, model: Llmk, n_slots: int, seq_len: int | None = None, kv_type="f32", page_len: int | None = None,
+                 n_pages: int | None = None):
         self.model, self.n_slots, self.V = model, n_slots, model.V
         self._h = C.c_void_p()
-        if kv_type == "f32":
+        if page_len is not None or n_pages is not None:
+            if page_len is None or n_pages is None:
+                raise ValueError("a paged batch takes page_len and n_pages")
+            if isinstance(kv_type, str) and kv_type not in KV_CACHE_TYPES:
+                raise ValueError(f"kv_type {kv_type!r}: one of {sorted(KV_CACHE_TYPES)}")
+            _ck(lib().llmk_pages_create(model._h, n_slots, seq_len or model.shape.seq_len, KV_CACHE_TYPES.get(kv_type, kv_type), page_len, n_pages,
+                                        C.byref(self._h)))
+        elif kv_type == "f32":
             _ck(lib().llmk_batch_create(model._h, n_slots, seq_len or model.shape.seq_len, C.byref(self._h)))
         else:
             if isinstance(kv_type, str) and kv_type not in KV_CACHE_TYPES:
@@ -711,6 +729,31 @@ class Batch:
         out = np.empty((max(n, 0), self.model.shape.kv_dim), np.float32)
         _ck(lib().llmk_cache_peek(self._h, which, layer, slot, pos0, n, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def release(self, slot: int, n_keep: int = 0):
+        """a paged batch: `slot` keeps positions 1..n_keep, the pages wholly behind them go back to the pool (llmk_pages_release)"""
+        _ck(lib().llmk_pages_release(self._h, slot, n_keep))
+
+    def share(self, dst_slot: int, src_slot: int, n_pos: int):
+        """a paged batch: dst_slot becomes src_slot's positions 1..n_pos -- full pages by reference, the last partial page as a copy
+        (llmk_pages_share); the first write into a shared page copies it"""
+        _ck(lib().llmk_pages_share(self._h, dst_slot, src_slot, n_pos))
+
+    def free_pages(self) -> int:
+        """a paged batch: the pages free right now (llmk_pages_free)"""
+        n = lib().llmk_pages_free(self._h)
+        if n < 0:
+            _ck(-n)
+        return n
+
+    def page_table(self, slot: int) -> list:
+        """verification hook of a paged batch: the slot's physical pages in table order (llmk_pages_table)"""
+        n = lib().llmk_pages_table(self._h, slot, None, 0)
+        if n < 0:
+            _ck(-n)
+        out = (C.c_int * max(n, 1))()
+        lib().llmk_pages_table(self._h, slot, out, n)
+        return list(out[:n])
 
     @staticmethod
     def _rows(slots, tokens, pos):

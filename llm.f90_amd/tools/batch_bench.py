@@ -282,6 +282,71 @@ def kv_types(m, shape, kinds, P: int, pos: int, iters: int, repeats: int):
     return out
 
 
+PAGED_ROWS = (8, 128)
+
+
+def paged(m, shape, page_len: int, pos: int, iters: int, repeats: int):
+    """--paged LEN: llmk_batch_time at PAGED_ROWS rows at positions 25 and `pos` on a dense batch and on a paged batch of page_len LEN
+    (llmk_pages_create, a pool of exactly the pages the rows need), f32 and f16, both alive together and alternating `repeats` times,
+    each measurement behind a warm-up of the same batch.  Then, on the paged batch, the wall clock of n - 1 llmk_pages_share calls
+    from slot 0 against n - 1 llmk_batch_fork calls of the same positions."""
+    positions = [q for q in (SAMPLED_POS, pos) if q <= shape.seq_len]
+    m.reset()
+    m.prefill([2] + [3 + i % (shape.vocab_size - 3) for i in range(max(positions) - 2)], 1)
+    out = []
+    for kind in ("f32", "f16"):
+        for q in positions:
+            slots, pair = max(PAGED_ROWS), None
+            while pair is None:
+                made = []
+                try:
+                    made.append(llmk.Batch(m, slots, q, kv_type=kind))
+                    made.append(llmk.Batch(m, slots, q, kv_type=kind, page_len=page_len, n_pages=slots * -(-q // page_len)))
+                    pair = made
+                except llmk.LlmkError as e:
+                    for b in made:
+                        b.close()
+                    if slots == 1:
+                        raise
+                    print(f"# {kind} pos {q}: no room for {slots} slots dense + paged ({e}); trying {slots // 2}", file=sys.stderr)
+                    slots //= 2
+            forms = dict(zip(("dense", "paged"), pair))
+            for n in PAGED_ROWS:
+                if n > slots:
+                    continue
+                ms = {form: [] for form in forms}
+                for _ in range(repeats):
+                    for form, b in forms.items():
+                        b.time(n, q, 3)                              # warm-up of this batch
+                        ms[form].append(b.time(n, q, iters))
+                row = {"kv": kind, "n": n, "pos": q, "page_len": page_len, "bytes": {form: b.cache_bytes() for form, b in forms.items()}}
+                for form, xs in ms.items():
+                    row[form + "_ms"], row[form + "_spread"] = med_spread(xs)
+                for call, what in (("share", lambda j: pair[1].share(j, 0, q - 1)), ("fork", lambda j: pair[1].fork(j, q - 1))):
+                    xs = []
+                    for _ in range(repeats):
+                        t0 = time.perf_counter()
+                        for j in range(1, n):
+                            what(j)
+                        xs.append((time.perf_counter() - t0) * 1e3)
+                    row[call + "_ms"], row[call + "_spread"] = med_spread(xs)
+                out.append(row)
+            for b in pair:
+                b.close()
+    return out
+
+
+def print_paged(shape_name, type_name, rows, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# batched decode, dense | paged K/V caches, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per form, the forms "
+          f"alternating in one process (spread = (max - min) / median); share | fork: wall clock of n - 1 calls on the paged batch, pos - 1 positions")
+    print(f"{'kv':>4} {'n':>5} {'pos':>6} {'page':>5} {'dense ms':>10} {'spread':>7} {'paged ms':>10} {'spread':>7} {'paged / dense':>14} {'share ms':>10} {'fork ms':>10} "
+          f"{'dense MB':>10} {'pool MB':>10}")
+    for r in rows:
+        print(f"{r['kv']:>4} {r['n']:5d} {r['pos']:6d} {r['page_len']:5d} {r['dense_ms']:10.3f} {r['dense_spread']:7.3f} {r['paged_ms']:10.3f} {r['paged_spread']:7.3f} "
+              f"{r['paged_ms'] / r['dense_ms']:14.3f} {r['share_ms']:10.3f} {r['fork_ms']:10.3f} {r['bytes']['dense'] / 1e6:10.1f} {r['bytes']['paged'] / 1e6:10.1f}")
+
+
 def spans(m, shape, pos: int, iters: int, repeats: int):
     """--spans: the three measurements of profiles/batch_spans.txt, every figure the median of `repeats` behind a warm-up"""
     out = {"a": [], "b": {}, "c": {}}
@@ -504,10 +569,20 @@ def main():
                     help="only the adapter table (llmk_lora_*): the pass at 8, 32 and 128 rows at position 25 with no adapter and with every "
                          "row on one of ADAPTERS adapters of rank RANK (default 1; 0: one per row); another build selected with LLMK_LIB "
                          "that has no llmk_lora_* measures the first alone")
+    ap.add_argument("--paged", type=int, default=0, metavar="LEN",
+                    help="only the paged table (llmk_pages_*): the pass at 8 and 128 rows at positions 25 and --pos on a dense and on a paged "
+                         "batch of page_len LEN, f32 and f16, alternating in one process; llmk_pages_share against llmk_batch_fork")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
     m, shape = build(a.shape, a.type, a.cls_q6k)
+    if a.paged:
+        rows = paged(m, shape, a.paged, a.pos, a.iters, a.repeats)
+        m.close()
+        print_paged(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "paged": rows}))
+        return
     if a.lora:
         rows = lora(m, shape, a.lora, a.iters, a.repeats)
         m.close()
