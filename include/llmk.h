@@ -709,12 +709,49 @@ int llmk_lora_assign(llmk_batch *b, int slot, llmk_lora *ad);
  * that is not a chain and llmk_tree_accept are LLMK_E_ARG before anything runs.  A pass's arithmetic does not depend on where a slot's
  * pages lie: the same sequence gives the same bits on any table.  llmk_pages_* on a batch of llmk_batch_create / llmk_cache_create, or
  * on NULL: LLMK_E_ARG (llmk_pages_free, llmk_pages_table: -LLMK_E_ARG).
- * Out of scope: q8_0 pages; the prefix, span and tree column-group kernels over pages; swapping pages to the host; any scheduler. */
+ * Out of scope: q8_0 pages; the span and tree column-group kernels over pages (shared stems: llmk_stems_*, below); swapping pages to the host; any scheduler. */
 int llmk_pages_create(llmk_ctx *ctx, int n_slots, int seq_len, int kv_type, int page_len, int n_pages, llmk_batch **out);
 int llmk_pages_release(llmk_batch *b, int slot, int n_keep);
 int llmk_pages_share(llmk_batch *b, int dst_slot, int src_slot, int n_pos);
 int llmk_pages_free(llmk_batch *b);    /* free pages now; negative LLMK_E_* on error */
 int llmk_pages_table(llmk_batch *b, int slot, int *pages_out, int cap);
+
+/* Stems: an opt-in of a paged batch.  Rows of a pass whose slots name the same physical pages at the head of
+ * their tables -- N completions of a prompt, a tree of stems -- read those pages ONCE per group instead of once per row, with (row,
+ * query head) pairs as the matrix instruction's columns, the way llmk_prefix_* reads a dense batch's one prefix; each row's remaining
+ * pages go through a paged form of the own-rows kernel and the existing fold joins the two.  Any number of stems in one pass, a stem
+ * length per group.  ("stems": the llmk_pages_*, llmk_batch_* and llmk_cache_* lists are closed.)
+ *
+ * enable:  on 0 or 1, else LLMK_E_ARG; NULL or a batch not made by llmk_pages_create: LLMK_E_ARG.  Off is the default, and with it off
+ *          (or never called) the batch allocates and enqueues exactly what it did and returns the same bits.  What only stem reads need
+ *          is allocated by the first pass that has a group, behind copy on write: should that allocation fail (LLMK_E_NOMEM, or a HIP
+ *          code), nothing of the pass has been launched and the tables stand as prepared -- the pages the pass would have written are
+ *          present and owned, the sequences' rows are what they were.
+ * The rule, with RG = max(1, 16 / (n_heads / n_kv_heads)) rows per group: for row i, cand(i) = (pos[i] - 1) / page_len table entries
+ * lie wholly in front of the page the row writes; common(i, j) = the leading entries equal in both slots' tables, at most
+ * min(cand(i), cand(j)).  Rows are walked in row order; an unassigned row i leads; G = max common(i, j) over the later unassigned rows;
+ * G == 0: ungrouped; else the members are i and, in row order, the later unassigned rows with common(i, j) >= (G + 1) / 2, up to RG rows
+ * in all, and the group's stem is the minimum of common(i, j) over them, in pages.  Rows left over when a group is full lead in their
+ * turn.  A stem is whole pages that every member sees entirely.  Grouping runs after copy on write, in llmk_batch_forward, llmk_batch_time
+ * and once for all steps of llmk_batch_decode / llmk_rows_decode; a pass in which no group forms is the pass with stem reads off, bit
+ * for bit.  llmk_span_forward, llmk_span_time and chain trees with more than one position per slot are not grouped.
+ * plan:    verification hook, host only: what a pass of rows slots[i] at pos[i] (llmk_batch_forward's checks, else LLMK_E_ARG) would do
+ *          on the tables as they are, whether or not stem reads are on.  group_out[i]: the row's group, numbered in the order the
+ *          leaders appear, -1 for a row in no group of two or more; stem_out[i]: the positions the stem kernel reads for it, a multiple of
+ *          page_len, 0 for an ungrouped row.  A pending copy on write does not change the answer: a stem ends in front of the page
+ *          pos[i] lies in.
+ * Deterministic: no float atomics, a fixed part order; the same call on the same state gives the same bits.  A grouped row's logits are
+ * within the 1e-4 bar of llmk_forward on its sequence alone and of the same pass with stem reads off, NOT bit-identical to either (its
+ * positions are summed in another split).  The sentence above -- a pass's arithmetic does not depend on where a slot's pages lie --
+ * holds unchanged with stem reads off; with them on it holds for any relabelling of physical pages that keeps the sharing pattern.
+ * Where it loses: a group costs one more launch per layer and a fold; behind a short stem (one shared page: +4 to +7 % per pass on
+ * Llama-2-7B) and on models with many query heads per kv head (TinyLlama: 2 rows per group, slower at every point measured) that is
+ * more than the reads it saves -- which is why it is an opt-in.  Behind a long stem with one query head per kv head it halves the
+ * pass at 128 rows.
+ * Out of scope: grouping inside span or tree passes; q8_0 pools; regrouping inside a decode; reordering rows to make longer stems; any
+ * automatic enable. */
+int llmk_stems_enable(llmk_batch *b, int on);
+int llmk_stems_plan(llmk_batch *b, int n, const int *slots, const int *pos, int *group_out, int *stem_out);
 
 /* Zero the KV cache (new sequence), as llama2.f90:316-318; the token record of the penalties, if the context has one, is zeroed too. */
 int llmk_reset(llmk_ctx *ctx);

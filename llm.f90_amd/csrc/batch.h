@@ -28,6 +28,7 @@ constexpr int BD_TILE = 16;          // cache rows per MFMA tile (the A operand'
 constexpr int BD_WAVES = 8;          // waves of an attention workgroup: tiles of a part go round robin
 constexpr int BD_MAX_PARTS = 8;      // workgroups a row's timesteps are split over, at most
 constexpr int BD_MAX_GROUP = 16;     // query heads per kv head, at most (the B operand's 16 columns)
+constexpr int BD_PART_STATES = 2 * BD_MAX_PARTS;      // part states per (row, kv head) of a folded pass: shared parts in front, own parts behind
 
 // The split rule.  A pass has n * n_kv_heads (row, kv head) pairs; with fewer of them than CUs a row's tiles are split over `parts`
 // workgroups, as long as every part still has a tile for each of its waves.  tiles per part (tpp) is ONE value for the pass, from its

@@ -328,6 +328,19 @@ struct llmk_batch {
         std::vector<PagePool::Copy> copies;      // the copies on write of the call in hand
         BdStore peek;                            // llmk_cache_peek's gathered rows (k alone), grown by reserve
         BdPages view() const { return BdPages{d_table, pool.width, pool.page_len, pool.n_pages}; }
+        // stem reads (llmk_stems_*, paged.h), built by the first pass that has a group: a batch that never has one has none of it
+        struct Stems {
+            DevBuf<BdStem> d_stems;              // [LLMK_MAX_BATCH / 2] the pass's groups: bd_attn_stem_kernel's column map ...
+            PinnedBuf<BdStem> h_stems;           // ... and the pinned words it is copied from
+            DevBuf<int> d_first;                 // [n_slots] a row's stem in rows by its slot, 0: in no group ...
+            PinnedBuf<int> h_first;              // ... likewise
+            // the part states of such a pass (a paged batch has no other use for them: no prefix, no column groups):
+            DevBuf<float2> d_ml;                 // [LLMK_MAX_BATCH][n_kv_heads][2 * BD_MAX_PARTS][kv_mul] {M, L} ...
+            DevBuf<float> d_o;                   // ... and that [hs] unnormalised outputs
+        };
+        std::unique_ptr<Stems> sr;
+        bool stems_on = false;                   // llmk_stems_enable
+        int pass_stems = 0, pass_stem_tiles = 0; // groups of the rows pg_stems grouped last (0: the pass is PAGED), the longest stem's tiles
     };
     std::unique_ptr<Pages> pg;
 };
@@ -1798,8 +1811,10 @@ static int pg_prepare(llmk_batch* b, int n, const int* slots, const int* pos, in
 //   PAGED a pass of a paged batch (llmk_pages_*): ROW's split, states and fold with bd_attn_paged_kernel in bd_attn_kernel's place --
 //         span passes too (such a batch has no shared prefix, no column groups and no trees).
 // OWN, SPAN and TREE leave np = pparts + parts states per (row, kv head) in the batch's PartStates (stride kv_mul): the prefix parts first.
+//   STEMS a pass of a paged batch in which stem reads formed a group (llmk_stems_*, pass_stems > 0): OWN's structure over pages --
+//         bd_attn_stem_kernel over the groups, bd_attn_paged_own_kernel from row `first` on, always folded.
 struct BdAttnPlan {
-    enum Kind { ROW, OWN, SPAN, TREE, PAGED } kind;
+    enum Kind { ROW, OWN, SPAN, TREE, PAGED, STEMS } kind;
     bool per_row;                   // ROW or PAGED: one workgroup per (kv head, row, part), states in d_po / d_pml
     bool grouped;                   // SPAN or TREE: the rows' kernel runs over column groups
     bool shared, fold;              // attached rows in the pass: the prefix kernel runs; the fold kernel runs
@@ -1816,7 +1831,7 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
     const llmk_ctx* c = b->ctx;
     BdAttnPlan p{};
     p.shared = b->pass_att > 0;
-    p.kind = b->pg ? BdAttnPlan::PAGED : b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
+    p.kind = b->pg ? (b->pg->pass_stems > 0 ? BdAttnPlan::STEMS : BdAttnPlan::PAGED) : b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
     p.per_row = p.kind == BdAttnPlan::ROW || p.kind == BdAttnPlan::PAGED;
     p.grouped = p.kind == BdAttnPlan::SPAN || p.kind == BdAttnPlan::TREE;
     p.units = p.grouped ? b->pass_groups : n;
@@ -1832,13 +1847,27 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
         p.ptpp = bd_tiles_per_part(b->P, p.pparts);
         p.first = b->px->d_first;
     }
+    if (p.kind == BdAttnPlan::STEMS) {
+        // the same with the groups of the pass in the place of the column groups and the longest stem in the place of P
+        const llmk_batch::Pages& pg = *b->pg;
+        own = 0;
+        for (int i = 0; i < n; ++i)
+            own = std::max(own, (b->h_rows[i].pos + step + BD_TILE - 1) / BD_TILE - pg.sr->h_first[b->h_rows[i].slot] / BD_TILE);
+        p.groups = pg.pass_stems;
+        p.pparts = bd_parts(p.groups, c->nkv, pg.pass_stem_tiles * BD_TILE, c->n_cu);
+        p.ptpp = bd_tiles_per_part(pg.pass_stem_tiles * BD_TILE, p.pparts);
+        p.first = pg.sr->d_first;
+    }
     p.parts = bd_parts(p.units, c->nkv, own * BD_TILE, c->n_cu);
     p.tpp = bd_tiles_per_part(own * BD_TILE, p.parts);
     p.np = p.pparts + p.parts;
+    static_assert(BD_PART_STATES == 2 * BD_MAX_PARTS, "np <= BD_PART_STATES: both part-state blocks (bd_part_states, Pages::Stems) hold that many per (row, kv head)");
     p.direct = p.grouped && !p.shared && p.parts == 1;
     p.fold = p.per_row ? p.parts > 1 : !p.direct;
     if (p.per_row) {
         p.po = b->d_po; p.pml = b->d_pml; p.stride = BD_MAX_GROUP;
+    } else if (p.kind == BdAttnPlan::STEMS) {
+        p.po = b->pg->sr->d_o; p.pml = b->pg->sr->d_ml; p.stride = c->kv_mul;
     } else {
         p.po = b->ps->d_o; p.pml = b->ps->d_ml; p.stride = c->kv_mul;
     }
@@ -1860,7 +1889,7 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
     HIPRET(pf_layers(c, w, b->d_tok, T, 0, (const float*)c->t[LLMK_RMS_FINAL_WEIGHT].data, e, b->lo && b->lo->groups > 0 ? b->lo.get() : nullptr,
                      [&](int l, PfEpiArgs& a) -> hipError_t {
         const auto kc = bd_cache_view<TC>(b, b->cache.k, l, 0, 0), vc = bd_cache_view<TC>(b, b->cache.v, l, 0, 0);
-        if (p.kind == BdAttnPlan::PAGED) {
+        if (b->pg) {
             if constexpr (BdKv<TC>::pageable) HIPRET(BdKv<TC>::epi_qkv_paged(a, bc, b->pg->view(), kc, vc, QKV, T, w.stream));
         } else {
             HIPRET(BdKv<TC>::epi_qkv(a, bc, kc, vc, p.kind == BdAttnPlan::TREE ? b->tr->args().rope_pos : nullptr, QKV, T, w.stream));
@@ -1895,6 +1924,16 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
                     if constexpr (BdKv<TC>::pageable)
                         hipLaunchKernelGGL((bd_attn_paged_kernel<HS, TC>), grid, block, pg_attn_smem(HS, b->seq_len), w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc,
                                            b->pg->view(), KV, c->kv_mul, E, p.tpp);
+                    break;
+                case BdAttnPlan::STEMS:
+                    if constexpr (BdKv<TC>::pageable) {
+                        const size_t pg_smem = pg_attn_smem(HS, b->seq_len);
+                        hipLaunchKernelGGL((bd_attn_stem_kernel<HS, TC>), dim3(c->nkv, p.groups, p.pparts), block, pg_smem, w.stream, w.Q, kc, vc, p.po, p.pml, bc,
+                                           b->pg->sr->d_stems, b->pg->view(), T, KV, c->kv_mul, E, p.ptpp, p.np);
+                        HIPRET(hipGetLastError());
+                        hipLaunchKernelGGL((bd_attn_paged_own_kernel<HS, TC>), grid, block, pg_smem, w.stream, w.Q, kc, vc, p.po, p.pml, bc, b->pg->view(), p.first,
+                                           KV, c->kv_mul, E, p.tpp, p.np, p.pparts);
+                    }
                     break;
             }
             HIPRET(hipGetLastError());
@@ -1985,7 +2024,7 @@ static int bd_time(llmk_batch* b, int n, int max_pos, int iters, const ScPlan& s
 
 extern "C" {
 
-int llmk_version(void) { return 411; }
+int llmk_version(void) { return 412; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -3190,6 +3229,7 @@ static hipError_t bd_upload_rows(llmk_batch* b, int n, const int* slots, const i
     b->pass_att = 0;
     b->pass_groups = 0;
     b->pass_tree = false;
+    if (b->pg) b->pg->pass_stems = 0;      // (pg_stems groups the rows of the passes that are grouped)
     if (b->n_attached > 0) {
         // the column map: the attached rows in row order, -1 up to the end of the last column group
         for (int i = 0; i < n; ++i)
@@ -3577,6 +3617,77 @@ static hipError_t bd_part_states(llmk_batch* b) {
     return hipSuccess;
 }
 
+// ---- stem reads (paged.h): the rows of a pass that name the same pages at the head of their tables read them once per group ----
+// Behind pg_prepare (copy on write has replaced what the pass writes) and bd_upload_rows: the uploaded rows grouped by the rule of
+// pg_stem_groups, the groups and the slots' first own rows ENQUEUED the way the rows went up.  Stem reads off, a dense batch or no group:
+// nothing is allocated or enqueued and the pass is the PAGED one.  A decode groups once: its tables do not change, later steps only
+// lengthen the rows' own ranges.
+static int pg_stems(llmk_batch* b, int n, const int* slots, const int* pos) {
+    if (!b->pg || !b->pg->stems_on) return LLMK_OK;
+    llmk_batch::Pages& pg = *b->pg;
+    llmk_ctx* c = b->ctx;
+    int group[LLMK_MAX_BATCH], stem[LLMK_MAX_BATCH];
+    const int ng = pg_stem_groups(pg.pool, bd_prefix_rg(c->kv_mul), n, slots, pos, group, stem);
+    if (ng == 0) return LLMK_OK;
+    if (!pg.sr) {
+        auto sr = std::make_unique<llmk_batch::Pages::Stems>();
+        HIPCHK(sr->d_stems.alloc(LLMK_MAX_BATCH / 2));
+        HIPCHK(sr->h_stems.alloc(LLMK_MAX_BATCH / 2));
+        HIPCHK(sr->d_first.alloc((size_t)b->n_slots));
+        HIPCHK(sr->h_first.alloc((size_t)b->n_slots));
+        const size_t heads = (size_t)LLMK_MAX_BATCH * c->nkv * c->kv_mul;      // (row, query head) pairs; BD_PART_STATES states each
+        int rc = bd_alloc_rc(sr->d_ml.alloc(heads * BD_PART_STATES));
+        if (rc == LLMK_OK) rc = bd_alloc_rc(sr->d_o.alloc(heads * BD_PART_STATES * c->hs));
+        if (rc) return rc;
+        HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
+            constexpr int HS = decltype(hs)::value;
+            return with_kv_type(b, [&](auto t) -> hipError_t {
+                using TC = decltype(t);
+                if constexpr (BdKv<TC>::pageable) {
+                    const int smem = (int)pg_attn_smem(HS, b->seq_len);
+                    HIPRET(hipFuncSetAttribute((const void*)bd_attn_stem_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+                    return hipFuncSetAttribute((const void*)bd_attn_paged_own_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+                }
+                return hipErrorNotSupported;
+            });
+        }));
+        pg.sr = std::move(sr);
+    }
+    memset(pg.sr->h_first, 0, (size_t)b->n_slots * sizeof(int));
+    pg.pass_stem_tiles = 0;
+    for (int i = 0, seen = 0; i < n; ++i) {
+        if (group[i] < 0) continue;
+        BdStem& st = pg.sr->h_stems[group[i]];
+        if (group[i] == seen) {      // a leader: groups are numbered in the order their leaders appear
+            st.slot = slots[i];
+            st.tiles = stem[i] / BD_TILE;
+            for (int& col : st.col) col = -1;
+            pg.pass_stem_tiles = std::max(pg.pass_stem_tiles, st.tiles);
+            ++seen;
+        }
+        int k = 0;
+        while (st.col[k] >= 0) ++k;
+        st.col[k] = i;
+        pg.sr->h_first[slots[i]] = stem[i];
+    }
+    pg.pass_stems = ng;
+    HIPCHK(hipMemcpyAsync(pg.sr->d_stems, pg.sr->h_stems, (size_t)ng * sizeof(BdStem), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(pg.sr->d_first, pg.sr->h_first, (size_t)b->n_slots * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return LLMK_OK;
+}
+
+int llmk_stems_enable(llmk_batch* b, int on) {
+    if (!b || !b->pg || (on != 0 && on != 1)) return LLMK_E_ARG;
+    b->pg->stems_on = on == 1;
+    return LLMK_OK;
+}
+
+int llmk_stems_plan(llmk_batch* b, int n, const int* slots, const int* pos, int* group_out, int* stem_out) {
+    if (!b || !b->pg || !group_out || !stem_out || !bd_rows_ok(b, n, slots, nullptr, pos, 1, false)) return LLMK_E_ARG;
+    pg_stem_groups(b->pg->pool, bd_prefix_rg(b->ctx->kv_mul), n, slots, pos, group_out, stem_out);
+    return LLMK_OK;
+}
+
 // ---- a shared prefix (batch.h): one copy of the K/V rows of positions 1..P, the slots attached to it keep their own rows behind it ----
 int llmk_prefix_set(llmk_batch* b, int n_pos) {
     if (!b || b->pg || n_pos < 0 || n_pos > std::min(b->seq_len, b->ctx->S) - 1) return LLMK_E_ARG;      // (a paged batch shares pages: llmk_pages_share)
@@ -3654,6 +3765,7 @@ int llmk_batch_forward(llmk_batch* b, int n, const int* slots, const int* tokens
     if (rc) return rc;
     if ((rc = pg_prepare(b, n, slots, pos, 1)) != LLMK_OK) return rc;
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos));
+    if ((rc = pg_stems(b, n, slots, pos)) != LLMK_OK) return rc;
     const int* ids;
     rc = bd_forward_sync(b, n, *std::max_element(pos, pos + n), logits_out != nullptr, sp, "llmk_batch_forward",
                          [&] { return llmk_batch_forward(b, n, slots, tokens, pos, logits_out, argmax_out); }, &ids);
@@ -3745,6 +3857,7 @@ static int rows_decode(llmk_batch* b, const char* who, int n, const int* slots, 
     if ((rc = pg_prepare(b, n, slots, pos0, steps)) != LLMK_OK) return rc;      // (every step's page up front: no host round trip inside a decode)
     HIPCHK(b->d_ids.reserve(nids, c->stream));
     HIPCHK(bd_upload_rows(b, n, slots, tokens, pos0));
+    if ((rc = pg_stems(b, n, slots, pos0)) != LLMK_OK) return rc;      // (once for all steps)
     HIPCHK(rows_upload_words(b, n, samplers != nullptr, pen, lp != nullptr));
     HIPCHK(hipMemsetAsync(b->d_err, 0, sizeof(unsigned), c->stream));
     const int max_pos0 = *std::max_element(pos0, pos0 + n);
@@ -3852,6 +3965,7 @@ int llmk_batch_time(llmk_batch* b, int n, int pos, int iters, float* avg_ms) {
     for (int i = 0; i < n; ++i) { slots[i] = i; tokens[i] = 1; posv[i] = pos; }
     if ((rc = pg_prepare(b, n, slots, posv, 1)) != LLMK_OK) return rc;
     HIPCHK(bd_upload_rows(b, n, slots, tokens, posv));
+    if ((rc = pg_stems(b, n, slots, posv)) != LLMK_OK) return rc;
     return bd_time(b, n, pos, iters, sp, avg_ms);
 }
 

@@ -5,6 +5,7 @@
 //   PagePool                 the host's allocator: lowest free page first, a reference count per page, every change undoable
 //   bd_attn_paged_kernel     bd_attn_kernel's work split over a slot's pages: the tiles' physical rows staged in LDS, then the shared
 //                            tile loop of attn_tiles.h with the tile's pointer taken from there
+//   pg_stem_groups / bd_attn_stem / bd_attn_paged_own      stem reads (llmk_stems_*): pages that rows share read once per group
 //   bd_epi_qkv_paged[_h]     bd_epi_qkv[_h]_kernel with the store row taken through the table
 //   bd_page_copy / bd_to_pages / bd_from_pages      copy on write and the partial page of a share; llmk_batch_fork; llmk_cache_peek
 // The rows of a page behind its slot's position hold whatever the page's last owner left: no kernel reads them (the tile loop clamps
@@ -12,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstddef>
 #include <vector>
@@ -153,6 +155,164 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_paged_kernel(const fl
             po[(pbase * BD_MAX_GROUP + q) * HS + d] = val;
             if (d == 0) pml[pbase * BD_MAX_GROUP + q] = make_float2(M, L);
         }
+    });
+}
+
+// ---- stem reads (llmk_stems_*): slots that name the same pages at the head of their tables read them once per pass     ------------
+// The structure of a dense pass with attached rows (batch.h: prefix kernel, own kernel, fold) over pages: any number of stems in one
+// pass, a stem length per group, and every tile found through a table.
+//   pg_stem_groups            the grouping rule: host, plain C++, a function of (tables, rows) alone
+//   bd_attn_stem_kernel       a group's shared pages against the query heads of up to RG member rows at once: one read per group
+//   bd_attn_paged_own_kernel  bd_attn_own_kernel through the row's table: cache rows first[slot] .. pos-1, never normalising
+// and bd_attn_fold_kernel (batch.h) as it stands: stride kv_mul, `first` telling which rows have stem parts.
+
+// The rule.  rg = bd_prefix_rg(kv_mul).  cand(i) = (pos[i] - 1) / page_len: the entries of row i's table wholly in front of the page
+// the row writes.  common(i, j): the leading entries equal (and present) in both slots' tables, at most min(cand(i), cand(j)).  Rows
+// are walked in row order; an unassigned row i leads: G = max common(i, j) over the later unassigned rows j; G == 0: i is in no
+// group.  Else its members are i and, in row order, the later unassigned rows with common(i, j) >= (G + 1) / 2, up to rg rows in all
+// -- a row that shares one page with the leader does not pull down a group that shares ten, one that diverged a page earlier still
+// joins -- and the group's stem is the minimum of common(i, j) over them, in pages.  Rows left over when a group is full lead in their
+// turn.  A stem is whole pages in front of every member's write page: no ragged tile, no causal edge, every member sees all of it.
+// group[i]: the row's group, numbered in the order the leaders appear, -1 for none; stem[i]: the positions the stem kernel reads for
+// it, 0 for none.  Returns the number of groups.
+inline int pg_stem_groups(const PagePool& pl, int rg, int n, const int* slots, const int* pos, int* group, int* stem) {
+    constexpr int OPEN = -2;
+    const auto common = [&](int i, int j) {
+        const int cap = std::min((pos[i] - 1) / pl.page_len, (pos[j] - 1) / pl.page_len);
+        const int *a = pl.table.data() + (size_t)slots[i] * pl.width, *b = pl.table.data() + (size_t)slots[j] * pl.width;
+        int k = 0;
+        while (k < cap && a[k] >= 0 && a[k] == b[k]) ++k;
+        return k;
+    };
+    for (int i = 0; i < n; ++i) { group[i] = OPEN; stem[i] = 0; }
+    int ng = 0;
+    for (int i = 0; i < n; ++i) {
+        if (group[i] != OPEN) continue;
+        int G = 0;
+        for (int j = i + 1; rg > 1 && j < n; ++j)
+            if (group[j] == OPEN) G = std::max(G, common(i, j));
+        if (G == 0) { group[i] = -1; continue; }
+        int members = 1, pages = INT_MAX;
+        group[i] = ng;
+        for (int j = i + 1; j < n && members < rg; ++j) {
+            if (group[j] != OPEN) continue;
+            const int c = common(i, j);
+            if (c < (G + 1) / 2) continue;
+            group[j] = ng;
+            pages = std::min(pages, c);
+            ++members;
+        }
+        for (int j = i; j < n; ++j)
+            if (group[j] == ng) stem[j] = pages * pl.page_len;
+        ++ng;
+    }
+    return ng;
+}
+
+// a group of the pass: the slot whose table the stem is read through (the leader's), the stem's tiles, and the members' rows of the
+// pass in row order, -1 behind the last
+struct BdStem { int slot, tiles; int col[BD_MAX_GROUP]; };
+
+// One workgroup per (kv head, group, stem part), 8 waves round robin.  Column c is (member c / kv_mul, query head c % kv_mul of the kv
+// head); columns from the last live one on repeat it and are not written out, as in bd_attn_prefix_body.  Tile kt of the stem starts
+// at physical row table[leader slot][kt / tpg] * page_len + (kt % tpg) * 16; the workgroup stages the rows of ITS tiles and of the
+// look-ahead tiles behind them in LDS behind the merge's block, as bd_attn_paged_kernel does, and the shared loop takes a tile's
+// pointer from one LDS word.  The split rule is ONE for the pass -- bd_parts(groups, n_kv_heads, the longest stem, n_cu) and
+// bd_tiles_per_part of the longest stem -- so a part can lie wholly behind a shorter group's stem: it leaves M = -inf, L = 0 and zeros
+// for every live column, which is what the fold accepts from an empty span part.  Part states: stride kv_mul, np per (row, kv head),
+// the stem's in front (batch.h, a pass with attached rows).  Dynamic LDS: pg_attn_smem.
+template <int HS, class T>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_stem_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                       const T* __restrict__ vc, float* __restrict__ po,
+                                                                       float2* __restrict__ pml, BdCaches bc,
+                                                                       const BdStem* __restrict__ stems, BdPages pg, int n, int KV,
+                                                                       int kv_mul, int E, int tpp, int np) {
+    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
+    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
+    int* tile_row = reinterpret_cast<int*>(pf_smem + attn_smem(NW, HS));      // [tiles of seq_len], this workgroup's filled in
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x, rg = bd_prefix_rg(kv_mul);
+    const BdStem& st = stems[blockIdx.y];
+    const int ntile = st.tiles;
+    int nr = 0;
+    while (nr < rg && (unsigned)st.col[nr] < (unsigned)n) ++nr;
+    // whole workgroup: no barrier is pending (a stem lies in front of a position of the slot, so it is shorter than seq_len)
+    if (nr == 0 || (unsigned)st.slot >= (unsigned)bc.n_slots || ntile < 1 || ntile * BD_TILE >= bc.seq_len) return;
+    const int live = nr * kv_mul, c = min(li, live - 1);
+    const int t0 = part * tpp, t1 = min(t0 + tpp, ntile);
+    const auto state = [&](int col) { return (((size_t)st.col[col / kv_mul] * nkv + kvh) * np + part) * kv_mul + col % kv_mul; };
+    if (t0 >= ntile) {
+        for (int idx = tid; idx < live * HS; idx += NW * WAVE) {
+            const size_t s = state(idx / HS);
+            po[s * HS + idx % HS] = 0.f;
+            if (idx % HS == 0) pml[s] = make_float2(-INFINITY, 0.f);
+        }
+        return;
+    }
+    {
+        const int tpg = pg.page_len / BD_TILE;
+        const int* tab = pg.table + (size_t)st.slot * pg.width;
+        for (int t = t0 + tid; t < min(t1 + NW, ntile); t += NW * WAVE) {
+            const unsigned e = min((unsigned)tab[t / tpg], (unsigned)(pg.n_pages - 1));
+            tile_row[t] = (int)e * pg.page_len + (t % tpg) * BD_TILE;
+        }
+    }
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)st.col[c / kv_mul] * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG);
+    __syncthreads();
+    float m_run, l_run;
+    pf_v4f O[NT];
+    const int P = ntile * BD_TILE;
+    attn_tiles<HS, T, NW>(qf, kc + (size_t)kvh * HS + g * DG, vc + (size_t)kvh * HS + NT * li, KV, P - 1, ntile, t0, t1, wid, li, g,
+                          [&](int r) { return r < P; }, m_run, l_run, O,
+                          [&](const T* p, int tile) { return p + (ptrdiff_t)(tile_row[tile] - tile * BD_TILE) * KV; });
+    attn_merge_waves<HS, NW>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
+        const size_t s = state(col);
+        po[s * HS + d] = val;
+        if (d == 0) pml[s] = make_float2(M, L);
+    });
+}
+
+// bd_attn_own_body's split and predicate through the row's table: cache rows lo .. pos-1 of the row's slot, lo = first[slot] (the
+// row's stem in rows, 0 for a row in no group), tiles counted from lo / 16 and staged as above; part `part` leaves state p0 + part,
+// never normalised.  One workgroup per (kv head, row, own part).  Dynamic LDS: pg_attn_smem.
+template <int HS, class T>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_paged_own_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                            const T* __restrict__ vc, float* __restrict__ po,
+                                                                            float2* __restrict__ pml, BdCaches bc, BdPages pg,
+                                                                            const int* __restrict__ first, int KV, int kv_mul, int E,
+                                                                            int tpp, int np, int p0) {
+    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
+    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
+    int* tile_row = reinterpret_cast<int*>(pf_smem + attn_smem(NW, HS));
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, b = blockIdx.y, part = blockIdx.z, nkv = gridDim.x;
+    const BdRow row = bc.rows[b];
+    if (!bd_row_ok(bc, row)) return;                  // whole workgroup: no barrier is pending
+    const int lo = first[row.slot], nrows = row.pos;
+    if ((unsigned)lo >= (unsigned)nrows) return;      // (the host ends a stem in front of the row's position)
+    const int ntile = (nrows + BD_TILE - 1) / BD_TILE, t0 = lo / BD_TILE + part * tpp, t1 = min(t0 + tpp, ntile);
+    {
+        const int tpg = pg.page_len / BD_TILE;
+        const int* tab = pg.table + (size_t)row.slot * pg.width;
+        for (int t = min(t0, ntile - 1) + tid; t < min(t1 + NW, ntile); t += NW * WAVE) {
+            const unsigned e = min((unsigned)tab[t / tpg], (unsigned)(pg.n_pages - 1));
+            tile_row[t] = (int)e * pg.page_len + (t % tpg) * BD_TILE;
+        }
+    }
+    const int h = kvh * kv_mul + min(li, kv_mul - 1);
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)b * E + (size_t)h * HS + g * DG);
+    __syncthreads();
+    float m_run, l_run;
+    pf_v4f O[NT];
+    attn_tiles<HS, T, NW>(qf, kc + (size_t)kvh * HS + g * DG, vc + (size_t)kvh * HS + NT * li, KV, nrows - 1, ntile, t0, t1, wid, li, g,
+                          [&](int r) { return lo <= r && r < nrows; }, m_run, l_run, O,
+                          [&](const T* p, int tile) { return p + (ptrdiff_t)(tile_row[tile] - tile * BD_TILE) * KV; });
+    attn_merge_waves<HS, NW>(m_run, l_run, O, kv_mul, [&](int q, int d, float M, float L, float val) {
+        const size_t s = (((size_t)b * nkv + kvh) * np + p0 + part) * kv_mul + q;
+        po[s * HS + d] = val;
+        if (d == 0) pml[s] = make_float2(M, L);
     });
 }
 

@@ -449,6 +449,19 @@ module llmk_binding
        integer(c_int), value :: slot, cap
        type(c_ptr), value :: pages_out
      end function
+     ! stems (include/llmk.h): rows of a paged batch that share pages read them once per group; slots / pos / group_out / stem_out
+     ! are C addresses of arrays of n entries
+     integer(c_int) function llmk_stems_enable(batch, on) bind(C, name="llmk_stems_enable")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: on
+     end function
+     integer(c_int) function llmk_stems_plan(batch, n, slots, pos, group_out, stem_out) bind(C, name="llmk_stems_plan")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: batch
+       integer(c_int), value :: n
+       type(c_ptr), value :: slots, pos, group_out, stem_out
+     end function
      ! the rows functions (include/llmk.h): a batch's per-row penalties, bias and log-prob records.  samplers / penalties travel as C
      ! addresses of arrays of n entries (c_loc of a `target` array, or c_null_ptr: greedy / none); logprobs likewise (c_loc of a
      ! `target` llmk_logprobs, or c_null_ptr: no records); the optional outputs of the hook are c_loc or c_null_ptr too

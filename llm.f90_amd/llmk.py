@@ -33,7 +33,8 @@ SYMBOLS = ["llmk_create", "llmk_create_tp", "llmk_tp_unique_id", "llmk_tp_init_c
            "llmk_cache_create", "llmk_cache_type", "llmk_cache_bytes", "llmk_cache_peek", "llmk_span_forward", "llmk_span_time",
            "llmk_tree_forward", "llmk_tree_accept", "llmk_tree_time",
            "llmk_lora_create", "llmk_lora_upload", "llmk_lora_destroy", "llmk_lora_assign",
-           "llmk_pages_create", "llmk_pages_release", "llmk_pages_share", "llmk_pages_free", "llmk_pages_table", "llmk_reset", "llmk_timings",
+           "llmk_pages_create", "llmk_pages_release", "llmk_pages_share", "llmk_pages_free", "llmk_pages_table",
+           "llmk_stems_enable", "llmk_stems_plan", "llmk_reset", "llmk_timings",
            "llmk_time_kernel", "llmk_cls_form", "llmk_peek", "llmk_tensor_checksum", "llmk_path", "llmk_tk_shapes", "llmk_tp_ranks_seen", "llmk_destroy", "llmk_strerror", "llmk_version"]
 PATH_NAMES = {0: "multi-kernel (5 launches per layer)", 1: "persistent whole-token kernel",
               2: "tensor-parallel rank: 6 launches per layer + one-shot peer-memory exchanges",
@@ -227,6 +228,9 @@ def lib():
             L.llmk_pages_share.argtypes = [vp, ci, ci, ci]
             L.llmk_pages_free.argtypes = [vp]
             L.llmk_pages_table.argtypes = [vp, ci, C.POINTER(ci), ci]
+        if hasattr(L, "llmk_stems_enable"):
+            L.llmk_stems_enable.argtypes = [vp, ci]
+            L.llmk_stems_plan.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
         L.llmk_reset.argtypes = [vp]
         L.llmk_timings.argtypes = [vp, cf]
         L.llmk_time_kernel.argtypes = [vp, ci, ci, cf, C.POINTER(C.c_double)]
@@ -754,6 +758,21 @@ class Batch:
         out = (C.c_int * max(n, 1))()
         lib().llmk_pages_table(self._h, slot, out, n)
         return list(out[:n])
+
+    def stem_reads(self, on: bool):
+        """a paged batch: rows of a pass whose slots name the same pages at the head of their tables read them once per group
+        (llmk_stems_enable); off is the default"""
+        _ck(lib().llmk_stems_enable(self._h, int(on)))
+
+    def stem_plan(self, slots, pos):
+        """verification hook of a paged batch (llmk_stems_plan): what a pass of rows slots[i] at pos[i] would do under stem reads on the
+        tables as they are -> (groups, stems): a row's group (-1: none) and the positions the stem kernel reads for it"""
+        a = [np.ascontiguousarray(x, np.int32) for x in (slots, pos)]
+        if not (a[0].ndim == 1 and a[0].shape == a[1].shape):
+            raise ValueError("one slot and one position per row")
+        out = [np.empty(a[0].shape, np.int32) for _ in range(2)]
+        _ck(lib().llmk_stems_plan(self._h, a[0].size, *(x.ctypes.data_as(C.POINTER(C.c_int)) for x in a + out)))
+        return out[0], out[1]
 
     @staticmethod
     def _rows(slots, tokens, pos):

@@ -347,6 +347,57 @@ def print_paged(shape_name, type_name, rows, iters, repeats):
               f"{r['paged_ms'] / r['dense_ms']:14.3f} {r['share_ms']:10.3f} {r['fork_ms']:10.3f} {r['bytes']['dense'] / 1e6:10.1f} {r['bytes']['paged'] / 1e6:10.1f}")
 
 
+def stems(m, shape, page_len: int, P: int, pos: int, iters: int, repeats: int):
+    """--paged LEN --stems: llmk_batch_time at SAMPLED_ROWS rows at positions 25 and `pos`, every slot behind ONE stem of min(P, position
+    - 1) positions, on a paged batch with stem reads off and on (llmk_stems_enable: slot 0 forked at the stem, the others sharing its
+    pages) and on a dense batch with the slots attached to the stem as its prefix (llmk_prefix_*), f32 and f16, all alive together, the
+    three forms alternating `repeats` times, each measurement behind a warm-up of the same form."""
+    positions = [q for q in (SAMPLED_POS, pos) if q <= shape.seq_len]
+    m.reset()
+    m.prefill([2] + [3 + i % (shape.vocab_size - 3) for i in range(max(min(P, q - 1) for q in positions) - 1)], 1)
+    out = []
+    for kind in ("f32", "f16"):
+        for q in positions:
+            behind, slots = min(P, q - 1), max(SAMPLED_ROWS)
+            dense = llmk.Batch(m, slots, q, kv_type=kind)
+            # (the pool: one copy of the stem's full pages, and per slot the pages behind them up to position q)
+            pages = llmk.Batch(m, slots, q, kv_type=kind, page_len=page_len, n_pages=behind // page_len + slots * (-(-q // page_len) - behind // page_len))
+            dense.set_prefix(behind)
+            pages.fork(0, behind)
+            for j in range(slots):
+                dense.attach(j)
+                if j:
+                    pages.share(j, 0, behind)
+            for n in SAMPLED_ROWS:
+                groups, stem = pages.stem_plan(range(n), [q] * n)
+                ms = {"off": [], "on": [], "prefix": []}
+                for _ in range(repeats):
+                    for form in ms:
+                        b = dense if form == "prefix" else pages
+                        if b is pages:
+                            b.stem_reads(form == "on")
+                        b.time(n, q, 3)                              # warm-up of this form
+                        ms[form].append(b.time(n, q, iters))
+                row = {"kv": kind, "n": n, "pos": q, "page_len": page_len, "stem": int(stem.max()), "groups": int(groups.max()) + 1}
+                for form, xs in ms.items():
+                    row[form + "_ms"], row[form + "_spread"] = med_spread(xs)
+                out.append(row)
+            dense.close()
+            pages.close()
+    return out
+
+
+def print_stems(shape_name, type_name, rows, iters, repeats):
+    print(f"# library {llmk.LIB_PATH} (llmk_version {llmk.lib().llmk_version()})")
+    print(f"# batched decode, stem reads, {shape_name} {type_name}: llmk_batch_time, median of {repeats} x {iters} passes per form, the forms alternating in "
+          f"one process (spread = (max - min) / median); off | on: a paged batch whose slots share the stem's pages; prefix: a dense batch attached to it")
+    print(f"{'kv':>4} {'n':>5} {'pos':>6} {'page':>5} {'stem':>6} {'groups':>7} {'off ms':>10} {'spread':>7} {'on ms':>10} {'spread':>7} {'prefix ms':>10} {'spread':>7} "
+          f"{'on / off':>9} {'on / prefix':>12}")
+    for r in rows:
+        print(f"{r['kv']:>4} {r['n']:5d} {r['pos']:6d} {r['page_len']:5d} {r['stem']:6d} {r['groups']:7d} {r['off_ms']:10.3f} {r['off_spread']:7.3f} {r['on_ms']:10.3f} "
+              f"{r['on_spread']:7.3f} {r['prefix_ms']:10.3f} {r['prefix_spread']:7.3f} {r['on_ms'] / r['off_ms']:9.3f} {r['on_ms'] / r['prefix_ms']:12.3f}")
+
+
 def spans(m, shape, pos: int, iters: int, repeats: int):
     """--spans: the three measurements of profiles/batch_spans.txt, every figure the median of `repeats` behind a warm-up"""
     out = {"a": [], "b": {}, "c": {}}
@@ -572,10 +623,20 @@ def main():
     ap.add_argument("--paged", type=int, default=0, metavar="LEN",
                     help="only the paged table (llmk_pages_*): the pass at 8 and 128 rows at positions 25 and --pos on a dense and on a paged "
                          "batch of page_len LEN, f32 and f16, alternating in one process; llmk_pages_share against llmk_batch_fork")
+    ap.add_argument("--stems", action="store_true",
+                    help="with --paged LEN: only the stem-reads table (llmk_stems_*): the pass at 8, 32 and 128 rows at positions 25 and --pos "
+                         "behind one shared stem of --shared-prefix positions (default 1000), stem reads off | on | a dense batch's prefix")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
 
     m, shape = build(a.shape, a.type, a.cls_q6k)
+    if a.paged and a.stems:
+        rows = stems(m, shape, a.paged, a.shared_prefix or 1000, a.pos, a.iters, a.repeats)
+        m.close()
+        print_stems(a.shape, a.type + ("+q6_K" if a.cls_q6k else ""), rows, a.iters, a.repeats)
+        if a.json:
+            print(json.dumps({"shape": a.shape, "type": a.type + ("+q6_K" if a.cls_q6k else ""), "stems": rows}))
+        return
     if a.paged:
         rows = paged(m, shape, a.paged, a.pos, a.iters, a.repeats)
         m.close()
