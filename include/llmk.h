@@ -595,7 +595,7 @@ int llmk_cache_peek(llmk_batch *b, int which, int layer, int slot, int pos0, int
  * State the span passes need -- logits rows beyond n_slots, part states, the group table -- is allocated by the first span call that
  * needs it: a batch that never calls these functions allocates and launches exactly what it did without them.
  * In a span pass the slot's K/V rows are read once per GROUP of 16 / (query heads per kv head) consecutive rows of a span
- * (bd_attn_span_kernel), not once per row.  LLMK_SPAN_ATTN=0 in the environment at llmk_batch_create / llmk_cache_create makes span
+ * (bd_attn_span_kernel), not once per row.  LLMK_SPAN_ATTN=0 in the environment at llmk_batch_create / llmk_cache_create / llmk_pages_create makes span
  * passes run the per-row attention kernels of llmk_batch_forward instead (an A/B switch, like LLMK_PF_F32_MFMA for the prompt GEMMs);
  * the results stay within the parity bar.
  * Out of scope: draft models and acceptance policies (the host compares argmax_out itself), spans inside llmk_batch_decode /
@@ -705,11 +705,14 @@ int llmk_lora_assign(llmk_batch *b, int slot, llmk_lora *ad);
  * On such a batch llmk_batch_forward / _decode / _fork / _time / _destroy, llmk_rows_*, llmk_lora_assign, llmk_cache_type, llmk_cache_bytes
  * (the pool's bytes) and llmk_cache_peek (through the table; a position without a page reads +0.0) keep their contracts, and
  * llmk_batch_fork takes fresh pages for the slot (LLMK_E_NOMEM: the slot keeps what it had).  llmk_span_forward, llmk_span_time and a
- * chain-only llmk_tree_forward run the per-row attention kernel (the form LLMK_SPAN_ATTN=0 selects).  llmk_prefix_*, a llmk_tree_forward
+ * chain-only llmk_tree_forward read a slot's pages once per GROUP of 16 / (query heads per kv head) consecutive rows of a span
+ * (bd_attn_span_paged_kernel: bd_attn_span_kernel's groups, parts and tile order with every tile found through the table), with the
+ * bits of the same spans on a dense batch of the same type; LLMK_SPAN_ATTN=0 in the environment at llmk_pages_create keeps the per-row
+ * attention kernel, as on a dense batch, within the parity bar.  llmk_prefix_*, a llmk_tree_forward
  * that is not a chain and llmk_tree_accept are LLMK_E_ARG before anything runs.  A pass's arithmetic does not depend on where a slot's
  * pages lie: the same sequence gives the same bits on any table.  llmk_pages_* on a batch of llmk_batch_create / llmk_cache_create, or
  * on NULL: LLMK_E_ARG (llmk_pages_free, llmk_pages_table: -LLMK_E_ARG).
- * Out of scope: q8_0 pages; the span and tree column-group kernels over pages (shared stems: llmk_stems_*, below); swapping pages to the host; any scheduler. */
+ * Out of scope: q8_0 pages; trees that are not chains (the tree column-group kernel over pages; shared stems: llmk_stems_*, below); swapping pages to the host; any scheduler. */
 int llmk_pages_create(llmk_ctx *ctx, int n_slots, int seq_len, int kv_type, int page_len, int n_pages, llmk_batch **out);
 int llmk_pages_release(llmk_batch *b, int slot, int n_keep);
 int llmk_pages_share(llmk_batch *b, int dst_slot, int src_slot, int n_pos);

@@ -1809,14 +1809,16 @@ static int pg_prepare(llmk_batch* b, int n, const int* slots, const int* pos, in
 //   TREE  a tree pass (pass_tree, llmk_tree_*): a span pass whose rows are rotated at rope_pos and whose column groups run
 //         bd_attn_tree_kernel -- the same groups, split rule, part states and fold.
 //   PAGED a pass of a paged batch (llmk_pages_*): ROW's split, states and fold with bd_attn_paged_kernel in bd_attn_kernel's place --
-//         span passes too (such a batch has no shared prefix, no column groups and no trees).
+//         span passes too under LLMK_SPAN_ATTN=0 (such a batch has no shared prefix and no trees).
+//   PSPAN a span pass of a paged batch (pass_groups > 0): SPAN's groups, split, states and fold with bd_attn_span_paged_kernel in
+//         bd_attn_span_kernel's place; never a prefix kernel.
 // OWN, SPAN and TREE leave np = pparts + parts states per (row, kv head) in the batch's PartStates (stride kv_mul): the prefix parts first.
 //   STEMS a pass of a paged batch in which stem reads formed a group (llmk_stems_*, pass_stems > 0): OWN's structure over pages --
 //         bd_attn_stem_kernel over the groups, bd_attn_paged_own_kernel from row `first` on, always folded.
 struct BdAttnPlan {
-    enum Kind { ROW, OWN, SPAN, TREE, PAGED, STEMS } kind;
+    enum Kind { ROW, OWN, SPAN, TREE, PAGED, PSPAN, STEMS } kind;
     bool per_row;                   // ROW or PAGED: one workgroup per (kv head, row, part), states in d_po / d_pml
-    bool grouped;                   // SPAN or TREE: the rows' kernel runs over column groups
+    bool grouped;                   // SPAN, PSPAN or TREE: the rows' kernel runs over column groups
     bool shared, fold;              // attached rows in the pass: the prefix kernel runs; the fold kernel runs
     int units;                      // grid.y of the rows' kernel: rows, or column groups of a span pass
     int parts, tpp;                 // own parts and their tiles
@@ -1831,9 +1833,9 @@ static BdAttnPlan bd_attn_plan(const llmk_batch* b, int n, int max_pos, int step
     const llmk_ctx* c = b->ctx;
     BdAttnPlan p{};
     p.shared = b->pass_att > 0;
-    p.kind = b->pg ? (b->pg->pass_stems > 0 ? BdAttnPlan::STEMS : BdAttnPlan::PAGED) : b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
+    p.kind = b->pg ? (b->pg->pass_stems > 0 ? BdAttnPlan::STEMS : b->pass_groups > 0 ? BdAttnPlan::PSPAN : BdAttnPlan::PAGED) : b->pass_tree ? BdAttnPlan::TREE : b->pass_groups > 0 ? BdAttnPlan::SPAN : p.shared ? BdAttnPlan::OWN : BdAttnPlan::ROW;
     p.per_row = p.kind == BdAttnPlan::ROW || p.kind == BdAttnPlan::PAGED;
-    p.grouped = p.kind == BdAttnPlan::SPAN || p.kind == BdAttnPlan::TREE;
+    p.grouped = p.kind == BdAttnPlan::SPAN || p.kind == BdAttnPlan::PSPAN || p.kind == BdAttnPlan::TREE;
     p.units = p.grouped ? b->pass_groups : n;
     // The split rule is bd_parts on the longest OWN range, counted in whole tiles from the one that holds row `first`.  Without
     // attached rows every range starts at tile 0 and the longest is the longest row's
@@ -1924,6 +1926,11 @@ static hipError_t bd_pass_of(llmk_batch* b, int n, int max_pos, bool want_logits
                     if constexpr (BdKv<TC>::pageable)
                         hipLaunchKernelGGL((bd_attn_paged_kernel<HS, TC>), grid, block, pg_attn_smem(HS, b->seq_len), w.stream, w.Q, kc, vc, w.XB, p.po, p.pml, bc,
                                            b->pg->view(), KV, c->kv_mul, E, p.tpp);
+                    break;
+                case BdAttnPlan::PSPAN:
+                    if constexpr (BdKv<TC>::pageable)
+                        hipLaunchKernelGGL((bd_attn_span_paged_kernel<HS, TC>), grid, block, pg_attn_smem(HS, b->seq_len), w.stream, w.Q, kc, vc, w.XB, p.po, p.pml,
+                                           bc, b->sn->d_groups, b->pg->view(), T, KV, c->kv_mul, E, p.tpp, p.np, p.direct);
                     break;
                 case BdAttnPlan::STEMS:
                     if constexpr (BdKv<TC>::pageable) {
@@ -3276,8 +3283,7 @@ static int bd_create(llmk_ctx* c, int n_slots, int seq_len, int kv_type, int pag
     }
     if (!with_kv_type(b.get(), [&](auto t) { return BdKv<decltype(t)>::shape_ok(c->KV); })) return LLMK_E_SHAPE;
     HIPCHK(hipSetDevice(c->cfg.device));
-    // (a paged batch's span passes run the per-row attention kernel: the column-group kernels do not read through a table)
-    b->span_attn = !paged && !(getenv("LLMK_SPAN_ATTN") && getenv("LLMK_SPAN_ATTN")[0] == '0');
+    b->span_attn = !(getenv("LLMK_SPAN_ATTN") && getenv("LLMK_SPAN_ATTN")[0] == '0');
     ScPlan sp;
     if ((rc = bd_ready(b.get(), &sp, n_slots)) != LLMK_OK) return rc;
     const size_t nb = LLMK_MAX_BATCH;
@@ -3987,7 +3993,8 @@ static bool span_ok(const llmk_batch* b, int n_spans, const llmk_span* spans, co
     return true;
 }
 // what a span pass needs beyond a batch's own, by the first call that needs it: logits rows beyond n_slots; the group table and the
-// part states of bd_attn_span_kernel (not with LLMK_SPAN_ATTN=0: the per-row kernels have theirs)
+// part states of bd_attn_span_kernel, on a paged batch of bd_attn_span_paged_kernel (not with LLMK_SPAN_ATTN=0: the per-row kernels
+// have theirs)
 // (groups: the table and the states are needed -- a tree pass always runs over column groups)
 static int span_setup(llmk_batch* b, int rows, bool groups) {
     llmk_ctx* c = b->ctx;
@@ -4003,8 +4010,12 @@ static int span_setup(llmk_batch* b, int rows, bool groups) {
     if (rc) return rc;
     HIPCHK(with_head_size(c->hs, [&](auto hs) -> hipError_t {
         constexpr int HS = decltype(hs)::value;
-        return with_kv_type(b, [](auto t) -> hipError_t {
-            return hipFuncSetAttribute((const void*)BdAttn<HS, decltype(t)>::span, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
+        return with_kv_type(b, [&](auto t) -> hipError_t {
+            using TC = decltype(t);
+            if constexpr (BdKv<TC>::pageable)
+                if (b->pg)
+                    return hipFuncSetAttribute((const void*)bd_attn_span_paged_kernel<HS, TC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg_attn_smem(HS, b->seq_len));
+            return hipFuncSetAttribute((const void*)BdAttn<HS, TC>::span, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_smem(BD_WAVES, HS));
         });
     }));
     b->sn = std::move(sn);

@@ -5,6 +5,7 @@
 //   PagePool                 the host's allocator: lowest free page first, a reference count per page, every change undoable
 //   bd_attn_paged_kernel     bd_attn_kernel's work split over a slot's pages: the tiles' physical rows staged in LDS, then the shared
 //                            tile loop of attn_tiles.h with the tile's pointer taken from there
+//   bd_attn_span_paged_kernel   bd_attn_span_kernel's column groups over a slot's pages: a span's rows read the slot once per group
 //   pg_stem_groups / bd_attn_stem / bd_attn_paged_own      stem reads (llmk_stems_*): pages that rows share read once per group
 //   bd_epi_qkv_paged[_h]     bd_epi_qkv[_h]_kernel with the store row taken through the table
 //   bd_page_copy / bd_to_pages / bd_from_pages      copy on write and the partial page of a share; llmk_batch_fork; llmk_cache_peek
@@ -154,6 +155,70 @@ __global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_paged_kernel(const fl
         } else {
             po[(pbase * BD_MAX_GROUP + q) * HS + d] = val;
             if (d == 0) pml[pbase * BD_MAX_GROUP + q] = make_float2(M, L);
+        }
+    });
+}
+
+// ---- span attention through the table                                                                                  ------------
+// bd_attn_span_body's work split over a slot's pages: one workgroup per (kv head, column group, part), the groups of span_upload
+// (BdGroup: up to bd_prefix_rg(kv_mul) consecutive rows of one span), the ONE split rule of the pass (bd_span_parts, part p of a group
+// takes tiles [p * tpp, (p + 1) * tpp) cut at the group's last tile -- possibly none), 8 waves round robin.  Column c is (row first +
+// c / kv_mul, query head c % kv_mul of the kv head); columns from the last live one on repeat it and are not written out.  The lane
+// of column c sees cache rows 0 .. pos(c's row) - 1: a paged batch has no attached slots, so every range starts at row 0.  The slot's
+// pages cross L2 once per group instead of once per row.
+// Where a tile lies is bd_attn_paged_kernel's answer: the physical rows of the workgroup's tiles [t0, t1) and of the NW look-ahead
+// tiles behind them (clamped to the group's last tile, as the loop clamps; an empty part stages that last tile alone, which the loop's
+// first request names) go to LDS behind the merge's block in one global round trip next to the Q load, and the loop takes a tile's
+// pointer from one LDS word.  Two kinds of rows are in reach and must stay unread:
+//   rows of the last tile behind the group's last position -- whatever the page's last owner left: the loop clamps every row index
+//       to rowl.pos - 1, and that row lies in the tile the clamp is applied in (tile <= ntile - 1 <= (rowl.pos - 1) / 16);
+//   rows of the span's later columns -- bd_epi_qkv_paged[_h]_kernel of this same pass has written them: the predicate r < vis alone
+//       keeps them out, as in the dense kernel.
+// direct (one part in the pass): the normalised output goes to `out`; else part `part` leaves state `part` of every (row, kv head) of
+// the group (stride kv_mul, np states) for bd_attn_fold_kernel.  Groups, parts, tile order and every statement of the arithmetic are
+// those of bd_attn_span_kernel on a dense batch that holds the same rows: the results are the same bits.  Dynamic LDS: pg_attn_smem.
+template <int HS, class T>
+__global__ __launch_bounds__(BD_WAVES * WAVE) void bd_attn_span_paged_kernel(const float* __restrict__ Q, const T* __restrict__ kc,
+                                                                             const T* __restrict__ vc, float* __restrict__ out,
+                                                                             float* __restrict__ po, float2* __restrict__ pml, BdCaches bc,
+                                                                             const BdGroup* __restrict__ groups, BdPages pg, int n, int KV,
+                                                                             int kv_mul, int E, int tpp, int np, int direct) {
+    constexpr int DG = HS / 4, NT = HS / 16, NW = BD_WAVES;
+    extern __shared__ __attribute__((aligned(16))) char pf_smem[];
+    int* tile_row = reinterpret_cast<int*>(pf_smem + attn_smem(NW, HS));      // [tiles of seq_len], this workgroup's filled in
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int kvh = blockIdx.x, part = blockIdx.z, nkv = gridDim.x;
+    const BdGroup gr = groups[blockIdx.y];
+    if (gr.first < 0 || gr.rows < 1 || gr.rows > bd_prefix_rg(kv_mul) || gr.rows > n - gr.first) return;      // whole workgroup: no barrier is pending
+    const BdRow row0 = bc.rows[gr.first], rowl = bc.rows[gr.first + gr.rows - 1];
+    if (!bd_row_ok(bc, row0) || !bd_row_ok(bc, rowl) || rowl.slot != row0.slot || rowl.pos != row0.pos + gr.rows - 1) return;
+    const int ntile = (rowl.pos + BD_TILE - 1) / BD_TILE, t0 = part * tpp, t1 = min(t0 + tpp, ntile);
+    {
+        const int tpg = pg.page_len / BD_TILE;
+        const int* tab = pg.table + (size_t)row0.slot * pg.width;
+        for (int t = min(t0, ntile - 1) + tid; t < min(t1 + NW, ntile); t += NW * WAVE) {
+            const unsigned e = min((unsigned)tab[t / tpg], (unsigned)(pg.n_pages - 1));
+            tile_row[t] = (int)e * pg.page_len + (t % tpg) * BD_TILE;
+        }
+    }
+    const int live = gr.rows * kv_mul, c = min(li, live - 1);
+    const int vis = row0.pos + c / kv_mul;            // this lane's column sees cache rows 0 .. vis-1
+    float qf[DG];
+    attn_load_q<HS>(qf, Q + (size_t)(gr.first + c / kv_mul) * E + (size_t)(kvh * kv_mul + c % kv_mul) * HS + g * DG);
+    __syncthreads();
+    float m_run, l_run;
+    pf_v4f O[NT];
+    attn_tiles<HS, T, NW>(qf, kc + (size_t)kvh * HS + g * DG, vc + (size_t)kvh * HS + NT * li, KV, rowl.pos - 1, ntile, t0, t1, wid, li, g,
+                          [&](int r) { return r < vis; }, m_run, l_run, O,
+                          [&](const T* p, int tile) { return p + (ptrdiff_t)(tile_row[tile] - tile * BD_TILE) * KV; });
+    attn_merge_waves<HS, NW>(m_run, l_run, O, live, [&](int col, int d, float M, float L, float val) {
+        const int b = gr.first + col / kv_mul, q = col % kv_mul;
+        if (direct) {
+            out[(size_t)b * E + (size_t)(kvh * kv_mul + q) * HS + d] = val / L;
+        } else {
+            const size_t s = (((size_t)b * nkv + kvh) * np + part) * kv_mul + q;
+            po[s * HS + d] = val;
+            if (d == 0) pml[s] = make_float2(M, L);
         }
     });
 }

@@ -29,7 +29,9 @@ behind P positions.  --kv f32 | f16 | q8_0 measures one type alone, --kv all the
     python -m llm_f90_amd.tools.batch_bench --shape llama2-7b --type q4_0 --cls-q6k --spans
 
 times span passes (llmk_span_*): (a) one span of 128 rows ending at --pos with bd_attn_span_kernel and with the per-row attention
-kernels (a second batch created under LLMK_SPAN_ATTN=0), on f32 and f16 caches, llmk_span_time, alternating; (b) a prompt of
+kernels (a second batch created under LLMK_SPAN_ATTN=0), on f32 and f16 caches, llmk_span_time, alternating -- and in the same
+alternation the two forms on a pool of 16-position pages (llmk_pages_create: bd_attn_span_paged_kernel | the paged per-row kernel;
+under LLMK_LIB, a build whose paged span passes know one form measures that form twice: the baseline); (b) a prompt of
 --pos - 24 tokens into one slot in spans of 128 against llmk_prefill + llmk_batch_fork, wall clock of the calls; (c) 112 decode rows
 at --pos with and without one 16-row chunk of another slot in the same pass, wall clock of the calls.
 
@@ -398,6 +400,9 @@ def print_stems(shape_name, type_name, rows, iters, repeats):
               f"{r['on_spread']:7.3f} {r['prefix_ms']:10.3f} {r['prefix_spread']:7.3f} {r['on_ms'] / r['off_ms']:9.3f} {r['on_ms'] / r['prefix_ms']:12.3f}")
 
 
+SPAN_PAGE_LEN = 16      # part (a)'s pools: the smallest page, a table word per tile
+
+
 def spans(m, shape, pos: int, iters: int, repeats: int):
     """--spans: the three measurements of profiles/batch_spans.txt, every figure the median of `repeats` behind a warm-up"""
     out = {"a": [], "b": {}, "c": {}}
@@ -411,17 +416,26 @@ def spans(m, shape, pos: int, iters: int, repeats: int):
         finally:
             del os.environ["LLMK_SPAN_ATTN"]
         span_b = llmk.Batch(m, 1, pos, kv_type=kind)
-        ms = {"span": [], "rows": []}
+        forms = {"span": span_b, "rows": rows_b}
+        if kind != "q8_0":      # (no q8_0 pools) the same two forms on a pool of exactly the pages the slot needs
+            pool = dict(kv_type=kind, page_len=SPAN_PAGE_LEN, n_pages=-(-pos // SPAN_PAGE_LEN))
+            os.environ["LLMK_SPAN_ATTN"] = "0"
+            try:
+                forms["paged_rows"] = llmk.Batch(m, 1, pos, **pool)
+            finally:
+                del os.environ["LLMK_SPAN_ATTN"]
+            forms["paged_span"] = llmk.Batch(m, 1, pos, **pool)
+        ms = {form: [] for form in forms}
         for _ in range(repeats):
-            for form, b in (("span", span_b), ("rows", rows_b)):
+            for form, b in forms.items():
                 b.time_spans(1, 128, pos0, 3)
                 ms[form].append(b.time_spans(1, 128, pos0, iters))
-        row = {"kv": kind, "pos0": pos0, "len": 128}
+        row = {"kv": kind, "pos0": pos0, "len": 128, "page_len": SPAN_PAGE_LEN}
         for form, xs in ms.items():
             row[form + "_ms"], row[form + "_spread"] = med_spread(xs)
         out["a"].append(row)
-        rows_b.close()
-        span_b.close()
+        for b in forms.values():
+            b.close()
     # (b) a prompt into one slot: spans against prefill + fork
     n = pos - 24
     prompt = [2] + [3 + i % (shape.vocab_size - 3) for i in range(n - 1)]
@@ -543,6 +557,12 @@ def print_spans(shape_name, type_name, r, iters, repeats):
     print(f"{'kv':>5} {'pos0':>6} {'len':>4} {'span ms':>9} {'spread':>7} {'per-row ms':>11} {'spread':>7} {'per-row / span':>15}")
     for x in r["a"]:
         print(f"{x['kv']:>5} {x['pos0']:6d} {x['len']:4d} {x['span_ms']:9.3f} {x['span_spread']:7.3f} {x['rows_ms']:11.3f} {x['rows_spread']:7.3f} {x['rows_ms'] / x['span_ms']:15.2f}")
+    print(f"# (a) the same on a pool of pages of {SPAN_PAGE_LEN} positions (llmk_pages_create): bd_attn_span_paged_kernel | LLMK_SPAN_ATTN=0, in the same alternation")
+    print(f"{'kv':>5} {'pos0':>6} {'len':>4} {'span ms':>9} {'spread':>7} {'per-row ms':>11} {'spread':>7} {'per-row / span':>15} {'paged / dense span':>19}")
+    for x in r["a"]:
+        if "paged_span_ms" in x:
+            print(f"{x['kv']:>5} {x['pos0']:6d} {x['len']:4d} {x['paged_span_ms']:9.3f} {x['paged_span_spread']:7.3f} {x['paged_rows_ms']:11.3f} {x['paged_rows_spread']:7.3f} "
+                  f"{x['paged_rows_ms'] / x['paged_span_ms']:15.2f} {x['paged_span_ms'] / x['span_ms']:19.3f}")
     x = r["b"]
     print(f"# (b) a prompt of {x['tokens']} tokens into one slot, wall clock of the calls (f32 caches)")
     print(f"  spans of 128 (Batch.ingest) {x['spans_ms']:9.3f} ms (spread {x['spans_spread']:.3f})   llmk_prefill + llmk_batch_fork {x['prefill_fork_ms']:9.3f} ms (spread {x['prefill_fork_spread']:.3f})")
