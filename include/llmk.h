@@ -83,7 +83,8 @@ typedef struct llmk_config {
     int32_t n_heads;     /* nh */
     int32_t n_kv_heads;  /* nkv */
     int32_t vocab_size;  /* V  */
-    int32_t seq_len;     /* S: KV-cache capacity (llama2.f90:311-313) */
+    int32_t seq_len;     /* S: KV-cache capacity (llama2.f90:311-313).  Bounded by device memory alone: 2 * n_layers * S * kv_dim floats of
+                          * cache (a context beyond ~40,400 positions runs the split decode attention, see llmk_forward) */
     int32_t weight_type; /* LLMK_TYPE_* of wqkv/wo/w13/w2/wcls */
     int32_t device;      /* HIP device ordinal */
     int32_t flags;       /* LLMK_FLAG_* */
@@ -178,7 +179,17 @@ int llmk_set_rope_freqs(llmk_ctx *ctx, const float *freqs, int n);
 /* The hot path: one token through the whole stack.  Replaces
  * `logits = transformer(token,pos,s,weights)` (llama2.f90:380).  token in [1,V], pos in [1,S],
  * both 1-based; positions must be fed in order 1,2,3,... (each call appends to the KV cache at
- * pos, llama2.f90:564-565).  logits_out: V floats, caller-owned host memory. */
+ * pos, llama2.f90:564-565).  logits_out: V floats, caller-owned host memory.
+ *
+ * Long contexts.  The multi-kernel path's decode attention keeps a position's score row in LDS, which holds seq_len up to 40,444
+ * ((516 + S) * 4 bytes <= 160 KB).  A context created with a larger seq_len runs the SPLIT decode attention instead (DESIGN.md
+ * section 3a2: the position's K/V rows over one workgroup per (kv head, part) on the matrix cores, then a fold per query head),
+ * which has no term in seq_len: llmk_create succeeds on the multi-kernel path (llmk_path == LLMK_PATH_MULTI_KERNEL -- the
+ * persistent kernel's own score rows end at half that length) and seq_len is limited by device memory alone.  LLMK_ATTN_SPLIT=1 in
+ * the environment at llmk_create selects it for a context of any seq_len.  Its logits are within the 1e-4 parity bar of the other
+ * kernel's, deterministic from run to run, and NOT bit-identical to them (another summation order); without the variable a
+ * context the score row fits runs what it always ran, bit for bit.  Every function that feeds the context's own sequence token by
+ * token takes the same path.  (More than 16 query heads per kv head: no split form, the old limit and LLMK_E_SHAPE stand.) */
 int llmk_forward(llmk_ctx *ctx, int token, int pos, float *logits_out);
 
 /* llmk_forward keeps the next greedy position in flight: once a caller has fed back the first maximum of

@@ -201,11 +201,13 @@ __device__ __forceinline__ void attn_load_q(float (&qf)[HS / 4], const float* __
 // the next tile is requested before this one is multiplied).  A wave without a visible row leaves m = -inf, l = 0, O = 0.
 // where(p, tile): the pointer a tile's loads start from, for a cache whose 16-row tiles do not lie one behind the other (paged.h: the
 // pages of a slot); AttnDense, the default, is the cache as it stands: p itself, and nothing of it is left in the code.
+// STRICT (attn_split.h): a NaN score counts even while the column has seen nothing finite (m = -inf), where the default gives it the
+// weight 0 of a masked row; every other score has the same weight either way.
 struct AttnDense {
     template <class P>
     __device__ __forceinline__ P operator()(P p, int) const { return p; }
 };
-template <int HS, class T, int NW, class Visible, class Where = AttnDense>
+template <int HS, class T, int NW, class Visible, class Where = AttnDense, bool STRICT = false>
 __device__ __forceinline__ void attn_tiles(const float (&qf)[HS / 4], typename AttnAhead<HS, T>::Ptr kb, typename AttnAhead<HS, T>::Ptr vb, int KV,
                                            int last, int ntile, int t0, int t1, int wid, int li, int g, Visible visible, float& m_run,
                                            float& l_run, pf_v4f (&O)[HS / 16], Where where = Where()) {
@@ -245,7 +247,7 @@ __device__ __forceinline__ void attn_tiles(const float (&qf)[HS / 4], typename A
         float p[4], rs = 0.f;
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-            p[v] = (any && sc[v] != -INFINITY) ? expf(sc[v] - m_new) : 0.f;
+            p[v] = ((any || STRICT) && sc[v] != -INFINITY) ? expf(sc[v] - m_new) : 0.f;
             rs += p[v];
         }
         rs += __shfl_xor(rs, 16, 64);

@@ -16,6 +16,7 @@
 #include "token_kernel.h"
 #include "prefill.h"
 #include "batch.h"
+#include "attn_split.h"
 #include "paged.h"
 #include "lora.h"
 #include "tp_p2p.h"
@@ -133,6 +134,10 @@ struct llmk_ctx {
     DevTensor t[LLMK_N_TENSORS];
     DevBuf<float> d_kc, d_vc;      // [L][S][KV]  (RunState, weight_module.f90:33-40)
     DevBuf<float> d_x, d_q, d_xb, d_hb, d_rope;
+    // attn_split.h: launch_attn runs attn_split_kernel + attn_split_fold_kernel over attn_parts parts per kv head (0: attn_kernel, and
+    // no states) -- chosen at create: seq_len beyond attn_kernel's LDS score row, or LLMK_ATTN_SPLIT=1
+    int attn_parts = 0;
+    DevBuf<float> d_attn_ps;       // [nhl][attn_parts][hs + 2] part states {m, l, o[hs]}
     DevBuf<float> d_logits;        // [V], then dev_words()
     DevBuf<int> d_tokpos, d_next;
     PinnedBuf<int> h_tokpos;    // pinned {token0, pos1}
@@ -478,13 +483,22 @@ hipError_t with_head_size(int hs, F f) {
     }
     return hipErrorInvalidValue;
 }
+// attn_kernel's dynamic LDS: the reduction words, then a score row of the whole context
+static size_t attn_row_smem(int S) { return (516 + (size_t)S) * sizeof(float); }
 hipError_t launch_attn(llmk_ctx* c, int l) {
     const float* kc = c->d_kc + (size_t)l * c->S * c->KVl;
     const float* vc = c->d_vc + (size_t)l * c->S * c->KVl;
-    const size_t smem = (516 + (size_t)c->S) * sizeof(float);
+    const size_t smem = attn_row_smem(c->S);
     return with_head_size(c->hs, [&](auto hs) {
         constexpr int HS = decltype(hs)::value;
         hipError_t pe;
+        if (c->attn_parts) {      // the position's rows split over (kv head, part) workgroups, then one fold per query head (attn_split.h)
+            if (prepare_only(attn_split_kernel<HS>, attn_smem(ATS_WAVES, HS), &pe)) return pe;
+            hipLaunchKernelGGL((attn_split_kernel<HS>), dim3(c->KVl / HS, c->attn_parts), dim3(ATS_WAVES * WAVE), attn_smem(ATS_WAVES, HS), c->stream,
+                               c->d_q, kc, vc, c->d_attn_ps, c->d_tokpos, c->KVl, c->kv_mul);
+            hipLaunchKernelGGL((attn_split_fold_kernel<HS>), dim3(c->nhl), dim3(ATS_FOLD_THREADS), 0, c->stream, c->d_attn_ps, c->d_xb, c->attn_parts);
+            return hipGetLastError();
+        }
         if (prepare_only(attn_kernel<HS>, smem, &pe)) return pe;
         hipLaunchKernelGGL((attn_kernel<HS>), dim3(c->nhl), dim3(256), smem, c->stream, c->d_q, kc, vc, c->d_xb, c->d_tokpos, c->KVl, c->kv_mul);
         return hipGetLastError();
@@ -2031,7 +2045,7 @@ static int bd_time(llmk_batch* b, int n, int max_pos, int iters, const ScPlan& s
 
 extern "C" {
 
-int llmk_version(void) { return 412; }
+int llmk_version(void) { return 413; }
 
 const char* llmk_strerror(int code) {
     switch (code) {
@@ -2146,6 +2160,12 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
     CK(c->d_xb.alloc((size_t)E));
     CK(c->d_hb.alloc((size_t)H));
     CK(c->d_part.alloc((size_t)E));
+    // The split attention where attn_kernel's score row does not fit the LDS, or where the environment asks for it; otherwise nothing
+    // of it exists.  (More than 16 query heads per kv head do not fit its MFMA columns: such a context keeps attn_kernel and its limit.)
+    if ((attn_row_smem(S) > LDS_MAX || (getenv("LLMK_ATTN_SPLIT") && getenv("LLMK_ATTN_SPLIT")[0] == '1')) && c->kv_mul <= ATS_MAX_GROUP) {
+        c->attn_parts = ats_parts(nkv / tp_size, S, c->n_cu);
+        CK(c->d_attn_ps.alloc((size_t)c->nhl * c->attn_parts * ats_state(hs)));
+    }
     // the logits, then the device's scratch words (scratch_layout.h TkDevWords: the sticky error word first)
     static_assert(sizeof(TkDevWords) % sizeof(float) == 0 && sizeof(TkHostWords) % sizeof(float) == 0, "the scratch words are whole floats' worth");
     const size_t logits_bytes = (size_t)V * sizeof(float) + sizeof(TkDevWords);
@@ -2181,7 +2201,7 @@ int llmk_create_tp(const llmk_config* cfg, int tp_rank, int tp_size, llmk_ctx** 
         if (pe == hipSuccess) pe = launch_w2(c, 0);
         if (pe == hipSuccess) pe = launch_cls(c);
         g_prepare = false;
-        if (pe == hipErrorInvalidValue) rc = LLMK_E_SHAPE;   // context or contraction width needs more than 160 KB of LDS
+        if (pe == hipErrorInvalidValue) rc = LLMK_E_SHAPE;   // a contraction width (or attn_kernel's context, where the split attention cannot stand in) needs more than 160 KB of LDS
         else CK(pe);
     }
     if (rc == LLMK_OK) {
