@@ -29,7 +29,9 @@
 // seen nothing finite), l becomes NaN and stays NaN through the rescales, and the merges multiply it by a factor -- even 0 -- and add
 // it: L is NaN.  +inf: m becomes +inf and the row's own weight expf(inf - inf) is NaN.  All -inf: every state keeps m = -inf, l = 0,
 // o = 0 and the fold divides 0 by 0.  A -inf score beside finite ones: weight 0 (it is not exponentiated at all).  As in attn_kernel,
-// a weight of 0 times a non-finite V element is NaN.
+// a weight of 0 times a non-finite V element is NaN.  That reaches the NEWEST row's V too, and is in no contract: the masked rows of the
+// ragged last tile load it (the clamp) and weigh it 0, so an infinite element there gives NaN, not +-inf, at every position that is no
+// multiple of 16 -- as attn_kernel does at every position that is no multiple of its batch (measured: tests/test_attn_split_op_gpu.py).
 // NOT a stand-alone header in spirit: it is prefill.h's MFMA attention pieces (attn_tiles.h) around a split rule and two kernels.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -33,6 +33,20 @@ PF_ROWS = 16        # csrc/prefill.h:756-757: a workgroup owns 16 queries, a wav
 PF_STRIDE = PF_ROWS * PF_ATT_WAVES      # rows between two tiles of the same wave (attn_tiles.h:138: kt += NW)
 
 
+ATS_TILE = 16       # csrc/attn_split.h: cache rows per MFMA tile
+ATS_WAVES = 8       # waves of a part's workgroup
+ATS_MAX_PARTS = 64
+ATS_MAX_GROUP = 16  # query heads per kv head the split form takes; more keep attn_kernel
+
+
+def ats_parts(n_kv_local: int, S: int, n_cu: int = TK_NCU) -> int:
+    """ats_parts (csrc/attn_split.h): the parts a kv head's rows are split into -- one workgroup per CU, at most ATS_MAX_PARTS, and
+    no more than leave each wave of a part a tile at the full context"""
+    ntile = -(-S // ATS_TILE)
+    full = -(-ntile // ATS_WAVES)
+    return max(1, min(n_cu // n_kv_local, full, ATS_MAX_PARTS))
+
+
 def attn_kernel_tiles(hs: int):
     """attn_kernel<HS> (csrc/kernels.h:632-635): LPT = HS/4 lanes share a timestep, 4 waves -> TPB timesteps per
     block-instruction, ATT_U of them per batch."""
